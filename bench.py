@@ -7,6 +7,11 @@ target index build (the analogue of PCL's per-align kd-tree build) + source load
 `iterations` fixed ICP iterations (NN search, gate, 17 sums, host Umeyama/SVD, transform).
 value = N_src * iterations * steps / wall time of the timed region (max over ranks).
 
+A plain run sets up, warms up, times the --steps steps and prints the line.  --full adds the other legs
+(CPU port baselines, pipeline 1, the alignment from the identity, events in all steps, host buffers,
+reference mode; for the chain its CPU baseline and self-checks).  --dump-outputs DIR writes the last
+timed step's results (the IcpResult of the pair, the composed poses of the chain) as DIR/<name>.npy.
+
 N = 1 : config.workload "icp_pair_1Mx1M_30it" (the configuration the metric is quoted on).
 N > 1 : BASELINE configs[3] — the same single pair, source sharded in N contiguous blocks,
         target replicated, one RCCL all-reduce of 17 doubles per iteration ("strong" scaling).
@@ -70,12 +75,37 @@ def parse():
                     help="chain: pairs registered SIDE BY SIDE on every GPU, each on a context of its own driven by its own thread "
                          "(rsreg_amd/chain.py: ChainRegistrar; the frames are read where they lie, through raw device pointers).  "
                          "0: the rank's pairs one after the other on one context, through cloud handles (rounds 2-5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the CPU port baselines, pipeline 1, the alignment from the identity, "
+                         "events in all steps, host buffers, the reference-mode pair (pair workload); the CPU baseline, the fresh-source "
+                         "steps and the in-flight vs sequential check (chain workload).  Without it only the warm-up and the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float64)")
     a = ap.parse_args()
     if a.size is None and a.workload == "pair":
         a.size = "N1M"
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        a.headline_only = True
     if a.headline_only:
         a.no_cpu_baseline = True
     return a
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (the inputs are seeded: the same arguments, the same inputs)."""
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(v, dtype=np.float64))
+
+
+def icp_result_arrays(res):
+    """What a caller of rsreg_icp_align receives in its IcpResult, timings left out."""
+    from rsreg_amd import api
+
+    return {"transform": api._rowmajor(res.transform), "converged": [res.converged], "state": [res.state], "iterations": [res.iterations],
+            "n_correspondences": [res.n_correspondences], "mse": [res.mse], "sums_last": list(res.sums_last)}
 
 
 def run_chain(a, rank, world, local_rank, dist, coll_dev="cuda"):
@@ -175,13 +205,15 @@ def run_chain(a, rank, world, local_rank, dist, coll_dev="cuda"):
             set_profiling(False)
     sync()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"poses": np.array(poses, np.float64)})
     L.rsreg_icp_grid_info((registrar.contexts[0] if registrar is not None else ctx).h, C.byref(gi))
     # the same step with records the handles have never measured under the SOURCE frames (re-uploaded with the clock stopped): in the
     # timed region above every handle keeps the bounding box an earlier load measured, which a stream of new frames has for its
     # targets (last pair's sources) but never for its sources
-    fresh_s, fresh_n = 0.0, (min(3, a.steps) if registrar is None else 0)   # (raw device pointers carry no measured box: every step is "fresh")
+    fresh_s, fresh_n = 0.0, (min(3, a.steps) if registrar is None and a.full else 0)   # (raw device pointers carry no measured box: every step is "fresh")
     seq_diff = None
-    if registrar is not None:
+    if registrar is not None and a.full:
         # every pair once more, alone and through the cloud handles (the path of rounds 2-5): the bits must be the same
         keep = registrar
         registrar = None
@@ -424,6 +456,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     T_gpu = api._rowmajor(res.transform)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, icp_result_arrays(res))
 
     if rank != 0:
         if dist is not None:

@@ -25,7 +25,7 @@ def run(args, env=None):
 
 
 def test_bench_json_contract():
-    j = run(["bench.py", "--size", "50k", "--steps", "2", "--warmup", "1", "--cpu-iterations", "2"])
+    j = run(["bench.py", "--size", "50k", "--steps", "2", "--warmup", "1", "--cpu-iterations", "2", "--full"])
     for k in REQUIRED:
         assert k in j, k
     assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["vs_baseline"] is None
@@ -37,6 +37,37 @@ def test_bench_json_contract():
     cb = j["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and "sample" in cb
     assert j["transform_error_vs_cpu_frobenius"] < 1e-4          # north-star bar
+    for leg in ("pipeline1_ms_per_step", "convergence_from_identity", "value_with_events_in_all_steps", "host_buffers", "reference_mode"):
+        assert leg in j, leg
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path, rs):
+    """A plain run (no --full) runs the warm-up and the timed steps only; --dump-outputs writes the IcpResult of the last timed
+    step as float64 .npy files, and a second run with the same arguments writes the same arrays (seeded inputs)."""
+    import numpy as np
+
+    names = ("transform", "converged", "state", "iterations", "n_correspondences", "mse", "sums_last")
+    outs = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        j = run(["bench.py", "--size", "50k", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+        assert abs(j["value"] - 50000 * 30 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+        for leg in ("pipeline1_ms_per_step", "convergence_from_identity", "value_with_events_in_all_steps", "host_buffers", "reference_mode",
+                    "cpu_baseline", "cpu_baseline_all_cores", "transform_error_vs_cpu_frobenius"):
+            assert leg not in j, leg
+        assert sorted(p.name for p in d.iterdir()) == sorted(n + ".npy" for n in names)
+        arr = {n: np.load(str(d / (n + ".npy"))) for n in names}
+        assert all(a.dtype == np.float64 for a in arr.values())
+        assert arr["transform"].shape == (4, 4) and arr["sums_last"].shape == (17,) and arr["iterations"][0] == 30
+        assert arr["n_correspondences"][0] > 0 and np.isfinite(arr["mse"][0])
+        err = float(np.linalg.norm(arr["transform"] - rs.synth.ground_truth(1, 0, "bench")))
+        assert abs(err - j["transform_error_vs_ground_truth_frobenius"]) < 1e-6
+        outs.append(arr)
+    for n in ("converged", "state", "iterations", "n_correspondences"):
+        np.testing.assert_array_equal(outs[0][n], outs[1][n])
+    for n in ("transform", "mse", "sums_last"):
+        np.testing.assert_allclose(outs[0][n], outs[1][n], rtol=1e-6, atol=1e-9)
 
 
 def test_bench_headline_only_runs_nothing_but_the_headline():
@@ -85,9 +116,9 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     assert r.returncode != 0 and not [l for l in r.stdout.split("\n") if l.startswith("{")]
 
 
-def test_bench_chain_workload():
+def test_bench_chain_workload(tmp_path, rs):
     """BASELINE configs[4] as bench.py runs it: consecutive pairs, one per GPU at a time, frames resident in HBM."""
-    j = run(["bench.py", "--workload", "chain", "--size", "50k", "--steps", "2", "--warmup", "1", "--cpu-iterations", "2"])
+    j = run(["bench.py", "--workload", "chain", "--size", "50k", "--steps", "2", "--warmup", "1", "--cpu-iterations", "2", "--full"])
     for k in REQUIRED:
         assert k in j, k
     assert j["scaling"] == "weak" and j["n_gpus"] == 1 and j["config"]["n_frames"] == 2 and j["config"]["pairs"] == 1
@@ -95,8 +126,14 @@ def test_bench_chain_workload():
     assert j["chain_pose_error_vs_ground_truth_frobenius_max"] < 0.05
     j2 = run(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port",
               str(29900 + os.getpid() % 90), "bench.py", "--gpus", "1", "--workload", "chain", "--size", "50k", "--steps", "2", "--warmup", "1",
-              "--no-cpu-baseline", "--force-dist"])
+              "--no-cpu-baseline", "--force-dist", "--dump-outputs", str(tmp_path / "chain")])
     assert j2["config"]["workload"] == j["config"]["workload"] and j2["value"] > 0
+    import numpy as np
+    poses = np.load(str(tmp_path / "chain" / "poses.npy"))          # the composed chain of the last timed step
+    assert poses.dtype == np.float64 and poses.shape == (2, 4, 4)
+    gt = [np.linalg.inv(rs.synth.frame_pose(0, "bench")) @ rs.synth.frame_pose(k, "bench") for k in range(2)]
+    err = max(float(np.linalg.norm(poses[k] - gt[k])) for k in range(2))
+    assert abs(err - j2["chain_pose_error_vs_ground_truth_frobenius_max"]) < 1e-6
 
 
 def test_device_resident_inputs_match_host_inputs():

@@ -160,7 +160,7 @@ def test_bench_chain_in_flight():
     """`bench.py --workload chain --frames F --in-flight K`: the contract line, config.in_flight, and the bench's own
     cross-check of every pair against the sequential cloud-handle path."""
     r = subprocess.run([sys.executable, "bench.py", "--workload", "chain", "--size", "50k", "--frames", "6", "--in-flight", "3", "--steps", "2",
-                        "--warmup", "1", "--cpu-iterations", "2"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+                        "--warmup", "1", "--cpu-iterations", "2", "--full"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.split("\n") if l.startswith("{")]
     assert len(lines) == 1

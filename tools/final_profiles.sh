@@ -9,7 +9,7 @@ step() { echo "[final_profiles] $1 ($(date +%T))"; }
 PART=${2:-all}   # A: the headline's measurements; B: schemes, chain, cold run; all: both (more than one gpurun call's 20 minutes)
 if [ "$PART" != B ]; then
 step bench
-timeout -k 10 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || { tail -5 $O/bench_n1.err; exit 1; }
 cut -c1-600 $O/bench_n1.json
 step "kernel stats"
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --headline-only > $O/kt.log 2>&1)
@@ -63,12 +63,12 @@ done
 head -12 $O/scheme_kernel_stats.txt
 timeout -k 10 300 python tools/scheme_times.py N300 16 2>&1 | grep -v amdgpu.ids > $O/scheme_times.txt; tail -8 $O/scheme_times.txt
 step "other workloads"
-timeout -k 10 300 python bench.py --workload chain --steps 5 --warmup 1 > $O/bench_chain_n1.json 2> $O/bench_chain.err; cut -c1-300 $O/bench_chain_n1.json
+timeout -k 10 300 python bench.py --workload chain --steps 5 --warmup 1 --full > $O/bench_chain_n1.json 2> $O/bench_chain.err; cut -c1-300 $O/bench_chain_n1.json
 step "chain of 16 frames, K pairs in flight (BASELINE configs[4] on one GPU)"
 : > $O/bench_chain_in_flight.jsonl
-for K in 0 1 2 3 4 6; do timeout -k 10 300 python bench.py --workload chain --size N300 --frames 16 --in-flight $K --steps 10 --warmup 2 --no-cpu-baseline >> $O/bench_chain_in_flight.jsonl 2>> $O/bench_chain.err; done
-for K in 0 1 3 4; do timeout -k 10 300 python bench.py --workload chain --size N1M --frames 8 --in-flight $K --steps 6 --warmup 2 --no-cpu-baseline >> $O/bench_chain_in_flight.jsonl 2>> $O/bench_chain.err; done
-timeout -k 10 300 python bench.py --workload chain --size N300 --frames 16 --in-flight 4 --steps 10 --warmup 2 --cpu-iterations 10 > $O/bench_chain16_k4.json 2>> $O/bench_chain.err
+for K in 0 1 2 3 4 6; do timeout -k 10 300 python bench.py --workload chain --size N300 --frames 16 --in-flight $K --steps 10 --warmup 2 --full --no-cpu-baseline >> $O/bench_chain_in_flight.jsonl 2>> $O/bench_chain.err; done
+for K in 0 1 3 4; do timeout -k 10 300 python bench.py --workload chain --size N1M --frames 8 --in-flight $K --steps 6 --warmup 2 --full --no-cpu-baseline >> $O/bench_chain_in_flight.jsonl 2>> $O/bench_chain.err; done
+timeout -k 10 300 python bench.py --workload chain --size N300 --frames 16 --in-flight 4 --steps 10 --warmup 2 --cpu-iterations 10 --full > $O/bench_chain16_k4.json 2>> $O/bench_chain.err
 python - $O/bench_chain_in_flight.jsonl <<'PY'
 import json, sys
 for l in open(sys.argv[1]):
