@@ -60,14 +60,16 @@ struct Tunables {
 #endif
 };
 
-inline Tunables tunables_from_environment()
+// The one list of the switches: every name is read here through `get` (std::getenv for the values; tunables_signature()
+// passes a getter that also records what it was asked for, so the signature covers exactly the names read here).
+template <typename Get> inline Tunables tunables_read(Get get)
 {
     Tunables v;
-    auto on = [](const char *n) { const char *e = std::getenv(n); return e && e[0] == '1'; };
-    auto off = [](const char *n) { const char *e = std::getenv(n); return e && e[0] == '0'; };
-    auto set = [](const char *n) { return std::getenv(n) != nullptr; };
-    if (const char *e = std::getenv("RSREG_CELL_CAP")) { const double c = std::atof(e); if (c > 0) v.cell_cap = c; }
-    if (const char *e = std::getenv("RSREG_DENSE_MAX_CELLS")) v.dense_max_cells = std::atoll(e);
+    auto on = [&get](const char *n) { const char *e = get(n); return e && e[0] == '1'; };
+    auto off = [&get](const char *n) { const char *e = get(n); return e && e[0] == '0'; };
+    auto set = [&get](const char *n) { return get(n) != nullptr; };
+    if (const char *e = get("RSREG_CELL_CAP")) { const double c = std::atof(e); if (c > 0) v.cell_cap = c; }
+    if (const char *e = get("RSREG_DENSE_MAX_CELLS")) v.dense_max_cells = std::atoll(e);
     if (on("RSREG_FORCE_HASH")) v.dense_max_cells = 0;
     v.keys64 = on("RSREG_KEYS64");
     v.full_table = on("RSREG_FULL_TABLE");
@@ -81,61 +83,55 @@ inline Tunables tunables_from_environment()
     v.one_side_worker = on("RSREG_ONE_SIDE_WORKER");
     v.scan_apart = on("RSREG_SCAN_APART");
     v.sort_small = on("RSREG_SORT_SMALL");
-    if (const char *e = std::getenv("RSREG_PLAIN_SOURCE_MAX")) v.plain_source_max = (size_t)std::atoll(e);
-    if (const char *e = std::getenv("RSREG_MORTON_BITS")) v.morton_bits = std::max(6, std::min(31, std::atoi(e)));
+    if (const char *e = get("RSREG_PLAIN_SOURCE_MAX")) v.plain_source_max = (size_t)std::atoll(e);
+    if (const char *e = get("RSREG_MORTON_BITS")) v.morton_bits = std::max(6, std::min(31, std::atoi(e)));
     v.worker = !on("RSREG_NO_WORKER");
     v.seed = !on("RSREG_NO_SEED");
     v.restart_apart = on("RSREG_RESTART_APART");
     v.scan_target = !set("RSREG_NO_SCAN");
     v.sched = !off("RSREG_SCHED");
-    if (const char *e = std::getenv("RSREG_SCHED_F4")) v.sched_f4 = std::atof(e);
-    if (const char *e = std::getenv("RSREG_SCHED_F2")) v.sched_f2 = std::atof(e);
-    if (const char *e = std::getenv("RSREG_SCHED_MIN_TILES")) v.sched_min_tiles = (uint32_t)std::atoll(e);
-    if (const char *e = std::getenv("RSREG_SCHED_AT")) v.sched_at = std::atoi(e);
+    if (const char *e = get("RSREG_SCHED_F4")) v.sched_f4 = std::atof(e);
+    if (const char *e = get("RSREG_SCHED_F2")) v.sched_f2 = std::atof(e);
+    if (const char *e = get("RSREG_SCHED_MIN_TILES")) v.sched_min_tiles = (uint32_t)std::atoll(e);
+    if (const char *e = get("RSREG_SCHED_AT")) v.sched_at = std::atoi(e);
     v.sched_f4 = std::min(std::max(v.sched_f4, 0.0), 1.0);
     v.sched_f2 = std::min(std::max(v.sched_f2, 0.0), 1.0 - v.sched_f4);   // (every tile at most once: up to 4 workgroups per tile)
     v.sched_xcd = !off("RSREG_SCHED_XCD");
-    if (const char *e = std::getenv("RSREG_SCHED_XCD_DEAL")) v.sched_xcd_deal = (uint32_t)std::atoi(e);
+    if (const char *e = get("RSREG_SCHED_XCD_DEAL")) v.sched_xcd_deal = (uint32_t)std::atoi(e);
     v.sched_keep = !off("RSREG_SCHED_KEEP");
-    if (const char *e = std::getenv("RSREG_CLOUD_POOL_MB")) v.cloud_pool_mb = std::max(0ll, std::atoll(e));
+    if (const char *e = get("RSREG_CLOUD_POOL_MB")) v.cloud_pool_mb = std::max(0ll, std::atoll(e));
     v.upload_wait_staged = on("RSREG_UPLOAD_WAIT_STAGED");
     v.ndt_watch = !set("RSREG_NDT_NO_WATCH");
     v.ndt_one_launch = on("RSREG_NDT_ONE_LAUNCH");
     v.ndt_resident_ls = on("RSREG_NDT_RESIDENT_LS");
 #ifdef RSREG_DIAG
-    v.dump_seed = std::getenv("RSREG_DUMP_SEED");
-    v.wave_times = std::getenv("RSREG_WAVE_TIMES");
-    v.edge_dump = std::getenv("RSREG_EDGE_DUMP");
+    v.dump_seed = get("RSREG_DUMP_SEED");
+    v.wave_times = get("RSREG_WAVE_TIMES");
+    v.edge_dump = get("RSREG_EDGE_DUMP");
     v.wave_times_light = set("RSREG_WAVE_TIMES_LIGHT");
     v.dump_nn_ms = set("RSREG_DUMP_NN_MS");
     v.sched_verbose = set("RSREG_SCHED_VERBOSE");
     v.grid_stats = set("RSREG_GRID_STATS");
-    if (const char *e = std::getenv("RSREG_DEBUG_SKIP")) v.debug_skip = (uint32_t)std::atoi(e);
+    if (const char *e = get("RSREG_DEBUG_SKIP")) v.debug_skip = (uint32_t)std::atoi(e);
 #endif
     return v;
 }
 
+inline Tunables tunables_from_environment() { return tunables_read([](const char *n) { return std::getenv(n); }); }
+
 // What the environment says about every switch above, as one string: two readings are compared by this, not by the bytes
-// of two structs (whose padding is indeterminate).
+// of two structs (whose padding is indeterminate).  The names are the ones tunables_read() asks for, so none can be left out.
 inline std::string tunables_signature()
 {
-    static const char *const names[] = {
-        "RSREG_CELL_CAP", "RSREG_DENSE_MAX_CELLS", "RSREG_FORCE_HASH", "RSREG_KEYS64", "RSREG_FULL_TABLE", "RSREG_FAR_ROWS", "RSREG_NO_WIDE_CELLS",
-        "RSREG_NO_ADAPTIVE_CELL", "RSREG_NO_BOX_CACHE", "RSREG_COUNT_SORT", "RSREG_SCAN_APART", "RSREG_CC_APART", "RSREG_SORT_SMALL",
-        "RSREG_PLAIN_SOURCE_MAX", "RSREG_MORTON_BITS", "RSREG_NO_WORKER", "RSREG_NO_SEED", "RSREG_RESTART_APART", "RSREG_NO_SCAN", "RSREG_SCHED",
-        "RSREG_SCHED_F4", "RSREG_SCHED_F2", "RSREG_SCHED_MIN_TILES", "RSREG_SCHED_AT", "RSREG_SCHED_XCD", "RSREG_SCHED_XCD_DEAL", "RSREG_SCHED_KEEP",
-        "RSREG_CLOUD_POOL_MB", "RSREG_UPLOAD_WAIT_STAGED", "RSREG_NDT_NO_WATCH", "RSREG_NDT_RESIDENT_LS", "RSREG_NDT_ONE_LAUNCH",
-#ifdef RSREG_DIAG
-        "RSREG_DUMP_SEED", "RSREG_WAVE_TIMES", "RSREG_EDGE_DUMP", "RSREG_WAVE_TIMES_LIGHT", "RSREG_DUMP_NN_MS", "RSREG_SCHED_VERBOSE", "RSREG_GRID_STATS",
-        "RSREG_DEBUG_SKIP",
-#endif
-    };
     std::string sig;
-    for (const char *n : names) {
+    (void)tunables_read([&sig](const char *n) {
         const char *e = std::getenv(n);
+        sig += n;
+        sig += '=';
         sig += e ? e : "\x01";
         sig += '\0';
-    }
+        return e;
+    });
     return sig;
 }
 
