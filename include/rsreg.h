@@ -96,13 +96,17 @@ typedef struct rsreg_icp_params {
     /* Optional correspondence filters (both off by default and in rsreg_icp_params_reference: the reference
      * constructs a CorrespondenceRejectorTrimmed and never attaches it, incremental_icp.hpp:38,
      * icp_edge_based_registration.hpp:36, ndt_edge_based_registration.hpp:33).  Either one makes the
-     * iteration run as RSREG_PIPELINE_STAGED. */
+     * iteration run as RSREG_PIPELINE_STAGED.  Both work on original records in the caller's order, also where
+     * the engine merges copies of a point (sources above 65 536 points): every tie goes to the lowest index, and
+     * the trim's cut can keep some copies of a point and drop others.  A context whose communicator has more
+     * than one rank refuses them (RSREG_ERR_INVALID_ARG): a rank holds only its block of the source. */
     int32_t use_reciprocal_correspondences;  /* icp.setUseReciprocalCorrespondences(true): a pair (s, t) is kept only if s
                                                 is also the nearest source point of t (lowest index among equidistant ones) */
     int32_t reserved1;
     double trim_overlap_ratio;               /* CorrespondenceRejectorTrimmed::setOverlapRatio(r), 0 < r < 1: of the gated
-                                                pairs the floor(r * count) closest are kept (equal distances: lowest
-                                                source index first); <= 0 or >= 1: no rejector */
+                                                pairs the floor(r * count) closest are kept, counted per source
+                                                record (equal distances: lowest source index first); <= 0 or >= 1:
+                                                no rejector */
 } rsreg_icp_params;
 
 /*

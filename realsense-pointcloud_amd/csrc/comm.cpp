@@ -108,6 +108,17 @@ int rsreg_comm_init(rsreg_ctx *ctx, const uint8_t id[RSREG_UNIQUE_ID_BYTES], int
     return RSREG_OK;
 }
 
+#ifdef RSREG_DIAG
+// diagnostic builds only: the context counts itself one of `nranks` ranks without a communicator (its sums stay local), so
+// that what a sharded alignment refuses can be checked on a box with one GPU
+extern "C" int rsreg_diag_set_nranks(rsreg_ctx *ctx, int nranks)
+{
+    if (!ctx || nranks < 1 || ctx->comm) return RSREG_ERR_INVALID_ARG;
+    ctx->nranks = nranks;
+    return RSREG_OK;
+}
+#endif
+
 int rsreg_comm_destroy(rsreg_ctx *ctx)
 {
     if (!ctx) return RSREG_ERR_INVALID_ARG;

@@ -1072,32 +1072,40 @@ int apply_filters(rsreg_ctx *ctx)
         }
     }
     if (s.prm.trim_overlap_ratio > 0.0 && s.prm.trim_overlap_ratio < 1.0) {
-        RSREG_HIP(ctx, ctx->d_keys.reserve((size_t)n * 8));
-        RSREG_HIP(ctx, ctx->d_keys_alt.reserve((size_t)n * 8));
-        RSREG_HIP(ctx, ctx->d_vals.reserve((size_t)n * 4));
-        RSREG_HIP(ctx, ctx->d_vals_alt.reserve((size_t)n * 4));
-        uint32_t *keys = ctx->d_keys.as<uint32_t>(), *vals = keys + n, *keys2 = ctx->d_keys_alt.as<uint32_t>(), *order = keys2 + n;
-        uint32_t *ws = ctx->d_vals.as<uint32_t>(), *cum = ctx->d_vals_alt.as<uint32_t>();
-        // (the distances' sort: the library's own, four digit passes that end in the pair they start from -- the keys are
-        // written into the pair that makes that (keys2, order); its state is cleared by the keys kernel on its way)
-        const Radix32Plan plan = radix32_plan(n, 0, 32);
-        const size_t sort_bytes = (size_t)plan.words * 4, scan_bytes = oscan_scratch_bytes<uint32_t>(n);
-        const size_t off_scan = (sort_bytes + 255) & ~(size_t)255;
-        RSREG_HIP(ctx, ctx->d_tmp.reserve(off_scan + scan_bytes + 256));
-        char *tmp = ctx->d_tmp.as<char>();
-        uint32_t *k_a = plan.ends_in_first ? keys2 : keys, *v_a = plan.ends_in_first ? order : vals;
-        uint32_t *k_b = k_a == keys ? keys2 : keys, *v_b = v_a == vals ? order : vals;
-        k_trim_keys<<<nb, kBlock, 0, st>>>(cw, ctx->d_corr_d2.as<float>(), n, k_a, v_a, ctx->d_tmp.as<uint32_t>(), plan.words);
+        // one key per ORIGINAL record, (d2, caller's index): ties at the cut go to the lowest index, also among the copies of
+        // a distinct point on the merged (Morton-ordered) path -- the library's own 64-bit sort over the bits the keys use
+        uint32_t idx_bits = 1;
+        while (idx_bits < 32 && (ns - 1u) >> idx_bits) ++idx_bits;
+        const unsigned sort_bits = 31u + idx_bits;
+        RSREG_HIP(ctx, ctx->d_keys.reserve((size_t)ns * 8));
+        RSREG_HIP(ctx, ctx->d_keys_alt.reserve((size_t)ns * 8));
+        RSREG_HIP(ctx, ctx->d_vals.reserve((size_t)ns * 4));
+        RSREG_HIP(ctx, ctx->d_vals_alt.reserve((size_t)ns * 4));
+        auto *keys = ctx->d_keys.as<unsigned long long>(), *keys2 = ctx->d_keys_alt.as<unsigned long long>();
+        uint32_t *vals = ctx->d_vals.as<uint32_t>(), *vals2 = ctx->d_vals_alt.as<uint32_t>();
+        const Radix32Plan plan = radix32_plan<unsigned long long>(ns, 0, sort_bits);
+        const size_t off_total = ((size_t)plan.words * 4 + 255) & ~(size_t)255;
+        RSREG_HIP(ctx, ctx->d_tmp.reserve(off_total + 256));
+        uint32_t *total = reinterpret_cast<uint32_t *>(ctx->d_tmp.as<char>() + off_total);
+        RSREG_HIP(ctx, hipMemsetAsync(total, 0, 4, st));
+        // (the keys are written into the pair the sort ends in, so that the result lies in (keys2, vals2); its state is
+        // cleared by the keys kernel on its way)
+        const bool start_in_out = plan.ends_in_first;
+        unsigned long long *k_a = start_in_out ? keys2 : keys, *k_b = start_in_out ? keys : keys2;
+        uint32_t *v_a = start_in_out ? vals2 : vals, *v_b = start_in_out ? vals : vals2;
+        const uint32_t nbs = div_up(ns, kBlock);
+        k_trim_keys<<<nbs, kBlock, 0, st>>>(corr_pos, cw, ctx->d_corr_d2.as<float>(), ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(),
+                                            ctx->d_first.as<uint32_t>(), ns, idx_bits, k_a, v_a, ctx->d_tmp.as<uint32_t>(), plan.words);
         RSREG_HIP(ctx, hipGetLastError());
         {
             bool in_first = false;
-            RSREG_HIP(ctx, radix32_sort_pairs<uint32_t>(plan, ctx->d_tmp.as<uint32_t>(), k_a, k_b, v_a, v_b, n, 0, 32, st, &in_first));   // stable: ties by position
-            if ((in_first ? v_a : v_b) != order) return fail(ctx, RSREG_ERR_STATE, "osort: the sorted pairs are not where they belong");
+            RSREG_HIP(ctx, radix32_sort_pairs<unsigned long long>(plan, ctx->d_tmp.as<uint32_t>(), k_a, k_b, v_a, v_b, ns, 0, sort_bits, st, &in_first));
+            if ((in_first ? v_a : v_b) != vals2) return fail(ctx, RSREG_ERR_STATE, "osort: the sorted pairs are not where they belong");
         }
-        k_trim_gather<<<nb, kBlock, 0, st>>>(cw, order, n, ws);
+        k_trim_count<<<nbs, kBlock, 0, st>>>(keys2, ns, idx_bits, total);
         RSREG_HIP(ctx, hipGetLastError());
-        RSREG_HIP(ctx, (oscan<uint32_t, true>(ws, cum, (size_t)n, 0u, tmp + off_scan, st)));
-        k_trim_apply<<<nb, kBlock, 0, st>>>(order, ws, cum, n, (float)s.prm.trim_overlap_ratio, cw, corr_pos);
+        k_trim_apply<<<nbs, kBlock, 0, st>>>(vals2, total, ns, (float)s.prm.trim_overlap_ratio, ctx->d_uniq_of.as<uint32_t>(), ctx->d_first.as<uint32_t>(),
+                                             cw, corr_pos);
         RSREG_HIP(ctx, hipGetLastError());
     }
     return RSREG_OK;
@@ -1972,6 +1980,10 @@ int rsreg_icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *
         return fail(ctx, RSREG_ERR_INVALID_ARG, "bad ICP parameters");
     if (params->max_correspondence_distance > ctx->gate_built_for)
         return fail(ctx, RSREG_ERR_INVALID_ARG, "max_correspondence_distance exceeds the one the target index was built for");
+    // the filters need the whole source: each rank would trim its own block with its own cut and index only its own block for
+    // the reciprocal search, a different answer from one GPU's (a global trim across ranks is not implemented)
+    if (ctx->nranks > 1 && filters_on(*params))
+        return fail(ctx, RSREG_ERR_INVALID_ARG, "reciprocal correspondences and the trimmed rejector need the whole source: not with more than one rank");
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     {
         int rcj = join_source(ctx);

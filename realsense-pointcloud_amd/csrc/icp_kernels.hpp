@@ -1354,38 +1354,54 @@ __global__ __launch_bounds__(kBlock) void k_recip_points(const float4 *cur, cons
     if (j < n_source) out[perm[j]] = cur[uniq_of[j]];
 }
 
-// CorrespondenceRejectorTrimmed: sort keys (squared distance of the matched points, unmatched ones last)
-// (sort_scratch: the state of the sort that follows, cleared on the way -- radix32.hpp)
-__global__ __launch_bounds__(kBlock) void k_trim_keys(const uint32_t *cw, const float *corr_d2, uint32_t n, uint32_t *keys, uint32_t *vals,
-                                                      uint32_t *sort_scratch, uint32_t sort_scratch_words)
-{
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (sort_scratch) radix32_clear(sort_scratch, sort_scratch_words, u, gridDim.x * blockDim.x);
-    if (u >= n) return;
-    keys[u] = cw[u] ? __float_as_uint(corr_d2[u]) : 0xffffffffu;   // (squared distances are >= 0: their bits order like the values)
-    vals[u] = u;
-}
-
-__global__ __launch_bounds__(kBlock) void k_trim_gather(const uint32_t *cw, const uint32_t *order, uint32_t n, uint32_t *ws)
+// CorrespondenceRejectorTrimmed over ORIGINAL records, not distinct points: the spec orders the pairs by (d2, caller's index),
+// and the cut may split the copies of a distinct point and interleave them with other points at the same distance (copies
+// at indices 5 and 900 of A, one of B at 300: keep 5 and 300, drop 900).  Every record j (sorted position) gets the key
+// (d2 bits << idx_bits) | caller's index; records whose copy is not in play (no match, or beyond cw[u]) get d2 bits
+// 0x7fffffff, above every distance.  The copies of u are ordered by caller's index and share d2, so those the cut keeps
+// are the first of u's copies in play: what k_export_corr_w expects of cw[u].
+// (sort_scratch: the state of the sort that follows, cleared on the way -- osort.hpp)
+constexpr uint32_t kTrimOut = 0x7fffffffu;
+__global__ __launch_bounds__(kBlock) void k_trim_keys(const int *corr_pos, const uint32_t *cw, const float *corr_d2, const uint32_t *perm,
+                                                      const uint32_t *uniq_of, const uint32_t *first, uint32_t n_source, uint32_t idx_bits,
+                                                      unsigned long long *keys, uint32_t *vals, uint32_t *sort_scratch, uint32_t sort_scratch_words)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) ws[j] = cw[order[j]];
+    if (sort_scratch) radix32_clear(sort_scratch, sort_scratch_words, j, gridDim.x * blockDim.x);
+    if (j >= n_source) return;
+    const uint32_t u = uniq_of[j];
+    const bool in_play = corr_pos[u] >= 0 && j - first[u] < cw[u];
+    const uint32_t hi = in_play ? __float_as_uint(corr_d2[u]) : kTrimOut;   // (squared distances are >= 0: their bits order like the values)
+    keys[j] = ((unsigned long long)hi << idx_bits) | perm[j];
+    vals[j] = j;
 }
 
-// of the pairs in order of distance, the first floor(ratio * count) are kept; cum = inclusive sums of ws
-__global__ __launch_bounds__(kBlock) void k_trim_apply(const uint32_t *order, const uint32_t *ws, const uint32_t *cum, uint32_t n, float ratio,
-                                                       uint32_t *cw, int *corr_pos)
+// the number of records in play: where the sorted keys leave them (*total: zero before the launch)
+__global__ __launch_bounds__(kBlock) void k_trim_count(const unsigned long long *keys, uint32_t n_source, uint32_t idx_bits, uint32_t *total)
 {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t total = cum[n - 1];
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_source) return;
+    const bool here = (uint32_t)(keys[r] >> idx_bits) != kTrimOut;
+    const bool next = r + 1 < n_source && (uint32_t)(keys[r + 1] >> idx_bits) != kTrimOut;
+    if (here && !next) *total = r + 1;
+}
+
+// of the records in order (d2, caller's index) the first floor(ratio * total) keep their match: every record the cut drops
+// lowers its distinct point's cw to its copy number (the dropped copies of u are the last of those in play), and the point
+// loses its match when its first copy is dropped
+__global__ __launch_bounds__(kBlock) void k_trim_apply(const uint32_t *order, const uint32_t *total_p, uint32_t n_source, float ratio,
+                                                       const uint32_t *uniq_of, const uint32_t *first, uint32_t *cw, int *corr_pos)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_source) return;
+    const uint32_t total = *total_p;
     const uint32_t k = (uint32_t)floorf(ratio * (float)total);   // (int)(floor(overlap_ratio_ * float(size))), in float like PCL
-    if (k >= total) return;                                       // "number_valid >= size": nothing to trim
-    const uint32_t before = cum[j] - ws[j];
-    const uint32_t keep = before >= k ? 0u : min(ws[j], k - before);
-    const uint32_t u = order[j];
-    cw[u] = keep;
-    if (!keep) corr_pos[u] = -1;
+    if (k >= total || r < k || r >= total) return;                // ("number_valid >= size": nothing to trim)
+    const uint32_t j = order[r];
+    const uint32_t u = uniq_of[j];
+    const uint32_t copy = j - first[u];
+    atomicMin(&cw[u], copy);
+    if (copy == 0) corr_pos[u] = -1;
 }
 
 // the sums of k_cov_reduce with the copies-in-play of every pair given explicitly
@@ -1408,6 +1424,7 @@ __global__ __launch_bounds__(kTile) void k_cov_reduce_w(const float4 *cur, const
 }
 
 // determineCorrespondences' list with the filters applied: of the copies of a distinct point the first cw[u] (lowest indices) keep their match
+// (the reciprocal filter keeps the first copy alone, the trim a prefix of the copies in play: k_trim_keys)
 __global__ __launch_bounds__(kBlock) void k_export_corr_w(const int *corr_pos, const float *corr_d2, const uint32_t *cw, const float4 *tgt,
                                                           const uint32_t *perm, const uint32_t *uniq_of, const uint32_t *first, uint32_t n,
                                                           int *index_out, float *d2_out)

@@ -31,6 +31,15 @@ def shard_blocks(n, rank, world, block=256):
     return idx[(idx // block) % world == rank]
 
 
+def filters_on(params):
+    """Whether ICP parameters turn a correspondence filter on: rsreg_icp_params, or a stepper's own with `use_reciprocal`."""
+    if params is None:
+        return False
+    recip = getattr(params, "use_reciprocal_correspondences", getattr(params, "use_reciprocal", 0))
+    ratio = float(getattr(params, "trim_overlap_ratio", 0.0))
+    return bool(recip) or 0.0 < ratio < 1.0
+
+
 def run_sharded_icp(stepper, allreduce, guess=None, max_steps=100000):
     """Drive one ICP alignment whose sums are combined across ranks.
 
@@ -39,7 +48,12 @@ def run_sharded_icp(stepper, allreduce, guess=None, max_steps=100000):
     allreduce : callable(np.ndarray[17] float64) -> the element-wise sum over all ranks.
     Returns the result of stepper.end().  All ranks take the same number of iterations because
     they evaluate the convergence criteria on the same (global) sums.
+    The correspondence filters (reciprocal correspondences, the trimmed rejector) are refused: each rank would filter
+    its own block (its own cut, a reciprocal index of its own points), not what one GPU computes.
     """
+    if filters_on(getattr(stepper, "params", None)):
+        raise ValueError("run_sharded_icp: reciprocal correspondences and the trimmed rejector need the whole source; "
+                         "a sharded alignment cannot use them")
     stepper.begin(guess)
     for _ in range(max_steps):
         stepper.search(False) if getattr(stepper, "_quiet_search", False) else stepper.search()

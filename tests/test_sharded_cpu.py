@@ -126,3 +126,25 @@ def test_two_rank_icp_over_gloo_matches_single_process(tmp_path, orc, rs):
     m0, m1, mref = (np.load(tmp_path / f) for f in ("meta_rank0.npy", "meta_rank1.npy", "meta_ref.npy"))
     np.testing.assert_array_equal(m0, m1)
     np.testing.assert_array_equal(m0, mref)
+
+
+@pytest.mark.parametrize("reciprocal,ratio,refused", [(1, 0.0, True), (0, 0.5, True), (1, 0.7, True), (0, 1.0, False), (0, -0.5, False)])
+def test_sharded_icp_refuses_the_correspondence_filters(orc, rs, reciprocal, ratio, refused):
+    """A rank holds one block of the source: it would trim with its own cut and search reciprocal pairs among its own points
+    only.  run_sharded_icp refuses the filters before the first step; a ratio outside (0, 1) is no filter and runs."""
+    from rsreg_amd import sharded, synth
+    tgt = synth.render_frame(0, "50k", "parity")
+    src = synth.render_frame(1, "50k", "parity")
+    p = orc.IcpParams.default()
+    p.max_iterations, p.criteria_mode, p.max_correspondence_distance = 3, 1, 0.01
+    p.use_reciprocal, p.trim_overlap_ratio = reciprocal, ratio
+    lo, hi = sharded.shard_range(len(src), 0, 2)
+    st = OracleStepper(np.ascontiguousarray(src.points[lo:hi]), tgt.points, p)
+    calls = []
+    st.begin = lambda guess, _b=st.begin: (calls.append("begin"), _b(guess))
+    if refused:
+        with pytest.raises(ValueError, match="whole source"):
+            sharded.run_sharded_icp(st, lambda v: 2 * v)
+        assert calls == []
+    else:
+        assert sharded.run_sharded_icp(st, lambda v: v).iterations >= 1

@@ -197,3 +197,81 @@ def test_ndt_shards_by_source_blocks(rs):
     np.testing.assert_array_equal(a.getFinalTransformation(), whole.getFinalTransformation())
     assert (a.result.iterations, a.result.n_derivative_passes) == (whole.result.iterations, whole.result.n_derivative_passes)
     assert lib.lib().rsreg_comm_destroy(ctx.h) == 0
+
+
+NATIVE_REFUSAL = r'''
+import sys
+sys.path.insert(0, %(root)r)
+import numpy as np
+from rsreg_amd import api, lib, synth
+tgt = synth.render_frame(0, "50k", "parity")
+src = synth.render_frame(1, "50k", "parity")
+
+
+def icp(ctx, recip, ratio, device=False):
+    a = api.IterativeClosestPoint(ctx)
+    a.params = api.icp_params(max_iterations=5, criteria_mode=1, max_correspondence_distance=0.01)
+    a.setUseReciprocalCorrespondences(recip)
+    a.setTrimmedRejectorOverlapRatio(ratio)
+    a.setInputSource(api.DeviceCloud(src, ctx) if device else src)
+    a.setInputTarget(api.DeviceCloud(tgt, ctx) if device else tgt)
+    return a
+
+
+# one of two ranks (the diagnostic build's stand-in for a two-rank communicator on a box with one GPU)
+two = api.Context(0)
+assert lib.lib().rsreg_diag_set_nranks(two.h, 2) == 0
+for recip, ratio in ((1, 0.0), (0, 0.5), (1, 0.5)):
+    for step in ("align", "align-device", "begin"):
+        a = icp(two, recip, ratio, step == "align-device")
+        try:
+            a.begin() if step == "begin" else a.align()
+        except lib.RsregError as e:
+            assert e.status == -1 and "more than one rank" in str(e), e     # RSREG_ERR_INVALID_ARG
+        else:
+            raise AssertionError("filters accepted on two ranks: %%s %%r" %% (step, (recip, ratio)))
+for ratio in (0.0, 1.0):     # no filter: the rank runs
+    icp(two, 0, ratio).align()
+# one rank of a real communicator: the whole source, the filters run and give the single-context answer
+one = api.Context(0)
+one.comm_init(api.comm_unique_id(), 0, 1)
+a, b = icp(one, 1, 0.5), icp(api.Context(0), 1, 0.5)
+a.align()
+b.align()
+assert bytes(a.result.transform) == bytes(b.result.transform) and a.result.n_correspondences == b.result.n_correspondences
+assert lib.lib().rsreg_comm_destroy(one.h) == 0
+print("REFUSED OK")
+'''
+
+
+def test_native_transport_refuses_filters_with_more_than_one_rank(rs):
+    """The native path (Context.comm_init + align): with more than one rank a context holds only its block of the source,
+    so reciprocal correspondences and the trimmed rejector are refused with RSREG_ERR_INVALID_ARG and a message.  Two
+    ranks need two GPUs; the context counts itself one of two through a hook of the diagnostic build (RSREG_DIAG=1 ->
+    librsreg_diag.so, same sources), in a child process.  A one-rank communicator keeps the filters."""
+    import subprocess
+    from rsreg_amd import lib
+    lib.build_diag()
+    env = dict(os.environ, RSREG_DIAG="1")
+    env.pop("RSREG_SO", None)
+    r = subprocess.run([sys.executable, "-c", NATIVE_REFUSAL % {"root": ROOT}], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=600)
+    assert r.returncode == 0 and "REFUSED OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
+@pytest.mark.parametrize("reciprocal,ratio", [(1, 0.0), (0, 0.5)])
+def test_stepwise_transport_refuses_filters(rs, reciprocal, ratio):
+    """run_sharded_icp driving the engine's step-wise form: refused before the first step."""
+    from rsreg_amd import api, lib, sharded, synth
+    lib.build()
+    icp = api.IterativeClosestPoint(api.Context(0))
+    icp.params = api.icp_params(max_iterations=5, criteria_mode=1, max_correspondence_distance=0.01)
+    icp.setUseReciprocalCorrespondences(reciprocal)
+    icp.setTrimmedRejectorOverlapRatio(ratio)
+    src = synth.render_frame(1, "50k", "parity")
+    lo, hi = sharded.shard_range(len(src), 0, 2)
+    icp.setInputSource(np.ascontiguousarray(src.points[lo:hi]))
+    icp.setInputTarget(synth.render_frame(0, "50k", "parity"))
+    with pytest.raises(ValueError, match="whole source"):
+        sharded.run_sharded_icp(icp, lambda v: 2 * v)
+    assert icp.ctx.icp_source_owner is not icp                     # nothing was loaded: begin never ran
