@@ -246,6 +246,24 @@ int rsreg_icp_update(rsreg_ctx *ctx, const double sums[RSREG_NUM_SUMS], float *t
                      int *done);
 int rsreg_icp_end(rsreg_ctx *ctx, rsreg_icp_result *result, void *aligned_out, size_t out_stride);
 
+/* Registration::getFitnessScore(max_range) (PCL 1.9 registration.hpp) after an alignment of this context: the source as it was
+ * handed in -- every record, exact copies once per record, in the caller's order -- moved by the final 4x4 of that alignment
+ * (guess included) with rsreg_transform_cloud's arithmetic; for each finite point the squared float distance d2 to its nearest
+ * finite target point, at ANY distance (not limited by the correspondence gate the target's index was built for); the mean of
+ * the d2 with d2 <= max_range.  *score = that mean, DBL_MAX when no point is in range (not an error); *n_within (nullable) =
+ * how many records were.
+ * PCL's quirk, kept: max_range is compared with the SQUARED distance (`if (nn_dists[0] <= max_range)`), not the distance;
+ * the default of getFitnessScore() is DBL_MAX (everything counts).  Non-finite source points are neither counted nor summed;
+ * the correspondence filters (reciprocal, trimmed) do not apply, as PCL's fitness score ignores rejectors.
+ * Valid after a completed alignment (rsreg_icp_align, _align_records, _align_cloud, rsreg_icp_end) until the next
+ * set_source / set_target, RSREG_ERR_STATE before.  Neither call changes the alignment's index or any later result: the
+ * search runs over an index of its own, built at the first call after a target change.
+ * With a communicator of more than one rank, rsreg_icp_fitness_score all-reduces the two numbers through it (each rank holds a
+ * block of the source); rsreg_icp_fitness_sums never does: sums[0] = this rank's count, sums[1] = its sum of d2 (f64), for
+ * callers that reduce across ranks themselves. */
+int rsreg_icp_fitness_score(rsreg_ctx *ctx, double max_range, double *score, uint64_t *n_within);
+int rsreg_icp_fitness_sums(rsreg_ctx *ctx, double max_range, double sums[2]);
+
 /* Host-only pieces of the iteration, exposed for tests and for callers that run the
  * all-reduce themselves. */
 int rsreg_umeyama_from_sums(const double sums[RSREG_NUM_SUMS], float t_out[16]);
@@ -387,6 +405,11 @@ int rsreg_ndt_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
 int rsreg_ndt_align_device(rsreg_ctx *ctx, const void *d_source, size_t n, size_t stride, int is_dense,
                            const float *guess, const rsreg_ndt_params *params, rsreg_ndt_result *result,
                            void *d_aligned_out);
+/* Registration::getFitnessScore(max_range) of the last rsreg_ndt_align / _align_device / _align_cloud, as
+ * rsreg_icp_fitness_score: PCL scores NDT against a kd-tree over the target's POINTS (not its voxels), which
+ * rsreg_ndt_set_target* keeps for this.  The same squared-range quirk; DBL_MAX when nothing is in range; RSREG_ERR_STATE before
+ * an alignment against the current NDT target. */
+int rsreg_ndt_fitness_score(rsreg_ctx *ctx, double max_range, double *score, uint64_t *n_within);
 
 /* ---- edge features: extract_edge_features (src/edge_extractor.hpp:7-39) -------------------- */
 /* The reference's TwoPhaseRegistrationScheme::extract_features (icp_edge...hpp:21-23, ndt_edge...hpp:18-20).

@@ -26,6 +26,7 @@
 #include <chrono>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <new>
 #include <sstream>
@@ -443,6 +444,18 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
     bool hasConverged() const { return res_.converged != 0; }
     Matrix4f getFinalTransformation() const { return final_; }
     int getConvergenceState() const { return res_.state; }
+    // Registration::getFitnessScore(max_range) of the last align() (host or device clouds): the mean squared distance from every
+    // finite source point at the final pose to its nearest target point, over the points whose SQUARED distance is <= max_range
+    // (PCL's quirk, kept); DBL_MAX when none is.  Throws rsreg::Error before an align() of the current source and target.
+    double getFitnessScore(double max_range = std::numeric_limits<double>::max())
+    {
+        rsreg_ctx *c = ctx_->get();
+        if (source_dirty_ || target_dirty_ || ctx_->icp_source_owner != this || ctx_->icp_target_owner != this)
+            throw Error(RSREG_ERR_STATE, "rsreg: getFitnessScore before align() of the current source and target");
+        double score = 0;
+        check(rsreg_icp_fitness_score(c, max_range, &score, nullptr), c);
+        return score;
+    }
     const rsreg_icp_result &result() const { return res_; }
 
   private:
@@ -485,8 +498,8 @@ template <typename PointSource, typename PointTarget> class NormalDistributionsT
         if (on != pcl_centroids_) target_dirty_ = true;
         pcl_centroids_ = on;
     }
-    void setInputSource(const SourcePtr &cloud) { source_ = cloud; dsource_ = nullptr; }
-    void setInputTarget(const TargetPtr &cloud) { target_ = cloud; dtarget_ = nullptr; target_dirty_ = true; }
+    void setInputSource(const SourcePtr &cloud) { source_ = cloud; dsource_ = nullptr; fit_fresh_ = false; }
+    void setInputTarget(const TargetPtr &cloud) { target_ = cloud; dtarget_ = nullptr; target_dirty_ = true; fit_fresh_ = false; }
 
     void align(PointCloud<PointSource> &output) { align(output, Matrix4f::Identity()); }
     void align(PointCloud<PointSource> &output, const Matrix4f &guess)
@@ -505,10 +518,11 @@ template <typename PointSource, typename PointTarget> class NormalDistributionsT
         check(rsreg_ndt_align(c, source_->points.data(), source_->size(), sizeof(PointSource), source_->is_dense, guess.data(),
                               &prm_, &res_, tmp.points.data(), sizeof(PointSource)), c);
         std::memcpy(final_.m, res_.transform, sizeof(final_.m));
+        fit_fresh_ = true;
         output = std::move(tmp);
     }
-    void setInputSource(const DeviceCloud<PointSource> &cloud) { dsource_ = &cloud; source_.reset(); }
-    void setInputTarget(const DeviceCloud<PointTarget> &cloud) { dtarget_ = &cloud; target_.reset(); target_dirty_ = true; }
+    void setInputSource(const DeviceCloud<PointSource> &cloud) { dsource_ = &cloud; source_.reset(); fit_fresh_ = false; }
+    void setInputTarget(const DeviceCloud<PointTarget> &cloud) { dtarget_ = &cloud; target_.reset(); target_dirty_ = true; fit_fresh_ = false; }
     void align(DeviceCloud<PointSource> &output) { align(output, Matrix4f::Identity()); }
     void align(DeviceCloud<PointSource> &output, const Matrix4f &guess)
     {
@@ -524,10 +538,22 @@ template <typename PointSource, typename PointTarget> class NormalDistributionsT
         }
         check(rsreg_ndt_align_cloud(c, dsource_->handle(), guess.data(), &prm_, &res_, output.handle()), c);
         std::memcpy(final_.m, res_.transform, sizeof(final_.m));
+        fit_fresh_ = true;
     }
     bool hasConverged() const { return res_.converged != 0; }
     Matrix4f getFinalTransformation() const { return final_; }
     double getTransformationProbability() const { return res_.trans_probability; }
+    // Registration::getFitnessScore(max_range) of the last align(), against the target's POINTS as PCL scores NDT; the same
+    // squared-range quirk and DBL_MAX as IterativeClosestPoint::getFitnessScore.  Throws rsreg::Error before an align().
+    double getFitnessScore(double max_range = std::numeric_limits<double>::max())
+    {
+        rsreg_ctx *c = ctx_->get();
+        if (!fit_fresh_ || ctx_->ndt_target_owner != this)
+            throw Error(RSREG_ERR_STATE, "rsreg: getFitnessScore before align() of the current source and target");
+        double score = 0;
+        check(rsreg_ndt_fitness_score(c, max_range, &score, nullptr), c);
+        return score;
+    }
     int getFinalNumIteration() const { return res_.iterations; }
     const rsreg_ndt_result &result() const { return res_; }
 
@@ -541,6 +567,7 @@ template <typename PointSource, typename PointTarget> class NormalDistributionsT
     const DeviceCloud<PointSource> *dsource_ = nullptr;
     const DeviceCloud<PointTarget> *dtarget_ = nullptr;
     bool target_dirty_ = true, pcl_centroids_ = false;
+    bool fit_fresh_ = false;   // the last align() is of the current source and target (getFitnessScore)
     std::pair<uint64_t, uint64_t> target_stamp_{0, 0};   // (id, version) of the device target as loaded
 };
 

@@ -8,6 +8,7 @@ Grid`` (src/icp_edge_based_registration.hpp:47,59-60) and ``pcl::transformPointC
 row/column maths convention; the column-major packing of the ABI is handled here.
 """
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -240,6 +241,12 @@ def ndt_params(reference=False, **kw):
     return p
 
 
+def _own_alignment(reg, owns):
+    """getFitnessScore belongs to the last alignment of THIS object: the context's state may be another object's since."""
+    if reg.result is None or not owns:
+        raise _l.RsregError(_l.RSREG_ERR_STATE, "getFitnessScore before this object's align()")
+
+
 class IterativeClosestPoint:
     """pcl::IterativeClosestPoint<PointXYZRGB, PointXYZRGB> on the MI355X."""
 
@@ -422,6 +429,27 @@ class IterativeClosestPoint:
         self.result = res
         return (res, out) if want_aligned else res
 
+    def getFitnessScore(self, max_range=sys.float_info.max):
+        """Registration::getFitnessScore(max_range) of the last alignment: the mean squared distance from every finite source
+        record at the final pose to its nearest target point, over the records whose SQUARED distance is <= max_range (PCL's
+        quirk: the range is compared with d^2); sys.float_info.max when none is (rsreg_icp_fitness_score).  With a communicator
+        of more than one rank the mean is over all ranks' records."""
+        return self.fitnessScore(max_range)[0]
+
+    def fitnessScore(self, max_range=sys.float_info.max):
+        """(score, records in range) -- getFitnessScore with the count."""
+        _own_alignment(self, self.ctx.icp_source_owner is self and self.ctx.icp_target_owner is self and not self._src_dirty and not self._tgt_dirty)
+        score, nr = C.c_double(0), C.c_uint64(0)
+        _l.check(_l.lib().rsreg_icp_fitness_score(self.ctx.h, float(max_range), C.byref(score), C.byref(nr)), self.ctx.h)
+        return score.value, nr.value
+
+    def fitness_sums(self, max_range=sys.float_info.max):
+        """This rank's (count, sum of d^2) of getFitnessScore, never all-reduced (rsreg_icp_fitness_sums): sharded.py adds them up."""
+        _own_alignment(self, self.ctx.icp_source_owner is self and self.ctx.icp_target_owner is self and not self._src_dirty and not self._tgt_dirty)
+        s = np.zeros(2, np.float64)
+        _l.check(_l.lib().rsreg_icp_fitness_sums(self.ctx.h, float(max_range), s.ctypes.data), self.ctx.h)
+        return s
+
     def grid_info(self):
         gi = _l.GridInfo()
         _l.check(_l.lib().rsreg_icp_grid_info(self.ctx.h, C.byref(gi)), self.ctx.h)
@@ -438,6 +466,7 @@ class NormalDistributionsTransform:
         self._tgt_dirty = True
         self.result = None
         self._pcl_centroids = False
+        self._fit_fresh = False   # the last align() is of the current source and target (getFitnessScore)
 
     def setPclCentroids(self, on):
         """Engine extra: search the voxels by PCL's own centroid arithmetic (a float running sum per voxel in input order,
@@ -469,10 +498,12 @@ class NormalDistributionsTransform:
 
     def setInputSource(self, cloud):
         self._src = cloud
+        self._fit_fresh = False
 
     def setInputTarget(self, cloud):
         self._tgt = cloud
         self._tgt_dirty = True
+        self._fit_fresh = False
 
     def _sync_target(self):
         if self._tgt is None or self._src is None:
@@ -500,6 +531,7 @@ class NormalDistributionsTransform:
             _l.check(_l.lib().rsreg_ndt_align_cloud(self.ctx.h, self._src.h, g.ctypes.data if g is not None else None,
                                                     C.byref(self.params), C.byref(res), out.h), self.ctx.h)
             self.result = res
+            self._fit_fresh = True
             return out
         keep, p, n, s = _records(self._src)
         out = self._src.points.copy() if isinstance(self._src, PointCloud) else np.zeros(n, POINT_DTYPE)
@@ -507,6 +539,7 @@ class NormalDistributionsTransform:
                                           g.ctypes.data if g is not None else None, C.byref(self.params),
                                           C.byref(res), out.ctypes.data, out.dtype.itemsize), self.ctx.h)
         self.result = res
+        self._fit_fresh = True
         src = self._src if isinstance(self._src, PointCloud) else None
         return PointCloud(out, width=src.width if src else n, height=src.height if src else 1,
                           is_dense=src.is_dense if src else False)
@@ -519,6 +552,18 @@ class NormalDistributionsTransform:
 
     def getTransformationProbability(self):
         return self.result.trans_probability
+
+    def getFitnessScore(self, max_range=sys.float_info.max):
+        """Registration::getFitnessScore(max_range) of the last alignment, against the target's POINTS as PCL scores NDT
+        (rsreg_ndt_fitness_score); the squared-range quirk and the sys.float_info.max of IterativeClosestPoint.getFitnessScore."""
+        return self.fitnessScore(max_range)[0]
+
+    def fitnessScore(self, max_range=sys.float_info.max):
+        """(score, records in range) -- getFitnessScore with the count."""
+        _own_alignment(self, self.ctx.ndt_target_owner is self and self._fit_fresh)
+        score, nr = C.c_double(0), C.c_uint64(0)
+        _l.check(_l.lib().rsreg_ndt_fitness_score(self.ctx.h, float(max_range), C.byref(score), C.byref(nr)), self.ctx.h)
+        return score.value, nr.value
 
     def derivatives(self, pose):
         self._sync_target()

@@ -20,6 +20,7 @@
 #include "icp_dense.hpp"
 #include "cellsort.hpp"
 #include "oscan.hpp"
+#include "fitness_kernels.hpp"
 
 using namespace rsreg;
 
@@ -446,6 +447,8 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
 {
     hipStream_t st = ctx->stream;
     ctx->have_target = false;
+    ctx->icp_fit_ok = false;   // (a new target: the fitness score waits for an alignment against it, and its index is rebuilt)
+    ctx->fit_icp.built = false;
     ctx->counts_pending = false;   // (of a build nobody asked the counts of: this one's take their place; cnt_dirty stays as it is)
     ctx->tgt_cloud_id = 0;
     ctx->n_target_raw = n;
@@ -647,6 +650,8 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
 int scan_target(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, double max_dist)
 {
     ctx->have_target = false;
+    ctx->icp_fit_ok = false;
+    ctx->fit_icp.built = false;
     ctx->tgt_cloud_id = 0;
     ctx->n_target_raw = n;
     std::memset(&ctx->grid_info, 0, sizeof(ctx->grid_info));
@@ -912,6 +917,7 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
     RSREG_HIP(ctx, ctx->h_sums.reserve(64 * 8));
     RSREG_HIP(ctx, ctx->d_smisc.reserve((64 + 1024 * 8) * sizeof(uint32_t)));
     RSREG_HIP(ctx, ctx->h_smisc.reserve(64 * sizeof(uint32_t)));
+    ctx->icp_fit_ok = false;   // (a new source: no fitness score until it is aligned)
     ctx->n_source = n;
     ctx->n_work = 0;
     ctx->src_cloud = nullptr;
@@ -1806,7 +1812,8 @@ int rsreg_ctx_destroy(rsreg_ctx *ctx)
                       &ctx->d_misc, &ctx->d_src_raw, &ctx->d_src_all, &ctx->d_uniq_of, &ctx->d_first, &ctx->d_src, &ctx->d_cur, &ctx->d_corr_pos, &ctx->d_corr_d2, &ctx->d_seed,
                       &ctx->d_partials, &ctx->d_sums, &ctx->d_icp_state, &ctx->d_corr_w, &ctx->d_recip_pts, &ctx->d_vox_in, &ctx->d_vox_out, &ctx->d_vox_cent, &ctx->d_ndt_vox, &ctx->d_ndt_src, &ctx->d_ndt_trans,
                       &ctx->d_ndt_partials, &ctx->d_ndt_out, &ctx->d_ndt_ctl, &ctx->d_ndt_seg, &ctx->d_comm, &ctx->d_skeys, &ctx->d_skeys_alt, &ctx->d_svals,
-                      &ctx->d_sflags, &ctx->d_sscan, &ctx->d_stmp, &ctx->d_smisc, &ctx->d_shist, &ctx->d_scan_keys, &ctx->d_cnt, &ctx->d_arrived};
+                      &ctx->d_sflags, &ctx->d_sscan, &ctx->d_stmp, &ctx->d_smisc, &ctx->d_shist, &ctx->d_scan_keys, &ctx->d_cnt, &ctx->d_arrived,
+                      &ctx->d_ndt_tgt, &ctx->d_fit_d2, &ctx->d_fit_partials, &ctx->d_fit_sums};
     if (ctx->stream_h2d) { (void)hipStreamSynchronize(ctx->stream_h2d); (void)hipStreamDestroy(ctx->stream_h2d); }
     ctx->h_stage_src.release();
     ctx->h_stage_tgt.release();
@@ -1819,6 +1826,9 @@ int rsreg_ctx_destroy(rsreg_ctx *ctx)
     ctx->h_stage.release();
     ctx->h_ndt.release();
     ctx->h_ndt_build.release();
+    ctx->h_fit.release();
+    ctx->fit_icp.release();
+    ctx->fit_ndt.release();
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_ndt)
         if (e) (void)hipEventDestroy(e);
@@ -2202,6 +2212,8 @@ int icp_end(rsreg_ctx *ctx, rsreg_icp_result *result, void *aligned_out, size_t 
         }
     }
     s.active = 0;
+    ctx->icp_fit_ok = true;   // getFitnessScore: this alignment's source, final transform and target
+    ctx->icp_fit_t = s.final_t;
     return RSREG_OK;
 }
 }  // namespace
@@ -2353,6 +2365,215 @@ int rsreg_transform_cloud(rsreg_ctx *ctx, const void *in, void *out, size_t n, s
             std::memcpy(dst + i * stride, xyz + 3 * i, 12);
         }
     });
+    return RSREG_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------- getFitnessScore
+namespace rsreg {
+namespace {
+
+// The cell of the fitness index: about four cells per point over the box (at most 2^24 cells, 4 096 along an axis), never so
+// small that the float rounding of a coordinate is a sizeable part of it.  Cells per axis: floor(extent / cell) + 2, rounded up
+// to whole blocks.
+void fit_layout(const float mn[3], const float mx[3], uint32_t nfin, FitIndex &fx)
+{
+    double e[3], emax = 0, big = 0;
+    for (int k = 0; k < 3; ++k) {
+        e[k] = (double)mx[k] - (double)mn[k];
+        emax = std::max(emax, e[k]);
+        big = std::max(big, std::max(std::fabs((double)mn[k]), std::fabs((double)mx[k])));
+    }
+    const double target = std::min(std::max(4.0 * nfin, 64.0), 16777216.0);
+    auto cells_along = [&](int k, double c) { return ((int64_t)std::floor(e[k] / c) + 2 + 3) & ~(int64_t)3; };
+    auto cells_for = [&](double c) { return (double)cells_along(0, c) * (double)cells_along(1, c) * (double)cells_along(2, c); };
+    double lo = std::max(std::max(emax / 4000.0, big * 1e-5), 1e-30);
+    if (emax == 0) lo = std::max(big * 1e-5, 1.0);
+    double cell = lo;
+    if (cells_for(lo) > target) {
+        double hi = std::max(emax, lo) * 2.0;   // (two cells per axis: 64 cells at most)
+        for (int it = 0; it < 100; ++it) {
+            const double mid = std::sqrt(lo * hi);
+            if (cells_for(mid) > target) lo = mid; else hi = mid;
+        }
+        cell = hi;
+    }
+    fx.cell = (float)cell;
+    fx.inv_cell = (float)(1.0 / (double)fx.cell);
+    for (int k = 0; k < 3; ++k) {
+        fx.origin[k] = mn[k];
+        fx.dims[k] = (int)cells_along(k, (double)fx.cell);
+    }
+}
+
+FitDev fit_dev(const FitIndex &fx)
+{
+    FitDev g{};
+    g.ox = fx.origin[0]; g.oy = fx.origin[1]; g.oz = fx.origin[2];
+    g.inv_cell = fx.inv_cell;
+    g.cell = fx.cell;
+    g.dx = fx.n_points ? fx.dims[0] : 0; g.dy = fx.dims[1]; g.dz = fx.dims[2];
+    g.bx = fx.dims[0] >> 2; g.by = fx.dims[1] >> 2; g.bz = fx.dims[2] >> 2;
+    g.mask = fx.d_mask.as<unsigned long long>();
+    g.start = fx.d_start.as<uint32_t>();
+    g.pts = fx.d_pts.as<float4>();
+    return g;
+}
+
+// box (one round trip), counts and occupancy words, prefix sum, scatter: on ctx->stream, into fx's own buffers
+int fit_build(rsreg_ctx *ctx, FitIndex &fx, const float4 *tgt, size_t n)
+{
+    hipStream_t st = ctx->stream;
+    fx.built = false;
+    fx.n_points = 0;
+    fx.dims[0] = fx.dims[1] = fx.dims[2] = 0;
+    RSREG_HIP(ctx, fx.d_box.reserve(64));
+    RSREG_HIP(ctx, ctx->h_fit.reserve(64));
+    uint32_t *h = ctx->h_fit.as<uint32_t>();
+    h[6] = 0;
+    if (n) {
+        RSREG_HIP(ctx, hipMemsetAsync(fx.d_box.ptr, 0xff, 12, st));
+        RSREG_HIP(ctx, hipMemsetAsync(fx.d_box.as<char>() + 12, 0, 20, st));
+        k_fit_bbox<<<std::min<uint32_t>(div_up((uint32_t)n, kBlock), 1024), kBlock, 0, st>>>(tgt, (uint32_t)n, fx.d_box.as<uint32_t>());
+        RSREG_HIP(ctx, hipGetLastError());
+        RSREG_HIP(ctx, hipMemcpyAsync(h, fx.d_box.ptr, 32, hipMemcpyDeviceToHost, st));
+        RSREG_HIP(ctx, hipStreamSynchronize(st));
+    }
+    const uint32_t nfin = h[6];
+    if (nfin == 0) {
+        fx.built = true;
+        return RSREG_OK;
+    }
+    float mn[3], mx[3];
+    for (int k = 0; k < 3; ++k) {
+        mn[k] = ordered_float(h[k]);
+        mx[k] = ordered_float(h[3 + k]);
+    }
+    fit_layout(mn, mx, nfin, fx);
+    fx.n_points = nfin;
+    const size_t blocks = (size_t)(fx.dims[0] >> 2) * (fx.dims[1] >> 2) * (fx.dims[2] >> 2), cells = blocks * 64;
+    const size_t count_bytes_before = fx.d_count.cap;
+    RSREG_HIP(ctx, fx.d_pts.reserve((size_t)nfin * sizeof(float4) + 16));
+    RSREG_HIP(ctx, fx.d_start.reserve((cells + 1) * 4));
+    RSREG_HIP(ctx, fx.d_count.reserve((cells + 1) * 4));
+    RSREG_HIP(ctx, fx.d_mask.reserve(blocks * 8));
+    RSREG_HIP(ctx, fx.d_scan.reserve(oscan_scratch_bytes<uint32_t>(cells + 1)));
+    if (fx.d_count.cap != count_bytes_before || count_bytes_before == 0)   // (a new buffer; an old one is zero after every scatter)
+        RSREG_HIP(ctx, hipMemsetAsync(fx.d_count.ptr, 0, fx.d_count.cap, st));
+    RSREG_HIP(ctx, hipMemsetAsync(fx.d_mask.ptr, 0, blocks * 8, st));
+    const FitDev g = fit_dev(fx);
+    uint32_t *count = fx.d_count.as<uint32_t>(), *start = fx.d_start.as<uint32_t>();
+    k_fit_count<<<div_up((uint32_t)n, kBlock), kBlock, 0, st>>>(tgt, (uint32_t)n, g, count, fx.d_mask.as<unsigned long long>());
+    RSREG_HIP(ctx, hipGetLastError());
+    RSREG_HIP(ctx, oscan<uint32_t>(count, start, cells + 1, 0u, fx.d_scan.ptr, st));
+    k_fit_scatter<<<div_up((uint32_t)n, kBlock), kBlock, 0, st>>>(tgt, (uint32_t)n, g, start, count, fx.d_pts.as<float4>());
+    RSREG_HIP(ctx, hipGetLastError());
+    fx.built = true;
+    return RSREG_OK;
+}
+
+// the float bound the search prunes with: never below max_range, so that no d2 with (double)d2 <= max_range is dropped
+float fit_limit2(double max_range)
+{
+    if (!(max_range >= 0)) return -1.0f;   // (negative or NaN: nothing is in range)
+    if (max_range >= (double)FLT_MAX) return __builtin_huge_valf();
+    float f = (float)max_range;
+    if ((double)f < max_range) f = std::nextafter(f, FLT_MAX);
+    return f;
+}
+
+}  // namespace
+
+int fitness_sums(rsreg_ctx *ctx, FitIndex &fx, const float4 *tgt, size_t n_tgt, const float4 *src, const uint32_t *perm, size_t n,
+                 const Mat4f &T, double max_range, double sums[2])
+{
+    hipStream_t st = ctx->stream;
+    if (n_tgt > 0xfffffff0ull || n > 0xfffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
+    if (!fx.built) {
+        int rc = fit_build(ctx, fx, tgt, n_tgt);
+        if (rc) return rc;
+    }
+    sums[0] = sums[1] = 0;
+    if (n == 0) return RSREG_OK;
+    const uint32_t nb = div_up((uint32_t)n, kBlock);
+    RSREG_HIP(ctx, ctx->d_fit_d2.reserve(n * 4 + 16));
+    RSREG_HIP(ctx, ctx->d_fit_partials.reserve((size_t)nb * 2 * 8));
+    RSREG_HIP(ctx, ctx->d_fit_sums.reserve(64));
+    RSREG_HIP(ctx, ctx->h_fit.reserve(64));
+    k_fit_search<<<nb, kBlock, 0, st>>>(src, (uint32_t)n, to_mat34(T), perm, fit_dev(fx), fit_limit2(max_range), max_range,
+                                        ctx->d_fit_d2.as<float>());
+    RSREG_HIP(ctx, hipGetLastError());
+    k_fit_tiles<<<nb, kBlock, 0, st>>>(ctx->d_fit_d2.as<float>(), (uint32_t)n, ctx->d_fit_partials.as<double>());
+    RSREG_HIP(ctx, hipGetLastError());
+    k_final_reduce<<<2, kReduceBlock, 0, st>>>(ctx->d_fit_partials.as<double>(), nb, ctx->d_fit_sums.as<double>());
+    RSREG_HIP(ctx, hipGetLastError());
+    double *h = ctx->h_fit.as<double>();
+    RSREG_HIP(ctx, hipMemcpyAsync(h, ctx->d_fit_sums.ptr, 16, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    sums[0] = h[0];
+    sums[1] = h[1];
+    return RSREG_OK;
+}
+
+}  // namespace rsreg
+
+namespace {
+
+// this rank's (count, sum of d2) of the last ICP alignment (rsreg_icp_fitness_sums / _score)
+int icp_fitness_block(rsreg_ctx *ctx, double max_range, double sums[2])
+{
+    if (!ctx->icp_fit_ok) return fail(ctx, RSREG_ERR_STATE, "no ICP alignment of the current source and target");
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = join_source(ctx);   // (nothing pending after an alignment; kept for the contract: the source's buffers are final)
+    if (rc) return rc;
+    rc = target_counts(ctx, true);   // (grid.n_points of a counting build nobody has waited for is only a bound)
+    if (rc) return rc;
+    const size_t n_tgt = ctx->grid.dense == 2 ? ctx->n_target_raw : ctx->grid.n_points;
+    return fitness_sums(ctx, ctx->fit_icp, ctx->d_tgt_sorted.as<float4>(), n_tgt, ctx->d_src_all.as<float4>(), ctx->d_perm.as<uint32_t>(),
+                        ctx->n_source, ctx->icp_fit_t, max_range, sums);
+}
+
+void fitness_result(const double sums[2], double *score, uint64_t *n_within)
+{
+    if (score) *score = sums[0] > 0 ? sums[1] / sums[0] : DBL_MAX;
+    if (n_within) *n_within = (uint64_t)sums[0];
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsreg_icp_fitness_sums(rsreg_ctx *ctx, double max_range, double sums[2])
+{
+    if (!ctx || !sums) return RSREG_ERR_INVALID_ARG;
+    return icp_fitness_block(ctx, max_range, sums);
+}
+
+int rsreg_icp_fitness_score(rsreg_ctx *ctx, double max_range, double *score, uint64_t *n_within)
+{
+    if (!ctx) return RSREG_ERR_INVALID_ARG;
+    double sums[2];
+    int rc = icp_fitness_block(ctx, max_range, sums);
+    if (rc) return rc;
+    if (ctx->nranks > 1) {   // (the same way as the 17 sums: every rank holds a block of the source)
+        rc = rsreg_comm_allreduce_f64(ctx, sums, 2);
+        if (rc) return rc;
+    }
+    fitness_result(sums, score, n_within);
+    return RSREG_OK;
+}
+
+int rsreg_ndt_fitness_score(rsreg_ctx *ctx, double max_range, double *score, uint64_t *n_within)
+{
+    if (!ctx) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->ndt_fit_ok) return fail(ctx, RSREG_ERR_STATE, "no NDT alignment against the current NDT target");
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    double sums[2];
+    int rc = fitness_sums(ctx, ctx->fit_ndt, ctx->d_ndt_tgt.as<float4>(), ctx->ndt_tgt_n, ctx->d_ndt_src.as<float4>(), nullptr, ctx->ndt_fit_n,
+                          ctx->ndt_fit_t, max_range, sums);
+    if (rc) return rc;
+    fitness_result(sums, score, n_within);
     return RSREG_OK;
 }
 

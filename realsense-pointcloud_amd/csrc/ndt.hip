@@ -334,6 +334,7 @@ int step_length(NdtRun &r, const double *x, double *dir, double step_init, doubl
 
 int load_ndt_source_device(rsreg_ctx *ctx, const void *d_source, size_t n, size_t stride)
 {
+    ctx->ndt_fit_ok = false;   // (d_ndt_src is about to change: no fitness score until an alignment of it)
     RSREG_HIP(ctx, ctx->d_ndt_trans.reserve(n * 12 + 16));
     RSREG_HIP(ctx, ctx->d_ndt_src.reserve((n + 1) * sizeof(float4)));
     RSREG_HIP(ctx, reserve_partials(ctx));
@@ -349,6 +350,7 @@ int load_ndt_source_device(rsreg_ctx *ctx, const void *d_source, size_t n, size_
 
 int load_ndt_source(rsreg_ctx *ctx, const void *source, size_t n, size_t stride)
 {
+    ctx->ndt_fit_ok = false;   // (d_ndt_src is about to change: no fitness score until an alignment of it)
     int rc_pack = pack_to_stage(ctx, source, n, stride);
     if (rc_pack) return rc_pack;
     RSREG_HIP(ctx, ctx->d_ndt_trans.reserve(n * 12 + 16));
@@ -406,6 +408,17 @@ int rsreg_ndt_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
     ctx->ndt_mean_cov_icov.clear();
     ctx->ndt_counts.clear();
     ctx->ndt_centroid.clear();
+    // the fitness score's view of the target: its points, one packed copy (the leaf sort below reuses the shared scratch)
+    ctx->ndt_fit_ok = false;
+    ctx->fit_ndt.built = false;
+    ctx->ndt_tgt_n = 0;
+    RSREG_HIP(ctx, ctx->d_ndt_tgt.reserve((n + 1) * sizeof(float4)));
+    if (n) {
+        k_ndt_keep_target<<<div_up((uint32_t)n, kNdtBlock), kNdtBlock, 0, st>>>(static_cast<const char *>(d_points), stride, (uint32_t)n,
+                                                                                ctx->d_ndt_tgt.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    ctx->ndt_tgt_n = n;
 
     // ---- bounding box of the finite points (pcl::getMinMax3D)
     RSREG_HIP(ctx, ctx->d_misc.reserve(64 * 4));
@@ -742,6 +755,9 @@ int ndt_align_loaded(rsreg_ctx *ctx, size_t n, const float *guess, const rsreg_n
         result->ms_derivatives = r.ms_derivatives;
         result->ms_total = r.ms_derivatives;
     }
+    ctx->ndt_fit_ok = true;   // getFitnessScore: d_ndt_src as loaded, the final transform, the target's points
+    ctx->ndt_fit_t = r.final_t;
+    ctx->ndt_fit_n = n;
     return RSREG_OK;
 }
 

@@ -647,6 +647,17 @@ __global__ __launch_bounds__(kNdtBlock) void k_ndt_load_source(const char *raw, 
     src[i] = make_float4(x, y, z, ndt_finite3(x, y, z) ? 1.0f : 0.0f);
 }
 
+// NDT's copy of its target's points for the fitness score (PCL scores NDT against a kd-tree over the target's points, not its
+// voxels): every record as (x, y, index, z), a non-finite one with x = +inf (the fitness index skips it)
+__global__ __launch_bounds__(kNdtBlock) void k_ndt_keep_target(const char *raw, size_t stride, uint32_t n, float4 *out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = reinterpret_cast<const float *>(raw + (size_t)i * stride);
+    const float x = p[0], y = p[1], z = p[2];
+    out[i] = ndt_finite3(x, y, z) ? tgt_rec(x, y, z, i) : tgt_rec(__uint_as_float(0x7f800000u), 0.0f, 0.0f, i);
+}
+
 // the aligned cloud of ndt.align() as records in HBM: the source record, xyz at the last evaluated pose
 // (a non-finite point keeps its coordinates), data[3] = 1; in and out may be the same array
 __global__ __launch_bounds__(kNdtBlock) void k_ndt_write_aligned(const char *in, size_t stride, uint32_t n, const float *xyz, char *out)

@@ -171,6 +171,29 @@ struct BrickEntry {          // 32 B, one hash-table slot
     uint32_t pad[3];
 };
 
+// Exact nearest-neighbour index over a target's points for Registration::getFitnessScore at ANY range (fitness_kernels.hpp,
+// DESIGN.md §4, getFitnessScore).  A dense grid of 4x4x4-cell blocks with one occupancy word each; cells are numbered
+// block-major, so a block's 64 cell starts are contiguous.  Built lazily, by the first fitness call after a target change, from the target's own records;
+// an instance belongs to one consumer (the ICP target, NDT's target) and shares no buffer with anything else.
+struct FitIndex {
+    bool built = false;
+    float origin[3] = {0, 0, 0};
+    float cell = 1, inv_cell = 1;
+    int dims[3] = {0, 0, 0};       // cells per axis (multiples of 4; 0: no finite point)
+    uint32_t n_points = 0;         // finite points indexed
+    DevBuf d_pts;                  // float4 {x, y, z, 0}, cell by cell
+    DevBuf d_start;                // uint32 per cell + 1: first point of each cell
+    DevBuf d_count;                // uint32 per cell + 1: build scratch, all zero between builds
+    DevBuf d_mask;                 // uint64 per block: which of its 64 cells hold a point
+    DevBuf d_scan;                 // the prefix sum's scratch
+    DevBuf d_box;                  // the box / count of the points (ordered uints)
+    void release()
+    {
+        for (DevBuf *b : {&d_pts, &d_start, &d_count, &d_mask, &d_scan, &d_box}) b->release();
+        built = false;
+    }
+};
+
 struct IcpState {
     rsreg_icp_params prm;
     Mat4f final_t, t_inc;
@@ -349,6 +372,16 @@ struct rsreg_ctx {
     std::vector<float> ndt_centroid;         // 3 per voxel
     rsreg::PinnedBuf h_ndt;
     rsreg::PinnedBuf h_ndt_build;   // the target build's transfers: the voxels' partial moments home, the finished table out (pageable copies cost a frame of the NDT-edge loop 0.1 ms)
+    rsreg::DevBuf d_ndt_tgt;        // float4 (x, y, index, z) of every target record (fitness score: PCL scores NDT against its target POINTS)
+    size_t ndt_tgt_n = 0;
+
+    // ---- getFitnessScore (icp.hip: fitness_sums): valid after a completed alignment, until the next source / target change
+    bool icp_fit_ok = false, ndt_fit_ok = false;
+    rsreg::Mat4f icp_fit_t, ndt_fit_t;   // the final transforms of those alignments
+    size_t ndt_fit_n = 0;                // records of the NDT source (d_ndt_src)
+    rsreg::FitIndex fit_icp, fit_ndt;    // one index per target kind: neither touches the alignment's own index
+    rsreg::DevBuf d_fit_d2, d_fit_partials, d_fit_sums;
+    rsreg::PinnedBuf h_fit;
 
     // ---- RCCL
     // rsreg_ctx_prepare: what a frame loop is about to need, made on a thread of its own while the caller goes on; whoever is
@@ -371,6 +404,13 @@ struct rsreg_ctx {
 namespace rsreg {
 
 void cloud_pool_clear(rsreg_ctx *ctx);   // cloud.hip: frees the buffers kept in ctx->cloud_pool
+
+// icp.hip: getFitnessScore's two numbers, sums[0] = records with a nearest target point at squared distance <= max_range,
+// sums[1] = the sum of those squared distances, over the records src[0 .. n) (float4 {x, y, z, valid}) moved by T.  perm
+// (nullable): record j is the caller's record perm[j] -- the sums run in the caller's order.  `fx` is built from the target
+// records tgt[0 .. n_tgt) (x, y, index, z) if it is not built yet.  On ctx->stream; waits for it.
+int fitness_sums(rsreg_ctx *ctx, FitIndex &fx, const float4 *tgt, size_t n_tgt, const float4 *src, const uint32_t *perm, size_t n,
+                 const Mat4f &T, double max_range, double sums[2]);
 
 inline int fail(rsreg_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess)
 {

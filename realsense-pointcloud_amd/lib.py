@@ -39,6 +39,7 @@ EXPORTS = [
     "rsreg_ndt_align_cloud", "rsreg_ndt_set_target_device", "rsreg_ndt_align_device",
     "rsreg_extract_edge_features", "rsreg_cloud_edge_features", "rsreg_cloud_edge_features_async",
     "rsreg_icp_grid_info", "rsreg_ctx_host_timing", "rsreg_lzf_max_encoded_size", "rsreg_lzf_encode", "rsreg_lzf_decode",
+    "rsreg_icp_fitness_score", "rsreg_icp_fitness_sums", "rsreg_ndt_fitness_score",
 ]
 
 
@@ -232,6 +233,9 @@ def lib():
     L.rsreg_comm_allreduce_f64.argtypes = [vp, vp, i32]
     L.rsreg_icp_grid_info.argtypes = [vp, C.POINTER(GridInfo)]
     L.rsreg_ctx_host_timing.argtypes = [vp, C.POINTER(HostTiming)]
+    L.rsreg_icp_fitness_score.argtypes = [vp, dbl, C.POINTER(dbl), C.POINTER(C.c_uint64)]
+    L.rsreg_icp_fitness_sums.argtypes = [vp, dbl, vp]
+    L.rsreg_ndt_fitness_score.argtypes = [vp, dbl, C.POINTER(dbl), C.POINTER(C.c_uint64)]
     u32 = C.c_uint32
     L.rsreg_cloud_create.argtypes = [vp, C.POINTER(vp)]
     L.rsreg_cloud_destroy.argtypes = [vp]

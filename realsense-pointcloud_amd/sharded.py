@@ -63,3 +63,25 @@ def run_sharded_icp(stepper, allreduce, guess=None, max_steps=100000):
         if done:
             break
     return stepper.end()
+
+
+def sharded_fitness_score(stepper, allreduce, max_range=None):
+    """Registration::getFitnessScore(max_range) of a sharded alignment (after ``run_sharded_icp``): every rank's
+    (count, sum of d^2) over its own source block, element-wise summed by ``allreduce`` as the 17 sums are.
+
+    stepper   : an object with fitness_sums(max_range) -> np.ndarray[2] float64 (this rank's count, sum of d^2): the
+                ``api.IterativeClosestPoint`` that ran this rank's block (rsreg_icp_fitness_sums, never all-reduced).
+    allreduce : callable(np.ndarray[2] float64) -> the element-wise sum over all ranks.
+    max_range : compared with the SQUARED distance, as in PCL; None: unbounded (sys.float_info.max).
+    Returns (score, records in range); the score is sys.float_info.max when no record of any rank is in range.
+    """
+    import sys
+
+    if max_range is None:
+        max_range = sys.float_info.max
+    local = np.ascontiguousarray(stepper.fitness_sums(max_range), np.float64)
+    if local.shape != (2,):
+        raise ValueError("fitness_sums must return two numbers (count, sum of d^2)")
+    total = np.ascontiguousarray(allreduce(local), np.float64)
+    count = int(round(float(total[0])))
+    return (float(total[1]) / float(total[0]) if total[0] > 0 else sys.float_info.max), count
