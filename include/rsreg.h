@@ -385,6 +385,33 @@ int rsreg_cloud_filter_async(rsreg_ctx *ctx, const rsreg_cloud *in, const float 
 int rsreg_cloud_transform(rsreg_ctx *ctx, const rsreg_cloud *in, const float transform[16], rsreg_cloud *out);
 /* PointCloud::operator+ : out = a followed by b (width = size, height = 1, is_dense = both); out may be a or b */
 int rsreg_cloud_concat(rsreg_ctx *ctx, const rsreg_cloud *a, const rsreg_cloud *b, rsreg_cloud *out);
+/* ---- cloud filters: the reference's pre-filter (src/capture.hpp:112-132, filter_pcl: PassThrough on z, then
+ * StatisticalOutlierRemoval with setMeanK(50), setStddevMulThresh(1.5)).  On the context's stream; `out` follows the
+ * versioning rules above (its version changes); in == out allowed.
+ *
+ * pcl::PassThrough (filters/impl/passthrough.hpp, PCL 1.9.1, recalled): field 0 = x, 1 = y, 2 = z.  A record with a non-finite
+ * x, y or z is removed; otherwise it is removed when v < lo || v > hi (negative: when lo <= v <= hi), float compares.  Kept
+ * records keep their order and all their bytes; out: width = kept, height = 1, is_dense = 1.  keep_organized: nothing is
+ * dropped, a removed record gets x = y = z = quiet NaN, width / height are the input's, is_dense = 0 if anything was
+ * removed.  Any other field: RSREG_ERR_INVALID_ARG (PCL warns and returns an empty cloud). */
+int rsreg_cloud_passthrough(rsreg_ctx *ctx, const rsreg_cloud *in, int field, float lo, float hi, int negative,
+                            int keep_organized, rsreg_cloud *out);
+/* pcl::StatisticalOutlierRemoval (filters/impl/statistical_outlier_removal.hpp, recalled) with an EXACT k-nearest-neighbour
+ * search over the finite records: distance = (float)(sum of the mean_k smallest non-self float distances, added in
+ * ascending order in double, / mean_k); a non-finite record has distance 0 and is kept unless `negative`;
+ * threshold = mean + stddev_mult * stddev over the distances (sums over all records, divided by n_valid); a record is
+ * removed when distance > threshold (negative: when distance <= threshold).  out: width = kept, height = 1, is_dense as
+ * the input's.  mean_k: 1 .. 64, RSREG_ERR_INVALID_ARG above (never an approximation); RSREG_ERR_INVALID_ARG too when
+ * the cloud has fewer than mean_k + 1 finite records (PCL reads past its arrays) or fewer than 2 (PCL divides by zero).
+ * Waits for the stream (the number of kept records). */
+typedef struct rsreg_sor_stats {
+    uint64_t n_valid, n_kept;   /* finite records; records in `out` */
+    double mean, stddev, threshold;
+} rsreg_sor_stats;
+int rsreg_cloud_sor(rsreg_ctx *ctx, const rsreg_cloud *in, int mean_k, double stddev_mult, int negative, rsreg_cloud *out,
+                    rsreg_sor_stats *stats /* may be NULL */);
+/* The first pass of rsreg_cloud_sor on its own: host_out[i] = record i's distance (n floats, the caller's record order) */
+int rsreg_cloud_knn_mean_distance(rsreg_ctx *ctx, const rsreg_cloud *in, int mean_k, float *host_out);
 /* icp.setInputTarget / setInputSource / align on handles; aligned_out (nullable, may be the source
  * cloud): the source records with xyz <- final * xyz and data[3] = 1 */
 int rsreg_icp_set_target_cloud(rsreg_ctx *ctx, const rsreg_cloud *cloud, double max_correspondence_distance);

@@ -19,6 +19,7 @@
 
 #include <sys/mman.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -610,6 +611,73 @@ template <typename PointT> class ApproximateVoxelGrid {
     }
   private:
     float leaf_[3] = {1.f, 1.f, 1.f};  // PCL default: IncrementalICP never sets it (incremental_icp.hpp:36)
+    typename PointCloud<PointT>::Ptr input_;
+    std::shared_ptr<Context> ctx_;
+};
+
+// ---- pcl::PassThrough<PointT> for the fields "x", "y" and "z" (csrc/filters.hip, rsreg_cloud_passthrough): the first step of the
+// reference's pre-filter (src/capture.hpp:112-132).  A record with a non-finite coordinate is always removed.  Any other field
+// name throws RSREG_ERR_INVALID_ARG from filter() (PCL warns and returns an empty cloud).  Always on the GPU: the host-cloud
+// form goes through a temporary DeviceCloud.
+template <typename PointT> class PassThrough {
+  public:
+    PassThrough() = default;
+    explicit PassThrough(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {}
+    void setInputCloud(const typename PointCloud<PointT>::Ptr &cloud) { input_ = cloud; }
+    void setFilterFieldName(const std::string &name) { field_ = name; }
+    void setFilterLimits(float lo, float hi) { lo_ = lo; hi_ = hi; }
+    void setNegative(bool negative) { negative_ = negative; }
+    void setFilterLimitsNegative(bool negative) { negative_ = negative; }   // (PCL's older spelling)
+    void setKeepOrganized(bool keep) { keep_organized_ = keep; }
+    void filter(PointCloud<PointT> &output)  // output may be *input
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        DeviceCloud<PointT> tmp(*input_, ctx_ ? ctx_ : Context::Default());
+        filter(tmp, tmp);
+        tmp.download(output);
+    }
+    void filter(const DeviceCloud<PointT> &input, DeviceCloud<PointT> &output)  // output may be the input
+    {
+        const int field = field_ == "x" ? 0 : (field_ == "y" ? 1 : (field_ == "z" ? 2 : -1));
+        check(rsreg_cloud_passthrough(input.context()->get(), input.handle(), field, lo_, hi_, negative_, keep_organized_, output.handle()),
+              input.context()->get());
+    }
+  private:
+    std::string field_;
+    float lo_ = FLT_MIN, hi_ = FLT_MAX;   // PCL's defaults
+    bool negative_ = false, keep_organized_ = false;
+    typename PointCloud<PointT>::Ptr input_;
+    std::shared_ptr<Context> ctx_;
+};
+
+// ---- pcl::StatisticalOutlierRemoval<PointT> with an exact k-nearest-neighbour search on the GPU (csrc/filters.hip,
+// rsreg_cloud_sor): the second step of the reference's pre-filter.  PCL's defaults: mean_k = 1, stddev_mult = 0.
+template <typename PointT> class StatisticalOutlierRemoval {
+  public:
+    StatisticalOutlierRemoval() = default;
+    explicit StatisticalOutlierRemoval(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {}
+    void setInputCloud(const typename PointCloud<PointT>::Ptr &cloud) { input_ = cloud; }
+    void setMeanK(int k) { mean_k_ = k; }
+    void setStddevMulThresh(double m) { stddev_mult_ = m; }
+    void setNegative(bool negative) { negative_ = negative; }
+    void filter(PointCloud<PointT> &output)  // output may be *input
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        DeviceCloud<PointT> tmp(*input_, ctx_ ? ctx_ : Context::Default());
+        filter(tmp, tmp);
+        tmp.download(output);
+    }
+    void filter(const DeviceCloud<PointT> &input, DeviceCloud<PointT> &output)  // output may be the input
+    {
+        check(rsreg_cloud_sor(input.context()->get(), input.handle(), mean_k_, stddev_mult_, negative_, output.handle(), &stats_),
+              input.context()->get());
+    }
+    const rsreg_sor_stats &stats() const { return stats_; }   // engine extra: the last filter()'s mean, stddev and threshold
+  private:
+    int mean_k_ = 1;
+    double stddev_mult_ = 0.0;
+    bool negative_ = false;
+    rsreg_sor_stats stats_{};
     typename PointCloud<PointT>::Ptr input_;
     std::shared_ptr<Context> ctx_;
 };

@@ -203,6 +203,13 @@ class DeviceCloud:
         _l.check(_l.lib().rsreg_cloud_download_async(self.h, out.ctypes.data + offset * POINT_DTYPE.itemsize, n), self.ctx.h)
         return n
 
+    def knn_mean_distance(self, mean_k):
+        """StatisticalOutlierRemoval's first pass on its own (rsreg_cloud_knn_mean_distance): for every record the mean
+        float distance to its mean_k nearest neighbours among the finite records (exact search), 0 for a non-finite record."""
+        out = np.zeros(self.info()[0], np.float32)
+        _l.check(_l.lib().rsreg_cloud_knn_mean_distance(self.ctx.h, self.h, int(mean_k), out.ctypes.data), self.ctx.h)
+        return out
+
     def copy(self):
         out = DeviceCloud(ctx=self.ctx)
         _l.check(_l.lib().rsreg_cloud_copy(self.ctx.h, self.h, out.h), self.ctx.h)
@@ -626,6 +633,96 @@ class ApproximateVoxelGrid:
                                                       self.leaf.ctypes.data, out.ctypes.data, C.byref(n_out)))
         out = out[: n_out.value].copy()
         return PointCloud(out, width=len(out), height=1, is_dense=False)
+
+
+def _filter_io(cloud, ctx, run):
+    """run(in, out) on device clouds: a DeviceCloud goes in as it is, a host PointCloud through a temporary one."""
+    if isinstance(cloud, DeviceCloud):
+        out = DeviceCloud(ctx=cloud.ctx)
+        run(cloud, out)
+        return out
+    tmp = DeviceCloud(cloud, ctx=ctx or default_context())
+    run(tmp, tmp)
+    out = tmp.download()
+    tmp.close()
+    return out
+
+
+class PassThrough:
+    """pcl::PassThrough<PointXYZRGB> on the GPU (csrc/filters.hip, rsreg_cloud_passthrough) for the fields x, y and z.  A
+    record with a non-finite coordinate is always removed.  Any other field name raises (PCL warns and returns an empty
+    cloud)."""
+    FIELDS = {"x": 0, "y": 1, "z": 2}
+
+    def __init__(self, ctx=None):
+        self.field = None
+        self.lo, self.hi = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)   # FLT_MIN, FLT_MAX
+        self.negative = False
+        self.keep_organized = False
+        self._in = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setFilterFieldName(self, name):
+        self.field = name
+
+    def setFilterLimits(self, lo, hi):
+        self.lo, self.hi = float(lo), float(hi)
+
+    def setNegative(self, negative):
+        self.negative = bool(negative)
+
+    setFilterLimitsNegative = setNegative
+
+    def setKeepOrganized(self, keep):
+        self.keep_organized = bool(keep)
+
+    def filter(self):
+        if self.field not in self.FIELDS:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "PassThrough filters on x, y or z, not %r" % (self.field,))
+        field = self.FIELDS[self.field]
+
+        def run(cin, cout):
+            _l.check(_l.lib().rsreg_cloud_passthrough(cin.ctx.h, cin.h, field, self.lo, self.hi, int(self.negative), int(self.keep_organized),
+                                                      cout.h), cin.ctx.h)
+        return _filter_io(self._in, self.ctx, run)
+
+
+class StatisticalOutlierRemoval:
+    """pcl::StatisticalOutlierRemoval<PointXYZRGB> on the GPU with an exact k-nearest-neighbour search (csrc/filters.hip,
+    rsreg_cloud_sor).  PCL's defaults: mean_k = 1, stddev_mult = 0.  `stats` holds the last call's rsreg_sor_stats."""
+
+    def __init__(self, ctx=None):
+        self.mean_k = 1
+        self.stddev_mult = 0.0
+        self.negative = False
+        self.stats = None
+        self._in = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setMeanK(self, k):
+        self.mean_k = int(k)
+
+    def setStddevMulThresh(self, m):
+        self.stddev_mult = float(m)
+
+    def setNegative(self, negative):
+        self.negative = bool(negative)
+
+    def filter(self):
+        st = _l.SorStats()
+
+        def run(cin, cout):
+            _l.check(_l.lib().rsreg_cloud_sor(cin.ctx.h, cin.h, self.mean_k, self.stddev_mult, int(self.negative), cout.h, C.byref(st)),
+                     cin.ctx.h)
+        out = _filter_io(self._in, self.ctx, run)
+        self.stats = st
+        return out
 
 
 def transformPointCloud(cloud, T, ctx=None):

@@ -1829,6 +1829,7 @@ int rsreg_ctx_destroy(rsreg_ctx *ctx)
     ctx->h_fit.release();
     ctx->fit_icp.release();
     ctx->fit_ndt.release();
+    ctx->knn.release();
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_ndt)
         if (e) (void)hipEventDestroy(e);

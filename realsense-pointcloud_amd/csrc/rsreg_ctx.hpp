@@ -194,6 +194,31 @@ struct FitIndex {
     }
 };
 
+// Exact k-nearest-neighbour index and scratch of the cloud filters (filters.hip, knn_kernels.hpp, DESIGN.md §4, cloud filters): a
+// dense grid of cells over the finite points' box, cells numbered x fastest, so a run of cells along x is ONE run of points.
+// Rebuilt by every call from the cloud it is given; it shares no buffer with the alignment's index or the fitness indices.
+struct KnnIndex {
+    float origin[3] = {0, 0, 0};
+    float cell = 1, inv_cell = 1;
+    int dims[3] = {0, 0, 0};
+    uint32_t n_points = 0;         // finite records indexed
+    DevBuf d_pts;                  // float4 {x, y, z, bits(record index)}, cell by cell
+    DevBuf d_start;                // uint32 per cell + 1: first point of each cell
+    DevBuf d_count;                // uint32 per cell + 1: build scratch, all zero between builds
+    DevBuf d_scan;                 // the prefix sums' scratch
+    DevBuf d_box;                  // the box / count of the finite points (ordered uints)
+    DevBuf d_dist;                 // float per record: its mean distance to its mean_k nearest neighbours
+    DevBuf d_flags, d_pos;         // uint32 per record: keep flag, position among the kept
+    DevBuf d_sums;                 // the threshold's two f64 sums
+    DevBuf d_out;                  // the kept records, before the output cloud takes them
+    PinnedBuf host;
+    void release()
+    {
+        for (DevBuf *b : {&d_pts, &d_start, &d_count, &d_scan, &d_box, &d_dist, &d_flags, &d_pos, &d_sums, &d_out}) b->release();
+        host.release();
+    }
+};
+
 struct IcpState {
     rsreg_icp_params prm;
     Mat4f final_t, t_inc;
@@ -399,6 +424,9 @@ struct rsreg_ctx {
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
     std::vector<std::pair<size_t, size_t>> ev_nn, ev_reduce, ev_transform, ev_allreduce;
+
+    // ---- PassThrough / StatisticalOutlierRemoval (filters.hip): index and scratch of their own (last: nothing above moves)
+    rsreg::KnnIndex knn;
 };
 
 namespace rsreg {

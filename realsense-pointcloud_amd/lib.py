@@ -16,7 +16,7 @@ ROOT = os.path.dirname(_HERE)
 DIAG = os.environ.get("RSREG_DIAG", "") == "1"
 SO_PATH = (os.environ.get("RSREG_SO") if DIAG else None) or os.path.join(_HERE, "librsreg_diag.so" if DIAG else "librsreg.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip"]
+SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) if os.path.isdir(CSRC) else []
 NUM_SUMS = 17
 RSREG_ERR_INVALID_ARG, RSREG_ERR_STATE = -1, -9   # include/rsreg.h: rsreg_status
@@ -40,6 +40,7 @@ EXPORTS = [
     "rsreg_extract_edge_features", "rsreg_cloud_edge_features", "rsreg_cloud_edge_features_async",
     "rsreg_icp_grid_info", "rsreg_ctx_host_timing", "rsreg_lzf_max_encoded_size", "rsreg_lzf_encode", "rsreg_lzf_decode",
     "rsreg_icp_fitness_score", "rsreg_icp_fitness_sums", "rsreg_ndt_fitness_score",
+    "rsreg_cloud_passthrough", "rsreg_cloud_sor", "rsreg_cloud_knn_mean_distance",
 ]
 
 
@@ -74,6 +75,10 @@ class IcpResult(C.Structure):
         ("ms_nn", C.c_double), ("ms_reduce", C.c_double), ("ms_transform", C.c_double),
         ("n_nn_launches", C.c_int32), ("n_scheduled_launches", C.c_int32), ("ms_allreduce", C.c_double),
     ]
+
+
+class SorStats(C.Structure):   # rsreg_sor_stats
+    _fields_ = [("n_valid", C.c_uint64), ("n_kept", C.c_uint64), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
 
 
 class NdtResult(C.Structure):
@@ -253,6 +258,9 @@ def lib():
     L.rsreg_cloud_filter.argtypes = [vp, vp, vp, vp]
     L.rsreg_cloud_filter_async.argtypes = [vp, vp, vp, vp]
     L.rsreg_cloud_transform.argtypes = [vp, vp, vp, vp]
+    L.rsreg_cloud_passthrough.argtypes = [vp, vp, i32, C.c_float, C.c_float, i32, i32, vp]
+    L.rsreg_cloud_sor.argtypes = [vp, vp, i32, dbl, i32, vp, C.POINTER(SorStats)]
+    L.rsreg_cloud_knn_mean_distance.argtypes = [vp, vp, i32, vp]
     L.rsreg_cloud_concat.argtypes = [vp, vp, vp, vp]
     L.rsreg_icp_set_target_cloud.argtypes = [vp, vp, dbl]
     L.rsreg_icp_target_is_cloud.argtypes = [vp, vp, dbl]
