@@ -1,61 +1,34 @@
 // fitness_kernels.hpp — device code of Registration::getFitnessScore (include/rsreg.h: rsreg_icp_fitness_score,
-// rsreg_ndt_fitness_score).  Included by icp.hip only, after icp_kernels.hpp (l2_simple, cell_pos, axis_gap, wave_sum).
+// rsreg_ndt_fitness_score): the search and the sums.  Included by icp.hip only (icp_kernels.hpp: wave_sum); the index itself,
+// its build and the bounds the search prunes with are pointgrid.hpp's.
 //
 // PCL 1.9 (registration.hpp):
 //   transformPointCloud(*input_, input_transformed, final_transformation_);
 //   for each point: tree_->nearestKSearch(point, 1, ...); if (nn_dists[0] <= max_range) { fitness_score += nn_dists[0]; ++nr; }
 //   return nr > 0 ? fitness_score / nr : DBL_MAX;
 //
-// The index (rsreg_ctx.hpp: FitIndex, DESIGN.md §4, getFitnessScore) is a dense grid of 4x4x4-cell blocks over the target's box: one 64-bit
-// occupancy word per block, the cells' starts numbered block-major.  A search walks shells of BLOCKS around the query's block
+// The index (rsreg_ctx.hpp: PointGrid, built with FitGridPolicy) is a dense grid of 4x4x4-cell blocks over the target's box:
+// one 64-bit occupancy word per block, the cells' starts numbered block-major.  A search walks shells of BLOCKS around the query's block
 // (clamped into the grid), skips empty blocks on their word and cells on a lower bound, and stops when the six slabs beyond
 // the last shell are all farther than the best distance found (or the range).  Nothing bounds the walk but that test: the
 // result is the exact nearest float distance at any range, for queries inside the box or far outside it.
 #pragma once
 
 #include "icp_kernels.hpp"
+#include "pointgrid.hpp"
 
 namespace rsreg {
 
-struct FitDev {
-    float ox, oy, oz, inv_cell, cell;
-    int dx, dy, dz;                   // cells per axis (multiples of 4; dx == 0: no point)
-    int bx, by, bz;                   // blocks per axis
-    const unsigned long long *mask;   // per block: occupied cells, bit = lz*16 + ly*4 + lx
-    const uint32_t *start;            // per cell, block-major, + 1: first point of the cell
-    const float4 *pts;                // {x, y, z, 0}, cell by cell
-};
-
-__device__ __forceinline__ int fit_axis_cell(float p, float origin, float inv_cell, int d)
-{
-    const float v = fminf(fmaxf(floorf(cell_pos(p, origin, inv_cell)), 0.0f), (float)(d - 1));
-    return (int)v;
-}
-
-__device__ __forceinline__ uint32_t fit_block_id(const FitDev &g, int bx, int by, int bz)
-{
-    return ((uint32_t)bz * (uint32_t)g.by + (uint32_t)by) * (uint32_t)g.bx + (uint32_t)bx;
-}
-
-// A lower bound on the squared float distance to anything beyond the per-axis gaps (cells).  axis_gap's kCellMargin covers the
-// rounding of the cell assignment inside the grid (4 096 cells at most along an axis: 1e-3 cells); the relative factor covers
-// what grows with the distance -- the rounding of (q - origin) * inv_cell for a query far outside the grid (3 ulp), that of
-// this sum (4 ulp) and of cell * cell against 1 / inv_cell (2 ulp), and l2_simple's own (5 ulp): 14 ulp of 2^-24, 1e-6 < 4e-6.
-__device__ __forceinline__ float fit_lb2(float gx, float gy, float gz, float cell2)
-{
-    return (gx * gx + gy * gy + gz * gz) * cell2 * 0.999996f;
-}
-
-__device__ __forceinline__ void fit_visit_block(const FitDev &g, int bx, int by, int bz, float ux, float uy, float uz, float cell2,
+__device__ __forceinline__ void fit_visit_block(const PointGridDev &g, int bx, int by, int bz, float ux, float uy, float uz, float cell2,
                                                 float qx, float qy, float qz, float &best, float &limit2)
 {
-    const uint32_t b = fit_block_id(g, bx, by, bz);
+    const uint32_t b = grid_block_id(g, bx, by, bz);
     unsigned long long m = g.mask[b];
     while (m) {
         const int bit = __ffsll((long long)m) - 1;
         m &= m - 1;
         const int x = (bx << 2) | (bit & 3), y = (by << 2) | ((bit >> 2) & 3), z = (bz << 2) | (bit >> 4);
-        if (fit_lb2(axis_gap(ux, x, x), axis_gap(uy, y, y), axis_gap(uz, z, z), cell2) > limit2) continue;
+        if (grid_lb2(axis_gap(ux, x, x), axis_gap(uy, y, y), axis_gap(uz, z, z), cell2) > limit2) continue;
         const uint32_t c = b * 64u + (uint32_t)bit;
         const uint32_t e = g.start[c + 1];
         for (uint32_t p = g.start[c]; p < e; ++p) {
@@ -68,13 +41,13 @@ __device__ __forceinline__ void fit_visit_block(const FitDev &g, int bx, int by,
 
 // The nearest squared float distance from q to the indexed points (+inf: none within limit2).  limit2: nothing farther is wanted
 // (+inf: unbounded).  Every cell that could hold a point at least as close as the best so far is opened.
-__device__ __forceinline__ float fit_nearest(const FitDev &g, float qx, float qy, float qz, float limit2)
+__device__ __forceinline__ float fit_nearest(const PointGridDev &g, float qx, float qy, float qz, float limit2)
 {
     float best = __int_as_float(0x7f800000);
     if (g.dx <= 0) return best;
     const float ux = cell_pos(qx, g.ox, g.inv_cell), uy = cell_pos(qy, g.oy, g.inv_cell), uz = cell_pos(qz, g.oz, g.inv_cell);
-    const int qbx = fit_axis_cell(qx, g.ox, g.inv_cell, g.dx) >> 2, qby = fit_axis_cell(qy, g.oy, g.inv_cell, g.dy) >> 2,
-              qbz = fit_axis_cell(qz, g.oz, g.inv_cell, g.dz) >> 2;
+    const int qbx = axis_cell(qx, g.ox, g.inv_cell, g.dx) >> 2, qby = axis_cell(qy, g.oy, g.inv_cell, g.dy) >> 2,
+              qbz = axis_cell(qz, g.oz, g.inv_cell, g.dz) >> 2;
     const float cell2 = g.cell * g.cell;
     // gaps to the whole grid along each axis: what a slab beyond a shell is at least away along the other two
     const float hx = axis_gap(ux, 0, g.dx - 1), hy = axis_gap(uy, 0, g.dy - 1), hz = axis_gap(uz, 0, g.dz - 1);
@@ -84,107 +57,37 @@ __device__ __forceinline__ float fit_nearest(const FitDev &g, float qx, float qy
         const int y0 = max(qby - rb, 0), y1 = min(qby + rb, g.by - 1);
         for (int bz = z0; bz <= z1; ++bz) {
             const float gz = axis_gap(uz, bz << 2, (bz << 2) + 3);
-            if (fit_lb2(0.0f, 0.0f, gz, cell2) > limit2) continue;
+            if (grid_lb2(0.0f, 0.0f, gz, cell2) > limit2) continue;
             for (int by = y0; by <= y1; ++by) {
                 const float gy = axis_gap(uy, by << 2, (by << 2) + 3);
-                if (fit_lb2(0.0f, gy, gz, cell2) > limit2) continue;
+                if (grid_lb2(0.0f, gy, gz, cell2) > limit2) continue;
                 const bool face = abs(bz - qbz) == rb || abs(by - qby) == rb;   // a face row: every block of it; else its two ends
                 const int xa = qbx - rb, xb = qbx + rb;
                 for (int bx = face ? max(xa, 0) : xa; bx <= (face ? min(xb, g.bx - 1) : xb); bx += face ? 1 : max(2 * rb, 1)) {
                     if (bx < 0 || bx >= g.bx) continue;
                     const float gx = axis_gap(ux, bx << 2, (bx << 2) + 3);
-                    if (fit_lb2(gx, gy, gz, cell2) > limit2) continue;
+                    if (grid_lb2(gx, gy, gz, cell2) > limit2) continue;
                     fit_visit_block(g, bx, by, bz, ux, uy, uz, cell2, qx, qy, qz, best, limit2);
                 }
             }
         }
         // every block not visited yet lies in one of the six slabs beyond this shell
         float lb = __int_as_float(0x7f800000);
-        if (qbx + rb + 1 < g.bx) lb = fminf(lb, fit_lb2(axis_gap(ux, (qbx + rb + 1) << 2, g.dx - 1), hy, hz, cell2));
-        if (qbx - rb - 1 >= 0) lb = fminf(lb, fit_lb2(axis_gap(ux, 0, ((qbx - rb - 1) << 2) + 3), hy, hz, cell2));
-        if (qby + rb + 1 < g.by) lb = fminf(lb, fit_lb2(hx, axis_gap(uy, (qby + rb + 1) << 2, g.dy - 1), hz, cell2));
-        if (qby - rb - 1 >= 0) lb = fminf(lb, fit_lb2(hx, axis_gap(uy, 0, ((qby - rb - 1) << 2) + 3), hz, cell2));
-        if (qbz + rb + 1 < g.bz) lb = fminf(lb, fit_lb2(hx, hy, axis_gap(uz, (qbz + rb + 1) << 2, g.dz - 1), cell2));
-        if (qbz - rb - 1 >= 0) lb = fminf(lb, fit_lb2(hx, hy, axis_gap(uz, 0, ((qbz - rb - 1) << 2) + 3), cell2));
+        if (qbx + rb + 1 < g.bx) lb = fminf(lb, grid_lb2(axis_gap(ux, (qbx + rb + 1) << 2, g.dx - 1), hy, hz, cell2));
+        if (qbx - rb - 1 >= 0) lb = fminf(lb, grid_lb2(axis_gap(ux, 0, ((qbx - rb - 1) << 2) + 3), hy, hz, cell2));
+        if (qby + rb + 1 < g.by) lb = fminf(lb, grid_lb2(hx, axis_gap(uy, (qby + rb + 1) << 2, g.dy - 1), hz, cell2));
+        if (qby - rb - 1 >= 0) lb = fminf(lb, grid_lb2(hx, axis_gap(uy, 0, ((qby - rb - 1) << 2) + 3), hz, cell2));
+        if (qbz + rb + 1 < g.bz) lb = fminf(lb, grid_lb2(hx, hy, axis_gap(uz, (qbz + rb + 1) << 2, g.dz - 1), cell2));
+        if (qbz - rb - 1 >= 0) lb = fminf(lb, grid_lb2(hx, hy, axis_gap(uz, 0, ((qbz - rb - 1) << 2) + 3), cell2));
         if (lb > limit2) break;
     }
     return best;
 }
 
-// ------------------------------------------------------------------------------ build
-// box[0..2] = min, [3..5] = max (ordered uints), [6] = number of finite points; box = {~0 x 3, 0 x 5} on entry
-__global__ __launch_bounds__(kBlock) void k_fit_bbox(const float4 *pts, uint32_t n, uint32_t *box)
-{
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    uint32_t cnt = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float4 t = pts[i];
-        const float x = t.x, y = t.y, z = tgt_z(t);
-        if (finite3(x, y, z)) {
-            mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
-            mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
-            ++cnt;
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        for (int k = 0; k < 3; ++k) {
-            mn[k] = fminf(mn[k], __shfl_down(mn[k], off));
-            mx[k] = fmaxf(mx[k], __shfl_down(mx[k], off));
-        }
-        cnt += __shfl_down(cnt, off);
-    }
-    if ((threadIdx.x & 63) == 0 && cnt) {
-        for (int k = 0; k < 3; ++k) {
-            atomicMin(&box[k], float_ordered(mn[k]));
-            atomicMax(&box[3 + k], float_ordered(mx[k]));
-        }
-        atomicAdd(&box[6], cnt);
-    }
-}
-
-__device__ __forceinline__ bool fit_point_cell(const FitDev &g, const float4 &t, uint32_t &cell, uint32_t &block, int &bit)
-{
-    const float x = t.x, y = t.y, z = tgt_z(t);
-    if (!finite3(x, y, z)) return false;
-    const int cx = fit_axis_cell(x, g.ox, g.inv_cell, g.dx), cy = fit_axis_cell(y, g.oy, g.inv_cell, g.dy),
-              cz = fit_axis_cell(z, g.oz, g.inv_cell, g.dz);
-    block = fit_block_id(g, cx >> 2, cy >> 2, cz >> 2);
-    bit = (cz & 3) << 4 | (cy & 3) << 2 | (cx & 3);
-    cell = block * 64u + (uint32_t)bit;
-    return true;
-}
-
-// points per cell and the blocks' occupancy words (count and mask zero on entry)
-__global__ __launch_bounds__(kBlock) void k_fit_count(const float4 *pts, uint32_t n, FitDev g, uint32_t *count, unsigned long long *mask)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t c, b;
-    int bit;
-    if (!fit_point_cell(g, pts[i], c, b, bit)) return;
-    atomicAdd(&count[c], 1u);
-    atomicOr(&mask[b], 1ull << bit);
-}
-
-// each finite point to a free place of its cell (start = exclusive prefix of the counts; the counts go back to zero).  The order
-// inside a cell is whatever the atomics make it: only distances are read from the index.
-__global__ __launch_bounds__(kBlock) void k_fit_scatter(const float4 *pts, uint32_t n, FitDev g, const uint32_t *start, uint32_t *count,
-                                                        float4 *sorted)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 t = pts[i];
-    uint32_t c, b;
-    int bit;
-    if (!fit_point_cell(g, t, c, b, bit)) return;
-    const uint32_t k = atomicSub(&count[c], 1u) - 1u;
-    sorted[start[c] + k] = make_float4(t.x, t.y, tgt_z(t), 0.0f);
-}
-
 // ------------------------------------------------------------------------------ score
 // Record j of the source (float4 {x, y, z, valid}) moved by T with k_apply_final's arithmetic, its nearest target distance;
 // out[perm[j]] = that distance if (double)d2 <= max_range, else -1 (not counted: outside the range, or a non-finite point)
-__global__ __launch_bounds__(kBlock) void k_fit_search(const float4 *src, uint32_t n, Mat34 T, const uint32_t *perm, FitDev g, float limit2,
+__global__ __launch_bounds__(kBlock) void k_fit_search(const float4 *src, uint32_t n, Mat34 T, const uint32_t *perm, PointGridDev g, float limit2,
                                                        double max_range, float *out)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;

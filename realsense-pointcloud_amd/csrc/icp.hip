@@ -1830,6 +1830,7 @@ int rsreg_ctx_destroy(rsreg_ctx *ctx)
     ctx->fit_icp.release();
     ctx->fit_ndt.release();
     ctx->knn.release();
+    ctx->filt.release();
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_ndt)
         if (e) (void)hipEventDestroy(e);
@@ -2375,105 +2376,6 @@ int rsreg_transform_cloud(rsreg_ctx *ctx, const void *in, void *out, size_t n, s
 namespace rsreg {
 namespace {
 
-// The cell of the fitness index: about four cells per point over the box (at most 2^24 cells, 4 096 along an axis), never so
-// small that the float rounding of a coordinate is a sizeable part of it.  Cells per axis: floor(extent / cell) + 2, rounded up
-// to whole blocks.
-void fit_layout(const float mn[3], const float mx[3], uint32_t nfin, FitIndex &fx)
-{
-    double e[3], emax = 0, big = 0;
-    for (int k = 0; k < 3; ++k) {
-        e[k] = (double)mx[k] - (double)mn[k];
-        emax = std::max(emax, e[k]);
-        big = std::max(big, std::max(std::fabs((double)mn[k]), std::fabs((double)mx[k])));
-    }
-    const double target = std::min(std::max(4.0 * nfin, 64.0), 16777216.0);
-    auto cells_along = [&](int k, double c) { return ((int64_t)std::floor(e[k] / c) + 2 + 3) & ~(int64_t)3; };
-    auto cells_for = [&](double c) { return (double)cells_along(0, c) * (double)cells_along(1, c) * (double)cells_along(2, c); };
-    double lo = std::max(std::max(emax / 4000.0, big * 1e-5), 1e-30);
-    if (emax == 0) lo = std::max(big * 1e-5, 1.0);
-    double cell = lo;
-    if (cells_for(lo) > target) {
-        double hi = std::max(emax, lo) * 2.0;   // (two cells per axis: 64 cells at most)
-        for (int it = 0; it < 100; ++it) {
-            const double mid = std::sqrt(lo * hi);
-            if (cells_for(mid) > target) lo = mid; else hi = mid;
-        }
-        cell = hi;
-    }
-    fx.cell = (float)cell;
-    fx.inv_cell = (float)(1.0 / (double)fx.cell);
-    for (int k = 0; k < 3; ++k) {
-        fx.origin[k] = mn[k];
-        fx.dims[k] = (int)cells_along(k, (double)fx.cell);
-    }
-}
-
-FitDev fit_dev(const FitIndex &fx)
-{
-    FitDev g{};
-    g.ox = fx.origin[0]; g.oy = fx.origin[1]; g.oz = fx.origin[2];
-    g.inv_cell = fx.inv_cell;
-    g.cell = fx.cell;
-    g.dx = fx.n_points ? fx.dims[0] : 0; g.dy = fx.dims[1]; g.dz = fx.dims[2];
-    g.bx = fx.dims[0] >> 2; g.by = fx.dims[1] >> 2; g.bz = fx.dims[2] >> 2;
-    g.mask = fx.d_mask.as<unsigned long long>();
-    g.start = fx.d_start.as<uint32_t>();
-    g.pts = fx.d_pts.as<float4>();
-    return g;
-}
-
-// box (one round trip), counts and occupancy words, prefix sum, scatter: on ctx->stream, into fx's own buffers
-int fit_build(rsreg_ctx *ctx, FitIndex &fx, const float4 *tgt, size_t n)
-{
-    hipStream_t st = ctx->stream;
-    fx.built = false;
-    fx.n_points = 0;
-    fx.dims[0] = fx.dims[1] = fx.dims[2] = 0;
-    RSREG_HIP(ctx, fx.d_box.reserve(64));
-    RSREG_HIP(ctx, ctx->h_fit.reserve(64));
-    uint32_t *h = ctx->h_fit.as<uint32_t>();
-    h[6] = 0;
-    if (n) {
-        RSREG_HIP(ctx, hipMemsetAsync(fx.d_box.ptr, 0xff, 12, st));
-        RSREG_HIP(ctx, hipMemsetAsync(fx.d_box.as<char>() + 12, 0, 20, st));
-        k_fit_bbox<<<std::min<uint32_t>(div_up((uint32_t)n, kBlock), 1024), kBlock, 0, st>>>(tgt, (uint32_t)n, fx.d_box.as<uint32_t>());
-        RSREG_HIP(ctx, hipGetLastError());
-        RSREG_HIP(ctx, hipMemcpyAsync(h, fx.d_box.ptr, 32, hipMemcpyDeviceToHost, st));
-        RSREG_HIP(ctx, hipStreamSynchronize(st));
-    }
-    const uint32_t nfin = h[6];
-    if (nfin == 0) {
-        fx.built = true;
-        return RSREG_OK;
-    }
-    float mn[3], mx[3];
-    for (int k = 0; k < 3; ++k) {
-        mn[k] = ordered_float(h[k]);
-        mx[k] = ordered_float(h[3 + k]);
-    }
-    fit_layout(mn, mx, nfin, fx);
-    fx.n_points = nfin;
-    const size_t blocks = (size_t)(fx.dims[0] >> 2) * (fx.dims[1] >> 2) * (fx.dims[2] >> 2), cells = blocks * 64;
-    const size_t count_bytes_before = fx.d_count.cap;
-    RSREG_HIP(ctx, fx.d_pts.reserve((size_t)nfin * sizeof(float4) + 16));
-    RSREG_HIP(ctx, fx.d_start.reserve((cells + 1) * 4));
-    RSREG_HIP(ctx, fx.d_count.reserve((cells + 1) * 4));
-    RSREG_HIP(ctx, fx.d_mask.reserve(blocks * 8));
-    RSREG_HIP(ctx, fx.d_scan.reserve(oscan_scratch_bytes<uint32_t>(cells + 1)));
-    if (fx.d_count.cap != count_bytes_before || count_bytes_before == 0)   // (a new buffer; an old one is zero after every scatter)
-        RSREG_HIP(ctx, hipMemsetAsync(fx.d_count.ptr, 0, fx.d_count.cap, st));
-    RSREG_HIP(ctx, hipMemsetAsync(fx.d_mask.ptr, 0, blocks * 8, st));
-    const FitDev g = fit_dev(fx);
-    uint32_t *count = fx.d_count.as<uint32_t>(), *start = fx.d_start.as<uint32_t>();
-    k_fit_count<<<div_up((uint32_t)n, kBlock), kBlock, 0, st>>>(tgt, (uint32_t)n, g, count, fx.d_mask.as<unsigned long long>());
-    RSREG_HIP(ctx, hipGetLastError());
-    RSREG_HIP(ctx, oscan<uint32_t>(count, start, cells + 1, 0u, fx.d_scan.ptr, st));
-    k_fit_scatter<<<div_up((uint32_t)n, kBlock), kBlock, 0, st>>>(tgt, (uint32_t)n, g, start, count, fx.d_pts.as<float4>());
-    RSREG_HIP(ctx, hipGetLastError());
-    fx.built = true;
-    return RSREG_OK;
-}
-
 // the float bound the search prunes with: never below max_range, so that no d2 with (double)d2 <= max_range is dropped
 float fit_limit2(double max_range)
 {
@@ -2486,13 +2388,14 @@ float fit_limit2(double max_range)
 
 }  // namespace
 
-int fitness_sums(rsreg_ctx *ctx, FitIndex &fx, const float4 *tgt, size_t n_tgt, const float4 *src, const uint32_t *perm, size_t n,
+int fitness_sums(rsreg_ctx *ctx, PointGrid &fx, const float4 *tgt, size_t n_tgt, const float4 *src, const uint32_t *perm, size_t n,
                  const Mat4f &T, double max_range, double sums[2])
 {
     hipStream_t st = ctx->stream;
     if (n_tgt > 0xfffffff0ull || n > 0xfffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
-    if (!fx.built) {
-        int rc = fit_build(ctx, fx, tgt, n_tgt);
+    if (!fx.built) {   // box (one round trip), counts and occupancy words, prefix sum, scatter: into fx's own buffers
+        RSREG_HIP(ctx, ctx->h_fit.reserve(64));
+        int rc = grid_build<FitGridPolicy>(ctx, fx, TargetRecords{tgt}, (uint32_t)n_tgt, 1, ctx->h_fit.as<uint32_t>());
         if (rc) return rc;
     }
     sums[0] = sums[1] = 0;
@@ -2502,7 +2405,7 @@ int fitness_sums(rsreg_ctx *ctx, FitIndex &fx, const float4 *tgt, size_t n_tgt, 
     RSREG_HIP(ctx, ctx->d_fit_partials.reserve((size_t)nb * 2 * 8));
     RSREG_HIP(ctx, ctx->d_fit_sums.reserve(64));
     RSREG_HIP(ctx, ctx->h_fit.reserve(64));
-    k_fit_search<<<nb, kBlock, 0, st>>>(src, (uint32_t)n, to_mat34(T), perm, fit_dev(fx), fit_limit2(max_range), max_range,
+    k_fit_search<<<nb, kBlock, 0, st>>>(src, (uint32_t)n, to_mat34(T), perm, grid_dev(fx), fit_limit2(max_range), max_range,
                                         ctx->d_fit_d2.as<float>());
     RSREG_HIP(ctx, hipGetLastError());
     k_fit_tiles<<<nb, kBlock, 0, st>>>(ctx->d_fit_d2.as<float>(), (uint32_t)n, ctx->d_fit_partials.as<double>());

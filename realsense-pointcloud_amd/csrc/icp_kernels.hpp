@@ -33,8 +33,6 @@
 namespace rsreg {
 
 constexpr unsigned long long kEmptyKey = ~0ull;
-constexpr float kCellMargin = 0.03f;   // slack (in cells) on every geometric lower bound: covers
-                                       // the float rounding of the point -> cell assignment
 
 struct GridDev {
     float ox, oy, oz, inv_cell, cell;
@@ -61,19 +59,6 @@ struct IcpDevState {
     unsigned long long ncorr;
     double svd_v[9];             // V of the previous solve: where the next Jacobi SVD starts
 };
-
-__device__ __forceinline__ float l2_simple(float qx, float qy, float qz, float tx, float ty, float tz)
-{
-    const float dx = __fsub_rn(qx, tx), dy = __fsub_rn(qy, ty), dz = __fsub_rn(qz, tz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
-// position in cell units relative to the grid origin; the SAME expression feeds the build
-// and every query, so equal coordinates always land in the same cell
-__device__ __forceinline__ float cell_pos(float p, float origin, float inv_cell)
-{
-    return __fmul_rn(__fsub_rn(p, origin), inv_cell);
-}
 
 __device__ __forceinline__ int cell_coord(float p, float origin, float inv_cell)
 {
@@ -113,14 +98,6 @@ __device__ __forceinline__ uint32_t hash_xyz16(float x, float y, float z)
     h ^= h >> 16;
     return h & 0xffffu;
 }
-
-// order-preserving float <-> uint map for atomicMin/atomicMax on floats
-__device__ __forceinline__ uint32_t float_ordered(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-using rsreg::ordered_float;   // (the host's way back: rsreg_ctx.hpp)
 
 // ------------------------------------------------------------------------------ grid build
 // per block: partial[0..2] = min (ordered uint), [3..5] = max, [6] = number of finite points
@@ -644,14 +621,6 @@ __device__ __forceinline__ bool brick_lookup(const GridDev &g, int bx, int by, i
         if (e.key == kEmptyKey) return false;
         slot = (slot + 1) & g.bmask;
     }
-}
-
-// lower bound (in cells) on the distance along one axis from a query at in-grid position u
-// (cell units) to cells lo..hi; kCellMargin absorbs the float rounding of cell assignment
-__device__ __forceinline__ float axis_gap(float u, int lo, int hi, float margin = kCellMargin)
-{
-    const float a = (float)lo - u, b = u - (float)(hi + 1);
-    return fmaxf(fmaxf(a, b) - margin, 0.0f);
 }
 
 // bits of a 4x4x4 brick whose local coordinates lie in [x0,x1] x [y0,y1] x [z0,z1] (all in 0..3)

@@ -14,7 +14,7 @@
 #include <cmath>
 
 #include "ndt_kernels.hpp"
-#include "oscan.hpp"
+#include "pointgrid.hpp"
 
 using namespace rsreg;
 
@@ -31,64 +31,6 @@ constexpr int kMinPointsPerVoxel = 6;
 constexpr double kMinCovarEigMult = 0.01;
 
 inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
-
-// order-preserving float <-> uint map (same as the ICP build's)
-__device__ __forceinline__ uint32_t f2o(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-float o2f(uint32_t u)
-{
-    uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    std::memcpy(&f, &v, 4);
-    return f;
-}
-
-__global__ __launch_bounds__(256) void k_ndt_bbox(const char *pts, size_t stride, uint32_t n, uint32_t *bbox)
-{
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    uint32_t cnt = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float *p = reinterpret_cast<const float *>(pts + (size_t)i * stride);
-        const float x = p[0], y = p[1], z = p[2];
-        if (ndt_finite3(x, y, z)) {
-            mn[0] = fminf(mn[0], x); mn[1] = fminf(mn[1], y); mn[2] = fminf(mn[2], z);
-            mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
-            ++cnt;
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        for (int k = 0; k < 3; ++k) {
-            mn[k] = fminf(mn[k], __shfl_down(mn[k], off));
-            mx[k] = fmaxf(mx[k], __shfl_down(mx[k], off));
-        }
-        cnt += __shfl_down(cnt, off);
-    }
-    // one set of atomics per workgroup, not per wave: they all hit the same seven words
-    __shared__ float smn[4][3], smx[4][3];
-    __shared__ uint32_t scnt[4];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        for (int k = 0; k < 3; ++k) { smn[wave][k] = mn[k]; smx[wave][k] = mx[k]; }
-        scnt[wave] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) {
-            for (int k = 0; k < 3; ++k) { mn[k] = fminf(mn[k], smn[w][k]); mx[k] = fmaxf(mx[k], smx[w][k]); }
-            cnt += scnt[w];
-        }
-        if (cnt) {
-            for (int k = 0; k < 3; ++k) {
-                atomicMin(&bbox[k], f2o(mn[k]));
-                atomicMax(&bbox[3 + k], f2o(mx[k]));
-            }
-            atomicAdd(&bbox[6], cnt);
-        }
-    }
-}
 
 struct Pose {
     double p[6];
@@ -436,20 +378,19 @@ int rsreg_ndt_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
     ctx->next_ndt_box.valid = false;
     ctx->last_ndt_box.valid = false;
     if (n && known.valid && known.nfin <= n && tunables().box_cache) {
-        auto host_f2o = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
-        for (int k = 0; k < 3; ++k) { h_misc[k] = host_f2o(known.mn[k]); h_misc[3 + k] = host_f2o(known.mx[k]); }
+        for (int k = 0; k < 3; ++k) { h_misc[k] = float_ordered(known.mn[k]); h_misc[3 + k] = float_ordered(known.mx[k]); }
         h_misc[6] = known.nfin;
         ctx->last_ndt_box = known;
     } else if (n) {
         // minima start at all ones, maxima and the count at zero (ordered-float encoding): two memsets, no upload + sync
         RSREG_HIP(ctx, hipMemsetAsync(d_misc, 0xff, 12, st));
         RSREG_HIP(ctx, hipMemsetAsync(d_misc + 3, 0, 52, st));
-        k_ndt_bbox<<<std::min<uint32_t>(div_up((uint32_t)n, 256), 256), 256, 0, st>>>(d_pts, pstride, (uint32_t)n, d_misc);
+        k_grid_box<<<std::min<uint32_t>(div_up((uint32_t)n, kBlock), 256), kBlock, 0, st>>>(StridedRecords{d_pts, pstride, nullptr}, (uint32_t)n, d_misc);
         RSREG_HIP(ctx, hipGetLastError());
         RSREG_HIP(ctx, hipMemcpyAsync(h_misc, d_misc, 64, hipMemcpyDeviceToHost, st));
         RSREG_HIP(ctx, hipStreamSynchronize(st));
         if (h_misc[6]) {   // (measured: the handle keeps it)
-            for (int k = 0; k < 3; ++k) { ctx->last_ndt_box.mn[k] = o2f(h_misc[k]); ctx->last_ndt_box.mx[k] = o2f(h_misc[3 + k]); }
+            for (int k = 0; k < 3; ++k) { ctx->last_ndt_box.mn[k] = ordered_float(h_misc[k]); ctx->last_ndt_box.mx[k] = ordered_float(h_misc[3 + k]); }
             ctx->last_ndt_box.nfin = h_misc[6];
             ctx->last_ndt_box.valid = true;
             ctx->last_ndt_box.exact = true;
@@ -466,7 +407,7 @@ int rsreg_ndt_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
     bp.inv_leaf = 1.0f / leaf;
     int div_b[3];
     for (int k = 0; k < 3; ++k) {
-        volatile float lo = o2f(h_misc[k]) * bp.inv_leaf, hi = o2f(h_misc[3 + k]) * bp.inv_leaf;
+        volatile float lo = ordered_float(h_misc[k]) * bp.inv_leaf, hi = ordered_float(h_misc[3 + k]) * bp.inv_leaf;
         bp.min_b[k] = (int)std::floor(lo);
         div_b[k] = (int)std::floor(hi) - bp.min_b[k] + 1;
     }

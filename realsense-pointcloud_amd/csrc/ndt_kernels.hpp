@@ -52,11 +52,6 @@ struct NdtPassParams {
     int mode;             // 0 score+gradient+Hessian, 1 score+gradient, 2 Hessian only
 };
 
-__device__ __forceinline__ bool ndt_finite3(float x, float y, float z)
-{
-    return isfinite(x) && isfinite(y) && isfinite(z);
-}
-
 // leaf key = ijk0 + ijk1*div0 + ijk2*div0*div1, ijk = floor(p*inv_leaf) - min_b (PCL formula)
 // (non-finite points get `invalid_key`, one above every leaf's: they sort last, and the sort only has to look at its bits)
 template <typename KeyT>
@@ -69,7 +64,7 @@ __global__ __launch_bounds__(kNdtBlock) void k_ndt_keys(const char *pts, size_t 
     const float *p = reinterpret_cast<const float *>(pts + (size_t)i * stride);
     const float x = p[0], y = p[1], z = p[2];
     KeyT key = invalid_key;
-    if (ndt_finite3(x, y, z)) {
+    if (finite3(x, y, z)) {
         const int i0 = (int)(floorf(__fmul_rn(x, bp.inv_leaf)) - (float)bp.min_b[0]);
         const int i1 = (int)(floorf(__fmul_rn(y, bp.inv_leaf)) - (float)bp.min_b[1]);
         const int i2 = (int)(floorf(__fmul_rn(z, bp.inv_leaf)) - (float)bp.min_b[2]);
@@ -644,7 +639,7 @@ __global__ __launch_bounds__(kNdtBlock) void k_ndt_load_source(const char *raw, 
     if (i >= n) return;
     const float *p = reinterpret_cast<const float *>(raw + (size_t)i * stride);
     const float x = p[0], y = p[1], z = p[2];
-    src[i] = make_float4(x, y, z, ndt_finite3(x, y, z) ? 1.0f : 0.0f);
+    src[i] = make_float4(x, y, z, finite3(x, y, z) ? 1.0f : 0.0f);
 }
 
 // NDT's copy of its target's points for the fitness score (PCL scores NDT against a kd-tree over the target's points, not its
@@ -655,7 +650,7 @@ __global__ __launch_bounds__(kNdtBlock) void k_ndt_keep_target(const char *raw, 
     if (i >= n) return;
     const float *p = reinterpret_cast<const float *>(raw + (size_t)i * stride);
     const float x = p[0], y = p[1], z = p[2];
-    out[i] = ndt_finite3(x, y, z) ? tgt_rec(x, y, z, i) : tgt_rec(__uint_as_float(0x7f800000u), 0.0f, 0.0f, i);
+    out[i] = finite3(x, y, z) ? tgt_rec(x, y, z, i) : tgt_rec(__uint_as_float(0x7f800000u), 0.0f, 0.0f, i);
 }
 
 // the aligned cloud of ndt.align() as records in HBM: the source record, xyz at the last evaluated pose
@@ -667,7 +662,7 @@ __global__ __launch_bounds__(kNdtBlock) void k_ndt_write_aligned(const char *in,
     const uint32_t *src = reinterpret_cast<const uint32_t *>(in + (size_t)i * stride);
     uint32_t *dst = reinterpret_cast<uint32_t *>(out + (size_t)i * stride);
     const float x = __uint_as_float(src[0]), y = __uint_as_float(src[1]), z = __uint_as_float(src[2]);
-    const bool ok = ndt_finite3(x, y, z);
+    const bool ok = finite3(x, y, z);
     if (out != in)
         for (uint32_t k = 3; k < stride / 4; ++k) dst[k] = src[k];
     dst[0] = ok ? __float_as_uint(xyz[3 * i]) : src[0];

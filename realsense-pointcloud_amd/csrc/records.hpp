@@ -1,5 +1,6 @@
 // records.hpp — small device helpers shared by the translation units that touch point records
-// (icp.hip through icp_kernels.hpp, cloud.hip): the 3x4 transform in PCL's operation order, record access.
+// (icp.hip through icp_kernels.hpp, cloud.hip, ndt.hip, filters.hip): the 3x4 transform in PCL's operation order, record
+// access, FLANN's distance, and the cell arithmetic every grid index here is built and searched with.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -39,6 +40,31 @@ __device__ __forceinline__ bool finite3(float x, float y, float z)
 __device__ __forceinline__ const float *rec_xyz(const char *base, size_t stride, size_t i)
 {
     return reinterpret_cast<const float *>(base + i * stride);
+}
+
+constexpr float kCellMargin = 0.03f;   // slack (in cells) on every geometric lower bound: covers
+                                       // the float rounding of the point -> cell assignment
+
+// FLANN L2_Simple<float>: ((dx*dx + dy*dy) + dz*dz), no contraction
+__device__ __forceinline__ float l2_simple(float qx, float qy, float qz, float tx, float ty, float tz)
+{
+    const float dx = __fsub_rn(qx, tx), dy = __fsub_rn(qy, ty), dz = __fsub_rn(qz, tz);
+    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
+// position in cell units relative to the grid origin; the SAME expression feeds the build
+// and every query, so equal coordinates always land in the same cell
+__device__ __forceinline__ float cell_pos(float p, float origin, float inv_cell)
+{
+    return __fmul_rn(__fsub_rn(p, origin), inv_cell);
+}
+
+// lower bound (in cells) on the distance along one axis from a query at in-grid position u
+// (cell units) to cells lo..hi; kCellMargin absorbs the float rounding of cell assignment
+__device__ __forceinline__ float axis_gap(float u, int lo, int hi, float margin = kCellMargin)
+{
+    const float a = (float)lo - u, b = u - (float)(hi + 1);
+    return fmaxf(fmaxf(a, b) - margin, 0.0f);
 }
 
 // A record of the sorted target array (both index kinds): x, y, ORIGINAL INDEX, z.  The index sits in the third

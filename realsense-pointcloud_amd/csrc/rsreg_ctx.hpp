@@ -85,12 +85,18 @@ struct PinnedBuf {
 // Bounding box and number of the finite points of a cloud: what an index build or a source load starts from (one kernel
 // pair and a round trip to the host).  A cloud handle keeps the box of its records as they are (cloud.hip: version), so a
 // frame that was the source of one pair and is the target of the next is not measured twice.
-// the way back from the order-preserving uint the kernels keep float minima / maxima in (icp_kernels.hpp: float_ordered)
-inline float ordered_float(uint32_t u)
+// The order-preserving float <-> uint map the kernels keep float minima / maxima in (atomicMin / atomicMax on floats), both ways
+RSREG_HD inline uint32_t float_ordered(float f)
+{
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+RSREG_HD inline float ordered_float(uint32_t u)
 {
     const uint32_t v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
     float f;
-    std::memcpy(&f, &v, 4);
+    __builtin_memcpy(&f, &v, 4);
     return f;
 }
 
@@ -171,22 +177,24 @@ struct BrickEntry {          // 32 B, one hash-table slot
     uint32_t pad[3];
 };
 
-// Exact nearest-neighbour index over a target's points for Registration::getFitnessScore at ANY range (fitness_kernels.hpp,
-// DESIGN.md §4, getFitnessScore).  A dense grid of 4x4x4-cell blocks with one occupancy word each; cells are numbered
-// block-major, so a block's 64 cell starts are contiguous.  Built lazily, by the first fitness call after a target change, from the target's own records;
-// an instance belongs to one consumer (the ICP target, NDT's target) and shares no buffer with anything else.
-struct FitIndex {
+// Dense grid of cells over the finite points of a cloud: the index of the exact searches (pointgrid.hpp builds it).
+// Cells are numbered either x fastest (a run of cells along x is ONE run of points: the k-NN walk of knn_kernels.hpp) or
+// block-major, 4x4x4 cells a block with one occupancy word each (a block's 64 cell starts are contiguous: the nearest-point
+// walk of fitness_kernels.hpp); which, and how fine the cells are, is the builder's policy.  An instance belongs to ONE
+// consumer (the ICP target's fitness score, NDT's, the cloud filters) and shares no buffer with the alignment's index or
+// with another instance.
+struct PointGrid {
     bool built = false;
     float origin[3] = {0, 0, 0};
     float cell = 1, inv_cell = 1;
-    int dims[3] = {0, 0, 0};       // cells per axis (multiples of 4; 0: no finite point)
-    uint32_t n_points = 0;         // finite points indexed
-    DevBuf d_pts;                  // float4 {x, y, z, 0}, cell by cell
+    int dims[3] = {0, 0, 0};       // cells per axis (0: nothing indexed)
+    uint32_t n_points = 0;         // finite points of the cloud
+    DevBuf d_pts;                  // float4 {x, y, z, the reader's tag}, cell by cell
     DevBuf d_start;                // uint32 per cell + 1: first point of each cell
     DevBuf d_count;                // uint32 per cell + 1: build scratch, all zero between builds
-    DevBuf d_mask;                 // uint64 per block: which of its 64 cells hold a point
-    DevBuf d_scan;                 // the prefix sum's scratch
-    DevBuf d_box;                  // the box / count of the points (ordered uints)
+    DevBuf d_mask;                 // block-major only: uint64 per block, which of its 64 cells hold a point
+    DevBuf d_scan;                 // the prefix sums' scratch
+    DevBuf d_box;                  // the box / count of the finite points (ordered uints)
     void release()
     {
         for (DevBuf *b : {&d_pts, &d_start, &d_count, &d_mask, &d_scan, &d_box}) b->release();
@@ -194,19 +202,8 @@ struct FitIndex {
     }
 };
 
-// Exact k-nearest-neighbour index and scratch of the cloud filters (filters.hip, knn_kernels.hpp, DESIGN.md §4, cloud filters): a
-// dense grid of cells over the finite points' box, cells numbered x fastest, so a run of cells along x is ONE run of points.
-// Rebuilt by every call from the cloud it is given; it shares no buffer with the alignment's index or the fitness indices.
-struct KnnIndex {
-    float origin[3] = {0, 0, 0};
-    float cell = 1, inv_cell = 1;
-    int dims[3] = {0, 0, 0};
-    uint32_t n_points = 0;         // finite records indexed
-    DevBuf d_pts;                  // float4 {x, y, z, bits(record index)}, cell by cell
-    DevBuf d_start;                // uint32 per cell + 1: first point of each cell
-    DevBuf d_count;                // uint32 per cell + 1: build scratch, all zero between builds
-    DevBuf d_scan;                 // the prefix sums' scratch
-    DevBuf d_box;                  // the box / count of the finite points (ordered uints)
+// Scratch of the cloud filters (filters.hip), per record of the cloud being filtered; not part of an index
+struct FilterScratch {
     DevBuf d_dist;                 // float per record: its mean distance to its mean_k nearest neighbours
     DevBuf d_flags, d_pos;         // uint32 per record: keep flag, position among the kept
     DevBuf d_sums;                 // the threshold's two f64 sums
@@ -214,7 +211,7 @@ struct KnnIndex {
     PinnedBuf host;
     void release()
     {
-        for (DevBuf *b : {&d_pts, &d_start, &d_count, &d_scan, &d_box, &d_dist, &d_flags, &d_pos, &d_sums, &d_out}) b->release();
+        for (DevBuf *b : {&d_dist, &d_flags, &d_pos, &d_sums, &d_out}) b->release();
         host.release();
     }
 };
@@ -404,7 +401,7 @@ struct rsreg_ctx {
     bool icp_fit_ok = false, ndt_fit_ok = false;
     rsreg::Mat4f icp_fit_t, ndt_fit_t;   // the final transforms of those alignments
     size_t ndt_fit_n = 0;                // records of the NDT source (d_ndt_src)
-    rsreg::FitIndex fit_icp, fit_ndt;    // one index per target kind: neither touches the alignment's own index
+    rsreg::PointGrid fit_icp, fit_ndt;    // one index per target kind: neither touches the alignment's own index
     rsreg::DevBuf d_fit_d2, d_fit_partials, d_fit_sums;
     rsreg::PinnedBuf h_fit;
 
@@ -426,7 +423,8 @@ struct rsreg_ctx {
     std::vector<std::pair<size_t, size_t>> ev_nn, ev_reduce, ev_transform, ev_allreduce;
 
     // ---- PassThrough / StatisticalOutlierRemoval (filters.hip): index and scratch of their own (last: nothing above moves)
-    rsreg::KnnIndex knn;
+    rsreg::PointGrid knn;            // rebuilt by every k-NN call from the cloud it is given
+    rsreg::FilterScratch filt;
 };
 
 namespace rsreg {
@@ -437,7 +435,7 @@ void cloud_pool_clear(rsreg_ctx *ctx);   // cloud.hip: frees the buffers kept in
 // sums[1] = the sum of those squared distances, over the records src[0 .. n) (float4 {x, y, z, valid}) moved by T.  perm
 // (nullable): record j is the caller's record perm[j] -- the sums run in the caller's order.  `fx` is built from the target
 // records tgt[0 .. n_tgt) (x, y, index, z) if it is not built yet.  On ctx->stream; waits for it.
-int fitness_sums(rsreg_ctx *ctx, FitIndex &fx, const float4 *tgt, size_t n_tgt, const float4 *src, const uint32_t *perm, size_t n,
+int fitness_sums(rsreg_ctx *ctx, PointGrid &fx, const float4 *tgt, size_t n_tgt, const float4 *src, const uint32_t *perm, size_t n,
                  const Mat4f &T, double max_range, double sums[2]);
 
 inline int fail(rsreg_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess)

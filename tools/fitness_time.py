@@ -5,7 +5,7 @@ alignment's index was built for (their nearest target lies farther than the gate
 
     python tools/fitness_time.py [--reps 20]
 Under `rocprofv3 --kernel-trace --stats -- python tools/fitness_time.py` the per-kernel times are k_fit_search / k_fit_tiles /
-k_final_reduce (every call) and k_fit_bbox / k_fit_count / k_oscan_* / k_fit_scatter (the build).  Prints one JSON line.
+k_final_reduce (every call) and k_grid_box / k_grid_count / k_oscan_* / k_grid_scatter (the build: pointgrid.hpp).  Prints one JSON line.
 """
 import argparse
 import json
