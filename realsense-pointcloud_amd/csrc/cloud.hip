@@ -23,7 +23,7 @@ struct rsreg_cloud {
     uint32_t width = 0, height = 1;
     int is_dense = 0;
     // rsreg_cloud_upload_async: the copy that fills this cloud may still be on the link
-    hipEvent_t ev_filled = nullptr;
+    Event ev_filled;
     mutable bool filling = false;
     uint64_t up_ticket = 0;   // the upload worker's job that stages the records and queues their copy
     // rsreg_cloud_filter_async: the side worker's job that runs the filter INTO this cloud; until it has run, n / width are
@@ -33,7 +33,7 @@ struct rsreg_cloud {
     int filter_worker = 0;   // which side worker of the context runs (ran) that job
     int filter_rc = 0;
     // rsreg_cloud_download_async: a copy of these records to the host may still be reading them
-    hipEvent_t ev_down = nullptr;
+    Event ev_down;
     mutable bool downloading = false;
     // which cloud this is and how often its records have been rewritten: an index built from (id, version) is still
     // good while both are unchanged (rsreg_icp_set_target_cloud)
@@ -137,7 +137,7 @@ hipError_t settle(const rsreg_cloud *c)
     if (!c->filling) return hipSuccess;
     c->filling = false;
     // first the worker has to have staged the records and queued their copy (the event is recorded behind it) ...
-    const int e = c->ctx->up_worker ? c->ctx->up_worker->wait(c->up_ticket) : 0;
+    const int e = c->ctx->up.worker ? c->ctx->up.worker->wait(c->up_ticket) : 0;
     if (e) return (hipError_t)e;
     return hipEventSynchronize(c->ev_filled);   // ... then the copy has to have arrived
 }
@@ -145,7 +145,7 @@ hipError_t settle(const rsreg_cloud *c)
 // A dropped cloud's buffer goes to the context's pool and the next cloud takes it from there (rsreg_ctx.hpp, CloudPool):
 // the frame loops create and drop half a dozen clouds per frame, and every hipFree is a device-wide synchronisation
 // (0.16 ms).  Every kernel and copy that touches a cloud runs on ctx->stream, so a buffer handed on is written only
-// after the work queued on its previous owner; the one other reader is a source load on ctx->stream_src, which the main
+// after the work queued on its previous owner; the one other reader is a source load on ctx->src.stream, which the main
 // stream is made to wait for before a buffer changes hands.
 void cloud_drop(rsreg_ctx *ctx, DevBuf &b)
 {
@@ -158,16 +158,14 @@ void cloud_drop(rsreg_ctx *ctx, DevBuf &b)
     }
     CloudPool &pool = ctx->cloud_pool;
     if (b.cap <= pool.limit && pool.held + b.cap <= pool.limit) {
-        if (ctx->src_pending) { (void)ctx->source_enqueued(); (void)hipStreamWaitEvent(ctx->stream, ctx->ev_src_done, 0); }
-        pool.slots.push_back({b.ptr, b.cap});
+        if (ctx->src_pending) { (void)ctx->source_enqueued(); (void)hipStreamWaitEvent(ctx->stream, ctx->src.ev_done, 0); }
         pool.held += b.cap;
-        b.ptr = nullptr;
-        b.cap = 0;
+        pool.slots.push_back(std::move(b));
         return;
     }
-    // the buffer is freed: whatever the source worker still has to queue reads it (load_source_queue on stream_src), so
+    // the buffer is freed: whatever the source worker still has to queue reads it (load_source_queue on src.stream), so
     // that work has to be queued AND finished first -- hipFree only waits for what is already on a stream
-    if (ctx->src_pending) { (void)ctx->source_enqueued(); (void)hipEventSynchronize(ctx->ev_src_done); }
+    if (ctx->src_pending) { (void)ctx->source_enqueued(); (void)hipEventSynchronize(ctx->src.ev_done); }
     (void)hipStreamSynchronize(ctx->stream);
     b.release();
 }
@@ -190,10 +188,9 @@ hipError_t cloud_reserve(rsreg_ctx *ctx, DevBuf &b, size_t bytes, bool growing =
             best = i;
     }
     if (best != pool.slots.size()) {
-        b.ptr = pool.slots[best].ptr;
-        b.cap = pool.slots[best].cap;
+        b = std::move(pool.slots[best]);
         pool.held -= b.cap;
-        pool.slots[best] = pool.slots.back();
+        if (best + 1 != pool.slots.size()) pool.slots[best] = std::move(pool.slots.back());
         pool.slots.pop_back();
         return hipSuccess;
     }
@@ -240,7 +237,6 @@ void cloud_pool_clear(rsreg_ctx *ctx)
     CloudPool &pool = ctx->cloud_pool;
     if (pool.slots.empty()) return;
     (void)hipStreamSynchronize(ctx->stream);
-    for (const CloudPool::Slot &sl : pool.slots) (void)hipFree(sl.ptr);
     pool.slots.clear();
     pool.held = 0;
 }
@@ -251,11 +247,11 @@ void rsreg_ctx::prep_join()
     if (!prep_thread.joinable()) return;
     prep_thread.join();
     if (prep_model.ptr) {   // (the pool is the caller's thread's: the buffer joins it here)
-        cloud_pool.slots.push_back({prep_model.ptr, prep_model.cap});
         cloud_pool.held += prep_model.cap;
-        prep_model.ptr = nullptr;
-        prep_model.cap = 0;
+        cloud_pool.slots.push_back(std::move(prep_model));
     }
+    if (prep_rc) (void)fail(this, RSREG_ERR_HIP, "rsreg_ctx_prepare", (hipError_t)prep_rc);
+    prep_rc = 0;
 }
 
 extern "C" {
@@ -274,32 +270,19 @@ int rsreg_ctx_prepare(rsreg_ctx *ctx, size_t frame_bytes, size_t model_bytes, un
     ctx->prep_rc = 0;
     const bool want_side = (flags & 1u) != 0;
     // (a second registration() of the process: the model's buffer of the first is in the pool already)
-    for (const CloudPool::Slot &sl : ctx->cloud_pool.slots)
+    for (const DevBuf &sl : ctx->cloud_pool.slots)
         if (sl.cap >= model_bytes + 16) model_bytes = 0;
     ctx->prep_thread = std::thread([ctx, frame_bytes, model_bytes, want_side] {
         auto ok = [&](hipError_t e) { if (e != hipSuccess && !ctx->prep_rc) ctx->prep_rc = (int)e; return e == hipSuccess; };
         if (!ok(hipSetDevice(ctx->device))) return;
         // in the order a frame loop needs them: the upload's stream and staging, the source's stream, the download's, the side sets'
-        if (!ctx->stream_copy) {
-            if (!ok(hipStreamCreateWithFlags(&ctx->stream_copy, hipStreamNonBlocking))) return;
-            ok(hipEventCreateWithFlags(&ctx->ev_copy_gate, hipEventDisableTiming));
-            for (hipEvent_t &e : ctx->ev_up) ok(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        if (frame_bytes) { ok(ctx->h_up[0].reserve(frame_bytes)); ok(ctx->h_up[1].reserve(frame_bytes)); }
-        if (!ctx->stream_src) {
-            if (!ok(hipStreamCreateWithFlags(&ctx->stream_src, hipStreamNonBlocking))) return;
-            ok(hipEventCreateWithFlags(&ctx->ev_src_done, hipEventDisableTiming));
-            ok(hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
-        }
-        if (!ctx->stream_down) {
-            if (!ok(hipStreamCreateWithFlags(&ctx->stream_down, hipStreamNonBlocking))) return;
-            ok(hipEventCreateWithFlags(&ctx->ev_down_gate, hipEventDisableTiming));
-            for (hipEvent_t &e : ctx->ev_down) ok(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        if (frame_bytes) for (auto &h : ctx->h_down) ok(h.reserve(frame_bytes));
+        if (!ok(ctx->up.ensure())) return;
+        if (frame_bytes) { ok(ctx->up.h[0].reserve(frame_bytes)); ok(ctx->up.h[1].reserve(frame_bytes)); }
+        if (!ok(ctx->src.ensure()) || !ok(ctx->down.ensure())) return;
+        if (frame_bytes) for (auto &h : ctx->down.h) ok(h.reserve(frame_bytes));
         if (want_side)
             for (auto &ss : ctx->side_sets)
-                if (!ss.stream) ok(hipStreamCreateWithFlags(&ss.stream, hipStreamNonBlocking));
+                ok(ss.stream.ensure());
         if (model_bytes) ok(ctx->prep_model.reserve(model_bytes + 16));
     });
     return RSREG_OK;
@@ -322,8 +305,6 @@ int rsreg_cloud_destroy(rsreg_cloud *c)
     if (!c) return RSREG_OK;
     (void)hipSetDevice(c->ctx->device);
     (void)settle(c);
-    if (c->ev_filled) (void)hipEventDestroy(c->ev_filled);
-    if (c->ev_down) (void)hipEventDestroy(c->ev_down);
     if (c->ctx->src_cloud == c) c->ctx->src_cloud = nullptr;   // (rsreg_icp_align_cloud then refuses to write an aligned cloud)
     cloud_drop(c->ctx, c->buf);
     delete c;
@@ -374,37 +355,33 @@ int upload_on_worker(rsreg_cloud *c, const void *points, size_t n, size_t stride
     RSREG_HIP(ctx, cloud_reserve(ctx, c->buf, n * stride + 16));
     if (n) {
         ctx->prep_join();
-        if (!ctx->stream_copy) {
-            RSREG_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_copy, hipStreamNonBlocking));
-            RSREG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_copy_gate, hipEventDisableTiming));
-            for (hipEvent_t &e : ctx->ev_up) RSREG_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        if (!ctx->up_worker) ctx->up_worker = new rsreg::TicketWorker();
-        if (!c->ev_filled) RSREG_HIP(ctx, hipEventCreateWithFlags(&c->ev_filled, hipEventDisableTiming));
+        RSREG_HIP(ctx, ctx->up.ensure());
+        if (!ctx->up.worker) ctx->up.worker.reset(new rsreg::TicketWorker());
+        RSREG_HIP(ctx, c->ev_filled.ensure());
         // the buffer may come from the pool: work queued on its previous owner (main stream) goes first
-        RSREG_HIP(ctx, hipEventRecord(ctx->ev_copy_gate, ctx->stream));
-        RSREG_HIP(ctx, hipStreamWaitEvent(ctx->stream_copy, ctx->ev_copy_gate, 0));
-        if (ctx->src_pending) { (void)ctx->source_enqueued(); RSREG_HIP(ctx, hipStreamWaitEvent(ctx->stream_copy, ctx->ev_src_done, 0)); }
+        RSREG_HIP(ctx, hipEventRecord(ctx->up.ev_gate, ctx->stream));
+        RSREG_HIP(ctx, hipStreamWaitEvent(ctx->up.stream, ctx->up.ev_gate, 0));
+        if (ctx->src_pending) { (void)ctx->source_enqueued(); RSREG_HIP(ctx, hipStreamWaitEvent(ctx->up.stream, ctx->src.ev_done, 0)); }
         char *dst = c->buf.as<char>();
         const char *src = static_cast<const char *>(points);
         hipEvent_t ev_filled = c->ev_filled;
         const size_t bytes = n * stride;
-        c->up_ticket = ctx->up_worker->post([ctx, dst, src, n, stride, bytes, ev_filled]() -> int {
+        c->up_ticket = ctx->up.worker->post([ctx, dst, src, n, stride, bytes, ev_filled]() -> int {
             hipError_t e = hipSetDevice(ctx->device);
             if (e != hipSuccess) return (int)e;
-            const int slot = ctx->up_next;
-            ctx->up_next ^= 1;
-            if (ctx->up_busy[slot]) {   // the copy that last used this staging buffer
-                if ((e = hipEventSynchronize(ctx->ev_up[slot])) != hipSuccess) return (int)e;
-                ctx->up_busy[slot] = false;
+            const int slot = ctx->up.next;
+            ctx->up.next ^= 1;
+            if (ctx->up.busy[slot]) {   // the copy that last used this staging buffer
+                if ((e = hipEventSynchronize(ctx->up.ev[slot])) != hipSuccess) return (int)e;
+                ctx->up.busy[slot] = false;
             }
-            if ((e = ctx->h_up[slot].reserve(bytes)) != hipSuccess) return (int)e;
-            char *stage = ctx->h_up[slot].as<char>();
+            if ((e = ctx->up.h[slot].reserve(bytes)) != hipSuccess) return (int)e;
+            char *stage = ctx->up.h[slot].as<char>();
             host_parallel_for(n, [=](size_t lo, size_t hi) { rsreg::stream_copy(stage + lo * stride, src + lo * stride, (hi - lo) * stride); });
-            if ((e = hipMemcpyAsync(dst, stage, bytes, hipMemcpyHostToDevice, ctx->stream_copy)) != hipSuccess) return (int)e;
-            if ((e = hipEventRecord(ctx->ev_up[slot], ctx->stream_copy)) != hipSuccess) return (int)e;
-            ctx->up_busy[slot] = true;
-            return (int)hipEventRecord(ev_filled, ctx->stream_copy);
+            if ((e = hipMemcpyAsync(dst, stage, bytes, hipMemcpyHostToDevice, ctx->up.stream)) != hipSuccess) return (int)e;
+            if ((e = hipEventRecord(ctx->up.ev[slot], ctx->up.stream)) != hipSuccess) return (int)e;
+            ctx->up.busy[slot] = true;
+            return (int)hipEventRecord(ev_filled, ctx->up.stream);
         });
         c->filling = true;
     }
@@ -415,7 +392,7 @@ int upload_on_worker(rsreg_cloud *c, const void *points, size_t n, size_t stride
     c->height = height;
     c->is_dense = is_dense;
     if (n && wait_staged) {
-        const int e = ctx->up_worker->wait(c->up_ticket);
+        const int e = ctx->up.worker->wait(c->up_ticket);
         if (e) return fail(ctx, RSREG_ERR_HIP, "an asynchronous upload failed", (hipError_t)e);
     }
     return RSREG_OK;
@@ -449,9 +426,9 @@ int rsreg_cloud_download(const rsreg_cloud *c, void *out, size_t capacity)
     const size_t bytes = c->n * c->stride, piece = piece_bytes(bytes), n_pieces = (bytes + piece - 1) / piece;
     RSREG_HIP(ctx, ctx->h_stage.reserve(bytes));
     while (ctx->ev_copy.size() < n_pieces) {
-        hipEvent_t e = nullptr;
-        RSREG_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->ev_copy.push_back(e);
+        Event e;
+        RSREG_HIP(ctx, e.ensure());
+        ctx->ev_copy.push_back(std::move(e));
     }
     char *stage = ctx->h_stage.as<char>();
     const char *src = c->buf.as<char>();
@@ -463,7 +440,7 @@ int rsreg_cloud_download(const rsreg_cloud *c, void *out, size_t capacity)
     char *dst = static_cast<char *>(out);
     std::atomic<int> err{(int)hipSuccess};
     const int device = ctx->device;
-    hipEvent_t *ev = ctx->ev_copy.data();
+    const Event *ev = ctx->ev_copy.data();
     parallel_pieces(n_pieces, [&, stage, dst, bytes, piece, device, ev](size_t p) {   // a piece is copied out while the next ones arrive
         const size_t off = p * piece, len = std::min(piece, bytes - off);
         hipError_t e = hipSetDevice(device);
@@ -565,12 +542,12 @@ int side_begin(rsreg_ctx *ctx, int follow, int *worker_out, int *set_out)
     ctx->side_turn[worker] ^= 1;
     rsreg_ctx::SideSet &ss = ctx->side_sets[set];
     ctx->prep_join();
-    if (!ss.stream) RSREG_HIP(ctx, hipStreamCreateWithFlags(&ss.stream, hipStreamNonBlocking));
-    if (!ctx->ev_side_gate) RSREG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_side_gate, hipEventDisableTiming));
-    if (!ctx->side_workers[worker]) ctx->side_workers[worker] = new rsreg::TicketWorker();
+    RSREG_HIP(ctx, ss.stream.ensure());
+    RSREG_HIP(ctx, ctx->ev_side_gate.ensure());
+    if (!ctx->side_workers[worker]) ctx->side_workers[worker].reset(new rsreg::TicketWorker());
     RSREG_HIP(ctx, hipEventRecord(ctx->ev_side_gate, ctx->stream));
     RSREG_HIP(ctx, hipStreamWaitEvent(ss.stream, ctx->ev_side_gate, 0));
-    if (ctx->src_pending) { (void)ctx->source_enqueued(); RSREG_HIP(ctx, hipStreamWaitEvent(ss.stream, ctx->ev_src_done, 0)); }
+    if (ctx->src_pending) { (void)ctx->source_enqueued(); RSREG_HIP(ctx, hipStreamWaitEvent(ss.stream, ctx->src.ev_done, 0)); }
     *worker_out = worker;
     *set_out = set;
     return RSREG_OK;
@@ -589,7 +566,7 @@ int side_wait_input(rsreg_ctx *ctx, const InFlight &f, hipStream_t st)
     if (!f.filling || !f.ev) return RSREG_OK;
     // (a third party's wait: a failed upload stays for the poster's own settle() to report, and this job does not run on
     // a buffer that was never filled)
-    if (ctx->up_worker && ctx->up_worker->peek(f.ticket)) return fail(ctx, RSREG_ERR_HIP, "the upload of this job's input cloud failed");
+    if (ctx->up.worker && ctx->up.worker->peek(f.ticket)) return fail(ctx, RSREG_ERR_HIP, "the upload of this job's input cloud failed");
     RSREG_HIP(ctx, hipStreamWaitEvent(st, f.ev, 0));
     return RSREG_OK;
 }
@@ -620,7 +597,7 @@ int rsreg_cloud_filter_async(rsreg_ctx *ctx, const rsreg_cloud *in, const float 
     // in the frame loops: they run on the side worker's thread.  The output cannot be larger than the input: room for that
     // is made here (the buffer pool is the caller's thread's).
     RSREG_HIP(ctx, cloud_reserve(ctx, out->buf, (chained ? in->buf.cap : in->n * stride) + 16));
-    if (!out->ev_filled) RSREG_HIP(ctx, hipEventCreateWithFlags(&out->ev_filled, hipEventDisableTiming));
+    RSREG_HIP(ctx, out->ev_filled.ensure());
     const float l0 = leaf[0], l1 = leaf[1], l2 = leaf[2];
     out->version++;
     out->n = 0; out->stride = stride; out->width = 0; out->height = 1; out->is_dense = 0;
@@ -671,7 +648,7 @@ int rsreg_cloud_edge_features_async(rsreg_ctx *ctx, const rsreg_cloud *in, rsreg
     const size_t stride = in->stride, n_in = in->n;
     const uint32_t w = in->width, h = in->height;
     RSREG_HIP(ctx, cloud_reserve(ctx, out->buf, n_in * stride + 16));
-    if (!out->ev_filled) RSREG_HIP(ctx, hipEventCreateWithFlags(&out->ev_filled, hipEventDisableTiming));
+    RSREG_HIP(ctx, out->ev_filled.ensure());
     const InFlight inf = in_flight_of(in);
     const char *src = in->buf.as<char>();
     out->version++;
@@ -742,49 +719,45 @@ int rsreg_cloud_download_async(const rsreg_cloud *c, void *out, size_t capacity)
     RSREG_HIP(ctx, settle(c));
     if (!c->n) return RSREG_OK;
     ctx->prep_join();
-    if (!ctx->stream_down) {
-        RSREG_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_down, hipStreamNonBlocking));
-        RSREG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_down_gate, hipEventDisableTiming));
-        for (hipEvent_t &e : ctx->ev_down) RSREG_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    if (!ctx->down_worker) {
-        ctx->down_worker = new rsreg::DownloadWorker();
-        ctx->down_worker->wait_ready = [](const rsreg::DownloadWorker::Job &j) -> int {
+    RSREG_HIP(ctx, ctx->down.ensure());
+    if (!ctx->down.worker) {
+        ctx->down.worker.reset(new rsreg::DownloadWorker());
+        ctx->down.worker->wait_ready = [](const rsreg::DownloadWorker::Job &j) -> int {
             hipError_t e = hipSetDevice(j.device);
             if (e == hipSuccess) e = hipEventSynchronize(static_cast<hipEvent_t>(j.ev));
             return (int)e;
         };
     }
     rsreg_cloud *mc = const_cast<rsreg_cloud *>(c);
-    if (!mc->ev_down) RSREG_HIP(ctx, hipEventCreateWithFlags(&mc->ev_down, hipEventDisableTiming));
+    RSREG_HIP(ctx, mc->ev_down.ensure());
     const size_t bytes = c->n * c->stride;
-    const int slot = ctx->down_next;
-    ctx->down_next = (ctx->down_next + 1) % rsreg::DownloadWorker::kSlots;
-    ctx->down_worker->wait_slot(slot);   // (the copy-out that last used this staging buffer)
+    const int slot = ctx->down.next;
+    ctx->down.next = (ctx->down.next + 1) % rsreg::DownloadWorker::kSlots;
+    ctx->down.worker->wait_slot(slot);   // (the copy-out that last used this staging buffer)
     {
         // (a failure before the job is posted must give the slot back: nobody else would, and the third download after it
         // would wait for ever)
-        hipError_t e = ctx->h_down[slot].reserve(bytes);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev_down_gate, ctx->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream_down, ctx->ev_down_gate, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_down[slot].ptr, c->buf.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream_down);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev_down[slot], ctx->stream_down);
-        if (e == hipSuccess) e = hipEventRecord(mc->ev_down, ctx->stream_down);
+        hipError_t e = ctx->down.h[slot].reserve(bytes);
+        if (e == hipSuccess) e = hipEventRecord(ctx->down.ev_gate, ctx->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->down.stream, ctx->down.ev_gate, 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->down.h[slot].ptr, c->buf.ptr, bytes, hipMemcpyDeviceToHost, ctx->down.stream);
+        if (e == hipSuccess) e = hipEventRecord(ctx->down.ev[slot], ctx->down.stream);
+        if (e == hipSuccess) e = hipEventRecord(mc->ev_down, ctx->down.stream);
         if (e != hipSuccess) {
-            ctx->down_worker->release_slot(slot);
+            ctx->down.worker->release_slot(slot);
             return rsreg::fail(ctx, RSREG_ERR_HIP, "rsreg_cloud_download_async", e);
         }
     }
     c->downloading = true;
-    ctx->down_worker->post(rsreg::DownloadWorker::Job{ctx->ev_down[slot], ctx->h_down[slot].as<char>(), static_cast<char *>(out), bytes, slot, ctx->device});
+    ctx->down.worker->post(rsreg::DownloadWorker::Job{ctx->down.ev[slot], ctx->down.h[slot].as<char>(), static_cast<char *>(out), bytes, slot, ctx->device});
     return RSREG_OK;
 }
 
 int rsreg_ctx_wait_downloads(rsreg_ctx *ctx)
 {
     if (!ctx) return RSREG_ERR_INVALID_ARG;
-    if (!ctx->down_worker) return RSREG_OK;
-    const int e = ctx->down_worker->wait_idle();
+    if (!ctx->down.worker) return RSREG_OK;
+    const int e = ctx->down.worker->wait_idle();
     if (e) return fail(ctx, RSREG_ERR_HIP, "an asynchronous download failed", (hipError_t)e);
     return RSREG_OK;
 }
@@ -827,11 +800,11 @@ int rsreg_cloud_concat(rsreg_ctx *ctx, const rsreg_cloud *a, const rsreg_cloud *
         if (na) e = hipMemcpyAsync(fresh.ptr, a->buf.ptr, na * stride, hipMemcpyDeviceToDevice, ctx->stream);
         if (e == hipSuccess && nb) e = hipMemcpyAsync(static_cast<char *>(fresh.ptr) + na * stride, b->buf.ptr, nb * stride, hipMemcpyDeviceToDevice, ctx->stream);
         if (e != hipSuccess) {
-            cloud_drop(ctx, fresh);   // (DevBuf has no destructor: hand the buffer back before reporting the error)
+            cloud_drop(ctx, fresh);   // (to the pool, not to a hipFree: hand the buffer back before reporting the error)
             RSREG_HIP(ctx, e);
         }
         cloud_drop(ctx, out->buf);   // (a or b may be `out`: its old buffer is reused only by work queued after these copies)
-        out->buf = fresh;
+        out->buf = std::move(fresh);
     }
     out->version++;
     out->n = total; out->stride = stride; out->width = (uint32_t)total; out->height = 1; out->is_dense = dense;
@@ -850,7 +823,7 @@ static void harvest_source_box(rsreg_ctx *ctx)
     // a small source was loaded by one launch that measured its box on the way (k_source_plain): the words are complete once
     // the stamp behind them is this load's -- which it is as soon as anything queued behind the launch has been waited for
     if (s && !ctx->src_pending && ctx->plain_box_seq && ctx->h_smisc.ptr) {
-        const uint32_t *hb = ctx->h_smisc.as<uint32_t>() + 48;
+        const uint32_t *hb = ctx->h_smisc.as<uint32_t>() + kHsPlainBox;
         if (__atomic_load_n(&hb[7], __ATOMIC_ACQUIRE) == ctx->plain_box_seq) {
             rsreg::CloudBox b;
             for (int k = 0; k < 3; ++k) { b.mn[k] = rsreg::ordered_float(hb[k]); b.mx[k] = rsreg::ordered_float(hb[3 + k]); }

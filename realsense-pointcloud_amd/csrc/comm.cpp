@@ -104,7 +104,7 @@ int rsreg_comm_init(rsreg_ctx *ctx, const uint8_t id[RSREG_UNIQUE_ID_BYTES], int
     ctx->comm = comm;
     ctx->rank = rank;
     ctx->nranks = nranks;
-    RSREG_HIP(ctx, ctx->d_comm.reserve(64 * sizeof(double)));
+    RSREG_HIP(ctx, ctx->d_comm.reserve(kCommBytes));
     return RSREG_OK;
 }
 

@@ -33,9 +33,9 @@ inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 hipEvent_t take_event(rsreg_ctx *ctx)
 {
     if (ctx->ev_used == ctx->ev_pool.size()) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        ctx->ev_pool.push_back(e);
+        Event e;
+        if (e.ensure(hipEventDefault) != hipSuccess) return nullptr;
+        ctx->ev_pool.push_back(std::move(e));
     }
     return ctx->ev_pool[ctx->ev_used++];
 }
@@ -72,6 +72,16 @@ double sum_events(rsreg_ctx *ctx, std::vector<std::pair<size_t, size_t>> &list)
     return ms;
 }
 
+float prune2_of(double max_dist)
+{
+    // squared search radius as a float that is never below the f64 gate PCL compares with
+    const double gate2 = max_dist * max_dist;
+    if (!(gate2 < (double)FLT_MAX)) return INFINITY;
+    float f = (float)gate2;
+    if ((double)f < gate2) f = std::nextafter(f, INFINITY);
+    return f;
+}
+
 GridDev grid_dev(const rsreg_ctx *ctx, double max_dist)
 {
     const GridParams &p = ctx->grid;
@@ -81,15 +91,7 @@ GridDev grid_dev(const rsreg_ctx *ctx, double max_dist)
     g.dx = p.dims[0]; g.dy = p.dims[1]; g.dz = p.dims[2];
     g.bmask = p.table_mask;
     g.max_ring = p.max_ring;
-    // squared search radius as a float that is never below the f64 gate PCL compares with
-    const double gate2 = max_dist * max_dist;
-    if (!(gate2 < (double)FLT_MAX)) {
-        g.prune2 = INFINITY;
-    } else {
-        float f = (float)gate2;
-        if ((double)f < gate2) f = std::nextafter(f, INFINITY);
-        g.prune2 = f;
-    }
+    g.prune2 = prune2_of(max_dist);
     g.bricks = ctx->d_table.as<BrickEntry>();
     g.cellpos = ctx->d_cellpos.as<uint32_t>();
     g.pts = ctx->d_tgt_sorted.as<float4>();
@@ -106,11 +108,9 @@ int host_cell_coord(float p, float origin, float inv_cell)
     return (int)f;
 }
 
-double cell_cap_from_env() { return tunables().cell_cap; }
-
 // bounding box + count of the finite points of a device-resident cloud (one host sync), on the given stream with
-// the given scratch: d_misc (64 words; result in the first 16), h_misc (pinned, 16 words), partial (1024 x 8 words)
-int device_bbox_on(rsreg_ctx *ctx, hipStream_t st, uint32_t *d_misc, uint32_t *h_misc, uint32_t *partial, const char *d_pts, size_t n,
+// the given scratch: d_misc (its kCounterWords are cleared), h_box (pinned, kBoxWords: the result), partial (kBoxPartialWords)
+int device_bbox_on(rsreg_ctx *ctx, hipStream_t st, uint32_t *d_misc, uint32_t *h_box, uint32_t *partial, const char *d_pts, size_t n,
                    size_t stride, float mn[3], float mx[3], uint32_t *nfin)
 {
     if (n == 0) {   // no kernel runs: the empty box
@@ -118,36 +118,32 @@ int device_bbox_on(rsreg_ctx *ctx, hipStream_t st, uint32_t *d_misc, uint32_t *h
         *nfin = 0;
         return RSREG_OK;
     }
-    if (n > 0) {
-        const uint32_t nb = std::min<uint32_t>(div_up((uint32_t)n, kBlock), 1024);
-        k_bbox<<<nb, kBlock, 0, st>>>(d_pts, stride, (uint32_t)n, partial);
-        RSREG_HIP(ctx, hipGetLastError());
-        k_bbox_final<<<1, kBlock, 0, st>>>(partial, nb, h_misc, d_misc);   // the box straight into the pinned host buffer (no copy queued); clears the counters
-        RSREG_HIP(ctx, hipGetLastError());
-    }
+    const uint32_t nb = std::min<uint32_t>(div_up((uint32_t)n, kBlock), kBoxPartialGroups);
+    k_bbox<<<nb, kBlock, 0, st>>>(d_pts, stride, (uint32_t)n, partial);
+    RSREG_HIP(ctx, hipGetLastError());
+    k_bbox_final<<<1, kBlock, 0, st>>>(partial, nb, h_box, d_misc);   // the box straight into the pinned host buffer (no copy queued); clears the counters
+    RSREG_HIP(ctx, hipGetLastError());
     RSREG_HIP(ctx, hipStreamSynchronize(st));
-    *nfin = h_misc[6];
-    for (int k = 0; k < 3; ++k) { mn[k] = ordered_float(h_misc[k]); mx[k] = ordered_float(h_misc[3 + k]); }
+    *nfin = h_box[6];
+    for (int k = 0; k < 3; ++k) { mn[k] = ordered_float(h_box[k]); mx[k] = ordered_float(h_box[3 + k]); }
+    return RSREG_OK;
+}
+
+// the scratch of the target's box (rsreg_ctx.hpp: the words of the small scratch buffers)
+int reserve_box_scratch(rsreg_ctx *ctx)
+{
+    RSREG_HIP(ctx, ctx->d_misc.reserve(kMiscWords * sizeof(uint32_t)));
+    RSREG_HIP(ctx, ctx->h_sums.reserve(kSumsBytes));
+    RSREG_HIP(ctx, ctx->d_comm.reserve(kCommPartialsAt + kBoxPartialWords * sizeof(uint32_t)));
     return RSREG_OK;
 }
 
 int device_bbox(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, float mn[3], float mx[3], uint32_t *nfin)
 {
-    RSREG_HIP(ctx, ctx->d_misc.reserve(64 * sizeof(uint32_t)));
-    RSREG_HIP(ctx, ctx->h_sums.reserve(64 * 8));
-    RSREG_HIP(ctx, ctx->d_comm.reserve(1024 * 8 * sizeof(uint32_t) + 64 * sizeof(double)));
+    int rc = reserve_box_scratch(ctx);
+    if (rc) return rc;
     return device_bbox_on(ctx, ctx->stream, ctx->d_misc.as<uint32_t>(), ctx->h_sums.as<uint32_t>(),
-                          reinterpret_cast<uint32_t *>(ctx->d_comm.as<char>() + 64 * sizeof(double)), d_pts, n, stride, mn, mx, nfin);
-}
-
-float prune2_of(double max_dist)
-{
-    // squared search radius as a float that is never below the f64 gate PCL compares with
-    const double gate2 = max_dist * max_dist;
-    if (!(gate2 < (double)FLT_MAX)) return INFINITY;
-    float f = (float)gate2;
-    if ((double)f < gate2) f = std::nextafter(f, INFINITY);
-    return f;
+                          reinterpret_cast<uint32_t *>(ctx->d_comm.as<char>() + kCommPartialsAt), d_pts, n, stride, mn, mx, nfin);
 }
 
 DenseDev dense_dev(const rsreg_ctx *ctx, double max_dist)
@@ -178,8 +174,6 @@ DenseDev dense_dev(const rsreg_ctx *ctx, double max_dist)
     return g;
 }
 
-long long dense_cell_budget() { return tunables().dense_max_cells; }
-
 // Dense-table index (icp_dense.hpp).  The grid geometry (ctx->grid) is already decided.
 // KeyT: the sort key's type -- uint32_t when the cell id and at least 6 bits of x position fit 32 bits (build_dense).
 template <typename KeyT>
@@ -188,8 +182,8 @@ int build_dense_keyed(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride
     hipStream_t st = ctx->stream;
     GridParams &gp = ctx->grid;
     const size_t total = (size_t)(gp.dims[0] + 2) * (gp.dims[1] + 2) * (gp.dims[2] + 2);
-    uint32_t *d_misc = ctx->d_misc.as<uint32_t>();
-    uint32_t *h_misc = ctx->h_smisc.as<uint32_t>() + 32;   // (+ 8, + 10: pinned words of the counts' own -- an alignment's sums land in h_sums)
+    uint32_t *stats = ctx->d_misc.as<uint32_t>() + kMiscStats;
+    uint32_t *h_stats = ctx->h_smisc.as<uint32_t>() + kHsCounts;   // (pinned words of the counts' own -- an alignment's sums land in h_sums)
     RSREG_HIP(ctx, ctx->d_keys.reserve(n * sizeof(KeyT)));
     RSREG_HIP(ctx, ctx->d_keys_alt.reserve(n * sizeof(KeyT)));
     const DenseDev g = dense_dev(ctx, max_dist);
@@ -239,7 +233,7 @@ int build_dense_keyed(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride
     if (one_tail) {
         uint32_t *scr = ctx->d_tmp.as<uint32_t>();
         k_dense_compact<KeyT><<<cplan.blocks, kCompactBlock, 0, st>>>(keys2, vals2, d_pts, stride, nfin, xbits, ctx->d_tgt_sorted.as<float4>(),
-                                                                      ctx->d_pos_of.as<uint32_t>(), cellslot, cellpos, d_misc + 8, h_misc + 8,
+                                                                      ctx->d_pos_of.as<uint32_t>(), cellslot, cellpos, stats, h_stats,
                                                                       gp.table_sparse ? table : nullptr,
                                                                       reinterpret_cast<unsigned long long *>(scr + cplan.off_state), scr + cplan.off_ticket);
         RSREG_HIP(ctx, hipGetLastError());
@@ -248,18 +242,18 @@ int build_dense_keyed(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride
         RSREG_HIP(ctx, hipGetLastError());
         RSREG_HIP(ctx, (oscan<unsigned long long>(flags, scan, (size_t)nfin, 0ull, scan_scratch, st)));
         k_dense_scatter<KeyT><<<nbf, kBlock, 0, st>>>(keys2, vals2, d_pts, stride, nfin, xbits, flags, scan, ctx->d_tgt_sorted.as<float4>(),
-                                                      ctx->d_pos_of.as<uint32_t>(), cellslot, cellpos, d_misc + 8, h_misc + 8,
+                                                      ctx->d_pos_of.as<uint32_t>(), cellslot, cellpos, stats, h_stats,
                                                       gp.table_sparse ? table : nullptr);
         RSREG_HIP(ctx, hipGetLastError());
     }
     if (!gp.table_sparse) {
-        k_dense_counts<<<nbf, kBlock, 0, st>>>(cellslot, cellpos, d_misc + 8, table);
+        k_dense_counts<<<nbf, kBlock, 0, st>>>(cellslot, cellpos, stats, table);
         RSREG_HIP(ctx, hipGetLastError());
         // counts -> first sorted point of every cell (in place), entry [total] = number of points
         RSREG_HIP(ctx, (oscan<uint32_t>(table, table, total + 1, 0u, scan_scratch, st)));
     }
     // occupancy word of every cell's 27-cell neighbourhood: a query never opens an empty cell
-    k_dense_nbr<<<nbf, kBlock, 0, st>>>(cellslot, d_misc + 8, g.sx, g.sxy, table + (total + 2));
+    k_dense_nbr<<<nbf, kBlock, 0, st>>>(cellslot, stats, g.sx, g.sxy, table + (total + 2));
     RSREG_HIP(ctx, hipGetLastError());
     return RSREG_OK;
 }
@@ -271,7 +265,7 @@ bool count_sort_pays(size_t n, size_t total)
     return tunables().count_sort && total <= std::max<size_t>(32 * n, (size_t)16 << 20) && total < (1ull << 31);
 }
 
-// sources up to this many points (the one-launch load's limit, kPlainSourceMax below) make their target's counting build leave
+// sources up to this many points (the one-launch load's default limit, tunables.hpp: plain_source_max) make their target's counting build leave
 // the occupancy words out when the gate fits into ring 1
 constexpr size_t kSmallSourceForTable = 65536;
 
@@ -280,8 +274,7 @@ int build_dense_counted(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stri
     hipStream_t st = ctx->stream;
     GridParams &gp = ctx->grid;
     const size_t total = (size_t)(gp.dims[0] + 2) * (gp.dims[1] + 2) * (gp.dims[2] + 2);
-    uint32_t *d_misc = ctx->d_misc.as<uint32_t>();
-    uint32_t *h_counts = ctx->h_smisc.as<uint32_t>() + 40;   // pinned words of the counts' own
+    uint32_t *h_counts = ctx->h_smisc.as<uint32_t>() + kHsCounts;   // pinned words of the counts' own
     // the counts are zero between builds (k_cc_scan puts them back); a new or larger buffer, or a build that did not
     // get to its end, starts from a memset
     RSREG_HIP(ctx, ctx->d_cnt.reserve((total + 16) * 4 + 2 * (size_t)kCcMaxSpans * 8));
@@ -297,7 +290,7 @@ int build_dense_counted(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stri
     uint32_t *cellslot = ctx->d_brick.as<uint32_t>(), *cellpos = ctx->d_cellpos.as<uint32_t>();
     uint32_t *table = ctx->d_dense.as<uint32_t>(), *occ = table + (total + 2);
     uint32_t *big = ctx->d_flags.as<uint32_t>();   // (n * 8 bytes: room for every cell beyond kCcSmall records)
-    uint32_t *stats = d_misc + 8;
+    uint32_t *stats = ctx->d_misc.as<uint32_t>() + kMiscStats;
     // per-span totals of the counts (what k_cc_scan's workgroups start from): two sets used in turn, each cleared by the
     // counting kernel of the build before the one that fills it; they lie in front of the counts (zeroed with them)
     const uint32_t chunks = cc_span_chunks(total), spans = cc_spans(total), span = chunks * kCcChunk;
@@ -352,7 +345,7 @@ int target_counts(rsreg_ctx *ctx, bool wait)
     if (wait) RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->counts_pending = false;
     ctx->cnt_dirty = false;   // (k_cc_scan has put the counts back to zero)
-    const uint32_t *h_counts = ctx->h_smisc.as<uint32_t>() + 40;
+    const uint32_t *h_counts = ctx->h_smisc.as<uint32_t>() + kHsCounts;
     GridParams &gp = ctx->grid;
     gp.n_cells = h_counts[0];
     gp.n_points = h_counts[1];
@@ -370,7 +363,7 @@ int build_dense(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doub
     GridParams &gp = ctx->grid;
     gp.dense = 1;
     const size_t total = (size_t)(gp.dims[0] + 2) * (gp.dims[1] + 2) * (gp.dims[2] + 2);
-    RSREG_HIP(ctx, ctx->h_smisc.reserve(64 * sizeof(uint32_t)));
+    RSREG_HIP(ctx, ctx->h_smisc.reserve(kHsWords * sizeof(uint32_t)));
     RSREG_HIP(ctx, ctx->d_vals.reserve(n * 4));
     RSREG_HIP(ctx, ctx->d_vals_alt.reserve(n * 4));
     RSREG_HIP(ctx, ctx->d_flags.reserve(n * 8));
@@ -388,7 +381,7 @@ int build_dense(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doub
     // the searches of gates up to four cells go through the occupancy words only (icp_dense.hpp: dense_far_blocks);
     // the row search of wider or unbounded gates reads table entries of empty cells too and needs all of them
     gp.table_sparse = (gp.max_ring <= 4 && !full_table && !tunables().far_rows) ? 1 : 0;
-    const uint32_t *h_counts = ctx->h_smisc.as<uint32_t>() + 40;
+    const uint32_t *h_counts = ctx->h_smisc.as<uint32_t>() + kHsCounts;
     const bool counted = count_sort_pays(n, total);
     if (counted) {
         gp.xbits = (int)kCcXBits;   // what the crowded cells are ordered by (g.x_slack follows)
@@ -471,9 +464,8 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
     ctx->last_tgt_box.valid = false;
     const bool no_box_cache = !tunables().box_cache;
     if (known.valid && !no_box_cache && n > 0) {
-        RSREG_HIP(ctx, ctx->d_misc.reserve(64 * sizeof(uint32_t)));
-        RSREG_HIP(ctx, ctx->h_sums.reserve(64 * 8));
-        RSREG_HIP(ctx, ctx->d_comm.reserve(1024 * 8 * sizeof(uint32_t) + 64 * sizeof(double)));
+        int rc = reserve_box_scratch(ctx);
+        if (rc) return rc;
         for (int k = 0; k < 3; ++k) { mn[k] = known.mn[k]; mx[k] = known.mx[k]; }
         nfin = known.nfin;
     } else {
@@ -486,7 +478,7 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
     ctx->last_tgt_box.exact = !(known.valid && !no_box_cache && n > 0) || known.exact;   // (measured just now, or what the handle knew)
     uint32_t *d_misc = ctx->d_misc.as<uint32_t>();
     uint32_t *h_misc = ctx->h_sums.as<uint32_t>();
-    const size_t misc_bytes = 16 * sizeof(uint32_t);
+    const size_t misc_bytes = kCounterWords * sizeof(uint32_t);
     ctx->grid_info.n_target_points = nfin;
     if (nfin == 0) {
         ctx->have_target = true;  // an empty index: every search comes back empty
@@ -503,7 +495,7 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
     // the cells of a dense cloud towards ~8 points per occupied cell.
     // the cap is tuned on 10^6-point D435i-like frames; sparser clouds (lower resolution of the same
     // scene: sample spacing ~ n^-1/2) do best with somewhat larger cells (swept at 50 k and 300 k points)
-    const double cap = cell_cap_from_env() * std::min(3.0, std::max(1.0, std::pow(1.0e6 / std::max<double>(nfin, 1.0e4), 0.28)));
+    const double cap = tunables().cell_cap * std::min(3.0, std::max(1.0, std::pow(1.0e6 / std::max<double>(nfin, 1.0e4), 0.28)));
     double extent = 0;
     for (int k = 0; k < 3; ++k) extent = std::max(extent, (double)mx[k] - (double)mn[k]);
     double cell;
@@ -539,12 +531,12 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
     {
         const long long padded = (long long)(gp.dims[0] + 2) * (gp.dims[1] + 2) * (gp.dims[2] + 2);
         // (the dense search addresses points by 32-bit byte offsets: 16 B x 2^28)
-        if (padded <= dense_cell_budget() && (unsigned long long)nfin + 4ull < (1ull << 28)) return build_dense(ctx, d_pts, n, stride, max_dist, nfin, ev0, ev1);
+        if (padded <= tunables().dense_max_cells && (unsigned long long)nfin + 4ull < (1ull << 28)) return build_dense(ctx, d_pts, n, stride, max_dist, nfin, ev0, ev1);
     }
 
     // ---- sort by (brick, cell in brick, xyz hash)
     // (the brick path counts with atomics in the words k_bbox_final clears; the dense table's kernels only store there)
-    if (known.valid && !no_box_cache && n > 0) RSREG_HIP(ctx, hipMemsetAsync(ctx->d_misc.ptr, 0, 16 * sizeof(uint32_t), st));
+    if (known.valid && !no_box_cache && n > 0) RSREG_HIP(ctx, hipMemsetAsync(ctx->d_misc.ptr, 0, misc_bytes, st));
     RSREG_HIP(ctx, ctx->d_keys.reserve(n * 8));
     RSREG_HIP(ctx, ctx->d_keys_alt.reserve(n * 8));
     RSREG_HIP(ctx, ctx->d_vals.reserve(n * 4));
@@ -588,11 +580,12 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
     RSREG_HIP(ctx, hipMemsetAsync(brickmask, 0, ((size_t)nfin + 1) * 8, st));
     k_scatter_sorted<<<nbf, kBlock, 0, st>>>(keys2, vals2, d_pts, stride, nfin, keep, cstart, bstart, pos, cid, bid,
                                              ctx->d_tgt_sorted.as<float4>(), ctx->d_cellpos.as<uint32_t>(), brickkey, brickmask,
-                                             brickbase, d_misc + 8);
+                                             brickbase, d_misc + kMiscStats);
     RSREG_HIP(ctx, hipGetLastError());
     RSREG_HIP(ctx, hipMemcpyAsync(h_misc, d_misc, misc_bytes, hipMemcpyDeviceToHost, st));
     RSREG_HIP(ctx, hipStreamSynchronize(st));
-    const uint32_t n_unique = h_misc[8], n_cells = h_misc[9], n_bricks = h_misc[11];
+    const uint32_t *h_stats = h_misc + kMiscStats;   // (k_scatter_sorted's stats[0 .. 3], copied home with the head of d_misc)
+    const uint32_t n_unique = h_stats[0], n_cells = h_stats[1], n_bricks = h_stats[3];
     gp.n_points = n_unique;
     gp.n_cells = n_cells;
     gp.n_bricks = n_bricks;
@@ -606,7 +599,7 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
     k_brick_insert<<<div_up(n_bricks, kBlock), kBlock, 0, st>>>(brickkey, brickmask, brickbase, n_bricks,
                                                                 ctx->d_table.as<BrickEntry>(), gp.table_mask);
     RSREG_HIP(ctx, hipGetLastError());
-    k_max_cell_count<<<div_up(n_cells, kBlock), kBlock, 0, st>>>(ctx->d_cellpos.as<uint32_t>(), n_cells, d_misc + 10);
+    k_max_cell_count<<<div_up(n_cells, kBlock), kBlock, 0, st>>>(ctx->d_cellpos.as<uint32_t>(), n_cells, d_misc + kMiscMaxCell);
     RSREG_HIP(ctx, hipGetLastError());
     if (ctx->profiling) (void)hipEventRecord(ev1, st);
     RSREG_HIP(ctx, hipMemcpyAsync(h_misc, d_misc, misc_bytes, hipMemcpyDeviceToHost, st));
@@ -617,7 +610,7 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
     gi.cell_size = gp.cell;
     gi.n_unique_points = n_unique;
     gi.n_cells = n_cells;
-    gi.max_points_per_cell = h_misc[10];
+    gi.max_points_per_cell = h_misc[kMiscMaxCell];
     gi.index_kind = 0;
     gi.index_bytes = (uint64_t)n_unique * sizeof(float4) + (uint64_t)slots * sizeof(BrickEntry) + ((uint64_t)n_cells + 1) * 4;
     if (ctx->profiling) {
@@ -691,19 +684,20 @@ int join_source(rsreg_ctx *ctx)
         ctx->n_work = (uint32_t)ctx->n_source;
         return RSREG_OK;
     }
-    RSREG_HIP(ctx, hipEventSynchronize(ctx->ev_src_done));
-    ctx->n_work = ctx->h_smisc.as<uint32_t>()[32];
+    RSREG_HIP(ctx, hipEventSynchronize(ctx->src.ev_done));
+    ctx->n_work = ctx->h_smisc.as<uint32_t>()[kHsDistinct];
     return RSREG_OK;
 }
 
-// Sources of at most this many points are searched in the caller's order (k_source_plain).  RSREG_SORT_SMALL=1: never.
-constexpr size_t kPlainSourceMax = 65536;
+// Sources of at most RSREG_PLAIN_SOURCE_MAX points are searched in the caller's order (k_source_plain), and never more than its
+// workgroups have room for a partial box each (d_smisc: kBoxPartialGroups).  RSREG_SORT_SMALL=1: never.
+constexpr size_t kPlainSourceLimit = (size_t)kBoxPartialGroups * kBlock;
 bool source_is_small(size_t n)
 {
-    return n <= tunables().plain_source_max && !tunables().sort_small;
+    return n <= std::min<size_t>(tunables().plain_source_max, kPlainSourceLimit) && !tunables().sort_small;
 }
 
-// The part of a source load that queues work on stream_src (after one round trip for the bounding box); runs on the
+// The part of a source load that queues work on src.stream (after one round trip for the bounding box); runs on the
 // context's worker thread (rsreg_ctx.hpp: SourceWorker) or, with RSREG_NO_WORKER=1, on the caller's.
 // `known`: the box of the cloud handle this source comes from, if the handle has one (by value: ctx->next_src_box belongs
 // to the caller's thread alone)
@@ -711,13 +705,13 @@ int load_source_queue(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride
 {
     {
         RSREG_HIP(ctx, hipSetDevice(ctx->device));   // (this may be the context's worker thread)
-        uint32_t *d_misc = ctx->d_smisc.as<uint32_t>();
-        uint32_t *h_misc = ctx->h_smisc.as<uint32_t>();
+        uint32_t *d_misc = ctx->d_smisc.as<uint32_t>(), *d_distinct = d_misc + kSmiscDistinct, *d_partials = d_misc + kSmiscPartials;
+        uint32_t *h_words = ctx->h_smisc.as<uint32_t>(), *h_distinct = h_words + kHsDistinct;
         if (source_is_small(n)) {
             // one launch, the caller's order -- on the MAIN stream: the streams of a process share a few hardware queues,
             // and a kernel on the source stream can find itself behind a 0.4 ms voxel filter of a side stream
             hipStream_t st = ctx->stream;
-            // (its box and finite count land in pinned words 48 .. 55 behind the stamp `seq`; the ticket word lives in a buffer of its
+            // (its box and finite count land in the pinned words kHsPlainBox behind the stamp `seq`; the ticket word lives in a buffer of its
             // own that is zero between launches)
             const bool box_too = tunables().box_cache;
             if (box_too && !ctx->d_plain_ticket.ptr) {
@@ -727,15 +721,15 @@ int load_source_queue(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride
             ctx->plain_box_seq = box_too ? ++ctx->plain_box_counter : 0u;
             k_source_plain<<<div_up((uint32_t)n, kBlock), kBlock, 0, st>>>(d_raw, stride, (uint32_t)n, ctx->d_src_all.as<float4>(), ctx->d_src.as<float4>(),
                                                                            ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(),
-                                                                           ctx->d_first.as<uint32_t>(), d_misc + 12, h_misc + 32,
-                                                                           box_too ? d_misc + 64 : nullptr, ctx->d_plain_ticket.as<uint32_t>(), h_misc + 48,
+                                                                           ctx->d_first.as<uint32_t>(), d_distinct, h_distinct,
+                                                                           box_too ? d_partials : nullptr, ctx->d_plain_ticket.as<uint32_t>(), h_words + kHsPlainBox,
                                                                            ctx->plain_box_seq);
             RSREG_HIP(ctx, hipGetLastError());
-            RSREG_HIP(ctx, hipEventRecord(ctx->ev_src_done, st));
+            RSREG_HIP(ctx, hipEventRecord(ctx->src.ev_done, st));
             return RSREG_OK;
         }
-        hipStream_t st = ctx->stream_src;
-        RSREG_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_main, 0));
+        hipStream_t st = ctx->src.stream;
+        RSREG_HIP(ctx, hipStreamWaitEvent(st, ctx->src.ev_main, 0));
         float mn[3], mx[3];
         uint32_t nfin = 0;
         const bool no_box_cache = !tunables().box_cache;
@@ -743,7 +737,7 @@ int load_source_queue(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride
             for (int k = 0; k < 3; ++k) { mn[k] = known.mn[k]; mx[k] = known.mx[k]; }
             nfin = known.nfin;
         } else {
-            int rc = device_bbox_on(ctx, st, d_misc, h_misc, d_misc + 64, d_raw, n, stride, mn, mx, &nfin);
+            int rc = device_bbox_on(ctx, st, d_misc, h_words + kHsSrcBox, d_partials, d_raw, n, stride, mn, mx, &nfin);
             if (rc) return rc;
         }
         for (int k = 0; k < 3; ++k) { ctx->last_src_box.mn[k] = mn[k]; ctx->last_src_box.mx[k] = mx[k]; }
@@ -753,7 +747,7 @@ int load_source_queue(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride
         double extent = 0;
         for (int k = 0; k < 3; ++k) extent = std::max(extent, (double)mx[k] - (double)mn[k]);
         // fine Morton resolution (a few mm): consecutive points then form compact blobs
-        float cell = (float)std::max(cell_cap_from_env() / 8.0, extent / 60000.0);
+        float cell = (float)std::max(tunables().cell_cap / 8.0, extent / 60000.0);
         // a 32-bit key (31 bits of Morton code + the invalid bit) halves the bytes the radix sort moves and saves it a pass
         // or two: the cell grows (by at most 2x: the search time moves by +- 1.5 % between 1.5 and 3 mm)
         // until the three axes need 31 bits together
@@ -855,10 +849,10 @@ int load_source_queue(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride
         }
         RSREG_HIP(ctx, (oscan<uint32_t>(keep, pos, n, 0u, ctx->d_stmp.ptr, st)));
         k_source_unique<<<nb, kBlock, 0, st>>>(ctx->d_src_all.as<float4>(), (uint32_t)n, keep, pos, ctx->d_first.as<uint32_t>(),
-                                               ctx->d_uniq_of.as<uint32_t>(), d_misc + 12, h_misc + 32,   // the number of distinct points: read at the join
+                                               ctx->d_uniq_of.as<uint32_t>(), d_distinct, h_distinct,   // the number of distinct points: read at the join
                                                ctx->d_src.as<float4>());
         RSREG_HIP(ctx, hipGetLastError());
-        RSREG_HIP(ctx, hipEventRecord(ctx->ev_src_done, st));
+        RSREG_HIP(ctx, hipEventRecord(ctx->src.ev_done, st));
         ctx->shist_dirty = false;   // (everything of this load is queued: the counts' two sets are where the next load expects them)
     }
     return RSREG_OK;
@@ -868,7 +862,7 @@ int load_source_queue(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride
 // query neighbouring cells) and merges exact copies of a point into one weighted point (the
 // RealSense (0,0,0) pixels are ~11 % of a frame: they are searched once, not 10^5 times).
 // d_perm: sorted position -> caller's index; d_uniq_of: sorted position -> distinct point.
-// Everything after the bounding box (one host sync) is only queued -- on ctx->stream_src, behind whatever the
+// Everything after the bounding box (one host sync) is only queued -- on ctx->src.stream, behind whatever the
 // main stream holds so far -- and joined by join_source: when the caller sets the source before the target (the
 // reference's order, incremental_icp.hpp:57-58) the load runs beside the target's index build.
 int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
@@ -883,11 +877,7 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
     const rsreg::CloudBox known = ctx->next_src_box;
     ctx->next_src_box.valid = false;
     ctx->prep_join();
-    if (!ctx->stream_src) {
-        RSREG_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_src, hipStreamNonBlocking));
-        RSREG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_src_done, hipEventDisableTiming));
-        RSREG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
-    }
+    RSREG_HIP(ctx, ctx->src.ensure());
     RSREG_HIP(ctx, ctx->d_src_all.reserve((n + 1) * sizeof(float4)));
     RSREG_HIP(ctx, ctx->d_src.reserve((n + 1) * sizeof(float4)));
     RSREG_HIP(ctx, ctx->d_cur.reserve((n + 1) * sizeof(float4)));
@@ -914,9 +904,9 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
         }
     }
     RSREG_HIP(ctx, ctx->d_sums.reserve(64 * 8));
-    RSREG_HIP(ctx, ctx->h_sums.reserve(64 * 8));
-    RSREG_HIP(ctx, ctx->d_smisc.reserve((64 + 1024 * 8) * sizeof(uint32_t)));
-    RSREG_HIP(ctx, ctx->h_smisc.reserve(64 * sizeof(uint32_t)));
+    RSREG_HIP(ctx, ctx->h_sums.reserve(kSumsBytes));
+    RSREG_HIP(ctx, ctx->d_smisc.reserve(kSmiscWords * sizeof(uint32_t)));
+    RSREG_HIP(ctx, ctx->h_smisc.reserve(kHsWords * sizeof(uint32_t)));
     ctx->icp_fit_ok = false;   // (a new source: no fitness score until it is aligned)
     ctx->n_source = n;
     ctx->n_work = 0;
@@ -925,7 +915,7 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
     ctx->icp.active = 0;
     if (n) {
         // the raw cloud may have been produced (uploaded, filtered, transformed) on the main stream just now
-        RSREG_HIP(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
+        RSREG_HIP(ctx, hipEventRecord(ctx->src.ev_main, ctx->stream));
         const bool no_worker = !tunables().worker;
         ctx->src_on_worker = false;
         ctx->src_plain = source_is_small(n);
@@ -936,7 +926,7 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
             ctx->src_on_worker = true;   // (until it is joined)
             // the rest -- a bounding-box round trip and ~25 launches -- on the context's worker thread: the caller goes on
             // (to the target's index build, in the reference's order of calls) while the source's queue is being filled
-            if (!ctx->src_worker) ctx->src_worker = new rsreg::SourceWorker();
+            if (!ctx->src_worker) ctx->src_worker.reset(new rsreg::SourceWorker());
             ctx->src_worker->post([ctx, d_raw, n, stride, known] { return load_source_queue(ctx, d_raw, n, stride, known); });
         }
         ctx->src_pending = true;
@@ -1673,14 +1663,13 @@ int update_from_sums(rsreg_ctx *ctx, const double *sums, int *done)
 // on the context's upload stream while the next one is being packed; `stage` / `ev`: the staging buffer of this kind of
 // cloud (source / target: one each, so that the target is packed while the source is still on the link) and the event behind
 // its last piece.  The stream `waiter` is made to wait for that event; the caller's buffer has been read when this returns.
-int upload_packed(rsreg_ctx *ctx, PinnedBuf &stage, hipEvent_t &ev, DevBuf &d_raw, const void *points, size_t n, size_t stride,
+int upload_packed(rsreg_ctx *ctx, PinnedBuf &stage, const Event &ev, DevBuf &d_raw, const void *points, size_t n, size_t stride,
                   hipStream_t waiter, double *ms_pack, double *ms_wait)
 {
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
-    if (!ctx->stream_h2d) RSREG_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_h2d, hipStreamNonBlocking));
-    if (!ev) RSREG_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else RSREG_HIP(ctx, hipEventSynchronize(ev));   // (the staging buffer's last trip over the link is over)
+    RSREG_HIP(ctx, ctx->h2d.ensure());
+    RSREG_HIP(ctx, hipEventSynchronize(ev));   // (the staging buffer's last trip over the link is over; at once if it has made none)
     const auto t1 = clk::now();
     RSREG_HIP(ctx, stage.reserve(n * 12 + 16));
     RSREG_HIP(ctx, d_raw.reserve(n * 12 + 16));
@@ -1696,9 +1685,9 @@ int upload_packed(rsreg_ctx *ctx, PinnedBuf &stage, hipEvent_t &ev, DevBuf &d_ra
                 for (size_t i = lo + a; i < lo + b; ++i) std::memcpy(dst + 3 * i, src + i * stride, 12);
             }
         });
-        RSREG_HIP(ctx, hipMemcpyAsync(d_raw.as<char>() + lo * 12, dst + 3 * lo, (hi - lo) * 12, hipMemcpyHostToDevice, ctx->stream_h2d));
+        RSREG_HIP(ctx, hipMemcpyAsync(d_raw.as<char>() + lo * 12, dst + 3 * lo, (hi - lo) * 12, hipMemcpyHostToDevice, ctx->h2d.stream));
     }
-    RSREG_HIP(ctx, hipEventRecord(ev, ctx->stream_h2d));
+    RSREG_HIP(ctx, hipEventRecord(ev, ctx->h2d.stream));
     RSREG_HIP(ctx, hipStreamWaitEvent(waiter, ev, 0));
     const auto t2 = clk::now();
     if (ms_wait) *ms_wait = std::chrono::duration<double, std::milli>(t1 - t0).count();
@@ -1786,102 +1775,23 @@ int rsreg_ctx_destroy(rsreg_ctx *ctx)
     ctx->prep_join();   // (rsreg_ctx_prepare's thread: what it made is released with everything else below)
     // The helper threads go first, in the order of who waits for whom -- a queued side job waits for the upload worker
     // (side_wait_input), an upload or a download for nothing of the others -- and every stream they fed is drained before
-    // a buffer, an event or a stream is released.
-    if (ctx->src_worker) {
-        ctx->src_worker->shutdown();
-        delete ctx->src_worker;
-        ctx->src_worker = nullptr;
-    }
-    for (rsreg::TicketWorker *w : ctx->side_workers)
+    // the context's members release themselves.
+    if (ctx->src_worker) ctx->src_worker->shutdown();
+    for (auto &w : ctx->side_workers)
         if (w) w->shutdown();
-    if (ctx->up_worker) ctx->up_worker->shutdown();
-    if (ctx->down_worker) ctx->down_worker->shutdown();
+    if (ctx->up.worker) ctx->up.worker->shutdown();
+    if (ctx->down.worker) ctx->down.worker->shutdown();
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stream_src) (void)hipStreamSynchronize(ctx->stream_src);
-    if (ctx->stream_copy) (void)hipStreamSynchronize(ctx->stream_copy);
-    if (ctx->stream_down) (void)hipStreamSynchronize(ctx->stream_down);
+    for (hipStream_t st : {(hipStream_t)ctx->src.stream, (hipStream_t)ctx->up.stream, (hipStream_t)ctx->down.stream, (hipStream_t)ctx->h2d.stream})
+        if (st) (void)hipStreamSynchronize(st);
     for (rsreg_ctx::SideSet &ss : ctx->side_sets)
         if (ss.stream) (void)hipStreamSynchronize(ss.stream);
     rsreg_comm_destroy(ctx);
-    if (ctx->recip) {   // the child context of the reciprocal index runs on this context's stream: it goes first
-        rsreg_ctx_destroy(ctx->recip);
-        ctx->recip = nullptr;
-    }
-    DevBuf *bufs[] = {&ctx->d_tgt_raw, &ctx->d_tgt_sorted, &ctx->d_table, &ctx->d_keys, &ctx->d_keys_alt, &ctx->d_vals,
-                      &ctx->d_vals_alt, &ctx->d_flags, &ctx->d_scan, &ctx->d_cellpos, &ctx->d_dense, &ctx->d_pos_of, &ctx->d_sched, &ctx->d_brick, &ctx->d_perm, &ctx->d_tmp, &ctx->d_plain_ticket,
-                      &ctx->d_misc, &ctx->d_src_raw, &ctx->d_src_all, &ctx->d_uniq_of, &ctx->d_first, &ctx->d_src, &ctx->d_cur, &ctx->d_corr_pos, &ctx->d_corr_d2, &ctx->d_seed,
-                      &ctx->d_partials, &ctx->d_sums, &ctx->d_icp_state, &ctx->d_corr_w, &ctx->d_recip_pts, &ctx->d_vox_in, &ctx->d_vox_out, &ctx->d_vox_cent, &ctx->d_ndt_vox, &ctx->d_ndt_src, &ctx->d_ndt_trans,
-                      &ctx->d_ndt_partials, &ctx->d_ndt_out, &ctx->d_ndt_ctl, &ctx->d_ndt_seg, &ctx->d_comm, &ctx->d_skeys, &ctx->d_skeys_alt, &ctx->d_svals,
-                      &ctx->d_sflags, &ctx->d_sscan, &ctx->d_stmp, &ctx->d_smisc, &ctx->d_shist, &ctx->d_scan_keys, &ctx->d_cnt, &ctx->d_arrived,
-                      &ctx->d_ndt_tgt, &ctx->d_fit_d2, &ctx->d_fit_partials, &ctx->d_fit_sums};
-    if (ctx->stream_h2d) { (void)hipStreamSynchronize(ctx->stream_h2d); (void)hipStreamDestroy(ctx->stream_h2d); }
-    ctx->h_stage_src.release();
-    ctx->h_stage_tgt.release();
-    if (ctx->ev_stage_src) (void)hipEventDestroy(ctx->ev_stage_src);
-    if (ctx->ev_stage_tgt) (void)hipEventDestroy(ctx->ev_stage_tgt);
-    for (hipEvent_t e : ctx->ev_home) (void)hipEventDestroy(e);
-    for (DevBuf *b : bufs) b->release();
-    ctx->h_sums.release();
-    ctx->h_smisc.release();
-    ctx->h_stage.release();
-    ctx->h_ndt.release();
-    ctx->h_ndt_build.release();
-    ctx->h_fit.release();
-    ctx->fit_icp.release();
-    ctx->fit_ndt.release();
-    ctx->knn.release();
-    ctx->filt.release();
-    for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_ndt)
-        if (e) (void)hipEventDestroy(e);
+    if (ctx->recip) rsreg_ctx_destroy(ctx->recip);   // the child context of the reciprocal index runs on this context's stream: it goes first
     cloud_pool_clear(ctx);
-    for (hipEvent_t e : ctx->ev_copy) (void)hipEventDestroy(e);
-    if (ctx->up_worker) {
-        ctx->up_worker->shutdown();
-        delete ctx->up_worker;
-        ctx->up_worker = nullptr;
-    }
-    if (ctx->stream_copy) {
-        (void)hipStreamSynchronize(ctx->stream_copy);
-        (void)hipStreamDestroy(ctx->stream_copy);
-        (void)hipEventDestroy(ctx->ev_copy_gate);
-        for (hipEvent_t e : ctx->ev_up) (void)hipEventDestroy(e);
-    }
-    for (rsreg::PinnedBuf &b : ctx->h_up) b.release();
-    if (ctx->down_worker) {
-        ctx->down_worker->shutdown();
-        delete ctx->down_worker;
-        ctx->down_worker = nullptr;
-    }
-    if (ctx->stream_down) {
-        (void)hipStreamSynchronize(ctx->stream_down);
-        (void)hipStreamDestroy(ctx->stream_down);
-        (void)hipEventDestroy(ctx->ev_down_gate);
-        for (hipEvent_t e : ctx->ev_down) (void)hipEventDestroy(e);
-    }
-    for (rsreg::PinnedBuf &b : ctx->h_down) b.release();
-    for (rsreg::TicketWorker *&w : ctx->side_workers) {
-        if (!w) continue;
-        w->shutdown();
-        delete w;
-        w = nullptr;
-    }
-    for (rsreg_ctx::SideSet &ss : ctx->side_sets) {
-        if (ss.stream) {
-            (void)hipStreamSynchronize(ss.stream);
-            (void)hipStreamDestroy(ss.stream);
-        }
-        for (DevBuf *b : {&ss.out, &ss.keys, &ss.keys_alt, &ss.vals, &ss.vals_alt, &ss.flags, &ss.scan, &ss.cent, &ss.misc, &ss.tmp}) b->release();
-        ss.host.release();
-    }
-    if (ctx->ev_side_gate) (void)hipEventDestroy(ctx->ev_side_gate);
-    if (ctx->stream_src) {
-        (void)hipStreamDestroy(ctx->stream_src);
-        (void)hipEventDestroy(ctx->ev_src_done);
-        (void)hipEventDestroy(ctx->ev_main);
-    }
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
+    const hipStream_t own = ctx->own_stream ? ctx->stream : nullptr;
     delete ctx;
+    if (own) (void)hipStreamDestroy(own);
     return RSREG_OK;
 }
 
@@ -1951,7 +1861,7 @@ int rsreg_icp_set_target(rsreg_ctx *ctx, const void *points, size_t n, size_t st
     // under k_cc_count / k_cc_scatter (a changed point re-derives another slot: a write past d_arrived).  Wait for it first.
     int rc = target_counts(ctx, true);
     if (rc) return rc;
-    rc = upload_packed(ctx, ctx->h_stage_tgt, ctx->ev_stage_tgt, ctx->d_tgt_raw, points, n, stride, ctx->stream, &ht.target_pack, &ht.target_stage_wait);
+    rc = upload_packed(ctx, ctx->h2d.h_tgt, ctx->h2d.ev_tgt, ctx->d_tgt_raw, points, n, stride, ctx->stream, &ht.target_pack, &ht.target_stage_wait);
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     rc = build_grid(ctx, ctx->d_tgt_raw.as<char>(), n, 12, max_correspondence_distance);   // (behind the upload, by the stream's order)
@@ -1974,11 +1884,11 @@ int rsreg_icp_set_source(rsreg_ctx *ctx, const void *points, size_t n, size_t st
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     int rc = join_source(ctx);   // (a load still in flight reads d_src_raw)
     if (rc) return rc;
-    // packed and sent piece by piece on the upload stream; the load itself (stream_src, the worker thread) starts behind the
+    // packed and sent piece by piece on the upload stream; the load itself (src.stream, the worker thread) starts behind the
     // event the main stream is made to wait for.  Nothing is waited for here: the caller goes on to rsreg_icp_set_target,
     // whose cloud is packed (into a staging buffer of its own) while this one is on the link and being sorted
     rsreg_host_timing &ht = ctx->host_timing;
-    rc = upload_packed(ctx, ctx->h_stage_src, ctx->ev_stage_src, ctx->d_src_raw, points, n, stride, ctx->stream, &ht.source_pack, &ht.source_stage_wait);
+    rc = upload_packed(ctx, ctx->h2d.h_src, ctx->h2d.ev_src, ctx->d_src_raw, points, n, stride, ctx->stream, &ht.source_pack, &ht.source_stage_wait);
     if (rc) return rc;
     return load_source(ctx, ctx->d_src_raw.as<char>(), n, 12);
 }
@@ -2112,9 +2022,9 @@ int icp_end(rsreg_ctx *ctx, rsreg_icp_result *result, void *aligned_out, size_t 
         const size_t piece = (size_t)1 << 18;
         const size_t pieces = (n + piece - 1) / piece;
         while (ctx->ev_home.size() < pieces) {
-            hipEvent_t e;
-            RSREG_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ctx->ev_home.push_back(e);
+            Event e;
+            RSREG_HIP(ctx, e.ensure());
+            ctx->ev_home.push_back(std::move(e));
         }
         for (size_t k = 0; k < pieces; ++k) {
             const size_t lo = k * piece, hi = std::min(n, lo + piece);
@@ -2313,11 +2223,11 @@ int rsreg_icp_grid_info(rsreg_ctx *ctx, rsreg_grid_info *info)
 #endif
     if (want_max && ctx->grid.dense == 1 && ctx->grid_info.max_points_per_cell == 0 && ctx->grid.n_points > 0) {
         const size_t total = (size_t)(ctx->grid.dims[0] + 2) * (ctx->grid.dims[1] + 2) * (ctx->grid.dims[2] + 2);
-        uint32_t *d = ctx->d_misc.as<uint32_t>() + 20;
+        uint32_t *d = ctx->d_misc.as<uint32_t>() + kMiscMaxCount;
         uint32_t h = 0;
         RSREG_HIP(ctx, hipMemsetAsync(d, 0, 4, ctx->stream));
         (void)total;
-        k_dense_max_count<<<256, kBlock, 0, ctx->stream>>>(ctx->d_cellpos.as<uint32_t>(), ctx->d_misc.as<uint32_t>() + 8, d);
+        k_dense_max_count<<<256, kBlock, 0, ctx->stream>>>(ctx->d_cellpos.as<uint32_t>(), ctx->d_misc.as<uint32_t>() + kMiscStats, d);
         RSREG_HIP(ctx, hipGetLastError());
         RSREG_HIP(ctx, hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, ctx->stream));
         RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));

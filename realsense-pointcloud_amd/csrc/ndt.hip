@@ -103,8 +103,8 @@ int derivative_pass_pp(NdtRun &r, NdtPassParams &pp, bool store_trans)
     pp.n_vox = ctx->ndt_n_voxels;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ctx->profiling) {
-        for (hipEvent_t &e : ctx->ev_ndt)
-            if (!e) (void)hipEventCreate(&e);
+        for (Event &e : ctx->ev_ndt)
+            (void)e.ensure(hipEventDefault);
         e0 = ctx->ev_ndt[0];
         e1 = ctx->ev_ndt[1];
         (void)hipEventRecord(e0, ctx->stream);
@@ -363,7 +363,7 @@ int rsreg_ndt_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
     ctx->ndt_tgt_n = n;
 
     // ---- bounding box of the finite points (pcl::getMinMax3D)
-    RSREG_HIP(ctx, ctx->d_misc.reserve(64 * 4));
+    RSREG_HIP(ctx, ctx->d_misc.reserve(kMiscWords * sizeof(uint32_t)));
     RSREG_HIP(ctx, ctx->h_ndt.reserve(kNdtHostBytes));
     const char *d_pts = static_cast<const char *>(d_points);
     const size_t pstride = stride;
@@ -384,10 +384,10 @@ int rsreg_ndt_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
     } else if (n) {
         // minima start at all ones, maxima and the count at zero (ordered-float encoding): two memsets, no upload + sync
         RSREG_HIP(ctx, hipMemsetAsync(d_misc, 0xff, 12, st));
-        RSREG_HIP(ctx, hipMemsetAsync(d_misc + 3, 0, 52, st));
+        RSREG_HIP(ctx, hipMemsetAsync(d_misc + kMiscBoxMax, 0, (kCounterWords - kMiscBoxMax) * sizeof(uint32_t), st));
         k_grid_box<<<std::min<uint32_t>(div_up((uint32_t)n, kBlock), 256), kBlock, 0, st>>>(StridedRecords{d_pts, pstride, nullptr}, (uint32_t)n, d_misc);
         RSREG_HIP(ctx, hipGetLastError());
-        RSREG_HIP(ctx, hipMemcpyAsync(h_misc, d_misc, 64, hipMemcpyDeviceToHost, st));
+        RSREG_HIP(ctx, hipMemcpyAsync(h_misc, d_misc, kCounterWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         RSREG_HIP(ctx, hipStreamSynchronize(st));
         if (h_misc[6]) {   // (measured: the handle keeps it)
             for (int k = 0; k < 3; ++k) { ctx->last_ndt_box.mn[k] = ordered_float(h_misc[k]); ctx->last_ndt_box.mx[k] = ordered_float(h_misc[3 + k]); }
@@ -473,21 +473,21 @@ int rsreg_ndt_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
         RSREG_HIP(ctx, hipGetLastError());
     }
     RSREG_HIP(ctx, (oscan<uint32_t>(start, sid, (size_t)nfin, 0u, ctx->d_tmp.ptr, st)));
-    k_ndt_seg_offsets<<<div_up(nfin, kNdtBlock), kNdtBlock, 0, st>>>(start, sid, nfin, seg_begin, d_misc + 8);
+    k_ndt_seg_offsets<<<div_up(nfin, kNdtBlock), kNdtBlock, 0, st>>>(start, sid, nfin, seg_begin, d_misc + kMiscStats);
     RSREG_HIP(ctx, hipGetLastError());
-    RSREG_HIP(ctx, hipMemcpyAsync(h_misc, d_misc, 64, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipMemcpyAsync(h_misc, d_misc, kCounterWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     // A grid of a few dozen leaves (the reference's 1 m resolution): the moments are launched for EVERY leaf of the box, the
     // workgroups beyond the occupied ones leave at once, and the number of occupied leaves comes home with the moments --
     // one round trip instead of two.
     const bool few_leaves = n_leaves <= 256 && ctx->ndt_centroid_mode != 1;
     if (!few_leaves) RSREG_HIP(ctx, hipStreamSynchronize(st));
-    const uint32_t nseg_launch = few_leaves ? (uint32_t)std::min<unsigned long long>(n_leaves, nfin) : h_misc[8];
+    const uint32_t nseg_launch = few_leaves ? (uint32_t)std::min<unsigned long long>(n_leaves, nfin) : h_misc[kMiscStats];
 
     // ---- per-voxel moments on the device, one block per occupied leaf
     const uint32_t n_parts = nseg_launch <= 2048 ? 16u : 1u;   // (the reference's 1 m voxels: two dozen of 10^4 points each)
     RSREG_HIP(ctx, ctx->d_ndt_out.reserve(std::max<size_t>((size_t)nseg_launch * n_parts * 10 * 8, 64 * 8)));
     k_ndt_voxel_stats<<<nseg_launch * n_parts, kNdtBlock, 0, st>>>(vals2, seg_begin, d_pts, pstride, n_parts, ctx->d_ndt_out.as<double>(),
-                                                                   few_leaves ? d_misc + 8 : nullptr);
+                                                                   few_leaves ? d_misc + kMiscStats : nullptr);
     RSREG_HIP(ctx, hipGetLastError());
     // (through pinned memory: [partial moments | PCL-mode centroid sums | later the finished table])
     const size_t n_parts_d = (size_t)nseg_launch * n_parts * 10, parts_bytes = n_parts_d * 8;
@@ -505,7 +505,7 @@ int rsreg_ndt_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
         csum = reinterpret_cast<const float *>(ctx->h_ndt_build.as<char>() + csum_off);
     }
     RSREG_HIP(ctx, hipStreamSynchronize(st));
-    const uint32_t nseg = h_misc[8];   // (few leaves: it came home with the moments)
+    const uint32_t nseg = h_misc[kMiscStats];   // (few leaves: it came home with the moments)
     if (nseg > nseg_launch) return fail(ctx, RSREG_ERR_STATE, "ndt: more occupied leaves than the grid has");
 
     // ---- host: mean, single-pass covariance, eigenvalue floor, inverse (App. A.6)

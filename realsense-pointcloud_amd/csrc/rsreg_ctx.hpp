@@ -11,6 +11,7 @@
 #include <string>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <cmath>
 #include <thread>
@@ -19,68 +20,53 @@
 #include "../../include/rsreg.h"
 #include "host_linalg.hpp"
 #include "tunables.hpp"
+#include "owned.hpp"
 #include "workers.hpp"
 
 namespace rsreg {
 
-// Growable device allocation; never shrinks, so steady-state calls allocate nothing.
-struct DevBuf {
-    void *ptr = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&ptr, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-    }
-    template <typename T> T *as() const { return static_cast<T *>(ptr); }
-};
-
 // Buffers of dropped device clouds, kept for the clouds to come (cloud.hip).  `limit`: bytes kept at most
 // (RSREG_CLOUD_POOL_MB, default 4096; 0 = every drop is a hipFree).
 struct CloudPool {
-    struct Slot {
-        void *ptr;
-        size_t cap;
-    };
-    std::vector<Slot> slots;
+    std::vector<DevBuf> slots;
     size_t held = 0;
     size_t limit = (size_t)tunables().cloud_pool_mb << 20;
 };
 
-struct PinnedBuf {
-    void *ptr = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipHostMalloc(&ptr, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (ptr) (void)hipHostFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-    }
-    template <typename T> T *as() const { return static_cast<T *>(ptr); }
-};
+// ---- The words of the small scratch buffers (uint32 words).  Kernels take plain pointers into them and index from there
+// (stats[k], box[k]); the host spells every offset with these names.  A box is min xyz | max xyz (ordered uints) | finite
+// count | a stamp or spare word.
+constexpr uint32_t kBoxWords = 8;
+constexpr uint32_t kBoxPartialGroups = 1024;   // k_bbox / k_source_plain leave one partial box per workgroup: so many at most
+constexpr uint32_t kBoxPartialWords = kBoxPartialGroups * kBoxWords;
+constexpr uint32_t kCounterWords = 16;         // the head of a device misc buffer: cleared by k_bbox_final, copied home by the brick / NDT builds
+// d_misc (main stream, the caller's thread; voxel.hip uses the buffer for its own words between index builds)
+constexpr uint32_t kMiscBoxMax = 3;                 // NDT's k_grid_box: maxima and count behind the three minima
+constexpr uint32_t kMiscStats = 8;                  // [8, 12) an index build's counts: the kernels' stats[0 .. 3]
+constexpr uint32_t kMiscMaxCell = kMiscStats + 2;   //   brick build: k_max_cell_count
+constexpr uint32_t kMiscMaxCount = 20;              // RSREG_DIAG: k_dense_max_count
+constexpr uint32_t kMiscWords = 64;
+// d_smisc (the source load's: src.stream and the source worker, or the main stream for a plain load)
+constexpr uint32_t kSmiscDistinct = 12;             // k_source_unique / k_source_plain: distinct points
+constexpr uint32_t kSmiscPartials = 64;             // [64, 64 + 1024 * 8) the source's box partials
+constexpr uint32_t kSmiscWords = kSmiscPartials + kBoxPartialWords;
+// h_smisc (pinned).  Two threads write disjoint words: the source worker its box, the caller's thread the rest.
+constexpr uint32_t kHsSrcBox = 0;                   // [0, 8)   k_bbox_final on src.stream: read by the source worker
+constexpr uint32_t kHsDistinct = 32;                // [32]     k_source_unique / k_source_plain: read at the join (caller)
+constexpr uint32_t kHsCounts = 40;                  // [40, 43) the target build's counts, k_cc_scan [0] [1], k_dense_compact / _scatter [0] [2] (caller)
+constexpr uint32_t kHsCountWords = 3;
+constexpr uint32_t kHsPlainBox = 48;                // [48, 56) k_source_plain's box and stamp: harvest_source_box (caller)
+constexpr uint32_t kHsWords = 64;
+// the target's box borrows its scratch: the head of h_sums (pinned double[64]) is where the box, or the head of d_misc, lands;
+// d_comm holds the partials behind the 64 doubles of an allreduce
+constexpr size_t kSumsBytes = 64 * sizeof(double);
+constexpr size_t kCommBytes = 64 * sizeof(double);
+constexpr size_t kCommPartialsAt = kCommBytes;      // (bytes)
+static_assert(kMiscBoxMax < kMiscStats && kMiscStats + 4 <= kCounterWords && kCounterWords <= kMiscMaxCount && kMiscMaxCount < kMiscWords, "d_misc");
+static_assert(kSmiscDistinct < kCounterWords && kCounterWords <= kSmiscPartials, "d_smisc");
+static_assert(kHsSrcBox + kBoxWords <= kHsDistinct && kHsDistinct < kHsCounts && kHsCounts + kHsCountWords <= kHsPlainBox &&
+              kHsPlainBox + kBoxWords <= kHsWords, "h_smisc");
+static_assert(kCounterWords * sizeof(uint32_t) <= kSumsBytes, "h_sums");
 
 // Bounding box and number of the finite points of a cloud: what an index build or a source load starts from (one kernel
 // pair and a round trip to the host).  A cloud handle keeps the box of its records as they are (cloud.hip: version), so a
@@ -195,11 +181,6 @@ struct PointGrid {
     DevBuf d_mask;                 // block-major only: uint64 per block, which of its 64 cells hold a point
     DevBuf d_scan;                 // the prefix sums' scratch
     DevBuf d_box;                  // the box / count of the finite points (ordered uints)
-    void release()
-    {
-        for (DevBuf *b : {&d_pts, &d_start, &d_count, &d_mask, &d_scan, &d_box}) b->release();
-        built = false;
-    }
 };
 
 // Scratch of the cloud filters (filters.hip), per record of the cloud being filtered; not part of an index
@@ -209,11 +190,6 @@ struct FilterScratch {
     DevBuf d_sums;                 // the threshold's two f64 sums
     DevBuf d_out;                  // the kept records, before the output cloud takes them
     PinnedBuf host;
-    void release()
-    {
-        for (DevBuf *b : {&d_dist, &d_flags, &d_pos, &d_sums, &d_out}) b->release();
-        host.release();
-    }
 };
 
 struct IcpState {
@@ -239,6 +215,9 @@ struct IcpState {
 
 }  // namespace rsreg
 
+// Every buffer, event and stream below releases itself (owned.hpp), and rsreg_ctx_destroy deletes the context only after
+// the helper threads have stopped and every stream has been drained: the order of the members does not matter.  The main
+// stream alone is a raw handle (it may be the caller's) and is destroyed last.
 struct rsreg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -281,6 +260,10 @@ struct rsreg_ctx {
     bool counts_pending = false;
     size_t counts_total = 0, counts_n = 0;   // (table entries and input points of that build: for index_bytes)
     size_t n_target_raw = 0;
+    rsreg::DevBuf d_scan_keys;           // no-index search (scan_target): one (distance, index) key per source point
+    const char *scan_raw = nullptr;      // ... and the records the index is built from if an alignment needs it after all
+    size_t scan_stride = 0;
+    uint64_t tgt_cloud_id = 0, tgt_cloud_version = 0;   // the device cloud the ICP target index was built from (0: none)
 
     // ---- ICP source
     bool have_source = false;
@@ -290,20 +273,23 @@ struct rsreg_ctx {
     size_t n_work = 0;            // distinct source points the iteration works on (exact copies merged)
     // the source is loaded on a stream of its own (so that it runs beside the target's index build when the
     // caller sets the source first, as the reference does) and joined where the alignment begins
-    hipStream_t stream_src = nullptr;
-    hipEvent_t ev_src_done = nullptr, ev_main = nullptr;
+    struct SourceLane {
+        rsreg::Stream stream;
+        rsreg::Event ev_done, ev_main;   // the load is done; what the main stream held when the load was asked for
+        hipError_t ensure() { return rsreg::ensure_lane(stream, {&ev_done, &ev_main}); }
+    } src;
     bool src_pending = false;
     rsreg::DevBuf d_plain_ticket; // k_source_plain's ticket word (zero between launches)
     uint32_t plain_box_seq = 0, plain_box_counter = 0;   // the stamp the pending plain load leaves behind its box in h_smisc[48 .. 55] (0: none)
     bool src_plain = false;       // the pending load is k_source_plain on the MAIN stream (every record a query of its own): nothing to wait for at the join
     bool src_on_worker = false;   // ... and its launches are being queued by the context's worker thread right now
-    rsreg::SourceWorker *src_worker = nullptr;   // (created with the first source load; RSREG_NO_WORKER=1: never, the load runs on the caller's thread)
-    // everything of a pending source load has been queued on stream_src (so that ev_src_done is the event of THIS load)
+    std::unique_ptr<rsreg::SourceWorker> src_worker;   // (created with the first source load; RSREG_NO_WORKER=1: never, the load runs on the caller's thread)
+    // everything of a pending source load has been queued on src.stream (so that src.ev_done is the event of THIS load)
     int source_enqueued() { return src_worker ? src_worker->wait() : 0; }
     rsreg::DevBuf d_skeys, d_skeys_alt, d_svals, d_sflags, d_sscan, d_stmp, d_smisc;   // its scratch (the target build has its own)
     rsreg::DevBuf d_shist;        // two sets of digit histograms of the source's sort, used in turn (k_source_keys_hist); the worker's
     bool shist_flip = false, shist_dirty = false;
-    rsreg::PinnedBuf h_smisc;
+    rsreg::PinnedBuf h_smisc;     // (the words of d_smisc / h_smisc: kSmisc*, kHs* above)
     rsreg::DevBuf d_src_all;      // float4 {x,y,z,valid} of every source point, spatially sorted
     rsreg::DevBuf d_uniq_of;      // uint32: sorted position -> distinct point id
     rsreg::DevBuf d_first;        // uint32[n_work+1]: first sorted position of each distinct point
@@ -328,12 +314,16 @@ struct rsreg_ctx {
     rsreg::CloudBox next_ndt_box, last_ndt_box;   // the same for the NDT target's grid (rsreg_ndt_set_target_cloud)
 
     rsreg::PinnedBuf h_stage;     // pinned staging for H2D / D2H of clouds
-    // host clouds of rsreg_icp_set_source / _set_target: a staging buffer each, the upload stream, the event behind each buffer's last copy
-    rsreg::PinnedBuf h_stage_src, h_stage_tgt;
-    hipStream_t stream_h2d = nullptr;
-    hipEvent_t ev_stage_src = nullptr, ev_stage_tgt = nullptr;
+    // host clouds of rsreg_icp_set_source / _set_target: the upload stream, a staging buffer for each kind of cloud and the
+    // event behind its last copy
+    struct StageLane {
+        rsreg::Stream stream;
+        rsreg::Event ev_src, ev_tgt;
+        rsreg::PinnedBuf h_src, h_tgt;
+        hipError_t ensure() { return rsreg::ensure_lane(stream, {&ev_src, &ev_tgt}); }
+    } h2d;
     rsreg_host_timing host_timing{};
-    std::vector<hipEvent_t> ev_home;   // one per piece of an aligned cloud on its way to the host (rsreg_icp_end)
+    std::vector<rsreg::Event> ev_home;   // one per piece of an aligned cloud on its way to the host (rsreg_icp_end)
     rsreg::IcpState icp;
 
     // ---- ApproximateVoxelGrid on the device (voxel.hip)
@@ -348,47 +338,27 @@ struct rsreg_ctx {
     static constexpr int kSideWorkers = 2;
     static constexpr int kSideSets = 2 * kSideWorkers;
     struct SideSet {
-        hipStream_t stream = nullptr;
+        rsreg::Stream stream;
         rsreg::DevBuf out, keys, keys_alt, vals, vals_alt, flags, scan, cent, misc, tmp;
         rsreg::PinnedBuf host;
     } side_sets[kSideSets];
     int side_turn[kSideWorkers] = {0, 0};   // which of its two sets a worker's next job takes
     int side_rr = 0;                          // the worker of the next job that follows no other
-    hipEvent_t ev_side_gate = nullptr;
-    rsreg::TicketWorker *side_workers[kSideWorkers] = {nullptr, nullptr};   // (queue those jobs: rsreg_cloud_filter_async returns at once)
+    rsreg::Event ev_side_gate;
+    std::unique_ptr<rsreg::TicketWorker> side_workers[kSideWorkers];   // (queue those jobs: rsreg_cloud_filter_async returns at once)
 
     // ---- NDT
     bool have_ndt_target = false;
     double ndt_resolution = 0;
     int ndt_centroid_mode = 0;              // 1: PCL's float running sum per voxel (rsreg_ndt_set_centroid_mode)
     int ndt_n_voxels = 0;
-    rsreg::DevBuf d_scan_keys;           // no-index search (scan_target): one (distance, index) key per source point
-    const char *scan_raw = nullptr;      // ... and the records the index is built from if an alignment needs it after all
-    size_t scan_stride = 0;
-    uint64_t tgt_cloud_id = 0, tgt_cloud_version = 0;   // the device cloud the ICP target index was built from (0: none)
-    rsreg::CloudPool cloud_pool;
-    std::vector<hipEvent_t> ev_copy;   // one per piece of a cloud download in flight (cloud.hip)
-    // rsreg_cloud_upload_async: a copy stream, two pinned staging buffers used in turn, the event behind the last copy
-    // out of each, and the event that lets the copy stream start only after what the main stream holds
-    hipStream_t stream_copy = nullptr;
-    hipEvent_t ev_copy_gate = nullptr, ev_up[2] = {nullptr, nullptr};
-    rsreg::PinnedBuf h_up[2];
-    bool up_busy[2] = {false, false};   // (these two: the upload worker's, once it exists)
-    int up_next = 0;
-    rsreg::TicketWorker *up_worker = nullptr;
-    // rsreg_cloud_download_async: a download stream, three pinned staging buffers with an event each, the copy-out thread
-    hipStream_t stream_down = nullptr;
-    hipEvent_t ev_down_gate = nullptr, ev_down[rsreg::DownloadWorker::kSlots] = {};
-    rsreg::PinnedBuf h_down[rsreg::DownloadWorker::kSlots];
-    int down_next = 0;
-    rsreg::DownloadWorker *down_worker = nullptr;
     uint64_t ndt_seq = 0;  // derivative passes launched; the final reduce stamps it into h_ndt
     rsreg::DevBuf d_ndt_vox;      // per voxel: 3 mean + 9 icov doubles + centroid float3 ...
     rsreg::DevBuf d_ndt_src, d_ndt_trans, d_ndt_partials, d_ndt_out;
     rsreg::DevBuf d_ndt_ctl;      // a line search in one launch (ndt_kernels.hpp: NdtLsCtl): its state, the next pass's parameters, its counters
     bool ndt_ls_failed = false;   // ... ran into one of its bounded waits once: the host advances the searches of this context from then on
     rsreg::DevBuf d_ndt_seg;      // first sorted point of every occupied leaf (NDT's own: d_cellpos belongs to the live ICP hash index)
-    hipEvent_t ev_ndt[2] = {nullptr, nullptr};   // NDT's own event pair (the pool's indices belong to an ICP begin..end)
+    rsreg::Event ev_ndt[2];   // NDT's own event pair (the pool's indices belong to an ICP begin..end)
     std::vector<double> ndt_mean_cov_icov;   // 21 per voxel (host copy)
     std::vector<int> ndt_counts;
     std::vector<float> ndt_centroid;         // 3 per voxel
@@ -405,24 +375,50 @@ struct rsreg_ctx {
     rsreg::DevBuf d_fit_d2, d_fit_partials, d_fit_sums;
     rsreg::PinnedBuf h_fit;
 
-    // ---- RCCL
+    // ---- device-resident clouds (cloud.hip)
+    rsreg::CloudPool cloud_pool;
+    std::vector<rsreg::Event> ev_copy;   // one per piece of a cloud download in flight
+    // rsreg_cloud_upload_async: a copy stream, the event that lets it start only after what the main stream holds, two pinned
+    // staging buffers used in turn and the event behind the last copy out of each
+    struct UploadLane {
+        rsreg::Stream stream;
+        rsreg::Event ev_gate, ev[2];
+        rsreg::PinnedBuf h[2];
+        bool busy[2] = {false, false};   // (these two: the upload worker's, once it exists)
+        int next = 0;
+        std::unique_ptr<rsreg::TicketWorker> worker;
+        hipError_t ensure() { return rsreg::ensure_lane(stream, {&ev_gate, &ev[0], &ev[1]}); }
+    } up;
+    // rsreg_cloud_download_async: a download stream, its gate, pinned staging buffers with an event each, the copy-out threads
+    struct DownloadLane {
+        static constexpr int kSlots = rsreg::DownloadWorker::kSlots;
+        rsreg::Stream stream;
+        rsreg::Event ev_gate, ev[kSlots];
+        rsreg::PinnedBuf h[kSlots];
+        int next = 0;
+        std::unique_ptr<rsreg::DownloadWorker> worker;
+        hipError_t ensure() { return rsreg::ensure_lane(stream, {&ev_gate, &ev[0], &ev[1], &ev[2], &ev[3]}); }
+    } down;
+    static_assert(DownloadLane::kSlots == 4, "DownloadLane::ensure names every slot's event");
     // rsreg_ctx_prepare: what a frame loop is about to need, made on a thread of its own while the caller goes on; whoever is
     // about to create one of these lazily joins that thread first (prep_join) and finds them there
     std::thread prep_thread;
     rsreg::DevBuf prep_model;     // a device buffer for the merged model, handed to the cloud pool at the join
-    int prep_rc = 0;
+    int prep_rc = 0;              // the first HIP error of that thread: reported (fail) by prep_join
     void prep_join();
     std::thread records_copy;     // rsreg_icp_align_records: the caller's source records on their way into aligned_out (joined by icp_end)
+
+    // ---- RCCL
     void *comm = nullptr;         // ncclComm_t
     int rank = 0, nranks = 1;
     rsreg::DevBuf d_comm;
 
     // ---- profiling events
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<rsreg::Event> ev_pool;
     size_t ev_used = 0;
     std::vector<std::pair<size_t, size_t>> ev_nn, ev_reduce, ev_transform, ev_allreduce;
 
-    // ---- PassThrough / StatisticalOutlierRemoval (filters.hip): index and scratch of their own (last: nothing above moves)
+    // ---- PassThrough / StatisticalOutlierRemoval (filters.hip): index and scratch of their own
     rsreg::PointGrid knn;            // rebuilt by every k-NN call from the cloud it is given
     rsreg::FilterScratch filt;
 };

@@ -21,7 +21,7 @@ namespace rsreg {
 // thread of the context's own, so that the caller's thread goes straight on to the target's index build
 // (incremental_icp.hpp:57-58: setInputSource, then setInputTarget): the two queues are then FILLED side by side, not only
 // drained side by side.  One job at a time; whoever needs the source (or hands one of its buffers on) waits for the
-// job to have queued everything first (wait), then for the GPU as before (ev_src_done).
+// job to have queued everything first (wait), then for the GPU as before (src.ev_done).
 struct SourceWorker {
     std::thread th;
     std::mutex m;
@@ -73,6 +73,7 @@ struct SourceWorker {
         }
         if (th.joinable()) th.join();
     }
+    ~SourceWorker() { shutdown(); }
 };
 
 // A copy of megabytes whose destination nobody reads soon -- a pinned staging buffer on its way to the DMA engine, a result the
@@ -260,6 +261,7 @@ struct DownloadWorker {
         for (std::thread &t : th)
             if (t.joinable()) t.join();
     }
+    ~DownloadWorker() { shutdown(); }
 };
 
 // Jobs run one after the other on a thread of their own, each with a ticket the poster can wait for.  The uploads that
@@ -329,8 +331,8 @@ struct TicketWorker {
         }
         if (th.joinable()) th.join();
     }
+    ~TicketWorker() { shutdown(); }
 };
-
 
 inline HostPool &host_pool()
 {
