@@ -80,13 +80,17 @@ static void orc_svd_jacobi(const double *A, int n, double *U, double *s, double 
             for (int i = 0; i < n; i++) U[i * n + k] = 0.0;
         }
     }
-    /* complete U to a full orthonormal basis (Gram-Schmidt against unit vectors) */
+    /* complete U to a full orthonormal basis: column k of V orthogonalised against the columns found so far, so that
+     * U V^T does nothing where A says nothing (collinear matches that coincide give the identity, not a spin about
+     * the line); the best unit vector instead when less than a squared norm of 1/64 is left of V's column */
     for (int k = rank; k < n; k++) {
         double best[6];
         double bestn = -1;
-        for (int e = 0; e < n; e++) {
+        int from_v = 0;
+        for (int e = -1; e < n; e++) {
+            if (e >= 0 && from_v) continue;
             double v[6];
-            for (int i = 0; i < n; i++) v[i] = (i == e) ? 1.0 : 0.0;
+            for (int i = 0; i < n; i++) v[i] = e < 0 ? V[i * n + k] : ((i == e) ? 1.0 : 0.0);
             for (int pass = 0; pass < 2; pass++)
                 for (int m = 0; m < k; m++) {
                     double d = 0;
@@ -95,7 +99,8 @@ static void orc_svd_jacobi(const double *A, int n, double *U, double *s, double 
                 }
             double nn = 0;
             for (int i = 0; i < n; i++) nn += v[i] * v[i];
-            if (nn > bestn) { bestn = nn; memcpy(best, v, sizeof(double) * n); }
+            if (e < 0) from_v = nn > 0.015625;
+            if (e < 0 ? from_v : nn > bestn) { bestn = nn; memcpy(best, v, sizeof(double) * n); }
         }
         double inv = 1.0 / sqrt(bestn);
         for (int i = 0; i < n; i++) U[i * n + k] = best[i] * inv;

@@ -121,12 +121,15 @@ template <int N> RSREG_HD inline void jacobi_svd(const double *A, SvdResult<N> &
             for (int i = 0; i < N; ++i) out.U[i * N + k] = 0.0;
         }
     }
-    // complete U with unit vectors orthogonalised against the columns found so far
+    // complete U: column k of V, else the best unit vector, orthogonalised against the columns found so far (the rule
+    // and its reason: complete_u3 below)
     for (int k = rank; k < N; ++k) {
         double best[N], bestn = -1;
-        for (int e = 0; e < N; ++e) {
+        bool from_v = false;
+        for (int e = -1; e < N; ++e) {
+            if (e >= 0 && from_v) continue;
             double v[N];
-            for (int i = 0; i < N; ++i) v[i] = i == e ? 1.0 : 0.0;
+            for (int i = 0; i < N; ++i) v[i] = e < 0 ? out.V[i * N + k] : (i == e ? 1.0 : 0.0);
             for (int pass = 0; pass < 2; ++pass)
                 for (int m = 0; m < k; ++m) {
                     double d = 0;
@@ -135,7 +138,8 @@ template <int N> RSREG_HD inline void jacobi_svd(const double *A, SvdResult<N> &
                 }
             double nn = 0;
             for (int i = 0; i < N; ++i) nn += v[i] * v[i];
-            if (nn > bestn) { bestn = nn; for (int i = 0; i < N; ++i) best[i] = v[i]; }
+            if (e < 0) from_v = nn > 0.015625;
+            if (e < 0 ? from_v : nn > bestn) { bestn = nn; for (int i = 0; i < N; ++i) best[i] = v[i]; }
         }
         const double inv = 1.0 / sqrt(bestn);
         for (int i = 0; i < N; ++i) out.U[i * N + k] = best[i] * inv;
@@ -148,10 +152,21 @@ template <int N> RSREG_HD inline void jacobi_svd(const double *A, SvdResult<N> &
 // reciprocal of its norm (one division per column instead of three).
 RSREG_HD inline double pick3(double a0, double a1, double a2, int i) { return i == 0 ? a0 : (i == 1 ? a1 : a2); }
 
-// the columns of U (row-major 3 x 3) from `rank` on: unit vectors orthogonalised against the columns found so far (a
-// cross-covariance of rank < 3: coplanar or collinear matches).  Shared by jacobi_svd3 and its lane-parallel twin on the
-// device (icp_kernels.hpp: umeyama_wave).
-RSREG_HD inline void complete_u3(double *U, int rank)
+// the columns of U (row-major 3 x 3) from `rank` on (a cross-covariance of rank < 3: coplanar or collinear matches, or
+// none that differ).  Shared by jacobi_svd3 and its lane-parallel twin on the device (icp_kernels.hpp: umeyama_wave).
+//
+// What the null space does: where the matches say nothing, the rotation R = U S V^T does nothing.  Column k of U is column k
+// of V (the ordered one, row-major 3 x 3) orthogonalised against the columns of U found so far, so that R maps the null
+// directions of the source onto themselves as far as the data allows: collinear matches that already coincide give R = I,
+// and moved ones the turn that takes one line onto the other, without a spin about it.  Rank 2 has one answer either way
+// (the normal, its sign fixed by the determinant rule in umeyama_from_sums).  Only when V's column lies within 7 degrees
+// of the columns found (what is left of it has a squared norm <= 1/64: a turn of more than 83 degrees) is it replaced by the
+// unit vector that keeps the largest norm.  What is left of a candidate may be an eighth of it: the first projection then
+// leaves 8 times its rounding error of the columns found in the result, and the second pass takes that out again (two
+// passes are enough for any candidate that keeps a norm well above the rounding error).  Rank 0 never gets here with a V other than the
+// identity: jacobi_svd3 resets it, so that R = I whatever the iteration started from (Eigen starts from U = V = I and has
+// nothing to rotate).
+RSREG_HD inline void complete_u3(double *U, int rank, const double *V)
 {
 #pragma clang fp contract(off)
     constexpr int N = 3;
@@ -159,11 +174,13 @@ RSREG_HD inline void complete_u3(double *U, int rank)
     for (int k = 0; k < N; ++k) {
         if (k < rank) continue;
         double best[3] = {0, 0, 0}, bestn = -1;
+        bool from_v = false;
 #pragma unroll
-        for (int e = 0; e < N; ++e) {
+        for (int e = -1; e < N; ++e) {
+            if (e >= 0 && from_v) continue;
             double v[3];
 #pragma unroll
-            for (int i = 0; i < N; ++i) v[i] = i == e ? 1.0 : 0.0;
+            for (int i = 0; i < N; ++i) v[i] = e < 0 ? V[i * N + k] : (i == e ? 1.0 : 0.0);
 #pragma unroll
             for (int pass = 0; pass < 2; ++pass)
 #pragma unroll
@@ -178,7 +195,8 @@ RSREG_HD inline void complete_u3(double *U, int rank)
             double nn = 0;
 #pragma unroll
             for (int i = 0; i < N; ++i) nn += v[i] * v[i];
-            if (nn > bestn) {
+            if (e < 0) from_v = nn > 0.015625;
+            if (e < 0 ? from_v : nn > bestn) {
                 bestn = nn;
 #pragma unroll
                 for (int i = 0; i < N; ++i) best[i] = v[i];
@@ -273,7 +291,13 @@ RSREG_HD inline void jacobi_svd3(const double *A, SvdResult<3> &out, const doubl
             for (int i = 0; i < N; ++i) out.U[i * N + k] = 0.0;
         }
     }
-    complete_u3(out.U, rank);
+    if (rank < 3) {
+        if (rank == 0) {   // the zero matrix: nothing was rotated, and a V the caller started from says nothing about it
+#pragma unroll
+            for (int i = 0; i < 9; ++i) out.V[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        }
+        complete_u3(out.U, rank, out.V);
+    }
 }
 
 RSREG_HD inline double det3(const double *M)

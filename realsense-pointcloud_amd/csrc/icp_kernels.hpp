@@ -1115,7 +1115,13 @@ __device__ __forceinline__ bool umeyama_wave(const double *sums, Mat4f &T, doubl
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int k = 0; k < 3; ++k) { U[i * 3 + k] = lane_bcast(Ur[k], i); Vf[i * 3 + k] = lane_bcast(Vr[k], i); }
-    if (rank < 3) complete_u3(U, rank);   // (coplanar / collinear matches: the scalar code, on every lane)
+    if (rank < 3) {   // (coplanar / collinear matches, or a zero matrix: the scalar code, on every lane)
+        if (rank == 0) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) Vf[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        }
+        complete_u3(U, rank, Vf);
+    }
 #pragma unroll
     for (int i = 0; i < 9; ++i) v_warm[i] = Vf[i];
     double S[3] = {1, 1, 1};
