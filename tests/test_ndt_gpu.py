@@ -1,7 +1,9 @@
 """GPU parity tests of the NDT path (voxel statistics kernel set + derivative pass + host
 Newton / More-Thuente) through the C ABI, against the numpy golden vectors and the CPU oracle.
 f64 statistics to 1e-10 relative; score / gradient / Hessian to 1e-9 relative of their scale;
-final transform within 1e-4 Frobenius of the oracle (north-star tolerance)."""
+final transform within 1e-4 Frobenius of the oracle (north-star tolerance).
+The paths these clouds do not reach (64-bit keys, sparse grids, degenerate voxels, unstaged sources, snap angles) and the
+independent 60-digit yardstick: tests/test_ndt_paths_gpu.py."""
 import numpy as np
 import pytest
 
