@@ -412,6 +412,27 @@ int rsreg_cloud_sor(rsreg_ctx *ctx, const rsreg_cloud *in, int mean_k, double st
                     rsreg_sor_stats *stats /* may be NULL */);
 /* The first pass of rsreg_cloud_sor on its own: host_out[i] = record i's distance (n floats, the caller's record order) */
 int rsreg_cloud_knn_mean_distance(rsreg_ctx *ctx, const rsreg_cloud *in, int mean_k, float *host_out);
+/* nearestKSearch of every record in its own cloud, EXACT: for every finite record the k finite records with the smallest
+ * float32 L2_Simple squared distances, the record itself and exact copies counted like any other; ascending by
+ * (d2, original record index), and among records whose d2 equals the k-th smallest value the lowest indices (the tie
+ * rule of every search here).  1 <= k <= 64; fewer than k finite records: RSREG_ERR_INVALID_ARG.  Host outputs, each nullable.
+ * index_out:    n*k int32 original record indices, ascending (d2, index); a non-finite record's row is all -1.
+ * sqr_dist_out: n*k float; a non-finite record's row is all 0. */
+int rsreg_cloud_knn(rsreg_ctx *ctx, const rsreg_cloud *in, int k, int32_t *index_out, float *sqr_dist_out);
+/* pcl::NormalEstimation with setKSearch(k), 3 <= k <= 64; viewpoint NULL = (0,0,0).
+ * out: n records of 32 bytes laid out as pcl::Normal: normal_x, normal_y, normal_z, 0.f, curvature, 0, 0, 0.
+ * width, height as the input's.  out != in.
+ * Over the k neighbours of rsreg_cloud_knn: C = (sum d d^T) / k - (sum d / k)(sum d / k)^T with d = neighbour - record in
+ * double, summed in a fixed order; normal = the unit eigenvector of C's smallest eigenvalue l0 (Jacobi, double), rounded to
+ * float; curvature = (float)|l0 / (l0 + l1 + l2)|, 0 when the trace is 0 (solvePlaneParameters); flipped when, with
+ * v = viewpoint - record in float, (v.x * nx + v.y * ny) + v.z * nz < 0 (flipNormalTowardsViewpoint).  All k neighbours in
+ * one place (trace 0): (0, 0, 1) before the flip, curvature 0.  A non-finite record gets four quiet NaNs (normal and
+ * curvature); if any record did, out's is_dense is 0, otherwise the input's.  Fewer than k finite records:
+ * RSREG_ERR_INVALID_ARG.  The same cloud gives the same bytes whatever the context has indexed before.
+ * DEVIATION FROM PCL 1.9.1, stated: PCL accumulates nine raw moments about the origin in float, in FLANN's neighbour order
+ * (computeMeanAndCovarianceMatrix); this is the covariance the formula defines, in double, about the record.  A PCL build
+ * agrees with it to PCL's own rounding. */
+int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const float viewpoint[3], rsreg_cloud *out);
 /* icp.setInputTarget / setInputSource / align on handles; aligned_out (nullable, may be the source
  * cloud): the source records with xyz <- final * xyz and data[3] = 1 */
 int rsreg_icp_set_target_cloud(rsreg_ctx *ctx, const rsreg_cloud *cloud, double max_correspondence_distance);

@@ -77,6 +77,22 @@ struct alignas(16) PointXYZRGB {
 };
 static_assert(sizeof(PointXYZRGB) == 32, "PointXYZRGB must stay byte-compatible with pcl::PointXYZRGB");
 
+// ---- pcl::Normal: 32 bytes, 16-byte aligned -- normal[3] + 0.f, then curvature and three words of padding
+struct alignas(16) Normal {
+    union {
+        float data_n[4];
+        float normal[3];
+        struct { float normal_x, normal_y, normal_z; };
+    };
+    union {
+        struct { float curvature; };
+        float data_c[4];
+    };
+    Normal() : data_n{0.f, 0.f, 0.f, 0.f}, data_c{0.f, 0.f, 0.f, 0.f} {}
+    Normal(float nx, float ny, float nz) : data_n{nx, ny, nz, 0.f}, data_c{0.f, 0.f, 0.f, 0.f} {}
+};
+static_assert(sizeof(Normal) == 32, "Normal must stay byte-compatible with pcl::Normal");
+
 // ---- storage of a cloud's points.  pcl::PointCloud keeps a std::vector with Eigen's aligned allocator; this one is
 // aligned too and can hand out records WITHOUT constructing them one by one, for the callers that overwrite every
 // record right away (a download of the merged cloud of 16 frames spent 25 ms of a 60 ms scheme constructing 4.9 M
@@ -679,6 +695,40 @@ template <typename PointT> class StatisticalOutlierRemoval {
     bool negative_ = false;
     rsreg_sor_stats stats_{};
     typename PointCloud<PointT>::Ptr input_;
+    std::shared_ptr<Context> ctx_;
+};
+
+// ---- pcl::NormalEstimation<PointInT, PointOutT> with setKSearch (3 .. 64) over an exact k-nearest-neighbour search on the GPU
+// (csrc/normals_kernels.hpp, rsreg_cloud_normals).  PointOutT: 32-byte records laid out as pcl::Normal.  The covariance is the
+// one the formula defines, in double about the query point -- PCL's float accumulation about the origin is not reproduced
+// (include/rsreg.h states the deviation).  No radius search, no setSearchSurface, no setIndices.
+template <typename PointInT, typename PointOutT = Normal> class NormalEstimation {
+    static_assert(sizeof(PointOutT) == 32, "the output records are laid out as pcl::Normal");
+  public:
+    NormalEstimation() = default;
+    explicit NormalEstimation(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {}
+    void setInputCloud(const typename PointCloud<PointInT>::Ptr &cloud) { input_ = cloud; }
+    void setKSearch(int k) { k_ = k; }
+    int getKSearch() const { return k_; }
+    void setViewPoint(float vx, float vy, float vz) { vp_[0] = vx; vp_[1] = vy; vp_[2] = vz; }
+    void getViewPoint(float &vx, float &vy, float &vz) const { vx = vp_[0]; vy = vp_[1]; vz = vp_[2]; }
+    void compute(PointCloud<PointOutT> &output)
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        const std::shared_ptr<Context> ctx = ctx_ ? ctx_ : Context::Default();
+        DeviceCloud<PointInT> tmp(*input_, ctx);
+        DeviceCloud<PointOutT> normals(ctx);
+        compute(tmp, normals);
+        normals.download(output);
+    }
+    void compute(const DeviceCloud<PointInT> &input, DeviceCloud<PointOutT> &output)
+    {
+        check(rsreg_cloud_normals(input.context()->get(), input.handle(), k_, vp_, output.handle()), input.context()->get());
+    }
+  private:
+    int k_ = 0;                            // PCL's default: no search set (compute() refuses it)
+    float vp_[3] = {0.f, 0.f, 0.f};
+    typename PointCloud<PointInT>::Ptr input_;
     std::shared_ptr<Context> ctx_;
 };
 

@@ -113,6 +113,21 @@ def default_context():
     return _default_ctx
 
 
+# pcl::Normal: 32 bytes -- normal_x, normal_y, normal_z, 0.f, curvature, three words of padding
+NORMAL_DTYPE = np.dtype({"names": ["normal_x", "normal_y", "normal_z", "data_n3", "curvature", "pad0", "pad1", "pad2"],
+                         "formats": ["<f4", "<f4", "<f4", "<f4", "<f4", "<u4", "<u4", "<u4"], "offsets": [0, 4, 8, 12, 16, 20, 24, 28], "itemsize": 32})
+
+
+class NormalCloud:
+    """width / height / is_dense / points like pcl::PointCloud<pcl::Normal>; points: NORMAL_DTYPE records."""
+
+    def __init__(self, points, width, height, is_dense):
+        self.points, self.width, self.height, self.is_dense = points, int(width), int(height), bool(is_dense)
+
+    def __len__(self):
+        return len(self.points)
+
+
 class DeviceCloud:
     """A cloud resident in HBM (rsreg_cloud): whole records plus width / height / is_dense.  What the
     reference's frame loop hands from step to step (filter -> align -> transformPointCloud -> operator+,
@@ -209,6 +224,39 @@ class DeviceCloud:
         out = np.zeros(self.info()[0], np.float32)
         _l.check(_l.lib().rsreg_cloud_knn_mean_distance(self.ctx.h, self.h, int(mean_k), out.ctypes.data), self.ctx.h)
         return out
+
+    def knn(self, k):
+        """nearestKSearch of every record in its own cloud (rsreg_cloud_knn, exact): (idx, d2), each (n, k) -- int32 original
+        record indices and float32 squared distances, ascending by (d2, index), ties: lowest index; the record itself and exact
+        copies count.  A non-finite record's row is -1 / 0."""
+        n = self.info()[0]
+        idx = np.zeros((n, int(k)), np.int32)
+        d2 = np.zeros((n, int(k)), np.float32)
+        _l.check(_l.lib().rsreg_cloud_knn(self.ctx.h, self.h, int(k), idx.ctypes.data, d2.ctypes.data), self.ctx.h)
+        return idx, d2
+
+    def normals_cloud(self, k, viewpoint=None):
+        """pcl::NormalEstimation with setKSearch(k) (rsreg_cloud_normals): a DeviceCloud of 32-byte pcl::Normal records."""
+        out = DeviceCloud(ctx=self.ctx)
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        _l.check(_l.lib().rsreg_cloud_normals(self.ctx.h, self.h, int(k), None if vp is None else vp.ctypes.data, out.h), self.ctx.h)
+        return out
+
+    def normals(self, k, viewpoint=None):
+        """(n, 4) float32: normal_x, normal_y, normal_z, curvature of every record (NaN for a non-finite one)."""
+        out = self.normals_cloud(k, viewpoint)
+        rec = out.download_normals().points
+        out.close()
+        return np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
+
+    def download_normals(self):
+        """download() of a cloud of pcl::Normal records (what NormalEstimation.compute returns): a NormalCloud."""
+        n, stride, w, h, dense = self.info()
+        if n and stride != NORMAL_DTYPE.itemsize:
+            raise ValueError("the device cloud does not hold 32-byte pcl::Normal records")
+        rec = np.zeros(n, NORMAL_DTYPE)
+        _l.check(_l.lib().rsreg_cloud_download(self.h, rec.ctypes.data, n), self.ctx.h)
+        return NormalCloud(rec, w, h, dense)
 
     def copy(self):
         out = DeviceCloud(ctx=self.ctx)
@@ -722,6 +770,48 @@ class StatisticalOutlierRemoval:
                      cin.ctx.h)
         out = _filter_io(self._in, self.ctx, run)
         self.stats = st
+        return out
+
+
+class NormalEstimation:
+    """pcl::NormalEstimation<PointXYZRGB, Normal> with setKSearch on the GPU over an exact k-nearest-neighbour search
+    (csrc/normals_kernels.hpp, rsreg_cloud_normals), 3 <= k <= 64.  The covariance is the one the formula defines, in double
+    about the query point: PCL's float accumulation about the origin is not reproduced (include/rsreg.h).  compute() of a
+    DeviceCloud gives a DeviceCloud of pcl::Normal records, of a host cloud a NormalCloud."""
+
+    def __init__(self, ctx=None):
+        self.k = 0                                   # PCL's default: no search set
+        self.viewpoint = (0.0, 0.0, 0.0)
+        self._in = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setKSearch(self, k):
+        self.k = int(k)
+
+    def getKSearch(self):
+        return self.k
+
+    def setViewPoint(self, vx, vy, vz):
+        self.viewpoint = (float(vx), float(vy), float(vz))
+
+    def getViewPoint(self):
+        return self.viewpoint
+
+    def compute(self):
+        if self._in is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCloud not called")
+        if isinstance(self._in, DeviceCloud):
+            return self._in.normals_cloud(self.k, self.viewpoint)
+        tmp = DeviceCloud(self._in, ctx=self.ctx or default_context())
+        try:
+            dev = tmp.normals_cloud(self.k, self.viewpoint)
+            out = dev.download_normals()
+            dev.close()
+        finally:
+            tmp.close()
         return out
 
 

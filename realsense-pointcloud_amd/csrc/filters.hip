@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "knn_kernels.hpp"
+#include "normals_kernels.hpp"
 
 using namespace rsreg;
 
@@ -66,6 +67,21 @@ int knn_mean_distance_device(rsreg_ctx *ctx, const CloudView &v, int mean_k, uin
         return fail(ctx, RSREG_ERR_INVALID_ARG, "the cloud has fewer than mean_k + 1 finite records");
     k_knn_mean_distance<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, st>>>(grid_dev(kx), mean_k, fs.d_dist.as<float>());
     RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
+// The index of the cloud for a search that keeps k neighbours (the record itself among them), on ctx->stream; refused when fewer
+// than k records are finite (PCL's nearestKSearch would return fewer than k: every caller here needs k).
+int knn_index_device(rsreg_ctx *ctx, const CloudView &v, int k, uint32_t *nfin_out)
+{
+    FilterScratch &fs = ctx->filt;
+    RSREG_HIP(ctx, fs.host.reserve(256));
+    RSREG_HIP(ctx, fs.d_dist.reserve(v.n * 4 + 16));   // (the count pass leaves a non-finite record's 0 there)
+    int rc = grid_build<KnnGridPolicy>(ctx, ctx->knn, StridedRecords{v.rec, v.stride, fs.d_dist.as<float>()}, (uint32_t)v.n, (uint32_t)k,
+                                       fs.host.as<uint32_t>());
+    if (rc) return rc;
+    *nfin_out = ctx->knn.n_points;
+    if (ctx->knn.n_points < (uint32_t)k) return fail(ctx, RSREG_ERR_INVALID_ARG, "the cloud has fewer than k finite records");
     return RSREG_OK;
 }
 
@@ -192,6 +208,65 @@ int rsreg_cloud_sor(rsreg_ctx *ctx, const rsreg_cloud *in, int mean_k, double st
         stats->threshold = threshold;
     }
     return RSREG_OK;
+}
+
+int rsreg_cloud_knn(rsreg_ctx *ctx, const rsreg_cloud *in, int k, int32_t *index_out, float *sqr_dist_out)
+{
+    CloudView v;
+    int rc = view_of(ctx, in, nullptr, v);
+    if (rc) return rc;
+    if (k < 1 || k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must be between 1 and 64");
+    uint32_t nfin = 0;
+    rc = knn_index_device(ctx, v, k, &nfin);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    const size_t cells = v.n * (size_t)k;
+    int32_t *d_idx = nullptr;
+    float *d_d2 = nullptr;
+    if (index_out) {
+        RSREG_HIP(ctx, fs.d_nn_idx.reserve(cells * 4 + 16));
+        d_idx = fs.d_nn_idx.as<int32_t>();
+        if (nfin < v.n) RSREG_HIP(ctx, hipMemsetAsync(d_idx, 0xff, cells * 4, st));   // a non-finite record's row: all -1
+    }
+    if (sqr_dist_out) {
+        RSREG_HIP(ctx, fs.d_nn_d2.reserve(cells * 4 + 16));
+        d_d2 = fs.d_nn_d2.as<float>();
+        if (nfin < v.n) RSREG_HIP(ctx, hipMemsetAsync(d_d2, 0, cells * 4, st));      // ... all 0
+    }
+    if (!d_idx && !d_d2) return RSREG_OK;
+    k_knn_indices<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), k, d_idx, d_d2);
+    RSREG_HIP(ctx, hipGetLastError());
+    if (d_idx) RSREG_HIP(ctx, hipMemcpyAsync(index_out, d_idx, cells * 4, hipMemcpyDeviceToHost, st));
+    if (d_d2) RSREG_HIP(ctx, hipMemcpyAsync(sqr_dist_out, d_d2, cells * 4, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    return RSREG_OK;
+}
+
+int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const float viewpoint[3], rsreg_cloud *out)
+{
+    CloudView v;
+    if (!out || out == in) return RSREG_ERR_INVALID_ARG;
+    int rc = view_of(ctx, in, out, v);
+    if (rc) return rc;
+    if (k < 3 || k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must be between 3 and 64");
+    uint32_t nfin = 0;
+    rc = knn_index_device(ctx, v, k, &nfin);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)v.n;
+    constexpr size_t kNormalBytes = 32;   // pcl::Normal
+    RSREG_HIP(ctx, fs.d_out.reserve(v.n * kNormalBytes + 16));
+    if (nfin < n) {
+        k_normals_not_finite<<<div_up(n, kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, fs.d_out.as<float>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    const float vp[3] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f, viewpoint ? viewpoint[2] : 0.0f};
+    k_normals<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), k, v.rec, v.stride, vp[0], vp[1], vp[2], fs.d_out.as<float>());
+    RSREG_HIP(ctx, hipGetLastError());
+    // a record that got NaNs makes the cloud not dense; otherwise it is what the input says
+    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kNormalBytes, v.width, v.height, nfin < n ? 0 : v.is_dense);
 }
 
 }  // extern "C"

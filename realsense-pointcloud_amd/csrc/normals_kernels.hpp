@@ -1,0 +1,301 @@
+// normals_kernels.hpp — the exact k-nearest-neighbour search of knn_kernels.hpp in its identity-carrying form, and
+// pcl::NormalEstimation (setKSearch) on top of it: device code of rsreg_cloud_knn and rsreg_cloud_normals (include/rsreg.h).
+// Included by filters.hip only.  k_knn_mean_distance is not touched: what StatisticalOutlierRemoval returns stays what it is.
+//
+// The search.  The same index (pointgrid.hpp, KnnGridPolicy), the same walk of shells of cells, the same float32 l2_simple,
+// one wave per query.  What the LDS selection carries is a 64-bit key, float bits of d2 << 32 | original record index:
+// d2 >= 0, so its bit pattern orders like its value, and no two records share a key.  The result of a query is the k
+// smallest keys, ascending: ascending by (d2, record index), and among records whose d2 equals the k-th smallest value the
+// lowest indices -- the project's tie rule ("ties: lowest index").  The record itself and exact copies are neighbours like any
+// other (PCL's nearestKSearch).  Two things differ from the value-only walk:
+//   * a candidate is taken when its KEY is below the k-th smallest key so far (not: its value not above the k-th value);
+//   * nothing ends at a bound of 0: every record at distance 0 has to be seen before the lowest indices among them are known.
+//     A cell is skipped only when its lower bound is ABOVE the k-th distance, so every record that ties with it is seen.
+//     (A pile of m exact copies therefore costs m / 64 loads per query of the pile: the missing-depth records of a raw frame.)
+// A neighbour's coordinates are read from the cloud's own records through the original index in the key: no position in
+// the cell-sorted array is kept and nothing is searched twice.
+//
+// The normal (PCL 1.9.1 features/normal_3d.h, recalled: computePointNormal, solvePlaneParameters, flipNormalTowardsViewpoint),
+// by the wave that searched, while the k keys are in LDS -- no n x k index array goes through HBM:
+//   d_i = neighbour_i - query in f64 (lanes 0 .. k-1); 3 first and 6 second moments summed over the wave by a fixed butterfly;
+//   C = (sum d d^T) / k - (sum d / k)(sum d / k)^T;  the eigenpairs of C by cyclic Jacobi in f64;
+//   normal = the unit eigenvector of the smallest eigenvalue l0, curvature = (float)|l0 / (l0 + l1 + l2)|, 0 when the trace is 0;
+//   flipped when, with v = viewpoint - p in float, (v.x * nx + v.y * ny) + v.z * nz < 0 (float, no contraction).
+//   A neighbourhood whose points all coincide (trace 0): (0, 0, 1) before the flip, curvature 0.
+//
+// STATED DEVIATION FROM PCL.  PCL's computeMeanAndCovarianceMatrix accumulates nine raw moments about the ORIGIN in float,
+// in FLANN's neighbour order: at 2 m range with centimetre neighbourhoods that loses percent-level accuracy in C, and under
+// ties it is not reproducible.  Here the covariance is the one the formula defines, in f64, about the query point, and the
+// result depends on nothing but the cloud: not on the grid, the launch or the run.  A PCL build agrees with it to PCL's own
+// rounding.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "knn_kernels.hpp"
+
+namespace rsreg {
+
+constexpr unsigned long long kKnnNoKey = ~0ull;   // above every key: the padding of the selection, the bound while fewer than k are kept
+
+// ------------------------------------------------------------------------------ search
+// Ascending bitonic sort of the keys buf[0 .. n) (n = 64, 128 or 256 >= count, padded), by the one wave of the workgroup; the k
+// smallest stay: count = min(count, k), bound = the k-th smallest key (kKnnNoKey while there are fewer), bound_d2 its distance.
+__device__ __forceinline__ void knn_select_keys(unsigned long long *buf, int lane, int k, int &count, unsigned long long &bound, float &bound_d2)
+{
+    const int n = count <= 64 ? 64 : (count <= 128 ? 128 : kKnnBuf);
+    for (int i = count + lane; i < n; i += kKnnWave) buf[i] = kKnnNoKey;
+    __syncthreads();
+    for (int s = 2; s <= n; s <<= 1) {
+        for (int j = s >> 1; j > 0; j >>= 1) {
+            for (int t = lane; t < (n >> 1); t += kKnnWave) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long a = buf[i], b = buf[l];
+                const bool up = (i & s) == 0;
+                if ((a > b) == up) {
+                    buf[i] = b;
+                    buf[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    count = min(count, k);
+    bound = count >= k ? buf[k - 1] : kKnnNoKey;
+    bound_d2 = count >= k ? __uint_as_float((uint32_t)(bound >> 32)) : __int_as_float(0x7f800000);
+}
+
+// The k smallest keys of the query q (a point of the index: at least k points are indexed) in buf[0 .. k), ascending.  Called by
+// every lane of the one wave of the workgroup; buf: kKnnBuf keys of LDS.  Returns behind a barrier.
+__device__ __forceinline__ void knn_walk_keys(const PointGridDev &g, const float4 q, int k, unsigned long long *buf, int lane)
+{
+    const float inf = __int_as_float(0x7f800000), cell2 = g.cell * g.cell;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const float ux = cell_pos(q.x, g.ox, g.inv_cell), uy = cell_pos(q.y, g.oy, g.inv_cell), uz = cell_pos(q.z, g.oz, g.inv_cell);
+    const int cx = axis_cell(q.x, g.ox, g.inv_cell, g.dx), cy = axis_cell(q.y, g.oy, g.inv_cell, g.dy), cz = axis_cell(q.z, g.oz, g.inv_cell, g.dz);
+    const int rmax = max(max(max(cx, g.dx - 1 - cx), max(cy, g.dy - 1 - cy)), max(cz, g.dz - 1 - cz));
+    int count = 0;
+    unsigned long long bound = kKnnNoKey;
+    float bound_d2 = inf;
+    bool dirty = false;
+    for (int r = 0; r <= rmax; ++r) {
+        const int side = 2 * r + 1, rows = side * side;
+        for (int base = 0; base < rows; base += kKnnWave) {
+            const int row = base + lane;
+            const int oy = row % side - r, oz = row / side - r, y = cy + oy, z = cz + oz;
+            const bool in = row < rows && y >= 0 && y < g.dy && z >= 0 && z < g.dz;
+            const bool face = abs(oy) == r || abs(oz) == r;   // a face row: every cell of it; else its two ends
+            const float gy = axis_gap(uy, y, y), gz = axis_gap(uz, z, z);
+            for (int pass = 0; pass < 2; ++pass) {
+                int x0, x1;
+                bool has = in;
+                if (face) {
+                    x0 = max(cx - r, 0);
+                    x1 = min(cx + r, g.dx - 1);
+                    has = has && pass == 0;
+                } else {
+                    x0 = x1 = pass == 0 ? cx - r : cx + r;
+                    has = has && x0 >= 0 && x0 < g.dx;
+                }
+                const float lb = has ? grid_lb2(axis_gap(ux, x0, x1), gy, gz, cell2) : inf;
+                uint32_t s = 0, e = 0;
+                if (has && !(lb > bound_d2)) {
+                    const size_t c0 = ((size_t)z * (size_t)g.dy + (size_t)y) * (size_t)g.dx;
+                    s = g.start[c0 + (size_t)x0];
+                    e = g.start[c0 + (size_t)x1 + 1];
+                }
+                unsigned long long todo = __ballot(e > s);
+                while (todo) {
+                    const int l = __ffsll((long long)todo) - 1;
+                    todo &= todo - 1;
+                    const uint32_t ss = __shfl(s, l), ee = __shfl(e, l);
+                    if (__shfl(lb, l) > bound_d2) continue;   // (the bound has come down since the row was fetched)
+                    for (uint32_t p = ss; p < ee; p += kKnnWave) {
+                        if (count > kKnnBuf - kKnnWave) {
+                            knn_select_keys(buf, lane, k, count, bound, bound_d2);
+                            dirty = false;
+                        }
+                        const uint32_t i = p + (uint32_t)lane;
+                        bool ok = i < ee;
+                        unsigned long long key = kKnnNoKey;
+                        if (ok) {
+                            const float4 t = g.pts[i];
+                            const float d = l2_simple(q.x, q.y, q.z, t.x, t.y, t.z);
+                            key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)__float_as_uint(t.w);
+                            ok = key < bound;
+                        }
+                        const unsigned long long m = __ballot(ok);
+                        if (ok) buf[count + __popcll(m & lt)] = key;
+                        count += __popcll(m);
+                        dirty = dirty || m != 0ull;
+                    }
+                }
+            }
+        }
+        if (count >= k) {
+            if (dirty) {
+                knn_select_keys(buf, lane, k, count, bound, bound_d2);
+                dirty = false;
+            }
+            // every cell not visited yet lies beyond one of the six faces of the cube of shell r
+            float out = inf;
+            if (cx + r + 1 < g.dx) out = fminf(out, grid_lb2(axis_gap(ux, cx + r + 1, g.dx - 1), 0.0f, 0.0f, cell2));
+            if (cx - r - 1 >= 0) out = fminf(out, grid_lb2(axis_gap(ux, 0, cx - r - 1), 0.0f, 0.0f, cell2));
+            if (cy + r + 1 < g.dy) out = fminf(out, grid_lb2(0.0f, axis_gap(uy, cy + r + 1, g.dy - 1), 0.0f, cell2));
+            if (cy - r - 1 >= 0) out = fminf(out, grid_lb2(0.0f, axis_gap(uy, 0, cy - r - 1), 0.0f, cell2));
+            if (cz + r + 1 < g.dz) out = fminf(out, grid_lb2(0.0f, 0.0f, axis_gap(uz, cz + r + 1, g.dz - 1), cell2));
+            if (cz - r - 1 >= 0) out = fminf(out, grid_lb2(0.0f, 0.0f, axis_gap(uz, 0, cz - r - 1), cell2));
+            if (out > bound_d2) break;   // (strictly: a record AT the k-th distance may still carry a lower index)
+        }
+    }
+    if (dirty) knn_select_keys(buf, lane, k, count, bound, bound_d2);
+    __syncthreads();
+}
+
+// rsreg_cloud_knn: row `record` of index_out (k int32, nullable) and of d2_out (k floats, nullable), queries in cell order.  The
+// rows of non-finite records have been filled before the launch.
+__global__ __launch_bounds__(kKnnWave) void k_knn_indices(PointGridDev g, int k, int32_t *index_out, float *d2_out)
+{
+    __shared__ unsigned long long buf[kKnnBuf];
+    const int lane = (int)threadIdx.x;
+    for (uint32_t j = blockIdx.x; j < g.n; j += gridDim.x) {
+        const float4 q = g.pts[j];
+        knn_walk_keys(g, q, k, buf, lane);
+        if (lane < k) {
+            const unsigned long long key = buf[lane];
+            const size_t at = (size_t)__float_as_uint(q.w) * (size_t)k + (size_t)lane;
+            if (index_out) index_out[at] = (int32_t)(uint32_t)key;
+            if (d2_out) d2_out[at] = __uint_as_float((uint32_t)(key >> 32));
+        }
+        __syncthreads();   // (the next query appends to the same buffer)
+    }
+}
+
+// ------------------------------------------------------------------------------ normals
+// the sum of v over the 64 lanes, the same bits in every lane: a butterfly, so every lane adds the same pairs in the same order
+__device__ __forceinline__ double wave_sum_fixed(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// Eigenvalues (ascending in ev) of the symmetric 3 x 3 matrix {a00, a01, a02, a11, a12, a22} and the unit eigenvector of the
+// smallest, by cyclic Jacobi in f64 (the rotations of host_linalg.hpp's eig_sym3; every index a compile-time constant).
+__device__ inline void eig_sym3_smallest(const double (&c)[6], double (&ev)[3], double (&vec)[3])
+{
+#pragma clang fp contract(off)
+    double A[9] = {c[0], c[1], c[2], c[1], c[3], c[4], c[2], c[4], c[5]}, V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int sweep = 0; sweep < 32; ++sweep) {
+        const double off = A[1] * A[1] + A[2] * A[2] + A[5] * A[5];
+        const double dia = A[0] * A[0] + A[4] * A[4] + A[8] * A[8];
+        if (off <= 1e-36 * dia || off == 0.0) break;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 3; ++q) {
+                const double apq = A[p * 3 + q];
+                if (apq == 0.0) continue;
+                const double th = (A[q * 3 + q] - A[p * 3 + p]) / (2.0 * apq);
+                const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+                const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const double a = A[i * 3 + p], b = A[i * 3 + q];
+                    A[i * 3 + p] = cs * a - sn * b;
+                    A[i * 3 + q] = sn * a + cs * b;
+                }
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const double a = A[p * 3 + i], b = A[q * 3 + i];
+                    A[p * 3 + i] = cs * a - sn * b;
+                    A[q * 3 + i] = sn * a + cs * b;
+                }
+                A[p * 3 + q] = A[q * 3 + p] = 0.0;   // (what the rotation was chosen for)
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const double a = V[i * 3 + p], b = V[i * 3 + q];
+                    V[i * 3 + p] = cs * a - sn * b;
+                    V[i * 3 + q] = sn * a + cs * b;
+                }
+            }
+    }
+    const double d0 = A[0], d1 = A[4], d2 = A[8];
+    int o0 = 0, o1 = 1, o2 = 2;   // ascending; equal values keep their order
+    if (pick3(d0, d1, d2, o1) < pick3(d0, d1, d2, o0)) { const int t = o0; o0 = o1; o1 = t; }
+    if (pick3(d0, d1, d2, o2) < pick3(d0, d1, d2, o0)) { const int t = o0; o0 = o2; o2 = t; }
+    if (pick3(d0, d1, d2, o2) < pick3(d0, d1, d2, o1)) { const int t = o1; o1 = o2; o2 = t; }
+    ev[0] = pick3(d0, d1, d2, o0);
+    ev[1] = pick3(d0, d1, d2, o1);
+    ev[2] = pick3(d0, d1, d2, o2);
+    const double x = pick3(V[0], V[1], V[2], o0), y = pick3(V[3], V[4], V[5], o0), z = pick3(V[6], V[7], V[8], o0);
+    const double inv = 1.0 / sqrt((x * x + y * y) + z * z);   // (orthogonal up to rounding: the norm is 1 within a few ulp)
+    vec[0] = x * inv;
+    vec[1] = y * inv;
+    vec[2] = z * inv;
+}
+
+// the 32-byte pcl::Normal records of the non-finite input records: four quiet NaNs (normal and curvature), pads 0
+__global__ __launch_bounds__(kBlock) void k_normals_not_finite(const char *rec, size_t stride, uint32_t n, float *out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = rec_xyz(rec, stride, i);
+    if (finite3(p[0], p[1], p[2])) return;
+    const float qnan = __uint_as_float(0x7fc00000u);
+    float4 *o = reinterpret_cast<float4 *>(out + (size_t)i * 8);
+    o[0] = make_float4(qnan, qnan, qnan, 0.0f);
+    o[1] = make_float4(qnan, 0.0f, 0.0f, 0.0f);
+}
+
+// One workgroup of ONE wave per query, queries in cell order: the search, then the normal of the k neighbours while their keys
+// are in LDS.  out: record `record` = {normal_x, normal_y, normal_z, 0, curvature, 0, 0, 0}.
+__global__ __launch_bounds__(kKnnWave) void k_normals(PointGridDev g, int k, const char *rec, size_t stride, float vpx, float vpy, float vpz, float *out)
+{
+#pragma clang fp contract(off)
+    __shared__ unsigned long long buf[kKnnBuf];
+    const int lane = (int)threadIdx.x;
+    for (uint32_t j = blockIdx.x; j < g.n; j += gridDim.x) {
+        const float4 q = g.pts[j];
+        knn_walk_keys(g, q, k, buf, lane);
+        double dx = 0.0, dy = 0.0, dz = 0.0;
+        if (lane < k) {
+            const float *t = rec_xyz(rec, stride, (size_t)(uint32_t)buf[lane]);
+            dx = (double)t[0] - (double)q.x;
+            dy = (double)t[1] - (double)q.y;
+            dz = (double)t[2] - (double)q.z;
+        }
+        __syncthreads();   // (the keys have been read: the next query may append)
+        const double sx = wave_sum_fixed(dx), sy = wave_sum_fixed(dy), sz = wave_sum_fixed(dz);
+        const double sxx = wave_sum_fixed(dx * dx), sxy = wave_sum_fixed(dx * dy), sxz = wave_sum_fixed(dx * dz);
+        const double syy = wave_sum_fixed(dy * dy), syz = wave_sum_fixed(dy * dz), szz = wave_sum_fixed(dz * dz);
+        const double kk = (double)k, mx = sx / kk, my = sy / kk, mz = sz / kk;
+        const double c[6] = {sxx / kk - mx * mx, sxy / kk - mx * my, sxz / kk - mx * mz, syy / kk - my * my, syz / kk - my * mz, szz / kk - mz * mz};
+        const double trace = (c[0] + c[3]) + c[5];
+        float nx = 0.0f, ny = 0.0f, nz = 1.0f, curv = 0.0f;
+        if (trace != 0.0) {
+            double ev[3], vec[3];
+            eig_sym3_smallest(c, ev, vec);
+            nx = (float)vec[0];
+            ny = (float)vec[1];
+            nz = (float)vec[2];
+            const double sum = (ev[0] + ev[1]) + ev[2];
+            curv = sum != 0.0 ? (float)fabs(ev[0] / sum) : 0.0f;
+        }
+        const float vx = __fsub_rn(vpx, q.x), vy = __fsub_rn(vpy, q.y), vz = __fsub_rn(vpz, q.z);
+        const float cos_view = __fadd_rn(__fadd_rn(__fmul_rn(vx, nx), __fmul_rn(vy, ny)), __fmul_rn(vz, nz));
+        if (cos_view < 0.0f) {
+            nx = -nx;
+            ny = -ny;
+            nz = -nz;
+        }
+        if (lane < 8) {
+            const float v = lane == 0 ? nx : (lane == 1 ? ny : (lane == 2 ? nz : (lane == 4 ? curv : 0.0f)));
+            out[(size_t)__float_as_uint(q.w) * 8 + (size_t)lane] = v;
+        }
+    }
+}
+
+}  // namespace rsreg

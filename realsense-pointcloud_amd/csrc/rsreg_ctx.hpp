@@ -188,7 +188,8 @@ struct FilterScratch {
     DevBuf d_dist;                 // float per record: its mean distance to its mean_k nearest neighbours
     DevBuf d_flags, d_pos;         // uint32 per record: keep flag, position among the kept
     DevBuf d_sums;                 // the threshold's two f64 sums
-    DevBuf d_out;                  // the kept records, before the output cloud takes them
+    DevBuf d_out;                  // the kept records (the normals), before the output cloud takes them
+    DevBuf d_nn_idx, d_nn_d2;      // rsreg_cloud_knn: k original indices / k squared distances per record
     PinnedBuf host;
 };
 

@@ -40,7 +40,7 @@ EXPORTS = [
     "rsreg_extract_edge_features", "rsreg_cloud_edge_features", "rsreg_cloud_edge_features_async",
     "rsreg_icp_grid_info", "rsreg_ctx_host_timing", "rsreg_lzf_max_encoded_size", "rsreg_lzf_encode", "rsreg_lzf_decode",
     "rsreg_icp_fitness_score", "rsreg_icp_fitness_sums", "rsreg_ndt_fitness_score",
-    "rsreg_cloud_passthrough", "rsreg_cloud_sor", "rsreg_cloud_knn_mean_distance",
+    "rsreg_cloud_passthrough", "rsreg_cloud_sor", "rsreg_cloud_knn_mean_distance", "rsreg_cloud_knn", "rsreg_cloud_normals",
 ]
 
 
@@ -261,6 +261,8 @@ def lib():
     L.rsreg_cloud_passthrough.argtypes = [vp, vp, i32, C.c_float, C.c_float, i32, i32, vp]
     L.rsreg_cloud_sor.argtypes = [vp, vp, i32, dbl, i32, vp, C.POINTER(SorStats)]
     L.rsreg_cloud_knn_mean_distance.argtypes = [vp, vp, i32, vp]
+    L.rsreg_cloud_knn.argtypes = [vp, vp, i32, vp, vp]
+    L.rsreg_cloud_normals.argtypes = [vp, vp, i32, vp, vp]
     L.rsreg_cloud_concat.argtypes = [vp, vp, vp, vp]
     L.rsreg_icp_set_target_cloud.argtypes = [vp, vp, dbl]
     L.rsreg_icp_target_is_cloud.argtypes = [vp, vp, dbl]
