@@ -35,6 +35,7 @@ extern "C" {
 #define RSREG_VERSION_MINOR 4
 
 typedef struct rsreg_ctx rsreg_ctx;
+typedef struct rsreg_cloud rsreg_cloud;   /* a cloud resident in HBM: "device-resident clouds" below */
 
 typedef enum rsreg_status {
     RSREG_OK = 0,
@@ -76,6 +77,17 @@ typedef enum rsreg_pipeline_mode {
                                   with the PCL criteria it behaves as FUSED */
 } rsreg_pipeline_mode;
 
+/* Which transformation estimate an ICP iteration solves.  RSREG_ESTIMATION_POINT_TO_PLANE_LLS is
+ * pcl::IterativeClosestPointWithNormals' default (TransformationEstimationPointToPlaneLLS): it needs the target's normals
+ * (rsreg_icp_set_target_normals*) and runs as RSREG_PIPELINE_STAGED whatever pipeline_mode asks for, like the correspondence
+ * filters: search -> k_plane_reduce -> 6-unknown host solve -> transform.  The reference declares the point type for it and
+ * never uses it (src/types.hpp:11-12).  A context whose communicator has more than one rank refuses it
+ * (RSREG_ERR_INVALID_ARG from rsreg_icp_begin): the all-reduce of the 32 sums is not implemented. */
+typedef enum rsreg_estimation {
+    RSREG_ESTIMATION_SVD = 0,                 /* TransformationEstimationSVD (Umeyama) from the 17 sums   */
+    RSREG_ESTIMATION_POINT_TO_PLANE_LLS = 1   /* the 6 x 6 linearised least squares from the 32 sums      */
+} rsreg_estimation;
+
 /*
  * ICP parameters = the setters the reference calls on pcl::IterativeClosestPoint
  *   setMaximumIterations / setMaxCorrespondenceDistance / setTransformationEpsilon /
@@ -88,7 +100,7 @@ typedef struct rsreg_icp_params {
     int32_t max_iterations;
     int32_t criteria_mode;                   /* rsreg_criteria_mode */
     int32_t pipeline_mode;                   /* rsreg_pipeline_mode */
-    int32_t reserved0;
+    int32_t estimation;                      /* rsreg_estimation; 0 in both presets; any other value: RSREG_ERR_INVALID_ARG */
     double max_correspondence_distance;
     double transformation_epsilon;
     double transformation_rotation_epsilon;  /* <= 0: use 1 - transformation_epsilon (PCL) */
@@ -129,6 +141,36 @@ typedef struct rsreg_ndt_params {
  * distance gate contribute.  These are what an N-GPU run all-reduces. */
 #define RSREG_NUM_SUMS 17
 
+/* The 32 sums one POINT-TO-PLANE iteration reduces the correspondences to (all f64).  For a kept pair: p = the transformed
+ * source point, q = its matched target point, n = that target record's normal (all float), W = how many source records
+ * the pair stands for (exact copies are searched once; with a correspondence filter: the copies it left in play).
+ * All arithmetic in double from the float inputs, every operation rounded once (no contraction):
+ *   a = p x n:  a0 = n.z*p.y - n.y*p.z,  a1 = n.x*p.z - n.z*p.x,  a2 = n.y*p.x - n.x*p.y
+ *   J = [a0 a1 a2 n.x n.y n.z]
+ *   r = ((n.x*q.x + n.y*q.y) + n.z*q.z) - ((n.x*p.x + n.y*p.y) + n.z*p.z)
+ *   a pair's terms: W * (J_i * J_j), W * (J_i * r), W * (r * r), W * (double)d2
+ *   [0] sum W over the gated pairs     [1] sum W * d2, the squared distance the search returned
+ *   [2] sum W over the pairs that entered the system     [3] sum W * r^2
+ *   [4..24] AtA = sum W J J^T, upper triangle row-major (00 01 .. 05 11 12 .. 55)     [25..30] Atb = sum W J r     [31] 0
+ * A pair whose normal has a non-finite component adds to [0] and [1] only (PCL's LLS skips it; its convergence criteria
+ * still see the correspondence).  [0] and [1] are bit-equal to sums [0] and [16] of rsreg_icp_sums after the same search;
+ * the order of the additions is fixed (per tile by halving over lanes, then the tiles), so the same inputs give the same
+ * 32 doubles on any context, at any launch.
+ * The solve (rsreg_plane_solve_from_sums, host, double): x = (alpha, beta, gamma, tx, ty, tz) = pinv(AtA) Atb by the Jacobi
+ * eigen-decomposition of AtA, over the eigen-directions that carry data: eigenvalue l_k counts when
+ *   l_k > ([2] + 80) * 2^-53 * trace(AtA)        (trace <= 6 l_max: relative to the largest eigenvalue, below 6 ([2] + 80) 2^-53)
+ * -- a sum of N <= [2] terms, however ordered, is off by at most (N + 16) 2^-53 sum|term|; for entry (i, j) sum|term| <=
+ * sqrt(AtA_ii AtA_jj) (Cauchy-Schwarz), so the error matrix has a Frobenius norm of at most ([2] + 16) 2^-53 trace(AtA), and by
+ * Weyl's inequality every eigenvalue is off by no more; the other 64 units cover the eigen-solver's own rounding.  A direction
+ * at or below the cut contributes nothing (the rule of the Umeyama solve: R = I where the data is silent); [2] == 0 or no
+ * direction above the cut: the identity.  T = PCL's constructTransformationMatrix (1.9.1, recalled): R = Rz(gamma) Ry(beta)
+ * Rx(alpha) with full sines and cosines in double, t = (tx, ty, tz), rounded to float.
+ * DEVIATIONS FROM PCL 1.9.1, stated: (1) PCL accumulates AtA and Atb pair by pair in its own order, partly through float
+ * intermediates; these are the sums the formulas define, in double, in the fixed order above.  (2) PCL computes
+ * ATA.inverse() * ATb, which on a singular or near-singular system (one plane, parallel planes) returns whatever the
+ * inverse's rounding leaves; that is not reproduced -- the pseudo-inverse above is. */
+#define RSREG_NUM_PLANE_SUMS 32
+
 typedef struct rsreg_icp_result {
     float transform[16];        /* final_transformation_, column-major                      */
     int32_t converged;          /* icp.hasConverged()                                       */
@@ -137,7 +179,8 @@ typedef struct rsreg_icp_result {
     int32_t reserved0;
     uint64_t n_correspondences; /* pairs accepted in the last iteration                     */
     double mse;                 /* mean squared distance of those pairs (last iteration)    */
-    double sums_last[RSREG_NUM_SUMS]; /* the 17 sums of the last iteration                  */
+    double sums_last[RSREG_NUM_SUMS]; /* the 17 sums of the last iteration (point-to-plane: [0] and [16] -- the
+                                         plane sums [0] and [1] -- the rest 0; all 32: rsreg_icp_plane_sums_last) */
     /* device-time breakdown of this call (ms, HIP events on the ctx stream); 0 if profiling off */
     double ms_total;
     double ms_nn;               /* dominant kernel: NN search (or the fused kernel)         */
@@ -268,6 +311,28 @@ int rsreg_icp_fitness_sums(rsreg_ctx *ctx, double max_range, double sums[2]);
  * all-reduce themselves. */
 int rsreg_umeyama_from_sums(const double sums[RSREG_NUM_SUMS], float t_out[16]);
 
+/* ---- point-to-plane ICP: pcl::IterativeClosestPointWithNormals (params->estimation = RSREG_ESTIMATION_POINT_TO_PLANE_LLS) ---- */
+/* The target's normals, one per target RECORD in the caller's order: three floats at `normals + i * stride` (pcl::Normal
+ * records: stride 32; PointXYZRGBNormal records: stride 48 with the pointer at normal_x).  Call it after
+ * rsreg_icp_set_target*; n must be that target's record count (RSREG_ERR_INVALID_ARG otherwise, RSREG_ERR_NO_TARGET without a
+ * target); any later rsreg_icp_set_target* drops the normals.  The host buffer has been read when the call returns.
+ * _cloud: a device cloud of the context, e.g. what rsreg_cloud_normals wrote (read on the context's stream: keep it alive
+ * and unchanged until the next synchronising call has returned).  An alignment in plane mode without normals:
+ * RSREG_ERR_STATE from rsreg_icp_begin.  rsreg_icp_align, _align_records, _align_cloud, rsreg_icp_end and the fitness score
+ * work as for point-to-point; source normals, where the records carry any, are copied, not rotated. */
+int rsreg_icp_set_target_normals(rsreg_ctx *ctx, const void *normals, size_t n, size_t stride);
+int rsreg_icp_set_target_normals_cloud(rsreg_ctx *ctx, const rsreg_cloud *normals);
+/* Step-wise form: begin -> { search -> plane_sums -> update_plane } ... -> end.  The 32 sums (RSREG_NUM_PLANE_SUMS above)
+ * over the accepted correspondences of the last search; the solve, compose and criteria of rsreg_icp_update from them
+ * (ncorr = [0], mse = [1] / [0]; ncorr < 3: RSREG_CONV_NO_CORRESPONDENCES).  In plane mode rsreg_icp_sums and
+ * rsreg_icp_update return RSREG_ERR_STATE, and these two do in point-to-point mode. */
+int rsreg_icp_plane_sums(rsreg_ctx *ctx, double sums[RSREG_NUM_PLANE_SUMS]);
+int rsreg_icp_update_plane(rsreg_ctx *ctx, const double sums[RSREG_NUM_PLANE_SUMS], float *t_inc_out, int *done);
+/* The 32 sums of the last iteration of the last plane alignment (all 0 after a point-to-point one). */
+int rsreg_icp_plane_sums_last(rsreg_ctx *ctx, double sums[RSREG_NUM_PLANE_SUMS]);
+/* The solve alone (host only, no ctx): t_out = the increment, column-major; *rank_out (nullable) = eigen-directions used. */
+int rsreg_plane_solve_from_sums(const double sums[RSREG_NUM_PLANE_SUMS], float t_out[16], int *rank_out);
+
 /* ---- pcl::transformPointCloud(in, out, Matrix4f) ------------------------------------ */
 /* incremental_icp.hpp:63, icp_edge...hpp:116-117, ndt_edge...hpp:104-105.  in == out is
  * allowed.  Records are copied whole (stride bytes) and xyz rewritten; when !is_dense,
@@ -338,7 +403,6 @@ int rsreg_comm_allreduce_f64(rsreg_ctx *ctx, double *host_buf, int count);
  * uploaded once and the merged cloud downloaded once.  A cloud belongs to the ctx it was created
  * on; handles given to rsreg_icp_set_*_cloud must stay alive and unchanged until the align that
  * uses them has returned. */
-typedef struct rsreg_cloud rsreg_cloud;
 int rsreg_cloud_create(rsreg_ctx *ctx, rsreg_cloud **out);
 int rsreg_cloud_destroy(rsreg_cloud *cloud);
 int rsreg_cloud_upload(rsreg_cloud *cloud, const void *points, size_t n, size_t stride, uint32_t width,

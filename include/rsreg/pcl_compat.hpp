@@ -21,6 +21,7 @@
 
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -92,6 +93,29 @@ struct alignas(16) Normal {
     Normal(float nx, float ny, float nz) : data_n{nx, ny, nz, 0.f}, data_c{0.f, 0.f, 0.f, 0.f} {}
 };
 static_assert(sizeof(Normal) == 32, "Normal must stay byte-compatible with pcl::Normal");
+
+// ---- pcl::PointXYZRGBNormal: 48 bytes, 16-byte aligned -- data[4], data_n[4], then rgb, curvature and two words of padding
+// (the reference declares it as rgb_normal_point, src/types.hpp:11-12, and never uses it)
+struct alignas(16) PointXYZRGBNormal {
+    float x = 0.f, y = 0.f, z = 0.f, data3 = 1.f;
+    union {
+        float data_n[4];
+        float normal[3];
+        struct { float normal_x, normal_y, normal_z; };
+    };
+    union {
+        struct { uint8_t b, g, r, a; };
+        float rgb;
+        uint32_t rgba;
+    };
+    float curvature = 0.f;
+    uint32_t pad_[2] = {0, 0};
+    PointXYZRGBNormal() : data_n{0.f, 0.f, 0.f, 0.f}, rgba(0xff000000u) {}
+};
+static_assert(sizeof(PointXYZRGBNormal) == 48, "PointXYZRGBNormal must stay byte-compatible with pcl::PointXYZRGBNormal");
+static_assert(offsetof(PointXYZRGBNormal, x) == 0 && offsetof(PointXYZRGBNormal, data_n) == 16 && offsetof(PointXYZRGBNormal, rgba) == 32 &&
+                  offsetof(PointXYZRGBNormal, curvature) == 36,
+              "PointXYZRGBNormal: xyz at 0, the normal at 16, rgb at 32, curvature at 36");
 
 // ---- storage of a cloud's points.  pcl::PointCloud keeps a std::vector with Eigen's aligned allocator; this one is
 // aligned too and can hand out records WITHOUT constructing them one by one, for the callers that overwrite every
@@ -400,6 +424,9 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
                                        prm_.max_correspondence_distance), c);
             target_dirty_ = false;
             ctx_->icp_target_owner = this;
+            target_set_(c, true);
+        } else {
+            target_set_(c, false);
         }
         // `output = input` (PCL copies the input cloud first, then rewrites xyz) is made inside the call, by the host threads that
         // write the aligned positions anyway (rsreg_icp_align_records): the records are never constructed or copied here
@@ -446,6 +473,9 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
             target_stamp_ = cloud_stamp(dtarget_->handle());
             target_dirty_ = false;
             ctx_->icp_target_owner = this;
+            target_set_(c, true);
+        } else {
+            target_set_(c, false);
         }
         const auto t2 = std::chrono::steady_clock::now();
         check(rsreg_icp_align_cloud(c, guess.data(), &prm_, &res_, output.handle()), c);
@@ -474,8 +504,12 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
         return score;
     }
     const rsreg_icp_result &result() const { return res_; }
+    virtual ~IterativeClosestPoint() = default;
 
-  private:
+  protected:
+    // the context holds this object's target (`fresh`: it has just been set): what a derived class hands over with it
+    // (IterativeClosestPointWithNormals: the target's normals, which a new target drops)
+    virtual void target_set_(rsreg_ctx *, bool /*fresh*/) {}
     std::shared_ptr<Context> ctx_;
     rsreg_icp_params prm_;
     rsreg_icp_result res_{};
@@ -487,6 +521,64 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
     bool source_dirty_ = true, target_dirty_ = true, reuse_target_index_ = false;
     std::pair<uint64_t, uint64_t> source_stamp_{0, 0}, target_stamp_{0, 0};   // (id, version) of the device clouds as loaded
     std::chrono::steady_clock::time_point t1_;
+};
+
+namespace detail {
+template <typename PointT, typename = void> struct has_normal : std::false_type {};
+template <typename PointT> struct has_normal<PointT, decltype((void)std::declval<PointT &>().normal_x)> : std::true_type {};
+}  // namespace detail
+
+// ---- pcl::IterativeClosestPointWithNormals: point-to-plane ICP with PCL's default estimator,
+// TransformationEstimationPointToPlaneLLS (rsreg.h: rsreg_estimation, RSREG_NUM_PLANE_SUMS; the two stated deviations from
+// PCL are there).  The target's normals come inside the target's records (a host cloud of PointXYZRGBNormal: xyz at stride
+// 48, the normals at byte 16) or beside them: setInputTargetNormals, for PointXYZRGB targets plus NormalEstimation's output,
+// on the host or in HBM.  align(out) copies the source records as IterativeClosestPoint does; the normals of the SOURCE
+// records, if they carry any, are not rotated in `out` (PCL rotates them; nothing downstream reads them).
+template <typename PointSource, typename PointTarget>
+class IterativeClosestPointWithNormals : public IterativeClosestPoint<PointSource, PointTarget> {
+    using Base = IterativeClosestPoint<PointSource, PointTarget>;
+
+  public:
+    explicit IterativeClosestPointWithNormals(std::shared_ptr<Context> ctx = Context::Default()) : Base(std::move(ctx))
+    {
+        this->prm_.estimation = RSREG_ESTIMATION_POINT_TO_PLANE_LLS;
+    }
+    // one normal per target record; the cloud must stay alive and unchanged until align has returned
+    void setInputTargetNormals(const PointCloud<Normal> &normals) { normals_ = &normals; dnormals_ = nullptr; normals_dirty_ = true; }
+    void setInputTargetNormals(const DeviceCloud<Normal> &normals) { dnormals_ = &normals; normals_ = nullptr; normals_dirty_ = true; }
+
+  protected:
+    void target_set_(rsreg_ctx *c, bool fresh) override
+    {
+        if (dnormals_ && cloud_stamp(dnormals_->handle()) != normals_stamp_) normals_dirty_ = true;   // (rewritten in place since)
+        if (!fresh && !normals_dirty_) return;
+        if (dnormals_) {
+            check(rsreg_icp_set_target_normals_cloud(c, dnormals_->handle()), c);
+            normals_stamp_ = cloud_stamp(dnormals_->handle());
+        } else if (normals_) {
+            check(rsreg_icp_set_target_normals(c, normals_->points.data(), normals_->size(), sizeof(Normal)), c);
+        } else {
+            set_record_normals_(c, detail::has_normal<PointTarget>());
+        }
+        normals_dirty_ = false;
+    }
+
+  private:
+    void set_record_normals_(rsreg_ctx *c, std::true_type)
+    {
+        if (!this->target_) throw Error(RSREG_ERR_STATE, "rsreg: a device-cloud target needs setInputTargetNormals");
+        const char *rec = reinterpret_cast<const char *>(this->target_->points.data());
+        check(rsreg_icp_set_target_normals(c, this->target_->size() ? rec + offsetof(PointTarget, data_n) : nullptr, this->target_->size(),
+                                           sizeof(PointTarget)), c);
+    }
+    void set_record_normals_(rsreg_ctx *, std::false_type)
+    {
+        throw Error(RSREG_ERR_STATE, "rsreg: the target's points carry no normals: setInputTargetNormals");
+    }
+    const PointCloud<Normal> *normals_ = nullptr;
+    const DeviceCloud<Normal> *dnormals_ = nullptr;
+    bool normals_dirty_ = true;
+    std::pair<uint64_t, uint64_t> normals_stamp_{0, 0};
 };
 
 // ---- pcl::NormalDistributionsTransform

@@ -511,6 +511,86 @@ class IterativeClosestPoint:
         return gi
 
 
+# pcl::PointXYZRGBNormal: 48 bytes -- data[4], data_n[4], then rgb, curvature and two words of padding
+POINT_NORMAL_DTYPE = np.dtype({"names": ["x", "y", "z", "w", "normal_x", "normal_y", "normal_z", "data_n3", "rgba", "curvature", "pad0", "pad1"],
+                               "formats": ["<f4"] * 8 + ["<u4", "<f4", "<u4", "<u4"], "offsets": list(range(0, 48, 4)), "itemsize": 48})
+
+
+class IterativeClosestPointWithNormals(IterativeClosestPoint):
+    """pcl::IterativeClosestPointWithNormals on the MI355X: point-to-plane ICP with PCL's default estimator,
+    TransformationEstimationPointToPlaneLLS (include/rsreg.h: rsreg_estimation, RSREG_NUM_PLANE_SUMS).  The target's normals
+    come with the target -- setInputTarget(cloud, normals) or setInputTargetNormals(normals), a NormalCloud / NORMAL_DTYPE
+    array, an (n, >= 3) float32 array or a DeviceCloud of pcl::Normal records (NormalEstimation.compute of a DeviceCloud) --
+    or inside it: a POINT_NORMAL_DTYPE array as the target hands over xyz at stride 48 and the normals at byte 16.  The
+    aligned cloud's own normals, if its records carry any, are copied, not rotated."""
+
+    def __init__(self, ctx=None):
+        super().__init__(ctx)
+        self.params.estimation = _l.ESTIMATION_POINT_TO_PLANE_LLS
+        self._normals = None
+        self._normals_dirty = True
+
+    def setInputTarget(self, cloud, normals=None):
+        super().setInputTarget(cloud)
+        self._normals = normals
+        self._normals_dirty = True
+
+    def setInputTargetNormals(self, normals):
+        self._normals = normals
+        self._normals_dirty = True
+
+    def _sync_inputs(self):
+        rebuilt = self._tgt_dirty or self.ctx.icp_target_owner is not self or getattr(self, "_tgt_gate", None) != self.params.max_correspondence_distance
+        if isinstance(self._tgt, DeviceCloud) and getattr(self, "_tgt_stamp", None) != self._tgt.stamp:
+            rebuilt = True
+        if isinstance(self._normals, DeviceCloud) and getattr(self, "_nrm_stamp", None) != self._normals.stamp:
+            self._normals_dirty = True
+        super()._sync_inputs()
+        if not (rebuilt or self._normals_dirty):   # (a new target index drops the normals of the one before)
+            return
+        L, h = _l.lib(), self.ctx.h
+        nrm = self._normals
+        if nrm is None:
+            pts = getattr(self._tgt, "points", self._tgt)
+            if not (isinstance(pts, np.ndarray) and pts.dtype.names and "normal_x" in pts.dtype.names):
+                raise _l.RsregError(_l.RSREG_ERR_STATE, "IterativeClosestPointWithNormals: the target has no normals (setInputTargetNormals)")
+            pts = np.ascontiguousarray(pts)
+            _l.check(L.rsreg_icp_set_target_normals(h, pts.ctypes.data + pts.dtype.fields["normal_x"][1], len(pts), pts.dtype.itemsize), h)
+        elif isinstance(nrm, DeviceCloud):
+            _l.check(L.rsreg_icp_set_target_normals_cloud(h, nrm.h), h)
+            self._nrm_stamp = nrm.stamp
+        else:
+            rec = np.ascontiguousarray(getattr(nrm, "points", nrm))
+            if rec.dtype.names:
+                off = rec.dtype.fields["normal_x"][1]
+                _l.check(L.rsreg_icp_set_target_normals(h, rec.ctypes.data + off, len(rec), rec.dtype.itemsize), h)
+            else:
+                if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] < 3:
+                    raise ValueError("normals must be a NormalCloud, a structured array with normal_x or an (n, >=3) float32 array")
+                _l.check(L.rsreg_icp_set_target_normals(h, rec.ctypes.data, rec.shape[0], rec.shape[1] * 4), h)
+        self._normals_dirty = False
+
+    # ---- step-wise form: begin -> { search -> plane_sums -> update_plane } -> end
+    def plane_sums(self):
+        s = np.zeros(_l.NUM_PLANE_SUMS, np.float64)
+        _l.check(_l.lib().rsreg_icp_plane_sums(self.ctx.h, s.ctypes.data), self.ctx.h)
+        return s
+
+    def update_plane(self, sums):
+        sums = np.ascontiguousarray(sums, np.float64)
+        if sums.size != _l.NUM_PLANE_SUMS:
+            raise ValueError("update_plane takes the 32 plane sums")
+        t = np.zeros(16, np.float32)
+        done = C.c_int(0)
+        _l.check(_l.lib().rsreg_icp_update_plane(self.ctx.h, sums.ctypes.data, t.ctypes.data, C.byref(done)), self.ctx.h)
+        return _rowmajor(t), bool(done.value)
+
+    def plane_sums_last(self):
+        s = np.zeros(_l.NUM_PLANE_SUMS, np.float64)
+        _l.check(_l.lib().rsreg_icp_plane_sums_last(self.ctx.h, s.ctypes.data), self.ctx.h)
+        return s
+
+
 class NormalDistributionsTransform:
     """pcl::NormalDistributionsTransform<PointXYZRGB, PointXYZRGB> on the MI355X."""
 
@@ -867,3 +947,15 @@ def umeyama_from_sums(sums):
     t = np.zeros(16, np.float32)
     _l.check(_l.lib().rsreg_umeyama_from_sums(sums.ctypes.data, t.ctypes.data))
     return _rowmajor(t)
+
+
+def plane_solve_from_sums(sums, want_rank=False):
+    """TransformationEstimationPointToPlaneLLS from the 32 plane sums (rsreg_plane_solve_from_sums, host only): the 4x4
+    increment, with want_rank also the number of eigen-directions of AtA that carried data."""
+    sums = np.ascontiguousarray(sums, np.float64)
+    if sums.size != _l.NUM_PLANE_SUMS:
+        raise ValueError("plane_solve_from_sums takes the 32 plane sums")
+    t = np.zeros(16, np.float32)
+    rank = C.c_int(0)
+    _l.check(_l.lib().rsreg_plane_solve_from_sums(sums.ctypes.data, t.ctypes.data, C.byref(rank)))
+    return (_rowmajor(t), rank.value) if want_rank else _rowmajor(t)

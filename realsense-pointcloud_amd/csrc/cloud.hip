@@ -870,6 +870,16 @@ int rsreg_icp_set_target_cloud(rsreg_ctx *ctx, const rsreg_cloud *c, double max_
     return RSREG_OK;
 }
 
+// the normals of the ICP target from a device cloud (what rsreg_cloud_normals wrote: 32-byte pcl::Normal records; any stride
+// whose first 12 bytes are the normal): one per target record
+extern "C" int rsreg_icp_set_target_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride);   // icp.hip
+int rsreg_icp_set_target_normals_cloud(rsreg_ctx *ctx, const rsreg_cloud *c)
+{
+    if (!ctx || !c || c->ctx != ctx) return RSREG_ERR_INVALID_ARG;
+    RSREG_HIP(ctx, settle(c));
+    return rsreg_icp_set_target_normals_device_(ctx, c->n ? c->buf.ptr : nullptr, c->n, c->stride);
+}
+
 // 1 when the context's ICP target index was built from this cloud, as it is now, for this gate: the ICP edge scheme
 // hands the same grown feature cloud to its coarse and to its refining ICP, one after the other
 // (icp_edge_based_registration.hpp:94-95,108-109), and the second of them may keep the index instead of building it again

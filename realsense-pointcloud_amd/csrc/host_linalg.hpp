@@ -412,6 +412,101 @@ inline void eig_sym3(const double *Ain, double *evals, double *evecs)
     }
 }
 
+// Symmetric N x N eigen-decomposition by cyclic two-sided Jacobi (row-major; only rotations about a non-zero off-diagonal
+// entry are made, so a row and column of exact zeros stays one and its unit vector an eigenvector, exactly); eigenvalues
+// ascending, vectors in columns.
+template <int N> inline void eig_sym(const double *Ain, double *evals, double *evecs)
+{
+    double A[N * N], V[N * N];
+    for (int i = 0; i < N * N; ++i) { A[i] = Ain[i]; V[i] = (i % (N + 1) == 0) ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        double off = 0, dia = 0;
+        for (int i = 0; i < N; ++i)
+            for (int j = 0; j < N; ++j) (i == j ? dia : off) += A[i * N + j] * A[i * N + j];
+        if (off <= 1e-34 * (dia + 1e-300)) break;
+        for (int p = 0; p + 1 < N; ++p)
+            for (int q = p + 1; q < N; ++q) {
+                const double apq = A[p * N + q];
+                if (apq == 0.0) continue;
+                const double th = (A[q * N + q] - A[p * N + p]) / (2.0 * apq);
+                const double t = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < N; ++k) {
+                    const double a = A[k * N + p], b = A[k * N + q];
+                    A[k * N + p] = c * a - s * b;
+                    A[k * N + q] = s * a + c * b;
+                }
+                for (int k = 0; k < N; ++k) {
+                    const double a = A[p * N + k], b = A[q * N + k];
+                    A[p * N + k] = c * a - s * b;
+                    A[q * N + k] = s * a + c * b;
+                }
+                for (int k = 0; k < N; ++k) {
+                    const double a = V[k * N + p], b = V[k * N + q];
+                    V[k * N + p] = c * a - s * b;
+                    V[k * N + q] = s * a + c * b;
+                }
+            }
+    }
+    int o[N];
+    for (int k = 0; k < N; ++k) o[k] = k;
+    for (int a = 0; a + 1 < N; ++a)
+        for (int b = a + 1; b < N; ++b)
+            if (A[o[b] * N + o[b]] < A[o[a] * N + o[a]]) { int t = o[a]; o[a] = o[b]; o[b] = t; }
+    for (int k = 0; k < N; ++k) {
+        evals[k] = A[o[k] * N + o[k]];
+        for (int i = 0; i < N; ++i) evecs[i * N + k] = V[i * N + o[k]];
+    }
+}
+
+// TransformationEstimationPointToPlaneLLS from the 32 sums of a point-to-plane iteration (layout, the rank rule and its
+// derivation: include/rsreg.h RSREG_NUM_PLANE_SUMS): x = (alpha, beta, gamma, tx, ty, tz) = pinv(AtA) Atb over the
+// eigen-directions of AtA that carry data, T = PCL's constructTransformationMatrix(x) (Rz Ry Rx, full sines and cosines in
+// double) rounded to float.  Nothing in the system, or nothing above the cut: the identity.  *rank_out (nullable): the
+// number of directions used.
+inline void plane_solve_from_sums(const double *sums, Mat4f &T, int *rank_out = nullptr)
+{
+    T = Mat4f::identity();
+    int rank = 0;
+    double x[6] = {0, 0, 0, 0, 0, 0};
+    if (sums[2] > 0) {
+        double A[36], evals[6], evecs[36], trace = 0;
+        int k = 4;
+        for (int r = 0; r < 6; ++r)
+            for (int c = r; c < 6; ++c) A[r * 6 + c] = A[c * 6 + r] = sums[k++];
+        for (int r = 0; r < 6; ++r) trace += A[r * 6 + r];
+        eig_sym<6>(A, evals, evecs);
+        const double cut = (sums[2] + 80.0) * 1.1102230246251565e-16 * trace;   // 2^-53
+        for (int e = 5; e >= 0; --e) {   // (largest first: the order the directions are added in is part of the result)
+            if (!(evals[e] > cut)) continue;
+            double d = 0;
+            for (int i = 0; i < 6; ++i) d += evecs[i * 6 + e] * sums[25 + i];
+            d /= evals[e];
+            for (int i = 0; i < 6; ++i) x[i] += evecs[i * 6 + e] * d;
+            ++rank;
+        }
+        for (int i = 0; i < 6; ++i)
+            if (!std::isfinite(x[i])) { rank = 0; break; }
+        if (rank == 0)
+            for (int i = 0; i < 6; ++i) x[i] = 0;
+    }
+    if (rank_out) *rank_out = rank;
+    if (rank == 0) return;
+    const double sa = std::sin(x[0]), ca = std::cos(x[0]), sb = std::sin(x[1]), cb = std::cos(x[1]), sg = std::sin(x[2]), cg = std::cos(x[2]);
+    T(0, 0) = float(cg * cb);
+    T(0, 1) = float(-sg * ca + cg * sb * sa);
+    T(0, 2) = float(sg * sa + cg * sb * ca);
+    T(1, 0) = float(sg * cb);
+    T(1, 1) = float(cg * ca + sg * sb * sa);
+    T(1, 2) = float(-cg * sa + sg * sb * ca);
+    T(2, 0) = float(-sb);
+    T(2, 1) = float(cb * sa);
+    T(2, 2) = float(cb * ca);
+    T(0, 3) = float(x[3]);
+    T(1, 3) = float(x[4]);
+    T(2, 3) = float(x[5]);
+}
+
 inline bool inv3(const double *M, double *Inv)
 {
     const double det = det3(M);

@@ -21,6 +21,7 @@
 #include "cellsort.hpp"
 #include "oscan.hpp"
 #include "fitness_kernels.hpp"
+#include "plane_kernels.hpp"
 
 using namespace rsreg;
 
@@ -1006,6 +1007,9 @@ bool filters_on(const rsreg_icp_params &p)
     return p.use_reciprocal_correspondences != 0 || (p.trim_overlap_ratio > 0.0 && p.trim_overlap_ratio < 1.0);
 }
 
+// point-to-plane ICP (rsreg_estimation): the 32 sums and the 6-unknown solve take the place of the 17 sums and Umeyama
+bool plane_on(const rsreg_icp_params &p) { return p.estimation == RSREG_ESTIMATION_POINT_TO_PLANE_LLS; }
+
 // reciprocal check of one matched pair: is the source point the nearest source point of its target point?
 template <bool kDense>
 __global__ __launch_bounds__(kBlock) void k_recip_filter(const float4 *tgt, int *corr_pos, uint32_t *cw, uint32_t n, DenseDev gd, GridDev gh,
@@ -1196,6 +1200,37 @@ int launch_sums(rsreg_ctx *ctx, double *sums, bool global)
         RSREG_HIP(ctx, hipGetLastError());
     }
     return fetch_sums(ctx, sums, global);
+}
+
+// The 32 sums of a point-to-plane iteration (include/rsreg.h: RSREG_NUM_PLANE_SUMS) over the search's pairs: k_plane_reduce in
+// the place of k_cov_reduce, k_final_reduce with a block per sum.  One rank only (rsreg_icp_begin): nothing is all-reduced.
+int launch_plane_sums(rsreg_ctx *ctx, double *sums)
+{
+    ctx->icp.idle_after_sums = false;
+    {
+        int rcr = ensure_restarted(ctx);
+        if (rcr) return rcr;
+    }
+    const uint32_t n = (uint32_t)ctx->n_work;
+    const uint32_t nb = reduce_blocks(n);
+    RSREG_HIP(ctx, ctx->d_plane_partials.reserve((size_t)nb * RSREG_NUM_PLANE_SUMS * 8));
+    {
+        ScopedEvents ev(ctx, &ctx->ev_reduce);
+        k_plane_reduce<<<nb, kTile, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(),
+                                                      filters_on(ctx->icp.prm) ? ctx->d_corr_w.as<uint32_t>() : nullptr,
+                                                      ctx->d_tgt_sorted.as<float4>(), ctx->d_normals.as<float4>(), n,
+                                                      ctx->d_plane_partials.as<double>());
+        RSREG_HIP(ctx, hipGetLastError());
+        k_final_reduce<<<RSREG_NUM_PLANE_SUMS, kReduceBlock, 0, ctx->stream>>>(ctx->d_plane_partials.as<double>(), nb, host_sums_target(ctx));
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    double *h = ctx->h_sums.as<double>();
+    if (ctx->comm) RSREG_HIP(ctx, hipMemcpyAsync(h, ctx->d_sums.ptr, RSREG_NUM_PLANE_SUMS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->icp.idle_after_sums = true;
+    (void)target_counts(ctx, false);
+    std::memcpy(sums, h, RSREG_NUM_PLANE_SUMS * 8);
+    return RSREG_OK;
 }
 
 // ---- tile schedule of the fused dense kernel (icp_dense.hpp: TileSched) -------------------------------------
@@ -1658,6 +1693,47 @@ int update_from_sums(rsreg_ctx *ctx, const double *sums, int *done)
     return RSREG_OK;
 }
 
+// The same for one point-to-plane iteration's 32 sums: TransformationEstimationPointToPlaneLLS (host_linalg.hpp:
+// plane_solve_from_sums) in the place of Umeyama.  result->sums_last keeps its layout: [0] and [16] are filled.
+int update_from_plane_sums(rsreg_ctx *ctx, const double *sums, int *done)
+{
+    IcpState &s = ctx->icp;
+    std::memcpy(s.plane_sums_last, sums, sizeof(s.plane_sums_last));
+    std::memset(s.sums_last, 0, sizeof(s.sums_last));
+    s.sums_last[0] = sums[0];
+    s.sums_last[16] = sums[1];
+    s.ncorr = (uint64_t)(sums[0] + 0.5);
+    if (s.ncorr < 3) {  // min_number_correspondences_
+        s.state = RSREG_CONV_NO_CORRESPONDENCES;
+        s.converged = 0;
+        *done = 1;
+        return RSREG_OK;
+    }
+    plane_solve_from_sums(sums, s.t_inc);
+    s.pending_transform = true;
+    s.final_t = mul(s.t_inc, s.final_t);
+    s.iterations++;
+    s.cur_mse = sums[1] / sums[0];
+    s.converged = criteria_has_converged(s) ? 1 : 0;
+    s.have_search = false;
+    *done = s.converged;
+    return RSREG_OK;
+}
+
+// the target's normals from records already in HBM (three floats at d_rec + i * stride), on the context's stream
+int set_normals_device(rsreg_ctx *ctx, const char *d_rec, size_t n, size_t stride)
+{
+    if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
+    if (n != ctx->n_target_raw) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per target record: the counts differ");
+    RSREG_HIP(ctx, ctx->d_normals.reserve((n + 1) * sizeof(float4)));
+    if (n) {
+        k_pack_normals<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(d_rec, stride, (uint32_t)n, ctx->d_normals.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    ctx->have_normals = true;
+    return RSREG_OK;
+}
+
 // A host cloud on its way into HBM, packed xyz (PCL's ICP reads nothing else of a point): the caller's records are
 // packed into pinned memory piece by piece (the pool of host threads, workers.hpp) and every piece goes over the PCIe link
 // on the context's upload stream while the next one is being packed; `stage` / `ev`: the staging buffer of this kind of
@@ -1838,6 +1914,7 @@ int rsreg_icp_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
 {
     (void)is_dense;
     if (!ctx || (n && !d_points) || stride < 12 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
+    ctx->have_normals = false;   // (of the target before this one)
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     return build_grid(ctx, static_cast<const char *>(d_points), n, stride, max_correspondence_distance);
 }
@@ -1845,6 +1922,7 @@ int rsreg_icp_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
 // (internal, cloud.hip) a target for the handful of source points already loaded: no index, see scan_target
 int rsreg_icp_set_target_scan_(rsreg_ctx *ctx, const void *d_points, size_t n, size_t stride, double max_correspondence_distance)
 {
+    ctx->have_normals = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     return scan_target(ctx, static_cast<const char *>(d_points), n, stride, max_correspondence_distance);
 }
@@ -1854,6 +1932,7 @@ int rsreg_icp_set_target(rsreg_ctx *ctx, const void *points, size_t n, size_t st
 {
     (void)is_dense;
     if (!ctx || (n && !points) || stride < 12) return RSREG_ERR_INVALID_ARG;
+    ctx->have_normals = false;   // (of the target before this one)
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     rsreg_host_timing &ht = ctx->host_timing;
     // a counting build that was queued and not waited for (build_dense) still reads d_tgt_raw on the main stream, and the
@@ -1906,12 +1985,19 @@ int rsreg_icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *
     // the reciprocal search, a different answer from one GPU's (a global trim across ranks is not implemented)
     if (ctx->nranks > 1 && filters_on(*params))
         return fail(ctx, RSREG_ERR_INVALID_ARG, "reciprocal correspondences and the trimmed rejector need the whole source: not with more than one rank");
+    if (params->estimation != RSREG_ESTIMATION_SVD && params->estimation != RSREG_ESTIMATION_POINT_TO_PLANE_LLS)
+        return fail(ctx, RSREG_ERR_INVALID_ARG, "unknown transformation estimation");
+    if (plane_on(*params)) {
+        // (the all-reduce of the 32 sums is not implemented, as a global trim is not)
+        if (ctx->nranks > 1) return fail(ctx, RSREG_ERR_INVALID_ARG, "point-to-plane ICP: not with more than one rank");
+        if (!ctx->have_normals) return fail(ctx, RSREG_ERR_STATE, "point-to-plane ICP needs rsreg_icp_set_target_normals after rsreg_icp_set_target");
+    }
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     {
         int rcj = join_source(ctx);
         if (rcj) return rcj;
     }
-    if (ctx->grid.dense == 2 && (ctx->n_work > kScanMaxSource || filters_on(*params))) {
+    if (ctx->grid.dense == 2 && (ctx->n_work > kScanMaxSource || filters_on(*params) || plane_on(*params))) {
         // the target was set for a handful of queries (scan_target); this alignment needs the index after all
         if (!ctx->scan_raw) return fail(ctx, RSREG_ERR_NO_TARGET, "the target cloud was released before its index was built");
         int rcb = build_grid(ctx, ctx->scan_raw, ctx->n_target_raw, ctx->scan_stride, ctx->gate_built_for);
@@ -1968,6 +2054,7 @@ int rsreg_icp_sums(rsreg_ctx *ctx, double sums[RSREG_NUM_SUMS])
 {
     if (!ctx || !sums) return RSREG_ERR_INVALID_ARG;
     if (!ctx->icp.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_icp_begin not called");
+    if (plane_on(ctx->icp.prm)) return fail(ctx, RSREG_ERR_STATE, "point-to-plane alignment: rsreg_icp_plane_sums");
     if (!ctx->icp.have_search) return fail(ctx, RSREG_ERR_STATE, "rsreg_icp_search not called for this iteration");
     return launch_sums(ctx, sums, false);
 }
@@ -1985,9 +2072,73 @@ int rsreg_icp_update(rsreg_ctx *ctx, const double sums[RSREG_NUM_SUMS], float *t
 {
     if (!ctx || !sums || !done) return RSREG_ERR_INVALID_ARG;
     if (!ctx->icp.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_icp_begin not called");
+    if (plane_on(ctx->icp.prm)) return fail(ctx, RSREG_ERR_STATE, "point-to-plane alignment: rsreg_icp_update_plane");
     int rc = update_from_sums(ctx, sums, done);
     if (rc) return rc;
     if (t_inc_out) std::memcpy(t_inc_out, ctx->icp.t_inc.m, 64);
+    return RSREG_OK;
+}
+
+int rsreg_icp_set_target_normals(rsreg_ctx *ctx, const void *normals, size_t n, size_t stride)
+{
+    if (!ctx || (n && !normals) || stride < 12) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
+    if (n != ctx->n_target_raw) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per target record: the counts differ");
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    // staged like the target: packed into pinned memory of its own, over the link on the upload stream, the main stream behind it
+    RSREG_HIP(ctx, ctx->h2d.ensure());
+    RSREG_HIP(ctx, ctx->ev_nrm.ensure());
+    RSREG_HIP(ctx, ctx->ev_nrm_packed.ensure());
+    RSREG_HIP(ctx, hipStreamWaitEvent(ctx->h2d.stream, ctx->ev_nrm_packed, 0));   // (normals set before may still be read from d_nrm_raw)
+    int rc = upload_packed(ctx, ctx->h_nrm, ctx->ev_nrm, ctx->d_nrm_raw, normals, n, stride, ctx->stream, nullptr, nullptr);
+    if (rc) return rc;
+    rc = set_normals_device(ctx, ctx->d_nrm_raw.as<char>(), n, 12);
+    if (rc) return rc;
+    RSREG_HIP(ctx, hipEventRecord(ctx->ev_nrm_packed, ctx->stream));
+    return RSREG_OK;
+}
+
+// (internal, cloud.hip: rsreg_icp_set_target_normals_cloud) normals already in HBM
+int rsreg_icp_set_target_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride)
+{
+    if (!ctx || (n && !d_normals) || stride < 12 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    return set_normals_device(ctx, static_cast<const char *>(d_normals), n, stride);
+}
+
+int rsreg_icp_plane_sums(rsreg_ctx *ctx, double sums[RSREG_NUM_PLANE_SUMS])
+{
+    if (!ctx || !sums) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->icp.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_icp_begin not called");
+    if (!plane_on(ctx->icp.prm)) return fail(ctx, RSREG_ERR_STATE, "point-to-point alignment: rsreg_icp_sums");
+    if (!ctx->icp.have_search) return fail(ctx, RSREG_ERR_STATE, "rsreg_icp_search not called for this iteration");
+    return launch_plane_sums(ctx, sums);
+}
+
+int rsreg_icp_update_plane(rsreg_ctx *ctx, const double sums[RSREG_NUM_PLANE_SUMS], float *t_inc_out, int *done)
+{
+    if (!ctx || !sums || !done) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->icp.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_icp_begin not called");
+    if (!plane_on(ctx->icp.prm)) return fail(ctx, RSREG_ERR_STATE, "point-to-point alignment: rsreg_icp_update");
+    int rc = update_from_plane_sums(ctx, sums, done);
+    if (rc) return rc;
+    if (t_inc_out) std::memcpy(t_inc_out, ctx->icp.t_inc.m, 64);
+    return RSREG_OK;
+}
+
+int rsreg_icp_plane_sums_last(rsreg_ctx *ctx, double sums[RSREG_NUM_PLANE_SUMS])
+{
+    if (!ctx || !sums) return RSREG_ERR_INVALID_ARG;
+    std::memcpy(sums, ctx->icp.plane_sums_last, sizeof(ctx->icp.plane_sums_last));
+    return RSREG_OK;
+}
+
+int rsreg_plane_solve_from_sums(const double sums[RSREG_NUM_PLANE_SUMS], float t_out[16], int *rank_out)
+{
+    if (!sums || !t_out) return RSREG_ERR_INVALID_ARG;
+    Mat4f T;
+    plane_solve_from_sums(sums, T, rank_out);
+    std::memcpy(t_out, T.m, sizeof(T.m));
     return RSREG_OK;
 }
 
@@ -2183,8 +2334,9 @@ int icp_align(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params
     int rc = rsreg_icp_begin(ctx, guess, params);
     if (rc) return rc;
     int done = 0;
-    double sums[RSREG_NUM_SUMS];
-    const bool filtered = filters_on(*params);   // the optional correspondence filters run between the staged kernels
+    double sums[RSREG_NUM_PLANE_SUMS];   // (the 17 of a point-to-point iteration, or the 32 of a point-to-plane one)
+    const bool plane = plane_on(*params);     // point-to-plane: staged, with its own sums and solve
+    const bool filtered = filters_on(*params) || plane;   // the optional correspondence filters run between the staged kernels
     const bool scan = ctx->grid.dense == 2;   // no index: the staged kernels (search over the whole target, sums)
     const bool fused = !filtered && !scan && (params->pipeline_mode == RSREG_PIPELINE_FUSED || params->pipeline_mode == RSREG_PIPELINE_DEVICE_LOOP);
     if (!filtered && !scan && params->pipeline_mode == RSREG_PIPELINE_DEVICE_LOOP && params->criteria_mode == RSREG_CRITERIA_FIXED) {
@@ -2198,10 +2350,10 @@ int icp_align(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params
         } else {
             rc = apply_pending_transform(ctx);
             if (!rc) rc = launch_search(ctx);
-            if (!rc) rc = launch_sums(ctx, sums, true);
+            if (!rc) rc = plane ? launch_plane_sums(ctx, sums) : launch_sums(ctx, sums, true);
         }
         if (rc) return rc;
-        rc = update_from_sums(ctx, sums, &done);
+        rc = plane ? update_from_plane_sums(ctx, sums, &done) : update_from_sums(ctx, sums, &done);
         if (rc) return rc;
     }
     return icp_end(ctx, result, aligned_out, out_stride, source_records);

@@ -200,6 +200,7 @@ struct IcpState {
     double prev_mse = 0, cur_mse = 0;
     uint64_t ncorr = 0;
     double sums_last[RSREG_NUM_SUMS] = {0};
+    double plane_sums_last[RSREG_NUM_PLANE_SUMS] = {0};   // point-to-plane: the 32 sums of the last iteration
     double svd_v[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};   // V of the previous Umeyama solve (warm start of the next)
     bool have_search = false;     // corr buffers hold the current iteration's search
     bool pending_transform = false;  // fused mode: t_inc not yet applied to d_cur
@@ -265,6 +266,14 @@ struct rsreg_ctx {
     const char *scan_raw = nullptr;      // ... and the records the index is built from if an alignment needs it after all
     size_t scan_stride = 0;
     uint64_t tgt_cloud_id = 0, tgt_cloud_version = 0;   // the device cloud the ICP target index was built from (0: none)
+    // point-to-plane ICP: the target's normals, float4 {nx, ny, nz, 0} per target RECORD in the caller's order (the sorted
+    // target records carry that index); dropped by every rsreg_icp_set_target*
+    bool have_normals = false;
+    rsreg::DevBuf d_normals;
+    rsreg::DevBuf d_nrm_raw;      // packed normals of a host buffer as they came over the link (n x float3) ...
+    rsreg::PinnedBuf h_nrm;       // ... their staging buffer (rsreg_icp_set_target_normals, on the upload stream like the target's) ...
+    rsreg::Event ev_nrm, ev_nrm_packed;   // ... the event behind its last copy, and: the main stream has read d_nrm_raw (made at first use)
+    rsreg::DevBuf d_plane_partials;   // double[32][blocks] of k_plane_reduce
 
     // ---- ICP source
     bool have_source = false;

@@ -19,6 +19,8 @@ CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) if os.path.isdir(CSRC) else []
 NUM_SUMS = 17
+NUM_PLANE_SUMS = 32                                      # include/rsreg.h: RSREG_NUM_PLANE_SUMS
+ESTIMATION_SVD, ESTIMATION_POINT_TO_PLANE_LLS = 0, 1     # include/rsreg.h: rsreg_estimation
 RSREG_ERR_INVALID_ARG, RSREG_ERR_STATE = -1, -9   # include/rsreg.h: rsreg_status
 UNIQUE_ID_BYTES = 128
 
@@ -41,6 +43,8 @@ EXPORTS = [
     "rsreg_icp_grid_info", "rsreg_ctx_host_timing", "rsreg_lzf_max_encoded_size", "rsreg_lzf_encode", "rsreg_lzf_decode",
     "rsreg_icp_fitness_score", "rsreg_icp_fitness_sums", "rsreg_ndt_fitness_score",
     "rsreg_cloud_passthrough", "rsreg_cloud_sor", "rsreg_cloud_knn_mean_distance", "rsreg_cloud_knn", "rsreg_cloud_normals",
+    "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
+    "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
 ]
 
 
@@ -53,7 +57,7 @@ class RsregError(RuntimeError):
 class IcpParams(C.Structure):
     _fields_ = [
         ("max_iterations", C.c_int32), ("criteria_mode", C.c_int32), ("pipeline_mode", C.c_int32),
-        ("reserved0", C.c_int32), ("max_correspondence_distance", C.c_double),
+        ("estimation", C.c_int32), ("max_correspondence_distance", C.c_double),
         ("transformation_epsilon", C.c_double), ("transformation_rotation_epsilon", C.c_double),
         ("euclidean_fitness_epsilon", C.c_double), ("use_reciprocal_correspondences", C.c_int32), ("reserved1", C.c_int32),
         ("trim_overlap_ratio", C.c_double),
@@ -223,6 +227,12 @@ def lib():
     L.rsreg_icp_update.argtypes = [vp, vp, vp, C.POINTER(i32)]
     L.rsreg_icp_end.argtypes = [vp, C.POINTER(IcpResult), vp, sz]
     L.rsreg_umeyama_from_sums.argtypes = [vp, vp]
+    L.rsreg_icp_set_target_normals.argtypes = [vp, vp, sz, sz]
+    L.rsreg_icp_set_target_normals_cloud.argtypes = [vp, vp]
+    L.rsreg_icp_plane_sums.argtypes = [vp, vp]
+    L.rsreg_icp_update_plane.argtypes = [vp, vp, vp, C.POINTER(i32)]
+    L.rsreg_icp_plane_sums_last.argtypes = [vp, vp]
+    L.rsreg_plane_solve_from_sums.argtypes = [vp, vp, C.POINTER(i32)]
     L.rsreg_transform_cloud.argtypes = [vp, vp, vp, sz, sz, i32, vp]
     L.rsreg_approx_voxel_grid.argtypes = [vp, sz, sz, vp, vp, C.POINTER(sz)]
     L.rsreg_approx_voxel_grid_gpu.argtypes = [vp, vp, sz, sz, vp, vp, C.POINTER(sz)]
