@@ -497,6 +497,54 @@ int rsreg_cloud_knn(rsreg_ctx *ctx, const rsreg_cloud *in, int k, int32_t *index
  * (computeMeanAndCovarianceMatrix); this is the covariance the formula defines, in double, about the record.  A PCL build
  * agrees with it to PCL's own rounding. */
 int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const float viewpoint[3], rsreg_cloud *out);
+/* pcl::IntegralImageNormalEstimation on an ORGANIZED cloud of w x h records P[r][c] (src/edge_extractor.hpp:9-15 runs it with
+ * AVERAGE_3D_GRADIENT, setMaxDepthChangeFactor(0.02f), setNormalSmoothingSize(10.0f) on every frame): a cost per pixel that
+ * does not depend on the scene, and no index.  PCL 1.9.1 features/impl/integral_image_normal.hpp, recalled; PCL is not
+ * available to check against, so what follows IS the contract.  f = max_depth_change_factor, s = normal_smoothing_size,
+ * B = (int)s, z = P.z; (a) - (d) are float32.
+ * (a) depth changes: M = 1 everywhere; for r in [0, h-1), c in [0, w-1): t = (f * (fabsf(z[r][c]) + 1.0f)) * 2.0f; if
+ *     fabsf(z[r][c] - z[r][c+1]) > t, or either depth is not finite, M[r][c] = M[r][c+1] = 0; likewise with z[r+1][c].
+ * (b) distance map: D[i] = 0 where M == 0, else (float)(w + h), i = r * w + c, then two sequential chamfer passes,
+ *     forward:  r = 1 .. h-1, c = 1 .. w-1:  m = min(min(D[i-w-1] + 1.4f, D[i-w] + 1.0f), min(D[i-1] + 1.0f, D[i-w+1] + 1.4f)),
+ *     backward: r = h-2 .. 0, c = w-2 .. 0:  m = min(min(D[i+w-1] + 1.4f, D[i+1] + 1.0f), min(D[i+w] + 1.0f, D[i+w+1] + 1.4f)),
+ *     each followed by  if (m < D[i]) D[i] = m.  The flat indices are PCL's: the forward pass never writes column 0 and at
+ *     c = w-1 reads D[r][0] as its "up-right"; the backward pass never writes column w-1 or row h-1 and at c = 0 reads
+ *     D[r][w-1] as its "lower-left".
+ * (c) window: for r in [B, h-B), c in [B, w-B) with finite z: sm = min(D[r][c], s); if sm > 2.0f the window size is
+ *     R = (int)sm, else the record has no normal; neither has anything in the B-wide border (w <= 2B or h <= 2B: no record
+ *     has a normal; not an error).
+ * (d) differences: DX[r][c] = P[r][c+1] - P[r][c-1], DY[r][c] = P[r+1][c] - P[r-1][c] per component for 1 <= r < h-1,
+ *     1 <= c < w-1, zero elsewhere; an element is finite when the float sum (x + y) + z is.
+ * (e) normal: over columns [c - R/2, c - R/2 + R) and rows [r - R/2, r - R/2 + R) (integer division: not centred for even R)
+ *     gx = the double sum of the finite DX elements, gy of the finite DY elements; none of either: no normal.
+ *     n = gy x gx in double, every product and difference one IEEE operation; l = (n0^2 + n1^2) + n2^2; l == 0: no normal;
+ *     n_i / sqrt(l), each rounded to float; flipped as rsreg_cloud_normals flips: with v = viewpoint - P in float, when
+ *     (v.x * nx + v.y * ny) + v.z * nz < 0.
+ * out (!= in): w x h records of 32 bytes laid out as pcl::Normal, width and height the input's, is_dense = 0 always.  A record
+ * without a normal: four quiet NaNs (normal and curvature), the other words 0.  A record with one: curvature = quiet NaN
+ * (this method defines none).  rect_out (nullable, host, w * h bytes): R of every record, 0 = no window -- (a) - (c) on
+ * their own; waits for the stream.  The same cloud gives the same bytes whatever the context ran before.
+ * RSREG_ERR_INVALID_ARG, out untouched: an unorganized cloud (height == 1), any method but AVERAGE_3D_GRADIENT,
+ * depth_dependent_smoothing, a border policy other than IGNORE, s outside (0, 64], f negative or not finite, a frame wider
+ * than 8192 pixels.
+ * DEVIATION FROM PCL 1.9.1, stated: PCL takes the window sums from a summed-area table filled by
+ * S[r][c] = S[r-1][c] + S[r][c-1] - S[r-1][c-1] + x in double; here gx, gy are the double sums of the window's elements
+ * themselves, row by row.  Where every coordinate is a multiple of 2^-12 below 16 all such sums are exact and the two
+ * agree in every bit; elsewhere they differ by the rounding of PCL's table, about 1e-11 of a sum. */
+enum rsreg_iin_method {   /* pcl::IntegralImageNormalEstimation::NormalEstimationMethod */
+    RSREG_IIN_COVARIANCE_MATRIX = 0, RSREG_IIN_AVERAGE_3D_GRADIENT = 1, RSREG_IIN_AVERAGE_DEPTH_CHANGE = 2, RSREG_IIN_SIMPLE_3D_GRADIENT = 3
+};
+enum rsreg_iin_border_policy { RSREG_IIN_BORDER_IGNORE = 0, RSREG_IIN_BORDER_MIRROR = 1 };   /* ...::BorderPolicy */
+typedef struct rsreg_iin_params {
+    int method;                       /* rsreg_iin_method */
+    float max_depth_change_factor, normal_smoothing_size;
+    int depth_dependent_smoothing, border_policy;
+    float viewpoint[3];
+} rsreg_iin_params;
+/* PCL's defaults: AVERAGE_3D_GRADIENT, 0.02f, 10.0f, no depth-dependent smoothing, IGNORE, viewpoint (0, 0, 0) */
+void rsreg_iin_params_default(rsreg_iin_params *params);
+int rsreg_cloud_integral_normals(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_iin_params *params /* NULL = defaults */,
+                                 rsreg_cloud *out, uint8_t *rect_out /* may be NULL */);
 /* icp.setInputTarget / setInputSource / align on handles; aligned_out (nullable, may be the source
  * cloud): the source records with xyz <- final * xyz and data[3] = 1 */
 int rsreg_icp_set_target_cloud(rsreg_ctx *ctx, const rsreg_cloud *cloud, double max_correspondence_distance);

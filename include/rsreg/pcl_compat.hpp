@@ -824,6 +824,44 @@ template <typename PointInT, typename PointOutT = Normal> class NormalEstimation
     std::shared_ptr<Context> ctx_;
 };
 
+// ---- pcl::IntegralImageNormalEstimation<PointInT, PointOutT> for organized clouds (csrc/iinormals_kernels.hpp,
+// rsreg_cloud_integral_normals), with the calls of src/edge_extractor.hpp:9-15.  AVERAGE_3D_GRADIENT, the IGNORE border policy
+// and no depth-dependent smoothing are what is implemented: compute() refuses anything else.  The window sums are the double
+// sums of the window's elements, not differences of PCL's table (include/rsreg.h states the deviation).
+template <typename PointInT, typename PointOutT = Normal> class IntegralImageNormalEstimation {
+    static_assert(sizeof(PointOutT) == 32, "the output records are laid out as pcl::Normal");
+  public:
+    enum NormalEstimationMethod { COVARIANCE_MATRIX = 0, AVERAGE_3D_GRADIENT = 1, AVERAGE_DEPTH_CHANGE = 2, SIMPLE_3D_GRADIENT = 3 };
+    enum BorderPolicy { BORDER_POLICY_IGNORE = 0, BORDER_POLICY_MIRROR = 1 };
+    IntegralImageNormalEstimation() { rsreg_iin_params_default(&prm_); }
+    explicit IntegralImageNormalEstimation(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) { rsreg_iin_params_default(&prm_); }
+    void setInputCloud(const typename PointCloud<PointInT>::Ptr &cloud) { input_ = cloud; }
+    void setNormalEstimationMethod(NormalEstimationMethod method) { prm_.method = (int)method; }
+    void setMaxDepthChangeFactor(float factor) { prm_.max_depth_change_factor = factor; }
+    void setNormalSmoothingSize(float size) { prm_.normal_smoothing_size = size; }
+    void setDepthDependentSmoothing(bool on) { prm_.depth_dependent_smoothing = on ? 1 : 0; }
+    void setBorderPolicy(BorderPolicy policy) { prm_.border_policy = (int)policy; }
+    void setViewPoint(float vx, float vy, float vz) { prm_.viewpoint[0] = vx; prm_.viewpoint[1] = vy; prm_.viewpoint[2] = vz; }
+    void getViewPoint(float &vx, float &vy, float &vz) const { vx = prm_.viewpoint[0]; vy = prm_.viewpoint[1]; vz = prm_.viewpoint[2]; }
+    void compute(PointCloud<PointOutT> &output)
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        const std::shared_ptr<Context> ctx = ctx_ ? ctx_ : Context::Default();
+        DeviceCloud<PointInT> tmp(*input_, ctx);
+        DeviceCloud<PointOutT> normals(ctx);
+        compute(tmp, normals);
+        normals.download(output);
+    }
+    void compute(const DeviceCloud<PointInT> &input, DeviceCloud<PointOutT> &output)
+    {
+        check(rsreg_cloud_integral_normals(input.context()->get(), input.handle(), &prm_, output.handle(), nullptr), input.context()->get());
+    }
+  private:
+    rsreg_iin_params prm_;
+    typename PointCloud<PointInT>::Ptr input_;
+    std::shared_ptr<Context> ctx_;
+};
+
 // ---- pcl::transformPointCloud(in, out, Matrix4f); in and out may be the same object
 template <typename PointT>
 void transformPointCloud(const PointCloud<PointT> &in, PointCloud<PointT> &out, const Matrix4f &T,

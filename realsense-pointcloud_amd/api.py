@@ -249,6 +249,29 @@ class DeviceCloud:
         out.close()
         return np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
 
+    def integral_normals_cloud(self, params=None, rect=False):
+        """pcl::IntegralImageNormalEstimation of this organized cloud (rsreg_cloud_integral_normals; params: iin_params(),
+        None = PCL's defaults): a DeviceCloud of 32-byte pcl::Normal records.  rect=True: (cloud, the window size of every
+        record as a uint8 array, 0 = no window)."""
+        out = DeviceCloud(ctx=self.ctx)
+        sizes = np.zeros(self.info()[0], np.uint8) if rect else None
+        rc = _l.lib().rsreg_cloud_integral_normals(self.ctx.h, self.h, None if params is None else C.byref(params), out.h,
+                                                   sizes.ctypes.data if rect else None)
+        if rc:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return (out, sizes) if rect else out
+
+    def integral_normals(self, params=None, rect=False):
+        """(n, 4) float32: normal_x, normal_y, normal_z, curvature (always NaN: the method defines none) of every record, NaN
+        where there is no normal; rect=True: (that, the window sizes)."""
+        res = self.integral_normals_cloud(params, rect)
+        out = res[0] if rect else res
+        rec = out.download_normals().points
+        out.close()
+        four = np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
+        return (four, res[1]) if rect else four
+
     def download_normals(self):
         """download() of a cloud of pcl::Normal records (what NormalEstimation.compute returns): a NormalCloud."""
         n, stride, w, h, dense = self.info()
@@ -292,6 +315,17 @@ def ndt_params(reference=False, **kw):
     p = _l.NdtParams()
     (_l.lib().rsreg_ndt_params_reference if reference else _l.lib().rsreg_ndt_params_default)(C.byref(p))
     for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def iin_params(**kw):
+    """rsreg_iin_params with PCL's defaults: AVERAGE_3D_GRADIENT, 0.02, 10.0, IGNORE, viewpoint (0, 0, 0)."""
+    p = _l.IinParams()
+    _l.lib().rsreg_iin_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k == "viewpoint":
+            v = (C.c_float * 3)(*[float(x) for x in v])
         setattr(p, k, v)
     return p
 
@@ -888,6 +922,59 @@ class NormalEstimation:
         tmp = DeviceCloud(self._in, ctx=self.ctx or default_context())
         try:
             dev = tmp.normals_cloud(self.k, self.viewpoint)
+            out = dev.download_normals()
+            dev.close()
+        finally:
+            tmp.close()
+        return out
+
+
+class IntegralImageNormalEstimation:
+    """pcl::IntegralImageNormalEstimation<PointXYZRGB, Normal> on the GPU for organized clouds (csrc/iinormals_kernels.hpp,
+    rsreg_cloud_integral_normals) as src/edge_extractor.hpp:9-15 sets it up: AVERAGE_3D_GRADIENT, the IGNORE border policy,
+    no depth-dependent smoothing; anything else is refused.  The window sums are the double sums of the window's elements,
+    not differences of PCL's table (include/rsreg.h states the deviation).  compute() of a DeviceCloud gives a DeviceCloud of
+    pcl::Normal records, of a host cloud a NormalCloud."""
+    COVARIANCE_MATRIX, AVERAGE_3D_GRADIENT, AVERAGE_DEPTH_CHANGE, SIMPLE_3D_GRADIENT = 0, 1, 2, 3
+    BORDER_POLICY_IGNORE, BORDER_POLICY_MIRROR = 0, 1
+
+    def __init__(self, ctx=None):
+        self.params = iin_params()
+        self._in = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setNormalEstimationMethod(self, method):
+        self.params.method = int(method)
+
+    def setMaxDepthChangeFactor(self, factor):
+        self.params.max_depth_change_factor = float(factor)
+
+    def setNormalSmoothingSize(self, size):
+        self.params.normal_smoothing_size = float(size)
+
+    def setDepthDependentSmoothing(self, on):
+        self.params.depth_dependent_smoothing = int(bool(on))
+
+    def setBorderPolicy(self, policy):
+        self.params.border_policy = int(policy)
+
+    def setViewPoint(self, vx, vy, vz):
+        self.params.viewpoint = (C.c_float * 3)(float(vx), float(vy), float(vz))
+
+    def getViewPoint(self):
+        return tuple(self.params.viewpoint)
+
+    def compute(self):
+        if self._in is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCloud not called")
+        if isinstance(self._in, DeviceCloud):
+            return self._in.integral_normals_cloud(self.params)
+        tmp = DeviceCloud(self._in, ctx=self.ctx or default_context())
+        try:
+            dev = tmp.integral_normals_cloud(self.params)
             out = dev.download_normals()
             dev.close()
         finally:

@@ -193,6 +193,15 @@ struct FilterScratch {
     PinnedBuf host;
 };
 
+// Scratch of IntegralImageNormalEstimation (iinormals.hip), per pixel of the organized frame it is given
+struct IinScratch {
+    DevBuf d_dist0, d_dist1, d_dist2;   // float: the distance map as set up, after the forward pass, after the backward pass
+    DevBuf d_grad;                      // 2 x float4: the horizontal and the vertical difference, .w = 1 where it is finite
+    DevBuf d_rect;                      // uint8: the window size R, 0 = no window
+    DevBuf d_out;                       // the pcl::Normal records, before the output cloud takes them
+    PinnedBuf host;                     // the window sizes on their way to the caller
+};
+
 struct IcpState {
     rsreg_icp_params prm;
     Mat4f final_t, t_inc;
@@ -431,6 +440,9 @@ struct rsreg_ctx {
     // ---- PassThrough / StatisticalOutlierRemoval (filters.hip): index and scratch of their own
     rsreg::PointGrid knn;            // rebuilt by every k-NN call from the cloud it is given
     rsreg::FilterScratch filt;
+
+    // ---- IntegralImageNormalEstimation (iinormals.hip)
+    rsreg::IinScratch iin;
 };
 
 namespace rsreg {

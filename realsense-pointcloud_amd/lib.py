@@ -16,11 +16,13 @@ ROOT = os.path.dirname(_HERE)
 DIAG = os.environ.get("RSREG_DIAG", "") == "1"
 SO_PATH = (os.environ.get("RSREG_SO") if DIAG else None) or os.path.join(_HERE, "librsreg_diag.so" if DIAG else "librsreg.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip"]
+SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) if os.path.isdir(CSRC) else []
 NUM_SUMS = 17
 NUM_PLANE_SUMS = 32                                      # include/rsreg.h: RSREG_NUM_PLANE_SUMS
 ESTIMATION_SVD, ESTIMATION_POINT_TO_PLANE_LLS = 0, 1     # include/rsreg.h: rsreg_estimation
+IIN_COVARIANCE_MATRIX, IIN_AVERAGE_3D_GRADIENT, IIN_AVERAGE_DEPTH_CHANGE, IIN_SIMPLE_3D_GRADIENT = 0, 1, 2, 3   # rsreg_iin_method
+IIN_BORDER_IGNORE, IIN_BORDER_MIRROR = 0, 1              # rsreg_iin_border_policy
 RSREG_ERR_INVALID_ARG, RSREG_ERR_STATE = -1, -9   # include/rsreg.h: rsreg_status
 UNIQUE_ID_BYTES = 128
 
@@ -45,6 +47,7 @@ EXPORTS = [
     "rsreg_cloud_passthrough", "rsreg_cloud_sor", "rsreg_cloud_knn_mean_distance", "rsreg_cloud_knn", "rsreg_cloud_normals",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
+    "rsreg_iin_params_default", "rsreg_cloud_integral_normals",
 ]
 
 
@@ -83,6 +86,11 @@ class IcpResult(C.Structure):
 
 class SorStats(C.Structure):   # rsreg_sor_stats
     _fields_ = [("n_valid", C.c_uint64), ("n_kept", C.c_uint64), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
+
+
+class IinParams(C.Structure):   # rsreg_iin_params
+    _fields_ = [("method", C.c_int32), ("max_depth_change_factor", C.c_float), ("normal_smoothing_size", C.c_float),
+                ("depth_dependent_smoothing", C.c_int32), ("border_policy", C.c_int32), ("viewpoint", C.c_float * 3)]
 
 
 class NdtResult(C.Structure):
@@ -273,6 +281,9 @@ def lib():
     L.rsreg_cloud_knn_mean_distance.argtypes = [vp, vp, i32, vp]
     L.rsreg_cloud_knn.argtypes = [vp, vp, i32, vp, vp]
     L.rsreg_cloud_normals.argtypes = [vp, vp, i32, vp, vp]
+    L.rsreg_iin_params_default.argtypes = [C.POINTER(IinParams)]
+    L.rsreg_iin_params_default.restype = None
+    L.rsreg_cloud_integral_normals.argtypes = [vp, vp, C.POINTER(IinParams), vp, vp]
     L.rsreg_cloud_concat.argtypes = [vp, vp, vp, vp]
     L.rsreg_icp_set_target_cloud.argtypes = [vp, vp, dbl]
     L.rsreg_icp_target_is_cloud.argtypes = [vp, vp, dbl]
