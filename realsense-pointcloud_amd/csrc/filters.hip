@@ -47,41 +47,32 @@ int view_of(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *out, Cloud
     return RSREG_OK;
 }
 
-// d_dist[i] = record i's mean distance to its mean_k nearest neighbours (0 for a non-finite record), *nfin_out = finite records.
-// The index of the cloud (pointgrid.hpp: one round trip to the host for the box) and the search: on ctx->stream, not waited for.
-int knn_mean_distance_device(rsreg_ctx *ctx, const CloudView &v, int mean_k, uint32_t *nfin_out)
-{
-    PointGrid &kx = ctx->knn;
-    FilterScratch &fs = ctx->filt;
-    hipStream_t st = ctx->stream;
-    if (mean_k < 1 || mean_k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "mean_k must be between 1 and 64");
-    RSREG_HIP(ctx, fs.host.reserve(256));
-    RSREG_HIP(ctx, fs.d_dist.reserve(v.n * 4 + 16));
-    int rc = grid_build<KnnGridPolicy>(ctx, kx, StridedRecords{v.rec, v.stride, fs.d_dist.as<float>()}, (uint32_t)v.n, (uint32_t)mean_k + 1u,
-                                       fs.host.as<uint32_t>());
-    if (rc) return rc;
-    const uint32_t nfin = kx.n_points;
-    *nfin_out = nfin;
-    // PCL reads past nn_dists when the tree holds fewer than mean_k + 1 points
-    if ((unsigned long long)nfin < (unsigned long long)mean_k + 1ull)
-        return fail(ctx, RSREG_ERR_INVALID_ARG, "the cloud has fewer than mean_k + 1 finite records");
-    k_knn_mean_distance<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, st>>>(grid_dev(kx), mean_k, fs.d_dist.as<float>());
-    RSREG_HIP(ctx, hipGetLastError());
-    return RSREG_OK;
-}
-
-// The index of the cloud for a search that keeps k neighbours (the record itself among them), on ctx->stream; refused when fewer
-// than k records are finite (PCL's nearestKSearch would return fewer than k: every caller here needs k).
-int knn_index_device(rsreg_ctx *ctx, const CloudView &v, int k, uint32_t *nfin_out)
+// The index of the cloud for a search that keeps `kept` neighbours (the record itself among them), on ctx->stream (pointgrid.hpp:
+// one round trip to the host for the box); *nfin_out = finite records.  Refused with `too_few` when fewer than `kept` records are
+// finite (PCL's nearestKSearch would return fewer: every caller here needs them all).
+int knn_index_device(rsreg_ctx *ctx, const CloudView &v, int kept, const char *too_few, uint32_t *nfin_out)
 {
     FilterScratch &fs = ctx->filt;
     RSREG_HIP(ctx, fs.host.reserve(256));
     RSREG_HIP(ctx, fs.d_dist.reserve(v.n * 4 + 16));   // (the count pass leaves a non-finite record's 0 there)
-    int rc = grid_build<KnnGridPolicy>(ctx, ctx->knn, StridedRecords{v.rec, v.stride, fs.d_dist.as<float>()}, (uint32_t)v.n, (uint32_t)k,
+    int rc = grid_build<KnnGridPolicy>(ctx, ctx->knn, StridedRecords{v.rec, v.stride, fs.d_dist.as<float>()}, (uint32_t)v.n, (uint32_t)kept,
                                        fs.host.as<uint32_t>());
     if (rc) return rc;
     *nfin_out = ctx->knn.n_points;
-    if (ctx->knn.n_points < (uint32_t)k) return fail(ctx, RSREG_ERR_INVALID_ARG, "the cloud has fewer than k finite records");
+    if (ctx->knn.n_points < (uint32_t)kept) return fail(ctx, RSREG_ERR_INVALID_ARG, too_few);
+    return RSREG_OK;
+}
+
+// d_dist[i] = record i's mean distance to its mean_k nearest neighbours (0 for a non-finite record): the index and the search,
+// not waited for.
+int knn_mean_distance_device(rsreg_ctx *ctx, const CloudView &v, int mean_k, uint32_t *nfin_out)
+{
+    if (mean_k < 1 || mean_k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "mean_k must be between 1 and 64");
+    // PCL reads past nn_dists when the tree holds fewer than mean_k + 1 points
+    int rc = knn_index_device(ctx, v, mean_k + 1, "the cloud has fewer than mean_k + 1 finite records", nfin_out);
+    if (rc) return rc;
+    k_knn_mean_distance<<<std::min<uint32_t>(*nfin_out, 1u << 16), kKnnWave, 0, ctx->stream>>>(grid_dev(ctx->knn), mean_k, ctx->filt.d_dist.as<float>());
+    RSREG_HIP(ctx, hipGetLastError());
     return RSREG_OK;
 }
 
@@ -217,7 +208,7 @@ int rsreg_cloud_knn(rsreg_ctx *ctx, const rsreg_cloud *in, int k, int32_t *index
     if (rc) return rc;
     if (k < 1 || k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must be between 1 and 64");
     uint32_t nfin = 0;
-    rc = knn_index_device(ctx, v, k, &nfin);
+    rc = knn_index_device(ctx, v, k, "the cloud has fewer than k finite records", &nfin);
     if (rc) return rc;
     FilterScratch &fs = ctx->filt;
     hipStream_t st = ctx->stream;
@@ -251,7 +242,7 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
     if (rc) return rc;
     if (k < 3 || k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must be between 3 and 64");
     uint32_t nfin = 0;
-    rc = knn_index_device(ctx, v, k, &nfin);
+    rc = knn_index_device(ctx, v, k, "the cloud has fewer than k finite records", &nfin);
     if (rc) return rc;
     FilterScratch &fs = ctx->filt;
     hipStream_t st = ctx->stream;

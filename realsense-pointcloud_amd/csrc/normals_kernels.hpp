@@ -1,19 +1,11 @@
-// normals_kernels.hpp — the exact k-nearest-neighbour search of knn_kernels.hpp in its identity-carrying form, and
-// pcl::NormalEstimation (setKSearch) on top of it: device code of rsreg_cloud_knn and rsreg_cloud_normals (include/rsreg.h).
-// Included by filters.hip only.  k_knn_mean_distance is not touched: what StatisticalOutlierRemoval returns stays what it is.
+// normals_kernels.hpp — the identity-carrying output of the exact k-nearest-neighbour search (knn_kernels.hpp: knn_walk<KnnKeys>)
+// and pcl::NormalEstimation (setKSearch) on top of it: device code of rsreg_cloud_knn and rsreg_cloud_normals (include/rsreg.h).
+// Included by filters.hip only.
 //
-// The search.  The same index (pointgrid.hpp, KnnGridPolicy), the same walk of shells of cells, the same float32 l2_simple,
-// one wave per query.  What the LDS selection carries is a 64-bit key, float bits of d2 << 32 | original record index:
-// d2 >= 0, so its bit pattern orders like its value, and no two records share a key.  The result of a query is the k
-// smallest keys, ascending: ascending by (d2, record index), and among records whose d2 equals the k-th smallest value the
-// lowest indices -- the project's tie rule ("ties: lowest index").  The record itself and exact copies are neighbours like any
-// other (PCL's nearestKSearch).  Two things differ from the value-only walk:
-//   * a candidate is taken when its KEY is below the k-th smallest key so far (not: its value not above the k-th value);
-//   * nothing ends at a bound of 0: every record at distance 0 has to be seen before the lowest indices among them are known.
-//     A cell is skipped only when its lower bound is ABOVE the k-th distance, so every record that ties with it is seen.
-//     (A pile of m exact copies therefore costs m / 64 loads per query of the pile: the missing-depth records of a raw frame.)
-// A neighbour's coordinates are read from the cloud's own records through the original index in the key: no position in
-// the cell-sorted array is kept and nothing is searched twice.
+// The search leaves a query's k smallest keys (float bits of d2 << 32 | original record index), ascending, in LDS.  The record
+// itself and exact copies are neighbours like any other (PCL's nearestKSearch).  A neighbour's coordinates are read from the
+// cloud's own records through the original index in the key: no position in the cell-sorted array is kept and nothing is
+// searched twice.
 //
 // The normal (PCL 1.9.1 features/normal_3d.h, recalled: computePointNormal, solvePlaneParameters, flipNormalTowardsViewpoint),
 // by the wave that searched, while the k keys are in LDS -- no n x k index array goes through HBM:
@@ -38,122 +30,7 @@
 
 namespace rsreg {
 
-constexpr unsigned long long kKnnNoKey = ~0ull;   // above every key: the padding of the selection, the bound while fewer than k are kept
-
 // ------------------------------------------------------------------------------ search
-// Ascending bitonic sort of the keys buf[0 .. n) (n = 64, 128 or 256 >= count, padded), by the one wave of the workgroup; the k
-// smallest stay: count = min(count, k), bound = the k-th smallest key (kKnnNoKey while there are fewer), bound_d2 its distance.
-__device__ __forceinline__ void knn_select_keys(unsigned long long *buf, int lane, int k, int &count, unsigned long long &bound, float &bound_d2)
-{
-    const int n = count <= 64 ? 64 : (count <= 128 ? 128 : kKnnBuf);
-    for (int i = count + lane; i < n; i += kKnnWave) buf[i] = kKnnNoKey;
-    __syncthreads();
-    for (int s = 2; s <= n; s <<= 1) {
-        for (int j = s >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < (n >> 1); t += kKnnWave) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const unsigned long long a = buf[i], b = buf[l];
-                const bool up = (i & s) == 0;
-                if ((a > b) == up) {
-                    buf[i] = b;
-                    buf[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    count = min(count, k);
-    bound = count >= k ? buf[k - 1] : kKnnNoKey;
-    bound_d2 = count >= k ? __uint_as_float((uint32_t)(bound >> 32)) : __int_as_float(0x7f800000);
-}
-
-// The k smallest keys of the query q (a point of the index: at least k points are indexed) in buf[0 .. k), ascending.  Called by
-// every lane of the one wave of the workgroup; buf: kKnnBuf keys of LDS.  Returns behind a barrier.
-__device__ __forceinline__ void knn_walk_keys(const PointGridDev &g, const float4 q, int k, unsigned long long *buf, int lane)
-{
-    const float inf = __int_as_float(0x7f800000), cell2 = g.cell * g.cell;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const float ux = cell_pos(q.x, g.ox, g.inv_cell), uy = cell_pos(q.y, g.oy, g.inv_cell), uz = cell_pos(q.z, g.oz, g.inv_cell);
-    const int cx = axis_cell(q.x, g.ox, g.inv_cell, g.dx), cy = axis_cell(q.y, g.oy, g.inv_cell, g.dy), cz = axis_cell(q.z, g.oz, g.inv_cell, g.dz);
-    const int rmax = max(max(max(cx, g.dx - 1 - cx), max(cy, g.dy - 1 - cy)), max(cz, g.dz - 1 - cz));
-    int count = 0;
-    unsigned long long bound = kKnnNoKey;
-    float bound_d2 = inf;
-    bool dirty = false;
-    for (int r = 0; r <= rmax; ++r) {
-        const int side = 2 * r + 1, rows = side * side;
-        for (int base = 0; base < rows; base += kKnnWave) {
-            const int row = base + lane;
-            const int oy = row % side - r, oz = row / side - r, y = cy + oy, z = cz + oz;
-            const bool in = row < rows && y >= 0 && y < g.dy && z >= 0 && z < g.dz;
-            const bool face = abs(oy) == r || abs(oz) == r;   // a face row: every cell of it; else its two ends
-            const float gy = axis_gap(uy, y, y), gz = axis_gap(uz, z, z);
-            for (int pass = 0; pass < 2; ++pass) {
-                int x0, x1;
-                bool has = in;
-                if (face) {
-                    x0 = max(cx - r, 0);
-                    x1 = min(cx + r, g.dx - 1);
-                    has = has && pass == 0;
-                } else {
-                    x0 = x1 = pass == 0 ? cx - r : cx + r;
-                    has = has && x0 >= 0 && x0 < g.dx;
-                }
-                const float lb = has ? grid_lb2(axis_gap(ux, x0, x1), gy, gz, cell2) : inf;
-                uint32_t s = 0, e = 0;
-                if (has && !(lb > bound_d2)) {
-                    const size_t c0 = ((size_t)z * (size_t)g.dy + (size_t)y) * (size_t)g.dx;
-                    s = g.start[c0 + (size_t)x0];
-                    e = g.start[c0 + (size_t)x1 + 1];
-                }
-                unsigned long long todo = __ballot(e > s);
-                while (todo) {
-                    const int l = __ffsll((long long)todo) - 1;
-                    todo &= todo - 1;
-                    const uint32_t ss = __shfl(s, l), ee = __shfl(e, l);
-                    if (__shfl(lb, l) > bound_d2) continue;   // (the bound has come down since the row was fetched)
-                    for (uint32_t p = ss; p < ee; p += kKnnWave) {
-                        if (count > kKnnBuf - kKnnWave) {
-                            knn_select_keys(buf, lane, k, count, bound, bound_d2);
-                            dirty = false;
-                        }
-                        const uint32_t i = p + (uint32_t)lane;
-                        bool ok = i < ee;
-                        unsigned long long key = kKnnNoKey;
-                        if (ok) {
-                            const float4 t = g.pts[i];
-                            const float d = l2_simple(q.x, q.y, q.z, t.x, t.y, t.z);
-                            key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)__float_as_uint(t.w);
-                            ok = key < bound;
-                        }
-                        const unsigned long long m = __ballot(ok);
-                        if (ok) buf[count + __popcll(m & lt)] = key;
-                        count += __popcll(m);
-                        dirty = dirty || m != 0ull;
-                    }
-                }
-            }
-        }
-        if (count >= k) {
-            if (dirty) {
-                knn_select_keys(buf, lane, k, count, bound, bound_d2);
-                dirty = false;
-            }
-            // every cell not visited yet lies beyond one of the six faces of the cube of shell r
-            float out = inf;
-            if (cx + r + 1 < g.dx) out = fminf(out, grid_lb2(axis_gap(ux, cx + r + 1, g.dx - 1), 0.0f, 0.0f, cell2));
-            if (cx - r - 1 >= 0) out = fminf(out, grid_lb2(axis_gap(ux, 0, cx - r - 1), 0.0f, 0.0f, cell2));
-            if (cy + r + 1 < g.dy) out = fminf(out, grid_lb2(0.0f, axis_gap(uy, cy + r + 1, g.dy - 1), 0.0f, cell2));
-            if (cy - r - 1 >= 0) out = fminf(out, grid_lb2(0.0f, axis_gap(uy, 0, cy - r - 1), 0.0f, cell2));
-            if (cz + r + 1 < g.dz) out = fminf(out, grid_lb2(0.0f, 0.0f, axis_gap(uz, cz + r + 1, g.dz - 1), cell2));
-            if (cz - r - 1 >= 0) out = fminf(out, grid_lb2(0.0f, 0.0f, axis_gap(uz, 0, cz - r - 1), cell2));
-            if (out > bound_d2) break;   // (strictly: a record AT the k-th distance may still carry a lower index)
-        }
-    }
-    if (dirty) knn_select_keys(buf, lane, k, count, bound, bound_d2);
-    __syncthreads();
-}
-
 // rsreg_cloud_knn: row `record` of index_out (k int32, nullable) and of d2_out (k floats, nullable), queries in cell order.  The
 // rows of non-finite records have been filled before the launch.
 __global__ __launch_bounds__(kKnnWave) void k_knn_indices(PointGridDev g, int k, int32_t *index_out, float *d2_out)
@@ -162,7 +39,7 @@ __global__ __launch_bounds__(kKnnWave) void k_knn_indices(PointGridDev g, int k,
     const int lane = (int)threadIdx.x;
     for (uint32_t j = blockIdx.x; j < g.n; j += gridDim.x) {
         const float4 q = g.pts[j];
-        knn_walk_keys(g, q, k, buf, lane);
+        knn_walk<KnnKeys>(g, q, k, buf, lane);
         if (lane < k) {
             const unsigned long long key = buf[lane];
             const size_t at = (size_t)__float_as_uint(q.w) * (size_t)k + (size_t)lane;
@@ -259,7 +136,7 @@ __global__ __launch_bounds__(kKnnWave) void k_normals(PointGridDev g, int k, con
     const int lane = (int)threadIdx.x;
     for (uint32_t j = blockIdx.x; j < g.n; j += gridDim.x) {
         const float4 q = g.pts[j];
-        knn_walk_keys(g, q, k, buf, lane);
+        knn_walk<KnnKeys>(g, q, k, buf, lane);
         double dx = 0.0, dy = 0.0, dz = 0.0;
         if (lane < k) {
             const float *t = rec_xyz(rec, stride, (size_t)(uint32_t)buf[lane]);

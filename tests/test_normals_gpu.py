@@ -88,6 +88,9 @@ def _input(name):
     if name == "lattice_copies":                            # 70 copies of one point behind the lattice: more zero distances than k
         xyz = lattice(12)
         return _cloud(np.concatenate([xyz, np.repeat(xyz[777][None], 70, axis=0)])), False
+    if name == "lattice_pile":                              # 300 copies: the pile alone overfills the 256-element buffer, so the
+        xyz = lattice(12)                                   # selection refills in the middle of a cell's run (and the value
+        return _cloud(np.concatenate([xyz, np.repeat(xyz[777][None], 300, axis=0)])), False   # search ends right after it)
     if name == "uniform1000":
         return _cloud(_uniform(1000, 1)), True
     if name == "uniform5000":
@@ -118,7 +121,7 @@ def _ref_normals(name, k, viewpoint=(0.0, 0.0, 0.0)):
     return N.normals(_input(name)[0].xyz, k, viewpoint, knn_result=_ref_knn(name, k))
 
 
-SEARCH = ([("lattice", 7), ("lattice", 27), ("lattice_copies", 64)] +
+SEARCH = ([("lattice", 7), ("lattice", 27), ("lattice_copies", 64), ("lattice_pile", 1), ("lattice_pile", 50), ("lattice_pile", 64)] +
           [(n, k) for n in ("uniform1000", "uniform5000", "sphere5000") for k in (1, 3, 10, 50, 64)] +
           [("non_finite", 20), ("frame_raw", 10), ("frame_raw", 50), ("frame_pass", 10), ("frame_pass", 50)])
 NORMALS = [(n, k) for n, k in SEARCH if k >= 3]
@@ -154,7 +157,8 @@ def test_knn_lattice_ties_by_hand(api, ctx):
     assert (only_idx == idx).all()
 
 
-@pytest.mark.parametrize("name,k", [("uniform5000", 50), ("non_finite", 20), ("frame_raw", 50), ("lattice_copies", 64)])
+@pytest.mark.parametrize("name,k", [("uniform5000", 50), ("non_finite", 20), ("frame_raw", 50), ("lattice_copies", 64),
+                                     ("lattice_pile", 64), ("lattice_pile", 2)])
 def test_search_within_sor(api, ctx, name, k):
     """sqrt and mean of d2[:, 1:] are knn_mean_distance(k - 1), bit for bit: the new search and the old one see the same values."""
     dc = api.DeviceCloud(_input(name)[0], ctx=ctx)
