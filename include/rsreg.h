@@ -354,6 +354,57 @@ int rsreg_approx_voxel_grid(const void *in, size_t n, size_t stride, const float
 int rsreg_approx_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_t n, size_t stride,
                                 const float leaf[3], void *out, size_t *n_out);
 
+/* ---- pcl::VoxelGrid<PointXYZRGB>::filter: one centroid per occupied leaf, in leaf order ---------------------------------
+ * The downsampler in front of NormalEstimation and IterativeClosestPointWithNormals; the reference's pre-filter declares a
+ * cloud_voxel_grid it never fills (src/capture.hpp:112-132).  PCL is not available to check against: what follows is
+ * recalled from PCL 1.9.1, filters/impl/voxel_grid.hpp and common/impl/centroid.hpp, and IS the contract.  All arithmetic is
+ * float32, one IEEE operation at a time (no contracted multiply-add); float -> int32 conversions saturate (a leaf coordinate
+ * past int32 is outside what PCL defines).
+ * (1) A record with a non-finite x, y or z takes no part: not in the box, not in a leaf, not in a count -- whatever is_dense
+ *     says (PCL's behaviour on a cloud flagged dense that holds NaNs is undefined).
+ * (2) Box: min_p, max_p = the componentwise minimum and maximum over the finite records; inv[a] = 1.0f / leaf[a];
+ *     d[a] = (int64)((max_p[a] - min_p[a]) * inv[a]) + 1.  If d[0] * d[1] * d[2] > INT32_MAX (PCL: "leaf size is too small",
+ *     output = input) the output is a copy of the input: all records, the input's width, height and is_dense, and
+ *     info->overflowed = 1 with every box field of info zero.
+ * (3) Leaf of a point p: min_b[a] = (int)floorf(min_p[a] * inv[a]), max_b likewise from max_p; div_b = max_b - min_b + 1;
+ *     divb_mul = (1, div_b[0], div_b[0] * div_b[1]); ijk[a] = (int)(floorf(p[a] * inv[a]) - (float)min_b[a]);
+ *     idx = ijk . divb_mul as an unsigned 32-bit value (products and sums modulo 2^32, as div_b and divb_mul are).
+ * (4) The output's leaves are in ascending idx.
+ * (5) A leaf's points are added in ascending input index.  STATED CHOICE: PCL's std::sort leaves the order inside a leaf
+ *     unspecified; this is the only point on which the result can differ from a PCL build.
+ * (6) A leaf with fewer than min_points_per_voxel points gives no output (default 0).
+ * (7) downsample_all_data = 1 (PCL's default, its CentroidPoint): float sums of x, y, z and of the r, g, b, a bytes (each
+ *     converted to float before it is added); xyz = sum / (float)n; each colour byte = (uint32_t)(sum / (float)n), packed
+ *     a << 24 | r << 16 | g << 8 | b.  (ApproximateVoxelGrid leaves alpha 0; here it is averaged.)
+ * (8) downsample_all_data = 0: xyz from the same sums, the colour PCL's default (r = g = b = 0, a = 255).
+ * (9) An output record is a zeroed record of the input's stride (>= 20, a multiple of 4, rgb at byte 16) with xyz, 1.0f in
+ *     the fourth float (both modes: a default-constructed point) and the colour set.  width = leaves kept, height = 1,
+ *     is_dense = 1.  An empty or all-non-finite input gives an empty output.
+ * A leaf that is not positive, not finite, or whose reciprocal is not finite: RSREG_ERR_INVALID_ARG.
+ * NOT BUILT: the filter-field limits (setFilterFieldName / setFilterLimits: run rsreg_cloud_passthrough first) and the saved
+ * leaf layout (setSaveLeafLayout, getCentroidIndex). */
+typedef struct rsreg_voxel_grid_params {
+    float leaf[3];
+    int downsample_all_data;
+    uint32_t min_points_per_voxel;
+} rsreg_voxel_grid_params;
+/* getMinBoxCoordinates, getMaxBoxCoordinates, getNrDivisions, getDivisionMultiplier of the last filter() and its counts */
+typedef struct rsreg_voxel_grid_info {
+    int32_t min_b[3], max_b[3], div_b[3], divb_mul[3];
+    uint64_t n_finite, n_leaves, n_out;   /* finite records; occupied leaves; records in the output */
+    int overflowed;
+} rsreg_voxel_grid_info;
+/* PCL's defaults: downsample_all_data = 1, min_points_per_voxel = 0; the leaf is unset (0: refused until it is set) */
+void rsreg_voxel_grid_params_default(rsreg_voxel_grid_params *params);
+/* The contract restated sequentially on the host (no context needed).  out must hold n records; in == out allowed. */
+int rsreg_voxel_grid(const void *in, size_t n, size_t stride, const float leaf[3], int downsample_all_data,
+                     uint32_t min_points, void *out, size_t *n_out, rsreg_voxel_grid_info *info /* may be NULL */);
+/* The same on the GPU, the same bytes (csrc/voxel.hip): the box, a stable radix sort of the records by leaf index over
+ * exactly the key bits the box needs, and per leaf the float sums in input order by the run kernels of the approximate
+ * filter.  No float atomics; the same bytes from any context. */
+int rsreg_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_t n, size_t stride, const rsreg_voxel_grid_params *params,
+                         void *out, size_t *n_out, rsreg_voxel_grid_info *info /* may be NULL */);
+
 /* ---- NDT: pcl::NormalDistributionsTransform<PointXYZRGB,PointXYZRGB> ---------------- */
 /* ndt.setInputTarget (ndt_edge...hpp:72): voxel binning + per-voxel mean / covariance /
  * regularised inverse covariance (VoxelGridCovariance). */
@@ -445,6 +496,11 @@ int rsreg_cloud_filter(rsreg_ctx *ctx, const rsreg_cloud *in, const float leaf[3
  * independently of the registration).  `in` must stay alive and unchanged until `out` has been used; in != out.  `in`
  * may be the output of rsreg_cloud_edge_features_async that has not run yet: the jobs run in the order of the calls. */
 int rsreg_cloud_filter_async(rsreg_ctx *ctx, const rsreg_cloud *in, const float leaf[3], rsreg_cloud *out);
+/* pcl::VoxelGrid::filter on a device cloud ("pcl::VoxelGrid" above is the contract); in == out allowed; `out` follows the
+ * versioning rules (its version changes, except that an overflowed filter of a cloud into itself leaves it as it is).
+ * Waits for the stream: once for the box, once for the number of leaves, once more when min_points_per_voxel > 1. */
+int rsreg_cloud_voxel_grid(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_voxel_grid_params *params, rsreg_cloud *out,
+                           rsreg_voxel_grid_info *info /* may be NULL */);
 /* pcl::transformPointCloud; in == out allowed */
 int rsreg_cloud_transform(rsreg_ctx *ctx, const rsreg_cloud *in, const float transform[16], rsreg_cloud *out);
 /* PointCloud::operator+ : out = a followed by b (width = size, height = 1, is_dense = both); out may be a or b */

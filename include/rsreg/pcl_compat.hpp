@@ -19,6 +19,7 @@
 
 #include <sys/mman.h>
 
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstddef>
@@ -719,6 +720,58 @@ template <typename PointT> class ApproximateVoxelGrid {
     }
   private:
     float leaf_[3] = {1.f, 1.f, 1.f};  // PCL default: IncrementalICP never sets it (incremental_icp.hpp:36)
+    typename PointCloud<PointT>::Ptr input_;
+    std::shared_ptr<Context> ctx_;
+};
+
+// ---- pcl::VoxelGrid<PointT>: one centroid per occupied leaf, in ascending leaf index; a leaf's points are added in ascending
+// input index (include/rsreg.h, "pcl::VoxelGrid", is the contract and states that one choice).  Default-constructed: the
+// sequential host restatement.  With a Context: the GPU filter (csrc/voxel.hip), the same bytes.  Not built: the filter-field
+// limits (run PassThrough first) and the saved leaf layout.
+template <typename PointT> class VoxelGrid {
+  public:
+    VoxelGrid() { rsreg_voxel_grid_params_default(&prm_); }
+    explicit VoxelGrid(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) { rsreg_voxel_grid_params_default(&prm_); }
+    void setLeafSize(float lx, float ly, float lz) { prm_.leaf[0] = lx; prm_.leaf[1] = ly; prm_.leaf[2] = lz; }
+    void setLeafSize(float l) { setLeafSize(l, l, l); }
+    void setDownsampleAllData(bool on) { prm_.downsample_all_data = on ? 1 : 0; }
+    bool getDownsampleAllData() const { return prm_.downsample_all_data != 0; }
+    void setMinimumPointsNumberPerVoxel(unsigned int n) { prm_.min_points_per_voxel = n; }
+    unsigned int getMinimumPointsNumberPerVoxel() const { return prm_.min_points_per_voxel; }
+    void setInputCloud(const typename PointCloud<PointT>::Ptr &cloud) { input_ = cloud; }
+    // of the last filter(): three ints each, as PCL's Eigen::Vector3i
+    std::array<int, 3> getMinBoxCoordinates() const { return {info_.min_b[0], info_.min_b[1], info_.min_b[2]}; }
+    std::array<int, 3> getMaxBoxCoordinates() const { return {info_.max_b[0], info_.max_b[1], info_.max_b[2]}; }
+    std::array<int, 3> getNrDivisions() const { return {info_.div_b[0], info_.div_b[1], info_.div_b[2]}; }
+    std::array<int, 3> getDivisionMultiplier() const { return {info_.divb_mul[0], info_.divb_mul[1], info_.divb_mul[2]}; }
+    const rsreg_voxel_grid_info &info() const { return info_; }   // engine extra: the counts, and whether the leaf was too small
+    void filter(PointCloud<PointT> &output)  // output may be *input
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        PointVector<PointT> out = uninitialized_points<PointT>(input_->size());
+        size_t n_out = 0;
+        if (ctx_)
+            check(rsreg_voxel_grid_gpu(ctx_->get(), input_->points.data(), input_->size(), sizeof(PointT), &prm_, out.data(), &n_out, &info_),
+                  ctx_->get());
+        else
+            check(rsreg_voxel_grid(input_->points.data(), input_->size(), sizeof(PointT), prm_.leaf, prm_.downsample_all_data,
+                                   prm_.min_points_per_voxel, out.data(), &n_out, &info_));
+        out.resize(n_out);
+        const uint32_t w = input_->width, h = input_->height;
+        const bool dense = input_->is_dense;
+        output.points = std::move(out);
+        // (PCL: a leaf too small for the box leaves the output a copy of the input)
+        output.width = info_.overflowed ? w : (uint32_t)n_out;
+        output.height = info_.overflowed ? h : 1;
+        output.is_dense = info_.overflowed ? dense : true;
+    }
+    void filter(const DeviceCloud<PointT> &input, DeviceCloud<PointT> &output)  // output may be the input
+    {
+        check(rsreg_cloud_voxel_grid(input.context()->get(), input.handle(), &prm_, output.handle(), &info_), input.context()->get());
+    }
+  private:
+    rsreg_voxel_grid_params prm_;
+    rsreg_voxel_grid_info info_{};
     typename PointCloud<PointT>::Ptr input_;
     std::shared_ptr<Context> ctx_;
 };

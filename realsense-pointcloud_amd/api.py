@@ -272,6 +272,16 @@ class DeviceCloud:
         four = np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
         return (four, res[1]) if rect else four
 
+    def voxel_grid(self, leaf, downsample_all_data=True, min_points=0):
+        """pcl::VoxelGrid::filter of this cloud (rsreg_cloud_voxel_grid): a new DeviceCloud with one centroid per occupied
+        leaf, in leaf order.  leaf: one float or three."""
+        f = VoxelGrid()
+        f.setLeafSize(*np.broadcast_to(np.asarray(leaf, np.float32), (3,)))
+        f.setDownsampleAllData(downsample_all_data)
+        f.setMinimumPointsNumberPerVoxel(min_points)
+        f.setInputCloud(self)
+        return f.filter()
+
     def download_normals(self):
         """download() of a cloud of pcl::Normal records (what NormalEstimation.compute returns): a NormalCloud."""
         n, stride, w, h, dense = self.info()
@@ -795,6 +805,83 @@ class ApproximateVoxelGrid:
                                                       self.leaf.ctypes.data, out.ctypes.data, C.byref(n_out)))
         out = out[: n_out.value].copy()
         return PointCloud(out, width=len(out), height=1, is_dense=False)
+
+
+class VoxelGrid:
+    """pcl::VoxelGrid<PointXYZRGB>: one centroid per occupied leaf, in ascending leaf index, a leaf's points added in ascending
+    input index (include/rsreg.h states the contract).  A DeviceCloud is filtered in HBM (rsreg_cloud_voxel_grid); a host cloud
+    on the GPU when a context was given (rsreg_voxel_grid_gpu), else by the sequential host restatement (rsreg_voxel_grid):
+    the same bytes from all three.  `info` holds the last filter()'s rsreg_voxel_grid_info.  Not built: the filter-field
+    limits (run PassThrough first) and the saved leaf layout."""
+
+    def __init__(self, ctx=None):
+        self.params = _l.VoxelGridParams()
+        _l.lib().rsreg_voxel_grid_params_default(C.byref(self.params))
+        self.info = None
+        self._in = None
+        self.ctx = ctx
+
+    def setLeafSize(self, lx, ly=None, lz=None):
+        """setLeafSize(lx, ly, lz), or setLeafSize(l) for a cubic leaf"""
+        ly, lz = (lx, lx) if ly is None else (ly, lz)
+        self.params.leaf[0], self.params.leaf[1], self.params.leaf[2] = float(lx), float(ly), float(lz)
+
+    def getLeafSize(self):
+        return np.array(self.params.leaf[:], np.float32)
+
+    def setDownsampleAllData(self, on):
+        self.params.downsample_all_data = int(bool(on))
+
+    def getDownsampleAllData(self):
+        return bool(self.params.downsample_all_data)
+
+    def setMinimumPointsNumberPerVoxel(self, n):
+        self.params.min_points_per_voxel = int(n)
+
+    def getMinimumPointsNumberPerVoxel(self):
+        return int(self.params.min_points_per_voxel)
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def getMinBoxCoordinates(self):
+        return np.array(self.info.min_b[:], np.int32)
+
+    def getMaxBoxCoordinates(self):
+        return np.array(self.info.max_b[:], np.int32)
+
+    def getNrDivisions(self):
+        return np.array(self.info.div_b[:], np.int32)
+
+    def getDivisionMultiplier(self):
+        return np.array(self.info.divb_mul[:], np.int32)
+
+    def filter(self):
+        if self._in is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCloud not called")
+        info = _l.VoxelGridInfo()
+        if isinstance(self._in, DeviceCloud):
+            out = DeviceCloud(ctx=self._in.ctx)
+            rc = _l.lib().rsreg_cloud_voxel_grid(self._in.ctx.h, self._in.h, C.byref(self.params), out.h, C.byref(info))
+            if rc:
+                out.close()
+            _l.check(rc, self._in.ctx.h)
+            self.info = info
+            return out
+        pts = np.ascontiguousarray(self._in.points)
+        out = np.zeros_like(pts)
+        n_out = C.c_size_t(0)
+        if self.ctx is not None:
+            _l.check(_l.lib().rsreg_voxel_grid_gpu(self.ctx.h, pts.ctypes.data, len(pts), pts.dtype.itemsize, C.byref(self.params),
+                                                   out.ctypes.data, C.byref(n_out), C.byref(info)), self.ctx.h)
+        else:
+            _l.check(_l.lib().rsreg_voxel_grid(pts.ctypes.data, len(pts), pts.dtype.itemsize, self.params.leaf, self.params.downsample_all_data,
+                                               self.params.min_points_per_voxel, out.ctypes.data, C.byref(n_out), C.byref(info)))
+        self.info = info
+        out = out[: n_out.value].view(np.uint8).copy().view(out.dtype)   # (byte for byte: .copy() of padded records drops the padding)
+        if info.overflowed:   # PCL: "leaf size is too small", the output is the input
+            return PointCloud(out, width=self._in.width, height=self._in.height, is_dense=self._in.is_dense)
+        return PointCloud(out, width=len(out), height=1, is_dense=True)
 
 
 def _filter_io(cloud, ctx, run):

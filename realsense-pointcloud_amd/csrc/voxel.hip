@@ -17,6 +17,11 @@
 // additions as PCL: a thread per short run, a wave per run of 48 points and more, and for the runs
 // of 1 024 points and more -- PCL's default 1 m leaf -- a workgroup that gets the same bits from a
 // scan of rounding steps, k_vox_huge_runs below), and sort the runs by their emission position.
+//
+// pcl::VoxelGrid (the second half of this file; contract: include/rsreg.h) is the same machinery under another key: the leaf
+// index inside the cloud's bounding box instead of a hash slot.  A run is then a whole leaf and the runs come out in key
+// order: no second sort.  The run kernels are shared (kLeaf: the fourth sum is the alpha byte's, not the rgb word's read as
+// a float, and a run leaves its count instead of an emission key).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -28,6 +33,7 @@
 #include "rsreg_ctx.hpp"
 #include "osort.hpp"
 #include "oscan.hpp"
+#include "pointgrid.hpp"
 
 namespace rsreg {
 namespace {
@@ -104,30 +110,39 @@ __global__ __launch_bounds__(kVBlock) void k_vox_starts(const uint32_t *skeys, c
 constexpr uint32_t kLongRun = 48;   // runs from this length on are summed by a whole wave (k_vox_long_runs)
 constexpr uint32_t kHugeRun = 1024; // and from this length on by a workgroup that scans instead of adding (k_vox_huge_runs)
 
+// (kLeaf, pcl::VoxelGrid: the runs are emitted in the order they have; the eighth word is the run's number of points)
+template <bool kLeaf>
 __device__ __forceinline__ void vox_store_run(const float acc[7], uint32_t a, uint32_t b, uint32_t n, uint32_t nfin, uint32_t r,
                                               const uint32_t *skeys, const uint32_t *svals, float *cent, uint32_t *ekey, uint32_t *erun)
 {
     const float cnt = (float)(b - a);
     float *o = cent + (size_t)r * 8;
     for (int k = 0; k < 7; ++k) o[k] = __fdiv_rn(acc[k], cnt);
+    if (kLeaf) {
+        o[7] = __uint_as_float(b - a);
+        return;
+    }
     const uint32_t slot = skeys[a];
     const bool last_of_slot = (b >= nfin) || skeys[b] != slot;
     ekey[r] = last_of_slot ? n + slot : svals[b];
     erun[r] = r;
 }
 
-// the seven values PCL accumulates for a point: x y z, the rgb field read as a float, r g b
+// the seven values PCL accumulates for a point: x y z, the rgb field read as a float (kLeaf, VoxelGrid's CentroidPoint: the
+// alpha byte), r g b
+template <bool kLeaf>
 __device__ __forceinline__ void vox_terms(const char *rec, float t[7])
 {
     const float *f = reinterpret_cast<const float *>(rec);
     const unsigned char *c = reinterpret_cast<const unsigned char *>(rec + 16);
-    t[0] = f[0]; t[1] = f[1]; t[2] = f[2]; t[3] = f[4];
+    t[0] = f[0]; t[1] = f[1]; t[2] = f[2]; t[3] = kLeaf ? (float)c[3] : f[4];
     t[4] = (float)c[2]; t[5] = (float)c[1]; t[6] = (float)c[0];
 }
 
 // One thread per run: the centroid record (sums in input order, like PCL) and the run's
 // emission key: the input position of the first point of the next run in the same slot, or
 // n + slot for the last run of a slot.  Long runs are only listed here (stats[2] counts them).
+template <bool kLeaf>
 __global__ __launch_bounds__(kVBlock) void k_vox_runs(const char *recs, size_t stride, uint32_t n, const uint32_t *skeys,
                                                       const uint32_t *svals, const uint32_t *start, uint32_t *stats,
                                                       float *cent /* 8 floats per run */, uint32_t *ekey, uint32_t *erun,
@@ -148,10 +163,10 @@ __global__ __launch_bounds__(kVBlock) void k_vox_runs(const char *recs, size_t s
     float acc[7] = {0, 0, 0, 0, 0, 0, 0};
     for (uint32_t p = a; p < b; ++p) {
         float t[7];
-        vox_terms(recs + (size_t)svals[p] * stride, t);
+        vox_terms<kLeaf>(recs + (size_t)svals[p] * stride, t);
         for (int k = 0; k < 7; ++k) acc[k] = __fadd_rn(acc[k], t[k]);
     }
-    vox_store_run(acc, a, b, n, nfin, r, skeys, svals, cent, ekey, erun);
+    vox_store_run<kLeaf>(acc, a, b, n, nfin, r, skeys, svals, cent, ekey, erun);
 }
 
 // The seven terms of a point from two loads when the records allow it (32-byte PointXYZRGB records, 16-byte aligned):
@@ -182,6 +197,7 @@ __device__ __forceinline__ VoxRaw vox_load(const char *rec, bool vec)
 // four chunks ahead (a gather from HBM takes longer than four chunks of additions), and chunk k + 1 is written to the
 // other half of the LDS buffer before chunk k is added.  Positions past the end of the run contribute +0.0f, which
 // leaves a float sum unchanged.
+template <bool kLeaf>
 __global__ __launch_bounds__(kVBlock) void k_vox_long_runs(const char *recs, size_t stride, uint32_t n, const uint32_t *skeys,
                                                            const uint32_t *svals, const uint32_t *start, const uint32_t *stats,
                                                            float *cent, uint32_t *ekey, uint32_t *erun, const uint32_t *long_runs)
@@ -211,7 +227,7 @@ __global__ __launch_bounds__(kVBlock) void k_vox_long_runs(const char *recs, siz
             float *col = &sh[w][half][0][lane];
             const bool in = i != 0xffffffffu;
             col[0 * 64] = v.x; col[1 * 64] = v.y; col[2 * 64] = v.z;
-            col[3 * 64] = __uint_as_float(v.rgb);
+            col[3 * 64] = kLeaf ? (in ? (float)(v.rgb >> 24) : 0.0f) : __uint_as_float(v.rgb);
             col[4 * 64] = in ? (float)((v.rgb >> 16) & 0xffu) : 0.0f;
             col[5 * 64] = in ? (float)((v.rgb >> 8) & 0xffu) : 0.0f;
             col[6 * 64] = in ? (float)(v.rgb & 0xffu) : 0.0f;
@@ -262,7 +278,7 @@ __global__ __launch_bounds__(kVBlock) void k_vox_long_runs(const char *recs, siz
         __builtin_amdgcn_wave_barrier();
         float all[7];
         for (int c = 0; c < 7; ++c) all[c] = __shfl(acc, c);
-        if (lane == 0) vox_store_run(all, a, b, n, nfin, r, skeys, svals, cent, ekey, erun);
+        if (lane == 0) vox_store_run<kLeaf>(all, a, b, n, nfin, r, skeys, svals, cent, ekey, erun);
     }
 }
 
@@ -422,13 +438,16 @@ __device__ __forceinline__ uint32_t h_window(const float (&t)[kHL], uint32_t s, 
     }
 }
 
+// kLeaf (pcl::VoxelGrid averages alpha too): the wave that sums b sums a behind it, window by window -- a colour window is a
+// few integer additions while the sum stays below 2^24, and the three coordinate waves are what the colour waves wait for.
+template <bool kLeaf>
 __global__ __launch_bounds__(kHB) void k_vox_huge_runs(const char *recs, size_t stride, uint32_t n, const uint32_t *skeys,
                                                        const uint32_t *svals, const uint32_t *start, const uint32_t *stats,
                                                        float *cent, uint32_t *ekey, uint32_t *erun, const uint32_t *huge_runs)
 {
     // [half][component: x y z rgb][window][row][column]
     __shared__ uint32_t sh[2][4][kHWins][kHL * kHPitch];
-    __shared__ uint32_t sh_s[6];
+    __shared__ uint32_t sh_s[7];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const bool loader = tid >= (uint32_t)(kHB - kHLoaders);
     const uint32_t tl = tid - (uint32_t)(kHB - kHLoaders);   // (loaders) 0 .. 127
@@ -479,6 +498,7 @@ __global__ __launch_bounds__(kHB) void k_vox_huge_runs(const char *recs, size_t 
         }
         __syncthreads();
         uint32_t s = 0u;   // (waves 0..5) the wave's component so far: +0.0f
+        uint32_t s_alpha = 0u;   // (kLeaf, wave 5) the alpha sum so far
         uint32_t half = 0u;
         for (uint32_t base = a; base < b; base += kHSuper, half ^= 1u) {
             if (loader) {
@@ -504,19 +524,25 @@ __global__ __launch_bounds__(kHB) void k_vox_huge_runs(const char *recs, size_t 
 #pragma unroll
                         for (int i = 0; i < kHL; ++i) t[i] = (float)((sh[half][3][w][(uint32_t)i * kHPitch + lane] >> shift) & 0xffu);
                         s = h_window<true>(t, s, lane);
+                        if (kLeaf && wave == 5u) {
+#pragma unroll
+                            for (int i = 0; i < kHL; ++i) t[i] = (float)(sh[half][3][w][(uint32_t)i * kHPitch + lane] >> 24);
+                            s_alpha = h_window<true>(t, s_alpha, lane);
+                        }
                     }
                 }
             }
             __syncthreads();   // (this half has been summed, the other one is laid out)
         }
         if (!loader && lane == 0u) sh_s[wave] = s;
+        if (kLeaf && wave == 5u && lane == 0u) sh_s[6] = s_alpha;
         __syncthreads();
         if (tid == 0) {
             float all[7];
             all[0] = __uint_as_float(sh_s[0]); all[1] = __uint_as_float(sh_s[1]); all[2] = __uint_as_float(sh_s[2]);
-            all[3] = 0.0f;   // (the sum PCL never reads)
+            all[3] = kLeaf ? __uint_as_float(sh_s[6]) : 0.0f;   // (ApproximateVoxelGrid: the sum PCL never reads)
             all[4] = __uint_as_float(sh_s[3]); all[5] = __uint_as_float(sh_s[4]); all[6] = __uint_as_float(sh_s[5]);
-            vox_store_run(all, a, b, n, nfin, r, skeys, svals, cent, ekey, erun);
+            vox_store_run<kLeaf>(all, a, b, n, nfin, r, skeys, svals, cent, ekey, erun);
         }
     }
 }
@@ -621,13 +647,13 @@ int voxel_filter_device(rsreg_ctx *ctx, const char *d_in, uint32_t N, size_t str
     RSREG_HIP(ctx, hipStreamSynchronize(st));
     const uint32_t nr = h[0];
     if (nr == 0) return RSREG_OK;
-    k_vox_runs<<<div_up_u(nr, kVBlock), kVBlock, 0, st>>>(d_in, stride, N, skeys, svals, start, stats, cent, ekey, erun, long_runs, huge_runs);
+    k_vox_runs<false><<<div_up_u(nr, kVBlock), kVBlock, 0, st>>>(d_in, stride, N, skeys, svals, start, stats, cent, ekey, erun, long_runs, huge_runs);
     RSREG_HIP(ctx, hipGetLastError());
-    k_vox_long_runs<<<std::min(div_up_u(nr, 4u), 2048u), kVBlock, 0, st>>>(d_in, stride, N, skeys, svals, start, stats, cent, ekey, erun,
+    k_vox_long_runs<false><<<std::min(div_up_u(nr, 4u), 2048u), kVBlock, 0, st>>>(d_in, stride, N, skeys, svals, start, stats, cent, ekey, erun,
                                                                            long_runs);
     RSREG_HIP(ctx, hipGetLastError());
     if (const uint32_t huge_at_most = (N - std::min(N, nr)) / (kHugeRun - 1u)) {   // (nr runs hold at least one point each)
-        k_vox_huge_runs<<<std::min(huge_at_most, 512u), kHB, 0, st>>>(d_in, stride, N, skeys, svals, start, stats, cent, ekey, erun, huge_runs);
+        k_vox_huge_runs<false><<<std::min(huge_at_most, 512u), kHB, 0, st>>>(d_in, stride, N, skeys, svals, start, stats, cent, ekey, erun, huge_runs);
         RSREG_HIP(ctx, hipGetLastError());
     }
     const uint32_t *emit_order = order;
@@ -667,6 +693,361 @@ extern "C" int rsreg_approx_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_
     uint32_t nr = 0;
     int rc = voxel_filter_device(ctx, ctx->d_vox_in.as<char>(), (uint32_t)n, stride, leaf, &nr, -1);
     if (rc || nr == 0) return rc;
+    RSREG_HIP(ctx, hipMemcpyAsync(ctx->h_stage.ptr, ctx->d_vox_out.ptr, (size_t)nr * stride, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    {
+        const char *stage = ctx->h_stage.as<char>();
+        char *dst = static_cast<char *>(out);
+        host_parallel_for(nr, [=](size_t lo, size_t hi) { std::memcpy(dst + lo * stride, stage + lo * stride, (hi - lo) * stride); });
+    }
+    *n_out = nr;
+    return RSREG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// pcl::VoxelGrid<PointXYZRGB>::filter (contract: include/rsreg.h, "pcl::VoxelGrid"; sequential restatement: voxel_host.cpp).
+//   box of the finite records (k_grid_box) -> the host reads it: the overflow branch, the leaf grid, the key bits
+//   k_vg_keys      key = leaf index, value = input position; a non-finite record gets a sentinel above every leaf
+//   osort          stable, over exactly the bits the largest key (and the sentinel, if one is needed) has
+//   k_vg_flags / oscan / k_vg_starts: where the leaves start -> the host reads their number
+//   k_vox_runs<true> / k_vox_long_runs<true> / k_vox_huge_runs<true>: the sums of a leaf in ascending input index
+//   (min_points_per_voxel > 1: k_vg_keep / oscan) k_vg_emit: the records, in key order
+// Keys are 32 bits wide unless the leaf indices use all 32 bits (div_b's product passes 2^31 although d's does not: the box
+// is measured twice, by a difference and by two floors): then the sentinel is bit 32 and the keys are 64 bits wide.
+namespace rsreg {
+namespace {
+
+struct LeafGrid {
+    float inv[3];
+    int min_b[3];
+    uint32_t mul[3];
+};
+
+// float -> int32 as the contract defines it: saturating
+__device__ __forceinline__ int vg_sat_i32(float f)
+{
+    if (f >= 2147483648.0f) return 2147483647;
+    if (f <= -2147483648.0f) return -2147483647 - 1;
+    return (int)f;
+}
+
+template <typename K>
+__global__ __launch_bounds__(kVBlock) void k_vg_keys(const char *recs, size_t stride, uint32_t n, LeafGrid g, K sentinel, K *keys, uint32_t *vals,
+                                                     uint32_t *stats, uint32_t *sort_scratch, uint32_t sort_scratch_words)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 4) stats[i] = 0u;
+    rsreg::radix32_clear(sort_scratch, sort_scratch_words, i, gridDim.x * blockDim.x);
+    if (i >= n) return;
+    const char *rec = recs + (size_t)i * stride;
+    float p[3];
+    if ((stride % 16 == 0) && ((reinterpret_cast<size_t>(recs) & 15) == 0)) {   // xyz in one 16-byte load
+        const float4 a = *reinterpret_cast<const float4 *>(rec);
+        p[0] = a.x; p[1] = a.y; p[2] = a.z;
+    } else {
+        const float *f = reinterpret_cast<const float *>(rec);
+        p[0] = f[0]; p[1] = f[1]; p[2] = f[2];
+    }
+    uint32_t idx = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float rel = __fsub_rn(floorf(__fmul_rn(p[a], g.inv[a])), (float)g.min_b[a]);
+        idx += (uint32_t)vg_sat_i32(rel) * g.mul[a];
+    }
+    keys[i] = finite3(p[0], p[1], p[2]) ? (K)idx : sentinel;
+    vals[i] = i;
+}
+
+// p = position in the sorted order; flag[p] = 1 where a leaf starts
+template <typename K>
+__global__ __launch_bounds__(kVBlock) void k_vg_flags(const K *skeys, uint32_t n, K sentinel, uint32_t *flag)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const K k = skeys[p];
+    flag[p] = (k != sentinel && (p == 0 || skeys[p - 1] != k)) ? 1u : 0u;
+}
+
+// leaf r starts at sorted position start[r]; stats[0] = number of leaves, stats[1] = number of finite records
+template <typename K>
+__global__ __launch_bounds__(kVBlock) void k_vg_starts(const K *skeys, K sentinel, const uint32_t *flag, const uint32_t *rid, uint32_t n,
+                                                       uint32_t *start, uint32_t *stats)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (flag[p]) start[rid[p]] = p;
+    if (p == n - 1) stats[0] = rid[p] + flag[p];
+    if (skeys[p] != sentinel && (p == n - 1 || skeys[p + 1] == sentinel)) stats[1] = p + 1;
+}
+
+// keep[r] = 1 when leaf r holds min_points points or more
+__global__ __launch_bounds__(kVBlock) void k_vg_keep(const uint32_t *start, uint32_t nr, uint32_t nfin, uint32_t min_points, uint32_t *keep)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nr) return;
+    const uint32_t b = (r + 1 < nr) ? start[r + 1] : nfin;
+    keep[r] = (b - start[r] >= min_points) ? 1u : 0u;
+}
+
+// output record pos[r] (r itself when every leaf is kept) = the centroid of leaf r: a zeroed record with xyz, 1.0f and the colour
+// (all_data: the truncated means of the four bytes; else a default point's); *n_kept = the records written
+__global__ __launch_bounds__(kVBlock) void k_vg_emit(const float *cent, const uint32_t *keep, const uint32_t *pos, uint32_t nr, int all_data,
+                                                     size_t stride, char *out, uint32_t *n_kept)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nr) return;
+    const bool kept = !keep || keep[r];
+    const uint32_t j = keep ? pos[r] : r;
+    if (r == nr - 1) *n_kept = j + (kept ? 1u : 0u);
+    if (!kept) return;
+    const float *c = cent + (size_t)r * 8;
+    char *rec = out + (size_t)j * stride;
+    for (size_t k = 20; k < stride; k += 4) *reinterpret_cast<uint32_t *>(rec + k) = 0u;
+    float *f = reinterpret_cast<float *>(rec);
+    f[0] = c[0];
+    f[1] = c[1];
+    f[2] = c[2];
+    f[3] = 1.0f;
+    uint32_t rgba = 0xff000000u;
+    if (all_data) rgba = ((uint32_t)c[3] << 24) | ((uint32_t)c[4] << 16) | ((uint32_t)c[5] << 8) | (uint32_t)c[6];
+    *reinterpret_cast<uint32_t *>(rec + 16) = rgba;
+}
+
+inline int32_t vg_host_sat_i32(float f)
+{
+    if (f >= 2147483648.0f) return INT32_MAX;
+    if (f <= -2147483648.0f) return INT32_MIN;
+    return (int32_t)f;
+}
+
+// What the host makes of the box: 1 = the leaf size is too small for it (PCL: the output is the input); else the leaf grid,
+// the info fields and the largest key a finite record can get.
+int vg_leaf_grid(const float mn[3], const float mx[3], const float leaf[3], LeafGrid &g, rsreg_voxel_grid_info &nfo, uint32_t &max_key)
+{
+    unsigned long long cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        g.inv[a] = 1.0f / leaf[a];
+        const float ext = mx[a] - mn[a];
+        const float v = ext * g.inv[a];
+        if (!(v < 2147483648.0f)) return 1;
+        cells *= (unsigned long long)((int64_t)v + 1);   // (a factor is 2^31 at the most and `cells` below 2^31 before it)
+        if (cells > (unsigned long long)INT32_MAX) return 1;
+    }
+    unsigned long long span = 1;   // the product of the divisions as it is, saturated at 2^32
+    for (int a = 0; a < 3; ++a) {
+        const float lo = mn[a] * g.inv[a], hi = mx[a] * g.inv[a];
+        nfo.min_b[a] = vg_host_sat_i32(std::floor(lo));
+        nfo.max_b[a] = vg_host_sat_i32(std::floor(hi));
+        const long long div = (long long)nfo.max_b[a] - (long long)nfo.min_b[a] + 1;   // (1 .. 2^32)
+        nfo.div_b[a] = (int32_t)(uint32_t)div;
+        if (span < (1ull << 32)) span = std::min(span * (unsigned long long)div, 1ull << 32);   // (span < 2^32, div <= 2^32: no overflow of 64 bits)
+        g.min_b[a] = nfo.min_b[a];
+    }
+    g.mul[0] = 1u;
+    g.mul[1] = (uint32_t)nfo.div_b[0];
+    g.mul[2] = (uint32_t)nfo.div_b[0] * (uint32_t)nfo.div_b[1];
+    for (int a = 0; a < 3; ++a) nfo.divb_mul[a] = (int32_t)g.mul[a];
+    max_key = (uint32_t)(span - 1);   // (2^32 leaves or more: the indices wrap and may be any 32-bit value)
+    return 0;
+}
+
+// everything behind the box for keys of type K; `bits`: of the sort; nr_out / n_out: leaves, records written to d_vox_out
+template <typename K>
+int vg_sorted_leaves(rsreg_ctx *ctx, const char *d_in, uint32_t N, size_t stride, const LeafGrid &g, K sentinel, unsigned bits,
+                     const rsreg_voxel_grid_params &prm, uint32_t *nr_out, uint32_t *n_out)
+{
+    hipStream_t st = ctx->stream;
+    const size_t n = N;
+    K *k_a = ctx->d_keys.as<K>(), *k_b = ctx->d_keys_alt.as<K>();
+    uint32_t *v_a = ctx->d_vals.as<uint32_t>(), *v_b = ctx->d_vals_alt.as<uint32_t>();
+    uint32_t *flag = ctx->d_flags.as<uint32_t>(), *rid = ctx->d_scan.as<uint32_t>();
+    float *cent = ctx->d_vox_cent.as<float>();
+    uint32_t *stats = ctx->d_misc.as<uint32_t>() + 32;
+    const uint32_t nb = div_up_u(N, kVBlock);
+    // one scratch block: [the sort's state, cleared by the keys kernel on its way | the scans' sums]
+    const Radix32Plan plan = radix32_plan<K>(n, 0, bits);
+    const size_t off_scan = ((size_t)plan.words * 4 + 255) & ~(size_t)255;
+    RSREG_HIP(ctx, ctx->d_tmp.reserve(off_scan + oscan_scratch_bytes<uint32_t>(n) + 256));
+    char *tmp = ctx->d_tmp.as<char>();
+    k_vg_keys<K><<<nb, kVBlock, 0, st>>>(d_in, stride, N, g, sentinel, k_a, v_a, stats, ctx->d_tmp.as<uint32_t>(), plan.words);
+    RSREG_HIP(ctx, hipGetLastError());
+    bool in_first = true;
+    RSREG_HIP(ctx, radix32_sort_pairs<K>(plan, ctx->d_tmp.as<uint32_t>(), k_a, k_b, v_a, v_b, n, 0, bits, st, &in_first));
+    const K *skeys = in_first ? k_a : k_b;
+    const uint32_t *svals = in_first ? v_a : v_b;
+    uint32_t *start = reinterpret_cast<uint32_t *>(in_first ? k_b : k_a);   // (the other pair is free)
+    uint32_t *keep = in_first ? v_b : v_a, *pos = keep + N;                 // (2 N words each)
+    k_vg_flags<K><<<nb, kVBlock, 0, st>>>(skeys, N, sentinel, flag);
+    RSREG_HIP(ctx, hipGetLastError());
+    RSREG_HIP(ctx, (oscan<uint32_t>(flag, rid, n, 0u, tmp + off_scan, st)));
+    k_vg_starts<K><<<nb, kVBlock, 0, st>>>(skeys, sentinel, flag, rid, N, start, stats);
+    RSREG_HIP(ctx, hipGetLastError());
+    uint32_t *h = ctx->h_sums.as<uint32_t>();
+    RSREG_HIP(ctx, hipMemcpyAsync(h, stats, 8, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    const uint32_t nr = h[0], nfin = h[1];
+    *nr_out = nr;
+    *n_out = 0;
+    if (nr == 0) return RSREG_OK;
+    uint32_t *long_runs = rid, *huge_runs = rid + N;   // (the run ids are dead once the starts are written; 2 N words)
+    k_vox_runs<true><<<div_up_u(nr, kVBlock), kVBlock, 0, st>>>(d_in, stride, N, nullptr, svals, start, stats, cent, nullptr, nullptr, long_runs, huge_runs);
+    RSREG_HIP(ctx, hipGetLastError());
+    if (N - nr >= kLongRun - 1u) {   // (nr leaves hold a point each: a leaf of kLongRun points needs so many more)
+        k_vox_long_runs<true><<<std::min(div_up_u(nr, 4u), 2048u), kVBlock, 0, st>>>(d_in, stride, N, nullptr, svals, start, stats, cent, nullptr, nullptr,
+                                                                                    long_runs);
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    if (const uint32_t huge_at_most = (N - nr) / (kHugeRun - 1u)) {
+        k_vox_huge_runs<true><<<std::min(huge_at_most, 512u), kHB, 0, st>>>(d_in, stride, N, nullptr, svals, start, stats, cent, nullptr, nullptr, huge_runs);
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    const bool drop = prm.min_points_per_voxel > 1u;
+    if (drop) {
+        k_vg_keep<<<div_up_u(nr, kVBlock), kVBlock, 0, st>>>(start, nr, nfin, prm.min_points_per_voxel, keep);
+        RSREG_HIP(ctx, hipGetLastError());
+        RSREG_HIP(ctx, (oscan<uint32_t>(keep, pos, nr, 0u, tmp + off_scan, st)));
+    }
+    k_vg_emit<<<div_up_u(nr, kVBlock), kVBlock, 0, st>>>(cent, drop ? keep : nullptr, drop ? pos : nullptr, nr, prm.downsample_all_data ? 1 : 0, stride,
+                                                         ctx->d_vox_out.as<char>(), stats + 4);
+    RSREG_HIP(ctx, hipGetLastError());
+    *n_out = nr;
+    if (drop) {
+        RSREG_HIP(ctx, hipMemcpyAsync(h + 4, stats + 4, 4, hipMemcpyDeviceToHost, st));
+        RSREG_HIP(ctx, hipStreamSynchronize(st));
+        *n_out = h[4];
+    }
+    return RSREG_OK;
+}
+
+bool vg_params_ok(const rsreg_voxel_grid_params *p)
+{
+    if (!p) return false;
+    for (int a = 0; a < 3; ++a)
+        if (!(p->leaf[a] > 0) || !std::isfinite(p->leaf[a]) || !std::isfinite(1.0f / p->leaf[a])) return false;
+    return true;
+}
+
+}  // namespace
+
+// The filter on records already in HBM, on the main stream with the main scratch set (like voxel_filter_device without a side
+// set).  The records land in ctx->d_vox_out, *n_out of them -- unless info->overflowed: then nothing is written and the
+// caller copies the input.
+int voxel_grid_device(rsreg_ctx *ctx, const char *d_in, uint32_t N, size_t stride, const rsreg_voxel_grid_params &prm, uint32_t *n_out,
+                      rsreg_voxel_grid_info *info)
+{
+    *n_out = 0;
+    std::memset(info, 0, sizeof *info);
+    if (N == 0) return RSREG_OK;
+    hipStream_t st = ctx->stream;
+    const size_t n = N;
+    RSREG_HIP(ctx, ctx->d_misc.reserve(256));
+    RSREG_HIP(ctx, ctx->h_sums.reserve(2048));
+    uint32_t *box = ctx->d_misc.as<uint32_t>(), *h = ctx->h_sums.as<uint32_t>();
+    // minima start at all ones, maxima and the count at zero (ordered-float encoding)
+    RSREG_HIP(ctx, hipMemsetAsync(box, 0xff, 12, st));
+    RSREG_HIP(ctx, hipMemsetAsync(box + 3, 0, (kBoxWords - 3) * sizeof(uint32_t), st));
+    k_grid_box<<<std::min<uint32_t>(div_up_u(N, kBlock), 1024), kBlock, 0, st>>>(StridedRecords{d_in, stride, nullptr}, N, box);
+    RSREG_HIP(ctx, hipGetLastError());
+    RSREG_HIP(ctx, hipMemcpyAsync(h, box, kBoxWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    info->n_finite = h[6];
+    if (h[6] == 0) return RSREG_OK;
+    float mn[3], mx[3];
+    for (int a = 0; a < 3; ++a) { mn[a] = ordered_float(h[a]); mx[a] = ordered_float(h[3 + a]); }
+    LeafGrid g;
+    uint32_t max_key = 0;
+    if (vg_leaf_grid(mn, mx, prm.leaf, g, *info, max_key)) {
+        info->overflowed = 1;
+        info->n_out = N;
+        *n_out = N;
+        return RSREG_OK;
+    }
+    // as many key bits as the largest leaf index has; the sentinel is the power of two above it, and takes part in the sort (one
+    // more bit) only if there is a non-finite record.  Leaf indices of all 32 bits leave no 32-bit sentinel: 64-bit keys then.
+    unsigned key_bits = 1;
+    while (key_bits < 32 && (max_key >> key_bits)) ++key_bits;
+    const unsigned bits = key_bits + (h[6] < N ? 1u : 0u);
+    RSREG_HIP(ctx, ctx->d_vox_out.reserve(n * stride));
+    RSREG_HIP(ctx, ctx->d_keys.reserve(n * 8));
+    RSREG_HIP(ctx, ctx->d_keys_alt.reserve(n * 8));
+    RSREG_HIP(ctx, ctx->d_vals.reserve(n * 8));
+    RSREG_HIP(ctx, ctx->d_vals_alt.reserve(n * 8));
+    RSREG_HIP(ctx, ctx->d_flags.reserve(n * 8));
+    RSREG_HIP(ctx, ctx->d_scan.reserve(n * 8));
+    RSREG_HIP(ctx, ctx->d_vox_cent.reserve(n * 32));
+    uint32_t nr = 0;
+    int rc;
+    if (key_bits == 32)
+        rc = vg_sorted_leaves<unsigned long long>(ctx, d_in, N, stride, g, 1ull << 32, bits, prm, &nr, n_out);
+    else
+        rc = vg_sorted_leaves<uint32_t>(ctx, d_in, N, stride, g, 1u << key_bits, bits, prm, &nr, n_out);
+    if (rc) return rc;
+    info->n_leaves = nr;
+    info->n_out = *n_out;
+    return RSREG_OK;
+}
+
+}  // namespace rsreg
+
+struct rsreg_cloud;
+extern "C" int rsreg_cloud_adopt_(rsreg_cloud *c, DevBuf *buf, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense);   // cloud.hip
+extern "C" const rsreg_ctx *rsreg_cloud_ctx_(const rsreg_cloud *c);                                                                      // cloud.hip
+
+extern "C" int rsreg_cloud_voxel_grid(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_voxel_grid_params *params, rsreg_cloud *out,
+                                      rsreg_voxel_grid_info *info)
+{
+    if (!ctx || !in || !out || rsreg_cloud_ctx_(in) != ctx || rsreg_cloud_ctx_(out) != ctx) return RSREG_ERR_INVALID_ARG;
+    if (!vg_params_ok(params)) return RSREG_ERR_INVALID_ARG;
+    size_t n = 0, stride = 0;
+    uint32_t width = 0, height = 0;
+    int is_dense = 0;
+    int rc = rsreg_cloud_info(in, &n, &stride, &width, &height, &is_dense);
+    if (rc) return rc;
+    if (stride < 20 || (stride & 3)) return fail(ctx, RSREG_ERR_INVALID_ARG, "records need rgb at byte 16 and a stride that is a multiple of 4");
+    if (n > 0x3ffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    const char *rec = static_cast<const char *>(rsreg_cloud_device_ptr(in));
+    if (n && !rec) return fail(ctx, RSREG_ERR_STATE, "the cloud's records are not available");
+    rsreg_voxel_grid_info nfo;
+    uint32_t n_out = 0;
+    rc = voxel_grid_device(ctx, rec, (uint32_t)n, stride, *params, &n_out, &nfo);
+    if (rc) return rc;
+    if (info) *info = nfo;
+    if (nfo.overflowed) return in == out ? RSREG_OK : rsreg_cloud_copy(ctx, in, out);
+    return rsreg_cloud_adopt_(out, &ctx->d_vox_out, n_out, stride, n_out, 1, 1);   // (in == out: the input has been consumed by now)
+}
+
+extern "C" int rsreg_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_t n, size_t stride, const rsreg_voxel_grid_params *params, void *out,
+                                    size_t *n_out, rsreg_voxel_grid_info *info)
+{
+    if (!ctx || !n_out || (n && (!in || !out)) || stride < 20 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
+    if (!vg_params_ok(params)) return RSREG_ERR_INVALID_ARG;
+    if (n > 0x3ffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
+    *n_out = 0;
+    rsreg_voxel_grid_info nfo;
+    std::memset(&nfo, 0, sizeof nfo);
+    if (info) *info = nfo;
+    if (n == 0) return RSREG_OK;
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    RSREG_HIP(ctx, ctx->d_vox_in.reserve(n * stride));
+    RSREG_HIP(ctx, ctx->h_stage.reserve(n * stride));
+    {
+        char *stage = ctx->h_stage.as<char>();
+        const char *src = static_cast<const char *>(in);
+        host_parallel_for(n, [=](size_t lo, size_t hi) { rsreg::stream_copy(stage + lo * stride, src + lo * stride, (hi - lo) * stride); });
+    }
+    RSREG_HIP(ctx, hipMemcpyAsync(ctx->d_vox_in.ptr, ctx->h_stage.ptr, n * stride, hipMemcpyHostToDevice, st));
+    uint32_t nr = 0;
+    int rc = voxel_grid_device(ctx, ctx->d_vox_in.as<char>(), (uint32_t)n, stride, *params, &nr, &nfo);
+    if (rc) return rc;
+    if (info) *info = nfo;
+    if (nfo.overflowed) {   // the output is the input
+        if (in != out) std::memmove(out, in, n * stride);
+        *n_out = n;
+        return RSREG_OK;
+    }
+    if (nr == 0) return RSREG_OK;
     RSREG_HIP(ctx, hipMemcpyAsync(ctx->h_stage.ptr, ctx->d_vox_out.ptr, (size_t)nr * stride, hipMemcpyDeviceToHost, st));
     RSREG_HIP(ctx, hipStreamSynchronize(st));
     {

@@ -48,6 +48,7 @@ EXPORTS = [
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
     "rsreg_iin_params_default", "rsreg_cloud_integral_normals",
+    "rsreg_voxel_grid_params_default", "rsreg_voxel_grid", "rsreg_voxel_grid_gpu", "rsreg_cloud_voxel_grid",
 ]
 
 
@@ -91,6 +92,15 @@ class SorStats(C.Structure):   # rsreg_sor_stats
 class IinParams(C.Structure):   # rsreg_iin_params
     _fields_ = [("method", C.c_int32), ("max_depth_change_factor", C.c_float), ("normal_smoothing_size", C.c_float),
                 ("depth_dependent_smoothing", C.c_int32), ("border_policy", C.c_int32), ("viewpoint", C.c_float * 3)]
+
+
+class VoxelGridParams(C.Structure):   # rsreg_voxel_grid_params
+    _fields_ = [("leaf", C.c_float * 3), ("downsample_all_data", C.c_int32), ("min_points_per_voxel", C.c_uint32)]
+
+
+class VoxelGridInfo(C.Structure):   # rsreg_voxel_grid_info
+    _fields_ = [("min_b", C.c_int32 * 3), ("max_b", C.c_int32 * 3), ("div_b", C.c_int32 * 3), ("divb_mul", C.c_int32 * 3),
+                ("n_finite", C.c_uint64), ("n_leaves", C.c_uint64), ("n_out", C.c_uint64), ("overflowed", C.c_int32)]
 
 
 class NdtResult(C.Structure):
@@ -284,6 +294,11 @@ def lib():
     L.rsreg_iin_params_default.argtypes = [C.POINTER(IinParams)]
     L.rsreg_iin_params_default.restype = None
     L.rsreg_cloud_integral_normals.argtypes = [vp, vp, C.POINTER(IinParams), vp, vp]
+    L.rsreg_voxel_grid_params_default.argtypes = [C.POINTER(VoxelGridParams)]
+    L.rsreg_voxel_grid_params_default.restype = None
+    L.rsreg_voxel_grid.argtypes = [vp, sz, sz, vp, i32, u32, vp, C.POINTER(sz), C.POINTER(VoxelGridInfo)]
+    L.rsreg_voxel_grid_gpu.argtypes = [vp, vp, sz, sz, C.POINTER(VoxelGridParams), vp, C.POINTER(sz), C.POINTER(VoxelGridInfo)]
+    L.rsreg_cloud_voxel_grid.argtypes = [vp, vp, C.POINTER(VoxelGridParams), vp, C.POINTER(VoxelGridInfo)]
     L.rsreg_cloud_concat.argtypes = [vp, vp, vp, vp]
     L.rsreg_icp_set_target_cloud.argtypes = [vp, vp, dbl]
     L.rsreg_icp_target_is_cloud.argtypes = [vp, vp, dbl]
