@@ -601,6 +601,99 @@ typedef struct rsreg_iin_params {
 void rsreg_iin_params_default(rsreg_iin_params *params);
 int rsreg_cloud_integral_normals(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_iin_params *params /* NULL = defaults */,
                                  rsreg_cloud *out, uint8_t *rect_out /* may be NULL */);
+/* ---- capture: a depth frame and a colour frame -> an organized PointXYZRGB cloud -----------------------------------------
+ * The step in front of everything above.  The reference makes the vertices and texture coordinates with rs2::pointcloud
+ * (map_to, calculate) and the records with convert_to_pcl (src/capture.hpp:72-107: the three-fifths centre crop that
+ * blur_filter.hpp repeats) or convert_to_pcl_new (src/capture_opencv.hpp:128-160: the whole frame), the colour through
+ * rgb_texture (src/capture.hpp:11-32).  Here the two images go in -- 5 bytes a pixel instead of the 32 of a record -- and the
+ * cloud is built in HBM.  librealsense is not available to check against: what follows is RECALLED from librealsense 2.3x
+ * (include/librealsense2/rsutil.h: rs2_deproject_pixel_to_point, rs2_transform_point_to_point, rs2_project_point_to_pixel;
+ * src/proc/pointcloud.cpp) and IS the contract.  All arithmetic is float32; every operation written below is one IEEE
+ * operation rounded once, in the order written (C's left-to-right parse), none contracted into a multiply-add.
+ *
+ * Images.  depth: p->depth.height rows of p->depth.width uint16 values, `depth_stride` bytes apart (even, >= 2 * width).
+ * colour: p->color.height rows of p->color.width pixels of p->color_bytes_per_pixel (3 or 4) bytes, `color_stride` bytes
+ * apart (>= bytes per pixel * width).  The two images need not have the same size.
+ * (1) Vertex of depth pixel (c, r) with raw value d:
+ *       depth = depth_scale * (float)d;   x = ((float)c - ppx) / fx;   y = ((float)r - ppy) / fy      (depth intrinsics)
+ *     and, when the depth model is RSREG_DISTORTION_INVERSE_BROWN_CONRADY (k = depth.coeffs):
+ *       r2 = x*x + y*y;   f = 1 + k[0]*r2 + k[1]*r2*r2 + k[4]*r2*r2*r2;
+ *       ux = x*f + 2*k[2]*x*y + k[3]*(r2 + 2*x*x);   uy = y*f + 2*k[3]*x*y + k[2]*(r2 + 2*y*y);   x = ux;  y = uy;
+ *     P = (depth * x, depth * y, depth).  For d = 0 these are the computed products: -0 where x or y is negative.
+ * (2) Texture coordinate: if P.z == 0 then (u, v) = (0, 0).  Otherwise, with R = rotation (column-major), t = translation:
+ *       q[k] = R[0+k]*P.x + R[3+k]*P.y + R[6+k]*P.z + t[k]    (k = 0, 1, 2; added left to right)
+ *       x = q[0] / q[2];   y = q[1] / q[2]
+ *     and, when the colour model is RSREG_DISTORTION_MODIFIED_BROWN_CONRADY (k = color.coeffs):
+ *       r2 = x*x + y*y;   f = 1 + k[0]*r2 + k[1]*r2*r2 + k[4]*r2*r2*r2;   x = x*f;   y = y*f;
+ *       dx = x + 2*k[2]*x*y + k[3]*(r2 + 2*x*x);   dy = y + 2*k[3]*x*y + k[2]*(r2 + 2*y*y);   x = dx;  y = dy;
+ *     (librealsense's form: dx, dy take the scaled x, y and the r2 from before the scaling), then with the colour intrinsics
+ *       px = x*fx + ppx;   py = y*fy + ppy;   u = px / (float)width;   v = py / (float)height
+ *     There is no half-pixel term here: the + .5f of (3) is the rounding.
+ * (3) Colour (rgb_texture): xi = min(max(I(u * (float)width + .5f), 0), width - 1), yi likewise from v and the height, where
+ *     I(t) is C's (int)t: truncation toward zero, and for a t that is NaN or outside [-2^31, 2^31) -- undefined in C -- INT_MIN,
+ *     what the x86 conversion the reference ran on gives, so that xi = 0.  (A GPU's conversion saturates: +inf would land on
+ *     width - 1.  The rule is written out in the code, not left to the instruction.)  The three bytes at
+ *     yi * color_stride + xi * bytes_per_pixel are, with color_bgr = 1 (the reference: "BGR due to Camera Model"),
+ *     b, g, r in that order; with color_bgr = 0, r, g, b.  A fourth byte is skipped.
+ * (4) Records: the window rows [r0, r1) x cols [c0, c1) of the depth image, row-major, goes to records 0, 1, 2 ... LINEARLY (the
+ *     reference's i++), not by output row: x, y, z, 1.0f, rgba = 0xff000000 | r << 16 | g << 8 | b, three zero words.  The
+ *     cloud has out_width * out_height records; those past the window's count stay the default PointXYZRGB
+ *     (0, 0, 0, 1, 0xff000000).  width = out_width, height = out_height, is_dense as given.
+ * Distortion models: none, inverse Brown-Conrady on the depth side, modified Brown-Conrady on the colour side.  Any other
+ * pairing (a model value of 0 .. 5) is accepted only when all five coefficients are zero and then acts as none (the D435i
+ * reports Brown-Conrady with zero coefficients); with a non-zero coefficient, or a model outside 0 .. 5: RSREG_ERR_INVALID_ARG.
+ * RSREG_DISTORTION_NONE ignores its coefficients.
+ * RSREG_ERR_INVALID_ARG as well, nothing written: a zero image size or output size; a window outside the depth image
+ * (0 <= r0 <= r1 <= height, 0 <= c0 <= c1 <= width must hold; an empty window is allowed: all records default);
+ * (r1 - r0) * (c1 - c0) > out_width * out_height; more than 2^31 - 16 records; bytes per pixel other than 3 or 4; a stride
+ * smaller than a row, or an odd depth stride.
+ * OUT OF SCOPE, not built: an asynchronous or deferred variant through the upload worker; the iterative (forward)
+ * Brown-Conrady, F-Theta and Kannala-Brandt models with non-zero coefficients; the infrared fallback, alignment of depth to
+ * colour as an image, and IMU handling of the reference's capture loop; the SIFT code of capture_opencv.hpp. */
+enum rsreg_distortion {   /* rs2_distortion, same values */
+    RSREG_DISTORTION_NONE = 0, RSREG_DISTORTION_MODIFIED_BROWN_CONRADY = 1, RSREG_DISTORTION_INVERSE_BROWN_CONRADY = 2,
+    RSREG_DISTORTION_FTHETA = 3, RSREG_DISTORTION_BROWN_CONRADY = 4, RSREG_DISTORTION_KANNALA_BRANDT4 = 5
+};
+typedef struct rsreg_intrinsics {   /* rs2_intrinsics, same order: 48 bytes */
+    int32_t width, height;
+    float ppx, ppy, fx, fy;
+    int32_t model;                  /* rsreg_distortion */
+    float coeffs[5];
+} rsreg_intrinsics;
+typedef struct rsreg_depth_params {   /* 192 bytes */
+    rsreg_intrinsics depth, color;
+    float rotation[9], translation[3];   /* rs2_extrinsics depth -> colour: column-major 3 x 3, metres */
+    float depth_scale;                   /* metres per depth unit (rs2::depth_sensor::get_depth_scale; D400: 0.001) */
+    int32_t color_bytes_per_pixel;       /* 3 or 4 */
+    int32_t color_bgr;                   /* 1: bytes b, g, r (the reference); 0: bytes r, g, b */
+    int32_t r0, r1, c0, c1;              /* the window over the depth image: rows [r0, r1), cols [c0, c1) */
+    uint32_t out_width, out_height;      /* the cloud's shape: out_width * out_height records */
+    int32_t is_dense;
+    uint32_t reserved[2];                /* 0 */
+} rsreg_depth_params;
+/* convert_to_pcl_new: the whole w x h depth frame, the cloud w x h, is_dense = 0.  Everything else is a placeholder for the
+ * caller to overwrite from the camera: both intrinsics w x h with ppx = w / 2, ppy = h / 2, fx = fy = w and no distortion,
+ * identity extrinsics, depth_scale 0.001, 3 bytes per pixel, color_bgr = 1. */
+void rsreg_depth_params_default(uint32_t w, uint32_t h, rsreg_depth_params *p);
+/* convert_to_pcl / BlurFilter, C integer division: rows [h/5, h/5*4), cols [w/5, w/5*4), out_width = w*3/5,
+ * out_height = h*3/5, is_dense = 1 (PCL's default, which the reference leaves untouched); the rest as above.  Window and
+ * shape disagree for many sizes -- w = 848: 507 columns are written into a cloud 508 wide -- which is the reference's
+ * behaviour and is kept: the fill is linear, the tail stays default. */
+void rsreg_depth_params_reference(uint32_t w, uint32_t h, rsreg_depth_params *p);
+/* The contract restated sequentially on the host (no context needed): host images in, out_width * out_height 32-byte records
+ * out (capacity_records must hold them); *width, *height, *is_dense (each nullable) receive the cloud's. */
+int rsreg_depth_to_cloud(const void *depth, size_t depth_stride, const void *color, size_t color_stride,
+                         const rsreg_depth_params *p, void *out, size_t capacity_records, uint32_t *width, uint32_t *height,
+                         int *is_dense);
+/* The same on the GPU, the same bytes (csrc/depthcloud.hip: one lane per record, two 16-byte stores).  Host images: the
+ * two images are staged and go over the link, not the records; both have been read when the call returns.  On the context's
+ * stream; `out` follows the versioning rules (its version changes). */
+int rsreg_cloud_from_depth(rsreg_ctx *ctx, const void *depth, size_t depth_stride, const void *color, size_t color_stride,
+                           const rsreg_depth_params *p, rsreg_cloud *out);
+/* ... with the two images already in HBM (d_depth 2-byte aligned): nothing crosses the link.  The images must stay alive and
+ * unchanged until the next synchronising call on the context has returned. */
+int rsreg_cloud_from_depth_device(rsreg_ctx *ctx, const void *d_depth, size_t depth_stride, const void *d_color,
+                                  size_t color_stride, const rsreg_depth_params *p, rsreg_cloud *out);
 /* icp.setInputTarget / setInputSource / align on handles; aligned_out (nullable, may be the source
  * cloud): the source records with xyz <- final * xyz and data[3] = 1 */
 int rsreg_icp_set_target_cloud(rsreg_ctx *ctx, const rsreg_cloud *cloud, double max_correspondence_distance);

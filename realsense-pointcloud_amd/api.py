@@ -282,6 +282,34 @@ class DeviceCloud:
         f.setInputCloud(self)
         return f.filter()
 
+    @classmethod
+    def from_depth(cls, ctx, depth, color, params, out=None):
+        """The capture step in HBM (rsreg_cloud_from_depth; include/rsreg.h, "capture"): a DeviceCloud of PointXYZRGB records
+        from a host depth image ((h, w) uint16) and a host colour image ((h, w, 3 or 4) uint8), rows may be padded -- the two
+        images cross the link, not the records.  params: depth_params().  out: a DeviceCloud to rewrite instead of a new one."""
+        ctx = ctx or default_context()
+        dev = out if out is not None else cls(ctx=ctx)
+        (keep_d, d_ptr, d_stride), (keep_c, c_ptr, c_stride) = _depth_image(depth), _color_image(color)
+        rc = _l.lib().rsreg_cloud_from_depth(ctx.h, d_ptr, d_stride, c_ptr, c_stride, C.byref(params), dev.h)
+        if rc and out is None:
+            dev.close()
+        _l.check(rc, ctx.h)
+        return dev
+
+    @classmethod
+    def from_depth_device(cls, ctx, d_depth, depth_stride, d_color, color_stride, params, out=None):
+        """from_depth with the two images already in HBM (rsreg_cloud_from_depth_device): device addresses (ints) and row
+        strides in bytes; nothing crosses the link.  The context is synchronized before this returns, so the images may go."""
+        ctx = ctx or default_context()
+        dev = out if out is not None else cls(ctx=ctx)
+        rc = _l.lib().rsreg_cloud_from_depth_device(ctx.h, int(d_depth), int(depth_stride), int(d_color), int(color_stride), C.byref(params), dev.h)
+        if rc == 0:
+            rc = _l.lib().rsreg_ctx_synchronize(ctx.h)
+        if rc and out is None:
+            dev.close()
+        _l.check(rc, ctx.h)
+        return dev
+
     def download_normals(self):
         """download() of a cloud of pcl::Normal records (what NormalEstimation.compute returns): a NormalCloud."""
         n, stride, w, h, dense = self.info()
@@ -338,6 +366,109 @@ def iin_params(**kw):
             v = (C.c_float * 3)(*[float(x) for x in v])
         setattr(p, k, v)
     return p
+
+
+def _depth_image(a):
+    """(keepalive, pointer, row stride in bytes) of an (h, w) uint16 image; rows may be padded"""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype.kind not in "ui" or a.dtype.itemsize != 2:
+        raise ValueError("the depth image must be an (h, w) uint16 array")
+    if a.shape[0] > 1 and (a.strides[1] != 2 or a.strides[0] < 2 * a.shape[1]) or a.shape[0] <= 1 and not a.flags.c_contiguous:
+        a = np.ascontiguousarray(a)
+    return a, a.ctypes.data, (a.strides[0] if a.shape[0] > 1 else 2 * a.shape[1])
+
+
+def _color_image(a):
+    """(keepalive, pointer, row stride in bytes) of an (h, w, 3 or 4) uint8 image; rows may be padded"""
+    a = np.asarray(a)
+    if a.ndim != 3 or a.dtype != np.uint8 or a.shape[2] not in (3, 4):
+        raise ValueError("the colour image must be an (h, w, 3 or 4) uint8 array")
+    bpp = a.shape[2]
+    if a.shape[0] > 1 and (a.strides[2] != 1 or a.strides[1] != bpp or a.strides[0] < bpp * a.shape[1]) or a.shape[0] <= 1 and not a.flags.c_contiguous:
+        a = np.ascontiguousarray(a)
+    return a, a.ctypes.data, (a.strides[0] if a.shape[0] > 1 else bpp * a.shape[1])
+
+
+def _set_intrinsics(s, width, height, ppx, ppy, fx, fy, model=0, coeffs=(0, 0, 0, 0, 0)):
+    s.width, s.height, s.ppx, s.ppy, s.fx, s.fy, s.model = int(width), int(height), float(ppx), float(ppy), float(fx), float(fy), int(model)
+    for i in range(5):
+        s.coeffs[i] = float(coeffs[i])
+
+
+def depth_params(w, h, reference=False, depth=None, color=None, rotation=None, translation=None, **kw):
+    """rsreg_depth_params for a w x h depth frame: the whole frame (convert_to_pcl_new), or with reference=True the reference's
+    three-fifths centre crop (convert_to_pcl).  depth / color: dicts of width, height, ppx, ppy, fx, fy[, model, coeffs];
+    rotation: 9 floats column-major, translation: 3; any other field of the struct by name."""
+    p = _l.DepthParams()
+    (_l.lib().rsreg_depth_params_reference if reference else _l.lib().rsreg_depth_params_default)(int(w), int(h), C.byref(p))
+    if depth is not None:
+        _set_intrinsics(p.depth, **depth)
+    if color is not None:
+        _set_intrinsics(p.color, **color)
+    if rotation is not None:
+        p.rotation = (C.c_float * 9)(*[float(v) for v in rotation])
+    if translation is not None:
+        p.translation = (C.c_float * 3)(*[float(v) for v in translation])
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class DepthToCloud:
+    """The capture step: rs2::pointcloud (map_to, calculate) + the reference's convert_to_pcl (src/capture.hpp:72-107; the whole
+    frame: convert_to_pcl_new, src/capture_opencv.hpp:128-160) from a depth and a colour image (include/rsreg.h, "capture",
+    states the contract).  With a context the cloud is built in HBM from the two images (rsreg_cloud_from_depth) and
+    compute() returns a DeviceCloud; without one it runs the sequential host restatement (rsreg_depth_to_cloud) and returns a
+    PointCloud: the same bytes from both."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx
+        self._depth = self._color = None
+        self._rotation, self._translation = (1, 0, 0, 0, 1, 0, 0, 0, 1), (0, 0, 0)
+        self._scale, self._bpp, self._bgr, self._crop = 0.001, 3, True, False
+
+    def setDepthIntrinsics(self, width, height, ppx, ppy, fx, fy, model=0, coeffs=(0, 0, 0, 0, 0)):
+        self._depth = dict(width=width, height=height, ppx=ppx, ppy=ppy, fx=fx, fy=fy, model=model, coeffs=tuple(coeffs))
+
+    def setColorIntrinsics(self, width, height, ppx, ppy, fx, fy, model=0, coeffs=(0, 0, 0, 0, 0)):
+        self._color = dict(width=width, height=height, ppx=ppx, ppy=ppy, fx=fx, fy=fy, model=model, coeffs=tuple(coeffs))
+
+    def setExtrinsics(self, rotation, translation):
+        """depth -> colour (rs2_extrinsics): rotation 9 floats column-major, translation 3 (metres)"""
+        self._rotation, self._translation = tuple(float(v) for v in rotation), tuple(float(v) for v in translation)
+
+    def setDepthScale(self, scale):
+        self._scale = float(scale)
+
+    def setColorLayout(self, bytes_per_pixel=3, bgr=True):
+        self._bpp, self._bgr = int(bytes_per_pixel), bool(bgr)
+
+    def setReferenceCrop(self, on):
+        """True: the reference's three-fifths centre crop with its shape and is_dense = 1 (convert_to_pcl); False: the frame"""
+        self._crop = bool(on)
+
+    def params(self, depth_shape, color_shape):
+        """the rsreg_depth_params compute() uses for images of these shapes (an intrinsics that was not set: the placeholder)"""
+        h, w = (self._depth["height"], self._depth["width"]) if self._depth else depth_shape[:2]
+        color = self._color
+        if color is None and tuple(color_shape[:2]) != (h, w):
+            ch, cw = color_shape[:2]
+            color = dict(width=cw, height=ch, ppx=cw / 2, ppy=ch / 2, fx=cw, fy=cw)
+        return depth_params(w, h, reference=self._crop, depth=self._depth, color=color, rotation=self._rotation, translation=self._translation,
+                            depth_scale=self._scale, color_bytes_per_pixel=self._bpp, color_bgr=int(self._bgr))
+
+    def compute(self, depth, color, out=None):
+        p = self.params(depth.shape, color.shape)
+        if tuple(depth.shape[:2]) != (p.depth.height, p.depth.width) or tuple(color.shape) != (p.color.height, p.color.width, p.color_bytes_per_pixel):
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "the images do not have the shapes of the intrinsics and the colour layout")
+        if self.ctx is not None:
+            return DeviceCloud.from_depth(self.ctx, depth, color, p, out=out)
+        (keep_d, d_ptr, d_stride), (keep_c, c_ptr, c_stride) = _depth_image(depth), _color_image(color)
+        n = p.out_width * p.out_height
+        pts = np.zeros(n, POINT_DTYPE)
+        w, h, dense = C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+        _l.check(_l.lib().rsreg_depth_to_cloud(d_ptr, d_stride, c_ptr, c_stride, C.byref(p), pts.ctypes.data, n, C.byref(w), C.byref(h), C.byref(dense)))
+        return PointCloud(pts, width=w.value, height=h.value, is_dense=bool(dense.value))
 
 
 def _own_alignment(reg, owns):

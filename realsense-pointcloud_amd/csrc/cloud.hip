@@ -482,6 +482,24 @@ int rsreg_cloud_adopt_(rsreg_cloud *c, DevBuf *buf, size_t n, size_t stride, uin
     return RSREG_OK;
 }
 
+// (internal: depthcloud.hip) a kernel on the context's stream is about to write n records of `stride` bytes straight into
+// `c`: what rsreg_cloud_upload does before its copy, and after it
+int rsreg_cloud_begin_write_(rsreg_cloud *c, size_t n, size_t stride, void **d_records)
+{
+    rsreg_ctx *ctx = c->ctx;
+    RSREG_HIP(ctx, settle(c));
+    RSREG_HIP(ctx, cloud_reserve(ctx, c->buf, n * stride + 16));
+    *d_records = c->buf.ptr;
+    return RSREG_OK;
+}
+
+int rsreg_cloud_end_write_(rsreg_cloud *c, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense)
+{
+    c->version++;
+    c->n = n; c->stride = stride; c->width = width; c->height = height; c->is_dense = is_dense;
+    return RSREG_OK;
+}
+
 int rsreg_cloud_copy(rsreg_ctx *ctx, const rsreg_cloud *in, rsreg_cloud *out)
 {
     int rc = check_pair(ctx, in, out);

@@ -202,6 +202,13 @@ struct IinScratch {
     PinnedBuf host;                     // the window sizes on their way to the caller
 };
 
+// Scratch of the capture step (depthcloud.hip): the depth and the colour image of one frame, in one piece
+struct DepthScratch {
+    PinnedBuf host;      // staged for the link ...
+    DevBuf d_images;     // ... and in HBM, where the kernel reads them
+    Event ev_up;         // behind the copy: the staging buffer is free again
+};
+
 struct IcpState {
     rsreg_icp_params prm;
     Mat4f final_t, t_inc;
@@ -443,6 +450,9 @@ struct rsreg_ctx {
 
     // ---- IntegralImageNormalEstimation (iinormals.hip)
     rsreg::IinScratch iin;
+
+    // ---- capture: depth + colour images -> cloud (depthcloud.hip)
+    rsreg::DepthScratch depth;
 };
 
 namespace rsreg {

@@ -16,13 +16,15 @@ ROOT = os.path.dirname(_HERE)
 DIAG = os.environ.get("RSREG_DIAG", "") == "1"
 SO_PATH = (os.environ.get("RSREG_SO") if DIAG else None) or os.path.join(_HERE, "librsreg_diag.so" if DIAG else "librsreg.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip"]
+SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip", "depthcloud.hip", "depth_host.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) if os.path.isdir(CSRC) else []
 NUM_SUMS = 17
 NUM_PLANE_SUMS = 32                                      # include/rsreg.h: RSREG_NUM_PLANE_SUMS
 ESTIMATION_SVD, ESTIMATION_POINT_TO_PLANE_LLS = 0, 1     # include/rsreg.h: rsreg_estimation
 IIN_COVARIANCE_MATRIX, IIN_AVERAGE_3D_GRADIENT, IIN_AVERAGE_DEPTH_CHANGE, IIN_SIMPLE_3D_GRADIENT = 0, 1, 2, 3   # rsreg_iin_method
 IIN_BORDER_IGNORE, IIN_BORDER_MIRROR = 0, 1              # rsreg_iin_border_policy
+# rsreg_distortion (rs2_distortion)
+DISTORTION_NONE, DISTORTION_MODIFIED_BROWN_CONRADY, DISTORTION_INVERSE_BROWN_CONRADY, DISTORTION_FTHETA, DISTORTION_BROWN_CONRADY, DISTORTION_KANNALA_BRANDT4 = range(6)
 RSREG_ERR_INVALID_ARG, RSREG_ERR_STATE = -1, -9   # include/rsreg.h: rsreg_status
 UNIQUE_ID_BYTES = 128
 
@@ -49,6 +51,7 @@ EXPORTS = [
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
     "rsreg_iin_params_default", "rsreg_cloud_integral_normals",
     "rsreg_voxel_grid_params_default", "rsreg_voxel_grid", "rsreg_voxel_grid_gpu", "rsreg_cloud_voxel_grid",
+    "rsreg_depth_params_default", "rsreg_depth_params_reference", "rsreg_depth_to_cloud", "rsreg_cloud_from_depth", "rsreg_cloud_from_depth_device",
 ]
 
 
@@ -101,6 +104,18 @@ class VoxelGridParams(C.Structure):   # rsreg_voxel_grid_params
 class VoxelGridInfo(C.Structure):   # rsreg_voxel_grid_info
     _fields_ = [("min_b", C.c_int32 * 3), ("max_b", C.c_int32 * 3), ("div_b", C.c_int32 * 3), ("divb_mul", C.c_int32 * 3),
                 ("n_finite", C.c_uint64), ("n_leaves", C.c_uint64), ("n_out", C.c_uint64), ("overflowed", C.c_int32)]
+
+
+class Intrinsics(C.Structure):   # rsreg_intrinsics (rs2_intrinsics)
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ppx", C.c_float), ("ppy", C.c_float), ("fx", C.c_float), ("fy", C.c_float),
+                ("model", C.c_int32), ("coeffs", C.c_float * 5)]
+
+
+class DepthParams(C.Structure):   # rsreg_depth_params
+    _fields_ = [("depth", Intrinsics), ("color", Intrinsics), ("rotation", C.c_float * 9), ("translation", C.c_float * 3),
+                ("depth_scale", C.c_float), ("color_bytes_per_pixel", C.c_int32), ("color_bgr", C.c_int32),
+                ("r0", C.c_int32), ("r1", C.c_int32), ("c0", C.c_int32), ("c1", C.c_int32),
+                ("out_width", C.c_uint32), ("out_height", C.c_uint32), ("is_dense", C.c_int32), ("reserved", C.c_uint32 * 2)]
 
 
 class NdtResult(C.Structure):
@@ -299,6 +314,12 @@ def lib():
     L.rsreg_voxel_grid.argtypes = [vp, sz, sz, vp, i32, u32, vp, C.POINTER(sz), C.POINTER(VoxelGridInfo)]
     L.rsreg_voxel_grid_gpu.argtypes = [vp, vp, sz, sz, C.POINTER(VoxelGridParams), vp, C.POINTER(sz), C.POINTER(VoxelGridInfo)]
     L.rsreg_cloud_voxel_grid.argtypes = [vp, vp, C.POINTER(VoxelGridParams), vp, C.POINTER(VoxelGridInfo)]
+    for f in ("rsreg_depth_params_default", "rsreg_depth_params_reference"):
+        getattr(L, f).argtypes = [u32, u32, C.POINTER(DepthParams)]
+        getattr(L, f).restype = None
+    L.rsreg_depth_to_cloud.argtypes = [vp, sz, vp, sz, C.POINTER(DepthParams), vp, sz, C.POINTER(u32), C.POINTER(u32), C.POINTER(i32)]
+    L.rsreg_cloud_from_depth.argtypes = [vp, vp, sz, vp, sz, C.POINTER(DepthParams), vp]
+    L.rsreg_cloud_from_depth_device.argtypes = [vp, vp, sz, vp, sz, C.POINTER(DepthParams), vp]
     L.rsreg_cloud_concat.argtypes = [vp, vp, vp, vp]
     L.rsreg_icp_set_target_cloud.argtypes = [vp, vp, dbl]
     L.rsreg_icp_target_is_cloud.argtypes = [vp, vp, dbl]
