@@ -12,11 +12,12 @@
 //   k_cc_scan     one pass over the counts (what lies in front of a workgroup's span comes from per-span totals the
 //                 counting kernel has left: no look-back): first record of every cell, the occupied cells in slot
 //                 order, and the counts back to zero for the next build;
-//   k_cc_scatter  record -> first record of its cell + its rank, in arrival order;
-//   k_cc_small    cells of at most 48 records, one lane per record: its place is the number of the cell's records with a
-//                 smaller (x position, original index);
-//   k_cc_big      crowded cells, one wave per cell: a counting sort of its own over 256 x buckets in LDS.
-// followed by k_dense_nbr as before.  It replaces keys + 2 histogram launches + 4 onesweep passes + k_dense_compact of
+//   k_cc_scatter  record -> first record of its cell + its rank, in arrival order (k_cc_scatter_nbr: the same launch also
+//                 makes the occupancy words, k_dense_nbr's work, where the index has them);
+//   k_cc_small_big  the in-cell order, in one launch: cells of at most 48 records, one lane per record: its place is the
+//                 number of the cell's records with a smaller (x position, original index) (cc_small_body); crowded cells,
+//                 one wave per cell: a counting sort of its own over 256 x buckets in LDS (cc_big_body).
+// It replaces keys + 2 histogram launches + 4 onesweep passes + k_dense_compact of
 // the sort-based build (9 launches; still there for grids too large to scan and as RSREG_COUNT_SORT=0), uses no sort of
 // any library, and moves every record twice instead of five times.
 // Exact copies: the sort-based build drops a record that equals its predecessor in sorted order; this one drops the
@@ -31,7 +32,7 @@ namespace rsreg {
 
 constexpr unsigned kCcBlock = 1024, kCcItems = 4, kCcTile = kCcBlock * kCcItems, kCcHash = 8192;
 constexpr uint32_t kCcDropped = 0xffffffffu, kCcEmpty = 0xffffffffu;
-constexpr uint32_t kCcSmall = 48;        // cells up to this many records: one lane per record (k_cc_small), beyond: one wave per cell
+constexpr uint32_t kCcSmall = 48;        // cells up to this many records: one lane per record (cc_small_body), beyond: one wave per cell
 constexpr uint32_t kCcXBits = 8;         // x buckets per cell the crowded cells are ordered by (and g.x_slack is set for)
 constexpr unsigned kCcScanItems = 16;    // table entries per thread of k_cc_scan: 16 384 per workgroup, all workgroups resident at 7 M cells
 
@@ -239,7 +240,7 @@ __global__ __launch_bounds__(kCcScanBlock) void k_cc_scan(uint32_t *gcnt, uint32
                 table[slots] = nrec;
             }
         }
-        // the crowded cells (k_cc_big takes them one wave each) are listed in any order: a wave pools its own and takes one
+        // the crowded cells (cc_big_body takes them one wave each) are listed in any order: a wave pools its own and takes one
         // place in the list for all of them (same-address atomics from every thread would queue up behind each other)
         uint32_t nb = 0;
 #pragma unroll
@@ -293,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_scatter(const char *pts, size_t s
 
 // k_cc_scatter and k_dense_nbr need k_cc_scan's results and nothing of each other: ONE launch, the occupancy words'
 // workgroups (the longer job: scattered atomics) in front.  Round 6: the build is count, scan, this, k_cc_small_big -- four
-// dependent launches where it had six (RSREG_CC_APART=1: the six).
+// dependent launches where it had six.
 __global__ __launch_bounds__(kBlock) void k_cc_scatter_nbr(const char *pts, size_t stride, uint32_t n, DenseDev g, const uint32_t *rank, const uint32_t *table,
                                                            float4 *arrived, uint32_t nbr_blocks, const uint32_t *cellslot, const uint32_t *stats, uint32_t *occ)
 {
@@ -302,7 +303,7 @@ __global__ __launch_bounds__(kBlock) void k_cc_scatter_nbr(const char *pts, size
 }
 
 // One lane per record of the arrival-order array, for the cells of at most kCcSmall records: the record belongs behind the
-// cell's records with a smaller (x position to 16 bits, original index).  Records of crowded cells are k_cc_big's.
+// cell's records with a smaller (x position to 16 bits, original index).  Records of crowded cells are cc_big_body's.
 // pos_of: original index -> position.
 __device__ __forceinline__ void cc_small_body(uint32_t bid, const float4 *arrived, const DenseDev &g, const uint32_t *table, float4 *sorted, uint32_t *pos_of,
                                               const uint32_t *stats)
@@ -328,12 +329,6 @@ __device__ __forceinline__ void cc_small_body(uint32_t bid, const float4 *arrive
     }
     sorted[s + before] = me;
     pos_of[idx] = s + before;
-}
-
-__global__ __launch_bounds__(kBlock) void k_cc_small(const float4 *arrived, DenseDev g, const uint32_t *table, float4 *sorted, uint32_t *pos_of,
-                                                     const uint32_t *stats)
-{
-    cc_small_body(blockIdx.x, arrived, g, table, sorted, pos_of, stats);
 }
 
 // The crowded cells (more than kCcSmall records: `big`, k_cc_scan's list), one wave per cell: count the cell's records per
@@ -381,12 +376,6 @@ __device__ __forceinline__ void cc_big_body(uint32_t bid, uint32_t nblocks, cons
         }
         __builtin_amdgcn_wave_barrier();
     }
-}
-
-__global__ __launch_bounds__(kBlock) void k_cc_big(const float4 *arrived, DenseDev g, const uint32_t *table, const uint32_t *big, float4 *sorted,
-                                                   uint32_t *pos_of, const uint32_t *stats)
-{
-    cc_big_body(blockIdx.x, gridDim.x, arrived, g, table, big, sorted, pos_of, stats);
 }
 
 // The in-cell order of the small cells and of the crowded ones touch different records: ONE launch, the crowded cells'

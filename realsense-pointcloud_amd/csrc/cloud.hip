@@ -410,8 +410,7 @@ int rsreg_cloud_upload_async(rsreg_cloud *c, const void *points, size_t n, size_
 // aligned, and the 0.2 ms it takes to stage a frame no longer sit on the caller's thread with the GPU idle.
 int rsreg_cloud_upload_deferred(rsreg_cloud *c, const void *points, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense)
 {
-    const bool on_caller = rsreg::tunables().upload_wait_staged;   // (dev: A/B)
-    return upload_on_worker(c, points, n, stride, width, height, is_dense, on_caller);
+    return upload_on_worker(c, points, n, stride, width, height, is_dense, false);
 }
 
 int rsreg_cloud_download(const rsreg_cloud *c, void *out, size_t capacity)
@@ -553,7 +552,7 @@ int side_begin(rsreg_ctx *ctx, int follow, int *worker_out, int *set_out)
 {
     int worker = follow;
     if (worker < 0) {
-        worker = tunables().one_side_worker ? 0 : ctx->side_rr;
+        worker = ctx->side_rr;
         ctx->side_rr = (ctx->side_rr + 1) % rsreg_ctx::kSideWorkers;
     }
     const int set = worker + rsreg_ctx::kSideWorkers * ctx->side_turn[worker];

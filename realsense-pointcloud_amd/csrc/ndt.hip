@@ -67,9 +67,10 @@ void gauss_constants(const rsreg_ndt_params &prm, double &d1, double &d2)
 
 void angle_terms(const double *p, NdtPassParams &pp) { ndt_angle_terms(p, pp.jang, pp.hang); }
 
-constexpr int kNdtLsOffset = 64;   // h_ndt, in doubles: where a finished resident line search leaves its NdtLs (behind the sums and the flag)
-constexpr size_t kNdtHostBytes = (kNdtLsOffset + 16) * 8 + sizeof(NdtLs) + sizeof(NdtLsCtl) + 64;   // sums, flag | NdtLs | the staged NdtLsCtl
-constexpr int kNdtFlagSlot = 32;  // h_ndt: 28 sums, then the pass number the final reduce stamps
+constexpr int kNdtFlagSlot = 32;  // h_ndt, in doubles: 28 sums, then the pass number the final reduce stamps
+constexpr size_t kNdtHostBytes = (kNdtFlagSlot + 1) * 8;   // the sums and the flag; rsreg_ndt_set_target_device borrows the head for its box words
+static_assert(kNdtAcc <= kNdtFlagSlot && (kNdtFlagSlot + 1) * 8 <= kNdtHostBytes && kCounterWords * sizeof(uint32_t) <= kNdtHostBytes,
+              "h_ndt: the flag slot lies behind the sums and inside the buffer, and so do the box words");
 
 // partial sums of a pass + the counter the final reduce counts its workgroups on (zero between passes)
 hipError_t reserve_partials(rsreg_ctx *ctx)
@@ -117,23 +118,13 @@ int derivative_pass_pp(NdtRun &r, NdtPassParams &pp, bool store_trans)
     uint32_t *ticket = reinterpret_cast<uint32_t *>(ctx->d_ndt_partials.as<double>() + (size_t)kPassBlocks * kNdtAcc);
     // one GPU: the 28 sums go straight into the pinned host buffer (no copy to queue behind the kernel)
     double *sums_out = ctx->comm ? ctx->d_ndt_out.as<double>() : h;
-    if (tunables().ndt_one_launch && kPassBlocks == 2 * kNdtBlock) {   // (k_ndt_pass_reduce adds slab t and slab t + 256)
-        // the pass and its final reduce in one launch: the workgroup that finishes last adds the slabs (same tree, same bits; measured
-        // 8 us per pass slower than the launch pair below -- round 6, as round 2's form was: opt-in)
-        k_ndt_pass_reduce<<<kPassBlocks, kNdtBlock, 0, ctx->stream>>>(ctx->d_ndt_src.as<float4>(), r.n, ctx->d_ndt_vox.as<NdtVoxel>(), pp,
-                                                                      store_trans ? ctx->d_ndt_trans.as<float>() : nullptr,
-                                                                      ctx->d_ndt_partials.as<double>(), sums_out, ticket,
-                                                                      watch ? const_cast<uint64_t *>(flag) : nullptr, seq);
-        RSREG_HIP(ctx, hipGetLastError());
-    } else {
-        k_ndt_pass<<<kPassBlocks, kNdtBlock, 0, ctx->stream>>>(ctx->d_ndt_src.as<float4>(), r.n, ctx->d_ndt_vox.as<NdtVoxel>(), pp,
-                                                               store_trans ? ctx->d_ndt_trans.as<float>() : nullptr,
-                                                               ctx->d_ndt_partials.as<double>());
-        RSREG_HIP(ctx, hipGetLastError());
-        k_ndt_final_reduce<<<kNdtAcc, kNdtBlock, 0, ctx->stream>>>(ctx->d_ndt_partials.as<double>(), kPassBlocks, sums_out, ticket,
-                                                                   watch ? const_cast<uint64_t *>(flag) : nullptr, seq);
-        RSREG_HIP(ctx, hipGetLastError());
-    }
+    k_ndt_pass<<<kPassBlocks, kNdtBlock, 0, ctx->stream>>>(ctx->d_ndt_src.as<float4>(), r.n, ctx->d_ndt_vox.as<NdtVoxel>(), pp,
+                                                           store_trans ? ctx->d_ndt_trans.as<float>() : nullptr,
+                                                           ctx->d_ndt_partials.as<double>());
+    RSREG_HIP(ctx, hipGetLastError());
+    k_ndt_final_reduce<<<kNdtAcc, kNdtBlock, 0, ctx->stream>>>(ctx->d_ndt_partials.as<double>(), kPassBlocks, sums_out, ticket,
+                                                               watch ? const_cast<uint64_t *>(flag) : nullptr, seq);
+    RSREG_HIP(ctx, hipGetLastError());
     if (ctx->profiling) (void)hipEventRecord(e1, ctx->stream);
     if (ctx->comm) {   // also on a one-rank communicator: same calls, same stream order
         int rc = rsreg_comm_allreduce_device_(ctx, ctx->d_ndt_out.as<double>(), kNdtAcc);
@@ -187,83 +178,20 @@ int derivative_pass(NdtRun &r, const double *p, const Mat4f &M, int mode, bool s
     return RSREG_OK;
 }
 
-// Can the 512 workgroups of k_ndt_line_search be resident together on this device?  (They wait for each other inside the launch.)
-bool line_search_fits(rsreg_ctx *ctx)
-{
-    static int fits[64] = {0};   // per device: 0 unknown, 1 yes, -1 no
-    int &f = fits[ctx->device & 63];
-    if (f == 0) {
-        int per_cu = 0, cus = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ndt_line_search, kNdtBlock, 0) == hipSuccess &&
-            hipGetDeviceProperties(&prop, ctx->device) == hipSuccess)
-            cus = prop.multiProcessorCount;
-        f = (long long)per_cu * cus >= kPassBlocks ? 1 : -1;
-    }
-    return f > 0;
-}
-
 // computeStepLengthMT (More-Thuente): the state machine of ndt_math.hpp, advanced by the host, a launch pair and a wait per
-// pass.  RSREG_NDT_RESIDENT_LS=1 (one GPU, no profiling): all the passes of the search in ONE launch (k_ndt_line_search,
-// which advances the machine itself) -- the same source on the same sums in the same order, the same bits
-// (tests/test_ndt_gpu.py), and measured no faster: a hand-over between workgroups of different XCDs costs what a kernel
-// boundary costs, so it is not the default.
+// pass (all the passes of a search in one resident launch were measured no faster: DESIGN.md §5e).
 int step_length(NdtRun &r, const double *x, double *dir, double step_init, double step_max, double step_min,
                 double &score, double *grad, double *hess, double &a_out)
 {
     rsreg_ctx *ctx = r.ctx;
     NdtLs ls;
     ndt_ls_begin(ls, x, dir, step_init, step_max, step_min, score, grad, hess);
-    const bool host_only = !tunables().ndt_resident_ls;
-    bool resident = ls.phase != kNdtLsDone && !host_only && !ctx->comm && !ctx->profiling && !ctx->ndt_ls_failed && line_search_fits(ctx);
-    if (resident) {
-        RSREG_HIP(ctx, ctx->d_ndt_ctl.reserve(sizeof(NdtLsCtl) + 64));
-        RSREG_HIP(ctx, ctx->h_ndt.reserve(kNdtHostBytes));
-        double *h = ctx->h_ndt.as<double>();
-        volatile uint64_t *flag = reinterpret_cast<volatile uint64_t *>(h + kNdtFlagSlot);
-        NdtLs *host_out = reinterpret_cast<NdtLs *>(h + kNdtLsOffset);
-        NdtLsCtl *stage = reinterpret_cast<NdtLsCtl *>(h + kNdtLsOffset + (sizeof(NdtLs) + 7) / 8 + 8);
-        std::memset(stage, 0, sizeof(NdtLsCtl));
-        stage->ls = ls;
-        stage->pp.d1 = r.d1;
-        stage->pp.d2 = r.d2;
-        stage->pp.r2 = (float)(r.prm.resolution * r.prm.resolution);
-        stage->pp.n_vox = ctx->ndt_n_voxels;
-        ndt_fill_pass(stage->pp, ls);
-        stage->release = 1;   // the first pass may start
-        const uint64_t seq = ++ctx->ndt_seq;
-        *flag = 0;
-        RSREG_HIP(ctx, hipMemcpyAsync(ctx->d_ndt_ctl.ptr, stage, sizeof(NdtLsCtl), hipMemcpyHostToDevice, ctx->stream));
-        k_ndt_line_search<<<kPassBlocks, kNdtBlock, 0, ctx->stream>>>(ctx->d_ndt_src.as<float4>(), r.n, ctx->d_ndt_vox.as<NdtVoxel>(), ctx->d_ndt_ctl.as<NdtLsCtl>(),
-                                                                    ctx->d_ndt_trans.as<float>(), ctx->d_ndt_partials.as<double>(), host_out,
-                                                                    const_cast<uint64_t *>(flag), seq);
-        RSREG_HIP(ctx, hipGetLastError());
-        // the outcome lands in pinned memory, the launch's number behind it; a stream query now and then notices a fault or a time-out
-        for (uint32_t spins = 1; *flag != seq; ++spins)
-            if ((spins & 0xFFFFu) == 0 && hipStreamQuery(ctx->stream) != hipErrorNotReady) break;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (*flag != seq) {
-            RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
-        if (*flag == seq) {
-            std::memcpy(&ls, host_out, sizeof(NdtLs));
-            r.passes += ls.passes;
-        } else {
-            // (a bounded wait inside the launch ran out: not again on this context; this search pass by pass, from its start)
-            ctx->ndt_ls_failed = true;
-            resident = false;
-            ndt_ls_begin(ls, x, dir, step_init, step_max, step_min, score, grad, hess);
-        }
-    }
-    if (!resident) {
-        while (ls.phase != kNdtLsDone) {
-            NdtPassParams pp;
-            ndt_fill_pass(pp, ls);
-            int rc = derivative_pass_pp(r, pp, ls.next_mode != 2);
-            if (rc) return rc;
-            ndt_ls_consume(ls, ctx->h_ndt.as<double>());
-        }
+    while (ls.phase != kNdtLsDone) {
+        NdtPassParams pp;
+        ndt_fill_pass(pp, ls);
+        int rc = derivative_pass_pp(r, pp, ls.next_mode != 2);
+        if (rc) return rc;
+        ndt_ls_consume(ls, ctx->h_ndt.as<double>());
     }
     for (int i = 0; i < 6; ++i) dir[i] = ls.dir[i];
     if (ls.passes) r.final_t = pose_matrix(ls.x_t);

@@ -2,14 +2,13 @@
 // for the host and the device (ndt_edge_based_registration.hpp:38-43,86-92: setStepSize / setTransformationEpsilon, align).
 //
 // PCL's computeStepLengthMT (More-Thuente) evaluates the score and its gradient at a sequence of trial steps, each a
-// derivative pass over the source cloud, each depending on the one before.  With the control on the host every pass
-// costs a round trip (launch, completion seen through pinned memory, a few microseconds of arithmetic, launch): 17 us on
-// top of 19 us of kernels.  The line search is therefore a small state machine (NdtLs) that one thread advances -- on the
-// host, or on the device at the end of a pass's final reduce, so that the trials of one line search are queued back to
-// back and the host looks in once per Newton iteration (the 6 x 6 SVD of the Newton step stays on the host: a Jacobi SVD
-// of that size is tens of microseconds of dependent f64 on one GPU lane).  Host and device run this very source with
-// -ffp-contract=off: f64 + - * / sqrt, comparisons, and the sine / cosine below instead of the platforms' libm (whose
-// last bits differ) -- the two give the same bits.
+// derivative pass over the source cloud, each depending on the one before.  The line search is a small state machine
+// (NdtLs) that the host advances between the passes (ndt.hip: step_length): a launch pair, the 28 sums seen through
+// pinned memory, a few microseconds of arithmetic, the next launch pair.  (A controller on the device that advanced the
+// machine inside one resident launch was built and measured no faster: DESIGN.md §5e.  The 6 x 6 SVD of the Newton step
+// is the host's in any case.)  The source compiles for the host and the device with -ffp-contract=off: f64 + - * / sqrt,
+// comparisons, and the sine / cosine below instead of the platforms' libm (whose last bits differ) -- the two give the
+// same bits.
 #pragma once
 
 #include <cmath>

@@ -27,9 +27,7 @@ struct Tunables {
     bool adaptive_cell = true;             // RSREG_NO_ADAPTIVE_CELL=1: the brick-hash build never refines its cell size
     bool box_cache = true;                 // RSREG_NO_BOX_CACHE=1: a cloud handle's bounding box is measured by every build / load
     bool count_sort = true;                // RSREG_COUNT_SORT=0: the index by sorting (k_dense_keys, radix sort, k_dense_compact) instead of counting (cellsort.hpp)
-    bool one_side_worker = false;          // RSREG_ONE_SIDE_WORKER=1: the side jobs of a context (filters, edge extractions of the frames ahead) on one thread as in rounds 3-5 (default: two, alternating)
     bool nbr_from_table = true;            // RSREG_NO_NBR_FROM_TABLE=1: the counting build makes the occupancy words for a small source too (default: left out when the gate fits into ring 1, the search reads them off the cell table)
-    bool cc_apart = false;                 // RSREG_CC_APART=1: the counting build's scatter / occupancy words / small cells / crowded cells as four launches (rounds 5; default: two)
     bool scan_apart = false;               // RSREG_SCAN_APART=1: sort-based build: flag, scan, scatter as three launches
     // ---- source
     bool sort_small = false;               // RSREG_SORT_SMALL=1: sources of <= 65 536 points are put into spatial order too
@@ -37,7 +35,6 @@ struct Tunables {
     int morton_bits = 23;                  // RSREG_MORTON_BITS: bits of the source's Morton keys (+ the invalid bit: three digit passes)
     bool worker = true;                    // RSREG_NO_WORKER=1: the source load's host side on the caller's thread
     bool seed = true;                      // RSREG_NO_SEED=1: searches never start from the previous iteration's match
-    bool restart_apart = false;            // RSREG_RESTART_APART=1: guess * source as a launch of its own
     bool scan_target = true;               // RSREG_NO_SCAN: an index even for a handful of source points
     // ---- tile schedule of the fused search kernel
     bool sched = true;                     // RSREG_SCHED=0
@@ -49,10 +46,7 @@ struct Tunables {
     bool sched_keep = true;                // RSREG_SCHED_KEEP=0: every alignment times a launch of its own and builds its own schedule
     // ---- clouds, NDT
     long long cloud_pool_mb = 4096;        // RSREG_CLOUD_POOL_MB
-    bool upload_wait_staged = false;       // RSREG_UPLOAD_WAIT_STAGED=1
     bool ndt_watch = true;                 // RSREG_NDT_NO_WATCH: hipStreamSynchronize instead of watching the stamped pass number
-    bool ndt_one_launch = false;           // RSREG_NDT_ONE_LAUNCH=1: a derivative pass as ONE launch whose last workgroup adds the slabs (k_ndt_pass_reduce; same bits, 8 us per pass SLOWER: DESIGN.md §5f) instead of k_ndt_pass + k_ndt_final_reduce
-    bool ndt_resident_ls = false;          // RSREG_NDT_RESIDENT_LS=1: all the passes of a line search in one launch (k_ndt_line_search; same bits, not faster: DESIGN.md §5e)
 #ifdef RSREG_DIAG
     const char *dump_seed = nullptr, *wave_times = nullptr, *edge_dump = nullptr;   // RSREG_DUMP_SEED, RSREG_WAVE_TIMES, RSREG_EDGE_DUMP: files
     bool wave_times_light = false, dump_nn_ms = false, sched_verbose = false, grid_stats = false;
@@ -78,16 +72,13 @@ template <typename Get> inline Tunables tunables_read(Get get)
     v.adaptive_cell = !on("RSREG_NO_ADAPTIVE_CELL");
     v.box_cache = !on("RSREG_NO_BOX_CACHE");
     v.count_sort = !off("RSREG_COUNT_SORT");
-    v.cc_apart = on("RSREG_CC_APART");
     v.nbr_from_table = !on("RSREG_NO_NBR_FROM_TABLE");
-    v.one_side_worker = on("RSREG_ONE_SIDE_WORKER");
     v.scan_apart = on("RSREG_SCAN_APART");
     v.sort_small = on("RSREG_SORT_SMALL");
     if (const char *e = get("RSREG_PLAIN_SOURCE_MAX")) v.plain_source_max = (size_t)std::atoll(e);
     if (const char *e = get("RSREG_MORTON_BITS")) v.morton_bits = std::max(6, std::min(31, std::atoi(e)));
     v.worker = !on("RSREG_NO_WORKER");
     v.seed = !on("RSREG_NO_SEED");
-    v.restart_apart = on("RSREG_RESTART_APART");
     v.scan_target = !set("RSREG_NO_SCAN");
     v.sched = !off("RSREG_SCHED");
     if (const char *e = get("RSREG_SCHED_F4")) v.sched_f4 = std::atof(e);
@@ -100,10 +91,7 @@ template <typename Get> inline Tunables tunables_read(Get get)
     if (const char *e = get("RSREG_SCHED_XCD_DEAL")) v.sched_xcd_deal = (uint32_t)std::atoi(e);
     v.sched_keep = !off("RSREG_SCHED_KEEP");
     if (const char *e = get("RSREG_CLOUD_POOL_MB")) v.cloud_pool_mb = std::max(0ll, std::atoll(e));
-    v.upload_wait_staged = on("RSREG_UPLOAD_WAIT_STAGED");
     v.ndt_watch = !set("RSREG_NDT_NO_WATCH");
-    v.ndt_one_launch = on("RSREG_NDT_ONE_LAUNCH");
-    v.ndt_resident_ls = on("RSREG_NDT_RESIDENT_LS");
 #ifdef RSREG_DIAG
     v.dump_seed = get("RSREG_DUMP_SEED");
     v.wave_times = get("RSREG_WAVE_TIMES");

@@ -633,14 +633,12 @@ def test_edge_features_and_filter_queued_on_the_side_worker(api, rs):
     assert L.rsreg_cloud_edge_features_async(other.h, unorganized.h, out.h) == lib.RSREG_ERR_INVALID_ARG
 
 
-@pytest.mark.parametrize("one_worker", ["0", "1"])
-def test_side_jobs_on_two_workers_and_on_one_give_the_synchronous_results(api, rs, monkeypatch, one_worker):
+def test_side_jobs_on_two_workers_give_the_synchronous_results(api, rs):
     """Round 6: the side jobs of a context alternate between two worker threads (two scratch sets and streams each); a job
     whose input is the output of a job still queued follows it on the same worker.  Twelve frames' extractions, each with
     two filters chained on it (one more than a worker has sets), all queued before anything is asked for: the records of
-    the synchronous calls, on two workers (default) and on one (RSREG_ONE_SIDE_WORKER=1)."""
-    monkeypatch.setenv("RSREG_ONE_SIDE_WORKER", one_worker)
-    ctx = api.Context(0)   # (a context looks at the environment when it is created)
+    the synchronous calls, on the two workers."""
+    ctx = api.Context(0)
     frames = [rs.synth.render_frame(k, "50k", "bench") for k in range(12)]
     leaves = (np.array([0.01, 0.01, 0.01], np.float32), np.array([0.05, 0.04, 0.03], np.float32))
 
@@ -664,7 +662,6 @@ def test_side_jobs_on_two_workers_and_on_one_give_the_synchronous_results(api, r
         _same_records(r1.download(), want[k][2])
         _same_records(e.download(), want[k][0])
         _same_records(r0.download(), want[k][1])
-    monkeypatch.delenv("RSREG_ONE_SIDE_WORKER")
 
 
 def test_contexts_and_clouds_go_away_with_work_of_their_helper_threads_in_flight(api, rs):

@@ -139,21 +139,6 @@ def test_pass_case(api, rs, refs, name):
         _check_aligned(n, out.xyz, out.points["w"], c["src"], c["bad"])
 
 
-def test_small_cases_with_the_reduce_in_the_same_launch_give_the_same_doubles(api, rs, monkeypatch):
-    def run():
-        out = []
-        for c in PASS.values():
-            n = _ndt(api, rs, c["src"], c["tgt"], c["res"], ctx=api.Context(0))   # (a context looks at the environment when it is created)
-            out.append(R.pack(*n.derivatives(np.asarray(c["pose"], np.float64))).tobytes())
-        return out
-    monkeypatch.delenv("RSREG_NDT_ONE_LAUNCH", raising=False)
-    two = run()
-    monkeypatch.setenv("RSREG_NDT_ONE_LAUNCH", "1")
-    one = run()
-    monkeypatch.delenv("RSREG_NDT_ONE_LAUNCH")
-    assert one == two
-
-
 @pytest.fixture(scope="module")
 def large(api, rs, refs):
     c = PASS["all_pass"]
@@ -198,20 +183,16 @@ def test_large_tiled_source(api, rs, large, n_src):
 
 
 @pytest.mark.parametrize("name", ["v64_n511_general", "large"])
-def test_resident_line_search_gives_the_same_bits(api, rs, monkeypatch, name):
+def test_line_search_repeats_bit_for_bit_in_a_fresh_context(api, rs, name):
     c = PASS["all_pass"] if name == "large" else PASS[name]
     src = K.tiled_source(c["src"], 262145, seed=3)[0] if name == "large" else c["src"]
     guess = np.eye(4, dtype=np.float32)
     guess[:3, 3] = (0.02, -0.01, 0.015)
 
     def run():
-        n = _ndt(api, rs, src, c["tgt"], c["res"], ctx=api.Context(0))   # (a context looks at the environment when it is created)
+        n = _ndt(api, rs, src, c["tgt"], c["res"], ctx=api.Context(0))
         out = n.align(guess)
         r = n.result
         return bytes(r.transform), r.score, r.iterations, r.n_derivative_passes, r.converged, out.xyz.tobytes()
-    monkeypatch.delenv("RSREG_NDT_RESIDENT_LS", raising=False)
     base = run()
-    monkeypatch.setenv("RSREG_NDT_RESIDENT_LS", "1")
-    res = run()
-    monkeypatch.delenv("RSREG_NDT_RESIDENT_LS")
-    assert res == base and base[3] > 1
+    assert run() == base and base[3] > 1

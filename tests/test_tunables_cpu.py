@@ -31,7 +31,7 @@ def switch_names(diag):
 
 def test_switch_names_are_found():
     plain, diag = switch_names(False), switch_names(True)
-    assert {"RSREG_CELL_CAP", "RSREG_ONE_SIDE_WORKER", "RSREG_NO_NBR_FROM_TABLE", "RSREG_NDT_RESIDENT_LS"} <= set(plain)
+    assert {"RSREG_CELL_CAP", "RSREG_NO_BOX_CACHE", "RSREG_NO_NBR_FROM_TABLE", "RSREG_NDT_NO_WATCH"} <= set(plain)
     assert "RSREG_DEBUG_SKIP" in diag and "RSREG_DEBUG_SKIP" not in plain and set(plain) < set(diag)
 
 
