@@ -553,6 +553,40 @@ int rsreg_cloud_knn(rsreg_ctx *ctx, const rsreg_cloud *in, int k, int32_t *index
  * (computeMeanAndCovarianceMatrix); this is the covariance the formula defines, in double, about the record.  A PCL build
  * agrees with it to PCL's own rounding. */
 int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const float viewpoint[3], rsreg_cloud *out);
+/* ---- radius search: every record's neighbours within a radius in its own cloud, EXACT.  Record j is a neighbour of the finite
+ * record i when j is finite and d2(i, j) < r2, with d2 the float32 L2_Simple squared distance of every search here and
+ * r2 = (float)((double)radius * (double)radius): KdTreeFLANN::radiusSearch's cast and the STRICT compare of FLANN's
+ * RadiusResultSet::addPoint, both recalled from PCL 1.9.1 / FLANN -- neither is available to check against, so this IS the
+ * contract.  The record itself and exact copies are neighbours like any other; a record AT the radius is not one.  No cap on the
+ * number of neighbours.  radius not finite or <= 0: RSREG_ERR_INVALID_ARG.  Every call builds its index (a round trip to the host
+ * for the box).
+ *
+ * host_out[i] = record i's number of neighbours (n uint32, the caller's record order): >= 1 for a finite record (itself), 0 for a
+ * non-finite one. */
+int rsreg_cloud_radius_count(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, uint32_t *host_out);
+/* pcl::RadiusOutlierRemoval (filters/impl/radius_outlier_removal.hpp, PCL 1.9.1, recalled): with count as above a record is
+ * removed when count <= min_neighbors (negative: when count > min_neighbors); a non-finite record goes by the same rule with its
+ * count of 0.  Kept records keep their order and all their bytes; out: width = kept, height = 1, is_dense as the input's.
+ * keep_organized: nothing is dropped, a removed record gets x = y = z = quiet NaN, width / height are the input's, is_dense = 0
+ * if anything was removed.  in == out allowed; `out` follows the versioning rules above.  *n_kept: the records kept.
+ * min_neighbors < 0: RSREG_ERR_INVALID_ARG.  Waits for the stream (the number of kept records).
+ * DEVIATION FROM PCL 1.9.1, stated: on a dense cloud PCL takes a k-nearest-neighbour shortcut and compares the
+ * (min_neighbors + 1)-th squared distance against r2 with `>`, which differs from the rule above only for a record at exactly
+ * the radius; here the one rule holds for every cloud. */
+int rsreg_cloud_radius_outlier_removal(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, int min_neighbors, int negative,
+                                       int keep_organized, rsreg_cloud *out, uint64_t *n_kept /* may be NULL */);
+/* pcl::NormalEstimation with setRadiusSearch(radius); viewpoint NULL = (0,0,0).  out: n pcl::Normal records as
+ * rsreg_cloud_normals writes them, width, height as the input's; out != in.
+ * Over the m neighbours within the radius (above): C = (sum d d^T) / m - (sum d / m)(sum d / m)^T with d = neighbour - record in
+ * double, then eigenvector, curvature, flip and the trace-0 case exactly as rsreg_cloud_normals.  m < 3: four quiet NaNs (PCL's
+ * computePointNormal returns false below three points).  A non-finite record gets four quiet NaNs; if any record got NaNs, out's
+ * is_dense is 0, otherwise the input's.  The sums run in an order that is a function of the cloud and the radius alone (inside
+ * a cell of the index the points lie in ascending record index): the same cloud gives the same bytes whatever the context has
+ * indexed before.  Waits for the stream (whether a record got NaNs).
+ * DEVIATION FROM PCL 1.9.1, stated: PCL accumulates nine raw moments about the origin in float, in FLANN's neighbour order
+ * (computeMeanAndCovarianceMatrix); this is the covariance the formula defines, in double, about the record.  A PCL build
+ * agrees with it to PCL's own rounding. */
+int rsreg_cloud_normals_radius(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, const float viewpoint[3], rsreg_cloud *out);
 /* pcl::IntegralImageNormalEstimation on an ORGANIZED cloud of w x h records P[r][c] (src/edge_extractor.hpp:9-15 runs it with
  * AVERAGE_3D_GRADIENT, setMaxDepthChangeFactor(0.02f), setNormalSmoothingSize(10.0f) on every frame): a cost per pixel that
  * does not depend on the scene, and no index.  PCL 1.9.1 features/impl/integral_image_normal.hpp, recalled; PCL is not

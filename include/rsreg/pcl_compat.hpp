@@ -843,10 +843,50 @@ template <typename PointT> class StatisticalOutlierRemoval {
     std::shared_ptr<Context> ctx_;
 };
 
-// ---- pcl::NormalEstimation<PointInT, PointOutT> with setKSearch (3 .. 64) over an exact k-nearest-neighbour search on the GPU
-// (csrc/normals_kernels.hpp, rsreg_cloud_normals).  PointOutT: 32-byte records laid out as pcl::Normal.  The covariance is the
-// one the formula defines, in double about the query point -- PCL's float accumulation about the origin is not reproduced
-// (include/rsreg.h states the deviation).  No radius search, no setSearchSurface, no setIndices.
+// ---- pcl::RadiusOutlierRemoval<PointT> over an exact radius search on the GPU (csrc/radius_kernels.hpp,
+// rsreg_cloud_radius_outlier_removal): a record is removed when it has min_neighbors or fewer neighbours within the radius, itself
+// counted, the compare at the radius strict (include/rsreg.h states the one deviation from PCL's dense-cloud shortcut).  PCL's
+// defaults: radius 0 (filter() refuses it), min_neighbors 1.
+template <typename PointT> class RadiusOutlierRemoval {
+  public:
+    RadiusOutlierRemoval() = default;
+    explicit RadiusOutlierRemoval(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {}
+    void setInputCloud(const typename PointCloud<PointT>::Ptr &cloud) { input_ = cloud; }
+    void setRadiusSearch(double radius) { radius_ = radius; }
+    double getRadiusSearch() const { return radius_; }
+    void setMinNeighborsInRadius(int m) { min_neighbors_ = m; }
+    int getMinNeighborsInRadius() const { return min_neighbors_; }
+    void setNegative(bool negative) { negative_ = negative; }
+    void setKeepOrganized(bool keep) { keep_organized_ = keep; }
+    void filter(PointCloud<PointT> &output)  // output may be *input
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        DeviceCloud<PointT> tmp(*input_, ctx_ ? ctx_ : Context::Default());
+        filter(tmp, tmp);
+        tmp.download(output);
+    }
+    void filter(const DeviceCloud<PointT> &input, DeviceCloud<PointT> &output)  // output may be the input
+    {
+        check(rsreg_cloud_radius_outlier_removal(input.context()->get(), input.handle(), radius_, min_neighbors_, negative_, keep_organized_,
+                                                 output.handle(), &n_kept_),
+              input.context()->get());
+    }
+    uint64_t kept() const { return n_kept_; }   // engine extra: the last filter()'s number of kept records
+  private:
+    double radius_ = 0.0;
+    int min_neighbors_ = 1;
+    bool negative_ = false, keep_organized_ = false;
+    uint64_t n_kept_ = 0;
+    typename PointCloud<PointT>::Ptr input_;
+    std::shared_ptr<Context> ctx_;
+};
+
+// ---- pcl::NormalEstimation<PointInT, PointOutT> on the GPU: with setKSearch (3 .. 64) over an exact k-nearest-neighbour search
+// (csrc/normals_kernels.hpp, rsreg_cloud_normals), or with setRadiusSearch over an exact radius search (csrc/radius_kernels.hpp,
+// rsreg_cloud_normals_radius; any number of neighbours, fewer than three give NaNs).  As in PCL exactly one of the two is set:
+// compute() refuses both and neither before any device call; setKSearch(0) / setRadiusSearch(0) unset them.  PointOutT: 32-byte
+// records laid out as pcl::Normal.  The covariance is the one the formula defines, in double about the query point -- PCL's float
+// accumulation about the origin is not reproduced (include/rsreg.h states the deviation).  No setSearchSurface, no setIndices.
 template <typename PointInT, typename PointOutT = Normal> class NormalEstimation {
     static_assert(sizeof(PointOutT) == 32, "the output records are laid out as pcl::Normal");
   public:
@@ -855,11 +895,14 @@ template <typename PointInT, typename PointOutT = Normal> class NormalEstimation
     void setInputCloud(const typename PointCloud<PointInT>::Ptr &cloud) { input_ = cloud; }
     void setKSearch(int k) { k_ = k; }
     int getKSearch() const { return k_; }
+    void setRadiusSearch(double radius) { radius_ = radius; }
+    double getRadiusSearch() const { return radius_; }
     void setViewPoint(float vx, float vy, float vz) { vp_[0] = vx; vp_[1] = vy; vp_[2] = vz; }
     void getViewPoint(float &vx, float &vy, float &vz) const { vx = vp_[0]; vy = vp_[1]; vz = vp_[2]; }
     void compute(PointCloud<PointOutT> &output)
     {
         if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        check_search();
         const std::shared_ptr<Context> ctx = ctx_ ? ctx_ : Context::Default();
         DeviceCloud<PointInT> tmp(*input_, ctx);
         DeviceCloud<PointOutT> normals(ctx);
@@ -868,10 +911,20 @@ template <typename PointInT, typename PointOutT = Normal> class NormalEstimation
     }
     void compute(const DeviceCloud<PointInT> &input, DeviceCloud<PointOutT> &output)
     {
-        check(rsreg_cloud_normals(input.context()->get(), input.handle(), k_, vp_, output.handle()), input.context()->get());
+        check_search();
+        if (radius_ != 0.0)
+            check(rsreg_cloud_normals_radius(input.context()->get(), input.handle(), radius_, vp_, output.handle()), input.context()->get());
+        else
+            check(rsreg_cloud_normals(input.context()->get(), input.handle(), k_, vp_, output.handle()), input.context()->get());
     }
   private:
-    int k_ = 0;                            // PCL's default: no search set (compute() refuses it)
+    void check_search() const
+    {
+        if (k_ != 0 && radius_ != 0.0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: both setKSearch and setRadiusSearch are set: set one of them to 0");
+        if (k_ == 0 && radius_ == 0.0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: neither setKSearch nor setRadiusSearch is set");
+    }
+    int k_ = 0;                            // PCL's defaults: no search set (compute() refuses it)
+    double radius_ = 0.0;
     float vp_[3] = {0.f, 0.f, 0.f};
     typename PointCloud<PointInT>::Ptr input_;
     std::shared_ptr<Context> ctx_;

@@ -249,6 +249,48 @@ class DeviceCloud:
         out.close()
         return np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
 
+    def radius_count(self, radius):
+        """radiusSearch of every record in its own cloud, counted (rsreg_cloud_radius_count, exact): uint32 per record, its
+        neighbours with float32 d2 < (float)(radius * radius) -- strictly, itself and exact copies among them; 0 for a non-finite
+        record."""
+        out = np.zeros(self.info()[0], np.uint32)
+        _l.check(_l.lib().rsreg_cloud_radius_count(self.ctx.h, self.h, float(radius), out.ctypes.data), self.ctx.h)
+        return out
+
+    def radius_outlier_removal(self, radius, min_neighbors, negative=False, keep_organized=False, out=None):
+        """pcl::RadiusOutlierRemoval (rsreg_cloud_radius_outlier_removal): a record is removed when its radius_count is
+        <= min_neighbors (negative: when it is above).  out: None = a new DeviceCloud, or a DeviceCloud of this context (this one
+        is allowed).  Returns (out, the number of kept records)."""
+        made = out is None
+        if made:
+            out = DeviceCloud(ctx=self.ctx)
+        kept = C.c_uint64(0)
+        rc = _l.lib().rsreg_cloud_radius_outlier_removal(self.ctx.h, self.h, float(radius), int(min_neighbors), int(bool(negative)),
+                                                         int(bool(keep_organized)), out.h, C.byref(kept))
+        if rc and made:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out, int(kept.value)
+
+    def normals_radius_cloud(self, radius, viewpoint=None):
+        """pcl::NormalEstimation with setRadiusSearch(radius) (rsreg_cloud_normals_radius): a DeviceCloud of 32-byte pcl::Normal
+        records; fewer than three neighbours within the radius: NaNs."""
+        out = DeviceCloud(ctx=self.ctx)
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        rc = _l.lib().rsreg_cloud_normals_radius(self.ctx.h, self.h, float(radius), None if vp is None else vp.ctypes.data, out.h)
+        if rc:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out
+
+    def normals_radius(self, radius, viewpoint=None):
+        """(n, 4) float32: normal_x, normal_y, normal_z, curvature of every record (NaN for a non-finite one and for one with
+        fewer than three neighbours within the radius)."""
+        out = self.normals_radius_cloud(radius, viewpoint)
+        rec = out.download_normals().points
+        out.close()
+        return np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
+
     def integral_normals_cloud(self, params=None, rect=False):
         """pcl::IntegralImageNormalEstimation of this organized cloud (rsreg_cloud_integral_normals; params: iin_params(),
         None = PCL's defaults): a DeviceCloud of 32-byte pcl::Normal records.  rect=True: (cloud, the window size of every
@@ -1105,14 +1147,59 @@ class StatisticalOutlierRemoval:
         return out
 
 
+class RadiusOutlierRemoval:
+    """pcl::RadiusOutlierRemoval<PointXYZRGB> on the GPU over an exact radius search (csrc/radius_kernels.hpp,
+    rsreg_cloud_radius_outlier_removal): a record is removed when it has min_neighbors or fewer neighbours within the radius,
+    itself counted, the compare at the radius strict.  PCL's defaults: radius 0 (filter() refuses it), min_neighbors 1.
+    `n_kept` holds the last call's number of kept records."""
+
+    def __init__(self, ctx=None):
+        self.radius = 0.0
+        self.min_neighbors = 1
+        self.negative = False
+        self.keep_organized = False
+        self.n_kept = None
+        self._in = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setRadiusSearch(self, radius):
+        self.radius = float(radius)
+
+    def getRadiusSearch(self):
+        return self.radius
+
+    def setMinNeighborsInRadius(self, m):
+        self.min_neighbors = int(m)
+
+    def getMinNeighborsInRadius(self):
+        return self.min_neighbors
+
+    def setNegative(self, negative):
+        self.negative = bool(negative)
+
+    def setKeepOrganized(self, keep):
+        self.keep_organized = bool(keep)
+
+    def filter(self):
+        def run(cin, cout):
+            _, self.n_kept = cin.radius_outlier_removal(self.radius, self.min_neighbors, self.negative, self.keep_organized, out=cout)
+        return _filter_io(self._in, self.ctx, run)
+
+
 class NormalEstimation:
-    """pcl::NormalEstimation<PointXYZRGB, Normal> with setKSearch on the GPU over an exact k-nearest-neighbour search
-    (csrc/normals_kernels.hpp, rsreg_cloud_normals), 3 <= k <= 64.  The covariance is the one the formula defines, in double
-    about the query point: PCL's float accumulation about the origin is not reproduced (include/rsreg.h).  compute() of a
-    DeviceCloud gives a DeviceCloud of pcl::Normal records, of a host cloud a NormalCloud."""
+    """pcl::NormalEstimation<PointXYZRGB, Normal> on the GPU: with setKSearch over an exact k-nearest-neighbour search
+    (csrc/normals_kernels.hpp, rsreg_cloud_normals), 3 <= k <= 64, or with setRadiusSearch over an exact radius search
+    (csrc/radius_kernels.hpp, rsreg_cloud_normals_radius), any number of neighbours.  As in PCL exactly one of the two is set:
+    compute() refuses both and neither; setKSearch(0) / setRadiusSearch(0) unset them.  The covariance is the one the formula
+    defines, in double about the query point: PCL's float accumulation about the origin is not reproduced (include/rsreg.h).
+    compute() of a DeviceCloud gives a DeviceCloud of pcl::Normal records, of a host cloud a NormalCloud."""
 
     def __init__(self, ctx=None):
         self.k = 0                                   # PCL's default: no search set
+        self.radius = 0.0
         self.viewpoint = (0.0, 0.0, 0.0)
         self._in = None
         self.ctx = ctx
@@ -1126,20 +1213,33 @@ class NormalEstimation:
     def getKSearch(self):
         return self.k
 
+    def setRadiusSearch(self, radius):
+        self.radius = float(radius)
+
+    def getRadiusSearch(self):
+        return self.radius
+
     def setViewPoint(self, vx, vy, vz):
         self.viewpoint = (float(vx), float(vy), float(vz))
 
     def getViewPoint(self):
         return self.viewpoint
 
+    def _normals_cloud(self, dev):
+        return dev.normals_radius_cloud(self.radius, self.viewpoint) if self.radius != 0.0 else dev.normals_cloud(self.k, self.viewpoint)
+
     def compute(self):
         if self._in is None:
             raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCloud not called")
+        if self.k != 0 and self.radius != 0.0:   # (before any device call, as PCL's initCompute)
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "both setKSearch and setRadiusSearch are set: set one of them to 0")
+        if self.k == 0 and self.radius == 0.0:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "neither setKSearch nor setRadiusSearch is set")
         if isinstance(self._in, DeviceCloud):
-            return self._in.normals_cloud(self.k, self.viewpoint)
+            return self._normals_cloud(self._in)
         tmp = DeviceCloud(self._in, ctx=self.ctx or default_context())
         try:
-            dev = tmp.normals_cloud(self.k, self.viewpoint)
+            dev = self._normals_cloud(tmp)
             out = dev.download_normals()
             dev.close()
         finally:

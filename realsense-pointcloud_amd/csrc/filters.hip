@@ -4,13 +4,16 @@
 //
 // PassThrough: one flag pass, a prefix sum of the flags (oscan.hpp), one ordered gather.  StatisticalOutlierRemoval: the exact
 // k-NN index and search of knn_kernels.hpp, the threshold's two sums in PCL's own order, then the same flag / scan / gather.
-// Everything runs on the context's stream with the index rsreg_ctx::knn and the scratch rsreg_ctx::filt: nothing here reads
-// or writes a buffer of the alignment's index or of the fitness indices.
+// pcl::RadiusOutlierRemoval and NormalEstimation by radius: the exact radius search of radius_kernels.hpp over an index of its own
+// placement, then the same flag / scan / gather, or k_normals' tail.
+// Everything runs on the context's stream with the index rsreg_ctx::knn and the scratch rsreg_ctx::filt (the radius search:
+// rsreg_ctx::rad too): nothing here reads or writes a buffer of the alignment's index or of the fitness indices.
 #include <cmath>
 #include <cstring>
 
 #include "knn_kernels.hpp"
 #include "normals_kernels.hpp"
+#include "radius_kernels.hpp"
 
 using namespace rsreg;
 
@@ -103,31 +106,14 @@ int compact_into(rsreg_ctx *ctx, const CloudView &v, rsreg_cloud *out, int is_de
     return rsreg_cloud_adopt_(out, &fs.d_out, kept, v.stride, kept, 1, is_dense);   // (in == out: the input has been consumed by now)
 }
 
-}  // namespace
-
-extern "C" {
-
-int rsreg_cloud_passthrough(rsreg_ctx *ctx, const rsreg_cloud *in, int field, float lo, float hi, int negative, int keep_organized,
-                            rsreg_cloud *out)
+// keep_organized: flags -> every record in ctx->filt.d_out, a removed one with x = y = z = quiet NaN (waits for the number of kept
+// records: is_dense is false if anything was removed), handed to `out` with the input's width and height
+int organized_into(rsreg_ctx *ctx, const CloudView &v, rsreg_cloud *out, uint32_t *n_kept_out)
 {
-    CloudView v;
-    if (!out) return RSREG_ERR_INVALID_ARG;
-    int rc = view_of(ctx, in, out, v);
-    if (rc) return rc;
-    // (PCL warns about a field it does not find and returns an empty cloud: here the call is refused)
-    if (field < 0 || field > 2) return fail(ctx, RSREG_ERR_INVALID_ARG, "PassThrough filters on field 0 (x), 1 (y) or 2 (z)");
     PointGrid &kx = ctx->knn;
     FilterScratch &fs = ctx->filt;
     hipStream_t st = ctx->stream;
     const uint32_t n = (uint32_t)v.n;
-    if (n) {
-        RSREG_HIP(ctx, fs.d_flags.reserve(v.n * 4 + 16));
-        k_pass_flags<<<div_up(n, kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, field, lo, hi, negative ? 1 : 0, fs.d_flags.as<uint32_t>());
-        RSREG_HIP(ctx, hipGetLastError());
-    }
-    uint32_t kept = 0;
-    if (!keep_organized) return compact_into(ctx, v, out, 1, &kept);
-    // every record stays; is_dense is false if anything was removed: the number of kept records decides
     uint32_t removed = 0;
     if (n) {
         RSREG_HIP(ctx, fs.d_pos.reserve(v.n * 4 + 16));
@@ -142,7 +128,94 @@ int rsreg_cloud_passthrough(rsreg_ctx *ctx, const rsreg_cloud *in, int field, fl
         RSREG_HIP(ctx, hipStreamSynchronize(st));
         removed = n - fs.host.as<uint32_t>()[8];
     }
+    *n_kept_out = n - removed;
     return rsreg_cloud_adopt_(out, &fs.d_out, v.n, v.stride, v.width, v.height, removed ? 0 : v.is_dense);
+}
+
+// The index of the cloud for a radius search and what a walk needs beside it (radius_kernels.hpp), on ctx->stream: pointgrid.hpp's
+// build (one round trip to the host for the box) with the radius as the smallest cell and the ordered placement -- a stable sort of
+// (cell, record) pairs.  count (nullable): the words of non-finite records are zeroed on the way.  No finite record: nothing is
+// indexed, *nfin_out = 0.
+int radius_index_device(rsreg_ctx *ctx, const CloudView &v, double radius, uint32_t *count, RadiusQuery *rq, uint32_t *nfin_out)
+{
+    FilterScratch &fs = ctx->filt;
+    RadiusScratch &rs = ctx->rad;
+    PointGrid &kx = ctx->knn;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)v.n;
+    if (v.n >= (1ull << 30)) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
+    RSREG_HIP(ctx, fs.host.reserve(256));
+    const RadiusRecords rd{v.rec, v.stride, count};
+    int rc = grid_build_placed<RadiusGridPolicy>(ctx, kx, rd, n, 1u, fs.host.as<uint32_t>(), radius,
+                                                 [&](const PointGridDev &g, uint32_t *, uint32_t *cell_count, size_t cells) {
+        for (int k = 0; k < 2; ++k) {
+            RSREG_HIP(ctx, rs.d_keys[k].reserve(v.n * 4 + 16));
+            RSREG_HIP(ctx, rs.d_vals[k].reserve(v.n * 4 + 16));
+        }
+        unsigned bits = 1;
+        while ((cells >> bits) != 0) ++bits;   // the keys: every cell and `cells` itself, the non-finite records' key
+        RSREG_HIP(ctx, rs.d_sort.reserve((size_t)osort_plan<uint32_t>(v.n, 0, bits).words * 4));
+        uint32_t *keys[2] = {rs.d_keys[0].as<uint32_t>(), rs.d_keys[1].as<uint32_t>()}, *vals[2] = {rs.d_vals[0].as<uint32_t>(), rs.d_vals[1].as<uint32_t>()};
+        k_radius_cell_keys<<<div_up(n, kBlock), kBlock, 0, st>>>(rd, n, g, (uint32_t)cells, keys[0], vals[0]);
+        RSREG_HIP(ctx, hipGetLastError());
+        bool in_first = true;
+        RSREG_HIP(ctx, osort_pairs_cleared<uint32_t>(rs.d_sort.as<uint32_t>(), keys[0], keys[1], vals[0], vals[1], v.n, 0, bits, st, &in_first));
+        const int at = in_first ? 0 : 1;
+        k_radius_place<<<div_up(kx.n_points, kBlock), kBlock, 0, st>>>(rd, kx.n_points, keys[at], vals[at], cell_count, kx.d_pts.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+        return (int)RSREG_OK;
+    });
+    if (rc) return rc;
+    *nfin_out = kx.n_points;
+    *rq = radius_query(radius, kx);
+    return RSREG_OK;
+}
+
+// d_count[i] = record i's neighbours within the radius, itself among them (0 for a non-finite record): the index and the search, not
+// waited for
+int radius_count_device(rsreg_ctx *ctx, const CloudView &v, double radius)
+{
+    if (!(radius > 0.0) || !std::isfinite(radius)) return fail(ctx, RSREG_ERR_INVALID_ARG, "the radius must be finite and above 0");
+    if (!v.n) return RSREG_OK;
+    RadiusScratch &rs = ctx->rad;
+    RSREG_HIP(ctx, rs.d_count.reserve(v.n * 4 + 16));
+    RadiusQuery rq;
+    uint32_t nfin = 0;
+    int rc = radius_index_device(ctx, v, radius, rs.d_count.as<uint32_t>(), &rq, &nfin);
+    if (rc) return rc;
+    if (!nfin) {   // (the build stops at the box: nothing has written the counts)
+        RSREG_HIP(ctx, hipMemsetAsync(rs.d_count.ptr, 0, v.n * 4, ctx->stream));
+        return RSREG_OK;
+    }
+    k_radius_count<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, ctx->stream>>>(grid_dev(ctx->knn), rq, rs.d_count.as<uint32_t>());
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsreg_cloud_passthrough(rsreg_ctx *ctx, const rsreg_cloud *in, int field, float lo, float hi, int negative, int keep_organized,
+                            rsreg_cloud *out)
+{
+    CloudView v;
+    if (!out) return RSREG_ERR_INVALID_ARG;
+    int rc = view_of(ctx, in, out, v);
+    if (rc) return rc;
+    // (PCL warns about a field it does not find and returns an empty cloud: here the call is refused)
+    if (field < 0 || field > 2) return fail(ctx, RSREG_ERR_INVALID_ARG, "PassThrough filters on field 0 (x), 1 (y) or 2 (z)");
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)v.n;
+    if (n) {
+        RSREG_HIP(ctx, fs.d_flags.reserve(v.n * 4 + 16));
+        k_pass_flags<<<div_up(n, kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, field, lo, hi, negative ? 1 : 0, fs.d_flags.as<uint32_t>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    uint32_t kept = 0;
+    if (!keep_organized) return compact_into(ctx, v, out, 1, &kept);
+    return organized_into(ctx, v, out, &kept);
 }
 
 int rsreg_cloud_knn_mean_distance(rsreg_ctx *ctx, const rsreg_cloud *in, int mean_k, float *host_out)
@@ -258,6 +331,80 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
     RSREG_HIP(ctx, hipGetLastError());
     // a record that got NaNs makes the cloud not dense; otherwise it is what the input says
     return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kNormalBytes, v.width, v.height, nfin < n ? 0 : v.is_dense);
+}
+
+int rsreg_cloud_radius_count(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, uint32_t *host_out)
+{
+    CloudView v;
+    if (!host_out) return RSREG_ERR_INVALID_ARG;
+    int rc = view_of(ctx, in, nullptr, v);
+    if (rc) return rc;
+    rc = radius_count_device(ctx, v, radius);
+    if (rc || !v.n) return rc;
+    RSREG_HIP(ctx, hipMemcpyAsync(host_out, ctx->rad.d_count.ptr, v.n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RSREG_OK;
+}
+
+int rsreg_cloud_radius_outlier_removal(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, int min_neighbors, int negative, int keep_organized,
+                                       rsreg_cloud *out, uint64_t *n_kept)
+{
+    CloudView v;
+    if (!out) return RSREG_ERR_INVALID_ARG;
+    int rc = view_of(ctx, in, out, v);
+    if (rc) return rc;
+    if (min_neighbors < 0) return fail(ctx, RSREG_ERR_INVALID_ARG, "min_neighbors must not be negative");
+    rc = radius_count_device(ctx, v, radius);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    const uint32_t n = (uint32_t)v.n;
+    if (n) {
+        RSREG_HIP(ctx, fs.d_flags.reserve(v.n * 4 + 16));
+        k_ror_flags<<<div_up(n, kBlock), kBlock, 0, ctx->stream>>>(ctx->rad.d_count.as<uint32_t>(), n, (uint32_t)min_neighbors, negative ? 1 : 0,
+                                                                  fs.d_flags.as<uint32_t>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    uint32_t kept = 0;
+    rc = keep_organized ? organized_into(ctx, v, out, &kept) : compact_into(ctx, v, out, v.is_dense, &kept);
+    if (rc) return rc;
+    if (n_kept) *n_kept = kept;
+    return RSREG_OK;
+}
+
+int rsreg_cloud_normals_radius(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, const float viewpoint[3], rsreg_cloud *out)
+{
+    CloudView v;
+    if (!out || out == in) return RSREG_ERR_INVALID_ARG;
+    int rc = view_of(ctx, in, out, v);
+    if (rc) return rc;
+    if (!(radius > 0.0) || !std::isfinite(radius)) return fail(ctx, RSREG_ERR_INVALID_ARG, "the radius must be finite and above 0");
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)v.n;
+    constexpr size_t kNormalBytes = 32;   // pcl::Normal
+    RSREG_HIP(ctx, fs.d_out.reserve(v.n * kNormalBytes + 16));
+    uint32_t nfin = 0, any_nan = 0;
+    if (n) {
+        RadiusQuery rq;
+        rc = radius_index_device(ctx, v, radius, nullptr, &rq, &nfin);
+        if (rc) return rc;
+        if (nfin < n) {
+            k_normals_not_finite<<<div_up(n, kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, fs.d_out.as<float>());
+            RSREG_HIP(ctx, hipGetLastError());
+        }
+        if (nfin) {
+            // a record with fewer than three neighbours gets NaNs too: whether one did comes back with the stream
+            uint32_t *d_any = ctx->knn.d_box.as<uint32_t>() + 8, *h_any = fs.host.as<uint32_t>() + 8;
+            RSREG_HIP(ctx, hipMemsetAsync(d_any, 0, 4, st));
+            const float vp[3] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f, viewpoint ? viewpoint[2] : 0.0f};
+            k_normals_radius<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), rq, vp[0], vp[1], vp[2], fs.d_out.as<float>(), d_any);
+            RSREG_HIP(ctx, hipGetLastError());
+            RSREG_HIP(ctx, hipMemcpyAsync(h_any, d_any, 4, hipMemcpyDeviceToHost, st));
+            RSREG_HIP(ctx, hipStreamSynchronize(st));
+            any_nan = *h_any;
+        }
+    }
+    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kNormalBytes, v.width, v.height, (nfin < n || any_nan) ? 0 : v.is_dense);
 }
 
 }  // extern "C"

@@ -127,6 +127,39 @@ __global__ __launch_bounds__(kBlock) void k_normals_not_finite(const char *rec, 
     o[1] = make_float4(qnan, 0.0f, 0.0f, 0.0f);
 }
 
+// The tail of both estimators (k neighbours here, the neighbours within a radius in radius_kernels.hpp), by every lane of the wave that
+// holds the sums over the kk neighbours of the query q (the same bits in every lane): the covariance, its smallest eigenpair, the
+// curvature, the flip towards the viewpoint; lanes 0 .. 7 write the record `q.w` of out.
+__device__ __forceinline__ void normal_from_sums(const float4 &q, double kk, double sx, double sy, double sz, double sxx, double sxy, double sxz, double syy,
+                                                 double syz, double szz, float vpx, float vpy, float vpz, int lane, float *out)
+{
+#pragma clang fp contract(off)
+    const double mx = sx / kk, my = sy / kk, mz = sz / kk;
+    const double c[6] = {sxx / kk - mx * mx, sxy / kk - mx * my, sxz / kk - mx * mz, syy / kk - my * my, syz / kk - my * mz, szz / kk - mz * mz};
+    const double trace = (c[0] + c[3]) + c[5];
+    float nx = 0.0f, ny = 0.0f, nz = 1.0f, curv = 0.0f;
+    if (trace != 0.0) {
+        double ev[3], vec[3];
+        eig_sym3_smallest(c, ev, vec);
+        nx = (float)vec[0];
+        ny = (float)vec[1];
+        nz = (float)vec[2];
+        const double sum = (ev[0] + ev[1]) + ev[2];
+        curv = sum != 0.0 ? (float)fabs(ev[0] / sum) : 0.0f;
+    }
+    const float vx = __fsub_rn(vpx, q.x), vy = __fsub_rn(vpy, q.y), vz = __fsub_rn(vpz, q.z);
+    const float cos_view = __fadd_rn(__fadd_rn(__fmul_rn(vx, nx), __fmul_rn(vy, ny)), __fmul_rn(vz, nz));
+    if (cos_view < 0.0f) {
+        nx = -nx;
+        ny = -ny;
+        nz = -nz;
+    }
+    if (lane < 8) {
+        const float v = lane == 0 ? nx : (lane == 1 ? ny : (lane == 2 ? nz : (lane == 4 ? curv : 0.0f)));
+        out[(size_t)__float_as_uint(q.w) * 8 + (size_t)lane] = v;
+    }
+}
+
 // One workgroup of ONE wave per query, queries in cell order: the search, then the normal of the k neighbours while their keys
 // are in LDS.  out: record `record` = {normal_x, normal_y, normal_z, 0, curvature, 0, 0, 0}.
 __global__ __launch_bounds__(kKnnWave) void k_normals(PointGridDev g, int k, const char *rec, size_t stride, float vpx, float vpy, float vpz, float *out)
@@ -148,30 +181,7 @@ __global__ __launch_bounds__(kKnnWave) void k_normals(PointGridDev g, int k, con
         const double sx = wave_sum_fixed(dx), sy = wave_sum_fixed(dy), sz = wave_sum_fixed(dz);
         const double sxx = wave_sum_fixed(dx * dx), sxy = wave_sum_fixed(dx * dy), sxz = wave_sum_fixed(dx * dz);
         const double syy = wave_sum_fixed(dy * dy), syz = wave_sum_fixed(dy * dz), szz = wave_sum_fixed(dz * dz);
-        const double kk = (double)k, mx = sx / kk, my = sy / kk, mz = sz / kk;
-        const double c[6] = {sxx / kk - mx * mx, sxy / kk - mx * my, sxz / kk - mx * mz, syy / kk - my * my, syz / kk - my * mz, szz / kk - mz * mz};
-        const double trace = (c[0] + c[3]) + c[5];
-        float nx = 0.0f, ny = 0.0f, nz = 1.0f, curv = 0.0f;
-        if (trace != 0.0) {
-            double ev[3], vec[3];
-            eig_sym3_smallest(c, ev, vec);
-            nx = (float)vec[0];
-            ny = (float)vec[1];
-            nz = (float)vec[2];
-            const double sum = (ev[0] + ev[1]) + ev[2];
-            curv = sum != 0.0 ? (float)fabs(ev[0] / sum) : 0.0f;
-        }
-        const float vx = __fsub_rn(vpx, q.x), vy = __fsub_rn(vpy, q.y), vz = __fsub_rn(vpz, q.z);
-        const float cos_view = __fadd_rn(__fadd_rn(__fmul_rn(vx, nx), __fmul_rn(vy, ny)), __fmul_rn(vz, nz));
-        if (cos_view < 0.0f) {
-            nx = -nx;
-            ny = -ny;
-            nz = -nz;
-        }
-        if (lane < 8) {
-            const float v = lane == 0 ? nx : (lane == 1 ? ny : (lane == 2 ? nz : (lane == 4 ? curv : 0.0f)));
-            out[(size_t)__float_as_uint(q.w) * 8 + (size_t)lane] = v;
-        }
+        normal_from_sums(q, (double)k, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz, vpx, vpy, vpz, lane, out);
     }
 }
 

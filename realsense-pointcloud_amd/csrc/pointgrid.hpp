@@ -33,12 +33,19 @@ struct KnnGridPolicy {   // k-NN of the cloud filters: a depth frame is a surfac
     static constexpr double kCellsPerPoint = 64.0, kMinCells = 4096.0, kMaxCells = 33554432.0;
     static constexpr bool kBlocks = false;
 };
+struct RadiusGridPolicy {   // radius search (radius_kernels.hpp): the cell is the radius (grid_layout's min_cell), so a ball's box is a few
+                            // cells a side; these numbers only cap the cells where the radius is tiny against the box -- the cell then
+                            // stays larger than the radius, as fine as the k-NN grid of the same cloud
+    static constexpr double kCellsPerPoint = 64.0, kMinCells = 4096.0, kMaxCells = 33554432.0;
+    static constexpr bool kBlocks = false;
+};
 constexpr int kGridMaxAxis = 4096;   // cells along an axis at most: what kCellMargin is argued for (grid_lb2)
 
 // The cell: about kCellsPerPoint cells per finite point over the box, never more than 4 000 along an axis, never so small that
-// the float rounding of a coordinate is a sizeable part of it.  Cells per axis: floor(extent / cell) + 2 (rounded up to whole blocks).
+// the float rounding of a coordinate is a sizeable part of it, never smaller than min_cell (a radius search: its radius).  Cells per
+// axis: floor(extent / cell) + 2 (rounded up to whole blocks).
 template <typename Policy>
-void grid_layout(const float mn[3], const float mx[3], uint32_t nfin, PointGrid &gx)
+void grid_layout(const float mn[3], const float mx[3], uint32_t nfin, PointGrid &gx, double min_cell = 0.0)
 {
     double e[3], emax = 0, big = 0;
     for (int k = 0; k < 3; ++k) {
@@ -54,6 +61,7 @@ void grid_layout(const float mn[3], const float mx[3], uint32_t nfin, PointGrid 
     auto cells_for = [&](double c) { return (double)cells_along(0, c) * (double)cells_along(1, c) * (double)cells_along(2, c); };
     double lo = std::max(std::max(emax / 4000.0, big * 1e-5), 1e-30);
     if (emax == 0) lo = std::max(big * 1e-5, 1.0);
+    lo = std::max(lo, std::min(min_cell, std::max(emax, lo) * 2.0));   // (two cells per axis hold any ball: no cell needs to be larger)
     double cell = lo;
     if (cells_for(lo) > target) {
         double hi = std::max(emax, lo) * 2.0;   // (two cells per axis)
@@ -239,10 +247,11 @@ __global__ __launch_bounds__(kBlock) void k_grid_scatter(Reader rd, uint32_t n, 
 
 // ------------------------------------------------------------------------------ host build
 // Indexes the n records of rd in gx's own buffers, on ctx->stream: box (one round trip through h, 8 pinned words), layout,
-// counts, prefix sum, scatter.  gx.n_points = the finite records; fewer than min_points (>= 1) of them: nothing is indexed and
-// gx.dims stay 0.
-template <typename Policy, typename Reader>
-int grid_build(rsreg_ctx *ctx, PointGrid &gx, const Reader &rd, uint32_t n, uint32_t min_points, uint32_t *h)
+// counts, prefix sum, placement.  gx.n_points = the finite records; fewer than min_points (>= 1) of them: nothing is indexed and
+// gx.dims stay 0.  place(g, start, count, cells) queues what puts the points into gx.d_pts cell by cell and leaves the counts zero;
+// the order inside a cell is the placement's (grid_build: whatever the atomics make it).
+template <typename Policy, typename Reader, typename Place>
+int grid_build_placed(rsreg_ctx *ctx, PointGrid &gx, const Reader &rd, uint32_t n, uint32_t min_points, uint32_t *h, double min_cell, Place place)
 {
     constexpr bool kBlocks = Policy::kBlocks;
     hipStream_t st = ctx->stream;
@@ -271,7 +280,7 @@ int grid_build(rsreg_ctx *ctx, PointGrid &gx, const Reader &rd, uint32_t n, uint
         mn[k] = ordered_float(h[k]);
         mx[k] = ordered_float(h[3 + k]);
     }
-    grid_layout<Policy>(mn, mx, nfin, gx);
+    grid_layout<Policy>(mn, mx, nfin, gx, min_cell);
     const size_t cells = (size_t)gx.dims[0] * (size_t)gx.dims[1] * (size_t)gx.dims[2];
     if (gx.dims[0] > kGridMaxAxis || gx.dims[1] > kGridMaxAxis || gx.dims[2] > kGridMaxAxis || cells > 0x7ffffff0ull)
         return fail(ctx, RSREG_ERR_STATE, "point grid layout out of range");
@@ -291,10 +300,20 @@ int grid_build(rsreg_ctx *ctx, PointGrid &gx, const Reader &rd, uint32_t n, uint
     k_grid_count<kBlocks><<<nb, kBlock, 0, st>>>(rd, n, g, count, gx.d_mask.as<unsigned long long>());
     RSREG_HIP(ctx, hipGetLastError());
     RSREG_HIP(ctx, oscan<uint32_t>(count, start, cells + 1, 0u, gx.d_scan.ptr, st));
-    k_grid_scatter<kBlocks><<<nb, kBlock, 0, st>>>(rd, n, g, start, count, gx.d_pts.as<float4>());
-    RSREG_HIP(ctx, hipGetLastError());
+    const int rc = place(g, start, count, cells);
+    if (rc) return rc;
     gx.built = true;
     return RSREG_OK;
+}
+
+template <typename Policy, typename Reader>
+int grid_build(rsreg_ctx *ctx, PointGrid &gx, const Reader &rd, uint32_t n, uint32_t min_points, uint32_t *h)
+{
+    return grid_build_placed<Policy>(ctx, gx, rd, n, min_points, h, 0.0, [&](const PointGridDev &g, uint32_t *start, uint32_t *count, size_t) {
+        k_grid_scatter<Policy::kBlocks><<<(n + kBlock - 1) / kBlock, kBlock, 0, ctx->stream>>>(rd, n, g, start, count, gx.d_pts.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+        return (int)RSREG_OK;
+    });
 }
 
 }  // namespace rsreg

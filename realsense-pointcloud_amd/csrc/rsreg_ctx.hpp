@@ -193,6 +193,13 @@ struct FilterScratch {
     PinnedBuf host;
 };
 
+// Scratch of the radius search (filters.hip, radius_kernels.hpp), per record of the cloud being searched; not part of an index
+struct RadiusScratch {
+    DevBuf d_keys[2], d_vals[2];   // uint32 per record, twice: (cell, record) pairs on their way through the stable sort that places the index
+    DevBuf d_sort;                 // the sort's scratch block
+    DevBuf d_count;                // uint32 per record: its neighbours within the radius
+};
+
 // Scratch of IntegralImageNormalEstimation (iinormals.hip), per pixel of the organized frame it is given
 struct IinScratch {
     DevBuf d_dist0, d_dist1, d_dist2;   // float: the distance map as set up, after the forward pass, after the backward pass
@@ -445,6 +452,7 @@ struct rsreg_ctx {
     // ---- PassThrough / StatisticalOutlierRemoval (filters.hip): index and scratch of their own
     rsreg::PointGrid knn;            // rebuilt by every k-NN call from the cloud it is given
     rsreg::FilterScratch filt;
+    rsreg::RadiusScratch rad;        // radius search: it indexes in `knn` too, with a placement of its own
 
     // ---- IntegralImageNormalEstimation (iinormals.hip)
     rsreg::IinScratch iin;
