@@ -306,16 +306,44 @@ __device__ __forceinline__ float sel3(float a, float b, float c, int i) { return
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 
-// running best: squared distance and original index (the tie-break) of the winning point -- its
-// place in the sorted array is looked up once at the end (pos_of), not carried through every
-// comparison; starts at "+inf, no point" so that the far-away sentinel points never win
+// running best: squared distance and original index (the tie-break) of the winning point as ONE 64-bit key,
+// d_bits << 32 | index, held as an IEEE double -- its place in the sorted array is looked up once at the end (pos_of),
+// not carried through every comparison; starts at "+inf, no point" so that the far-away sentinel points never win.
+// Why a double orders like the key: squared distances are >= 0 and never NaN (finite query, finite or sentinel target),
+// so d's bits are at most 0x7f800000 -- the sign bit of the double is 0 and its exponent field at most 0x7f8, below the
+// 0x7ff of inf / NaN.  Every key is a finite non-negative double, and for those IEEE order is the unsigned order of the
+// bits; d = 0 makes the key a subnormal double, which the kernels keep (f64 denormals are on by default).  So the
+// running best is one v_min_f64 per candidate -- no compare, no selects, no branch -- and the lower index still wins
+// among equal distances.
 struct DBest {
-    float d;
-    uint32_t idx;
+    double key;
 };
 
+__device__ __forceinline__ DBest dbest_none() { return DBest{__hiloint2double((int)0x7f800000u, (int)0xffffffffu)}; }
+__device__ __forceinline__ float dbest_d(const DBest &b) { return __uint_as_float((uint32_t)__double2hiint(b.key)); }
+__device__ __forceinline__ uint32_t dbest_idx(const DBest &b) { return (uint32_t)__double2loint(b.key); }
+
+// min of two keys: one v_min_f64 (finite, never NaN: the canonicalising pair the compiler puts around fmin is not needed)
+__device__ __forceinline__ double min_key(double a, double b)
+{
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// the same with a candidate's key taken as |key| (a source modifier, no instruction): should a distance ever come out as a
+// NaN with its sign set -- a query that a broken transform has made NaN --, the key is a large positive double that never
+// wins, as it never won the unsigned compare; without the modifier it would be a negative one that always does
+__device__ __forceinline__ double min_key_cand(double best, double key)
+{
+    double r;
+    asm("v_min_f64 %0, %1, |%2|" : "=v"(r) : "v"(best), "v"(key));
+    return r;
+}
+
 // FLANN L2_Simple in its own order ((dx^2 + dy^2) + dz^2, nothing fused); x and y go through
-// the packed f32 pipe straight out of the loaded register pair; a record is (x, y, index, z), see tgt_rec
+// the packed f32 pipe straight out of the loaded register pair; a record is (x, y, index, z), see tgt_rec:
+// d takes z's place, which leaves (index, d) as the register pair of the key
 __device__ __forceinline__ void dconsider(DBest &b, f32x2 qxy, float qz, const u32x4 &t)
 {
     const f32x2 txy = {__uint_as_float(t.x), __uint_as_float(t.y)};
@@ -323,13 +351,7 @@ __device__ __forceinline__ void dconsider(DBest &b, f32x2 qxy, float qz, const u
     const f32x2 sq = dxy * dxy;
     const float dz = __fsub_rn(qz, __uint_as_float(t.w));
     const float d = __fadd_rn(__fadd_rn(sq.x, sq.y), __fmul_rn(dz, dz));
-    // (distance, original index) ordered as one 64-bit key: squared distances are >= 0, so their bit patterns
-    // order like their values, and the lower index wins among equal distances
-    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | t.z;
-    const unsigned long long bkey = ((unsigned long long)__float_as_uint(b.d) << 32) | b.idx;
-    const bool better = key < bkey;
-    b.d = better ? d : b.d;
-    b.idx = better ? t.z : b.idx;
+    b.key = min_key_cand(b.key, __hiloint2double((int)__float_as_uint(d), (int)t.z));
 }
 
 // score 4 consecutive points starting at byte offset `po` (reading past the end of a cell
@@ -417,10 +439,12 @@ __device__ __forceinline__ void dwalk_step(DWalk &w, DBest &b, __amdgpu_buffer_r
     dconsider(b, qxy, qz, t1);
     dconsider(b, qxy, qz, t2);
     dconsider(b, qxy, qz, t3);
-    limit2 = min_nn(limit2, b.d);
+    limit2 = min_nn(limit2, dbest_d(b));
     // beyond this chunk (in walking direction) every point of the cell is at least `gap` away in x
     const float gap = (w.back ? qxy.x - __uint_as_float(t0.x) : __uint_as_float(t3.x) - qxy.x) - x_slack;
-    if (gap > 0.0f && gap * gap + w.yz2 > limit2) w.left = 0;
+    // (a select, not a branch: as `if (gap > 0 && ...) left = 0` this was two nested divergent regions per trip)
+    const bool done = (gap > 0.0f) & (gap * gap + w.yz2 > limit2);
+    w.left = done ? 0 : w.left;
 }
 
 struct DDiag {       // diagnostic launches only: per-lane step counts and two clock stamps
@@ -465,7 +489,7 @@ __device__ __forceinline__ void dense_seed(const DRes &rs, const DQuery &q, int 
     if (seed_pos >= 0) {
         const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rs.pts, (uint32_t)seed_pos * 16u, 0, 0);
         dconsider(b, f32x2{q.qx, q.qy}, q.qz, t);
-        limit2 = fminf(limit2, b.d);
+        limit2 = fminf(limit2, dbest_d(b));
     }
 }
 
@@ -675,7 +699,7 @@ __device__ __forceinline__ void dense_far_row(const DenseDev &g, const DRes &rs,
         dwalk_open(w, u32x2{s1, e1}, false, yz2, sp);   // the part to the right, from its left end
         while (w.left > 0) dwalk_step(w, b, rs.pts, qxy, q.qz, x_slack, limit2);
     }
-    limit2 = fminf(limit2, b.d);
+    limit2 = fminf(limit2, dbest_d(b));
 }
 
 template <bool kDiag = false>
@@ -743,7 +767,7 @@ __device__ __forceinline__ void dense_far_row_occ(const DenseDev &g, const DRes 
         dwalk_open(w, u32x2{s1, e1}, false, yz2, sp);
         while (w.left > 0) dwalk_step(w, b, rs.pts, qxy, q.qz, x_slack, limit2);
     }
-    limit2 = fminf(limit2, b.d);
+    limit2 = fminf(limit2, dbest_d(b));
 }
 
 template <bool kDiag = false>
@@ -800,10 +824,11 @@ __device__ __forceinline__ void dense_far_blocks(const DenseDev &g, const DRes &
 __device__ __forceinline__ Best dense_result(const DenseDev &g, const DBest &b)
 {
     Best out{~0ull, -1, FLT_MAX};
-    if (b.idx != 0xffffffffu) {
-        out.key = ((unsigned long long)__float_as_uint(b.d) << 32) | b.idx;
-        out.pos = (int)g.pos_of[b.idx];
-        out.d2 = b.d;
+    const uint32_t idx = dbest_idx(b);
+    if (idx != 0xffffffffu) {
+        out.key = (unsigned long long)__double_as_longlong(b.key);
+        out.pos = (int)g.pos_of[idx];
+        out.d2 = dbest_d(b);
     }
     return out;
 }
@@ -820,7 +845,7 @@ __device__ __forceinline__ Best nn_query_dense(const DenseDev &g, float qx, floa
     const DRes rs = dense_res(g);
     const DQuery q = dense_query(g, qx, qy, qz);
     float limit2 = g.prune2;
-    DBest b{__uint_as_float(0x7f800000u), 0xffffffffu};
+    DBest b = dbest_none();
     dense_near<kDiag, kFar == 3>(g, rs, q, seed_pos, b, limit2, sp, dg);
     if (kDiag) dg->t_near = wall_clock64();
     const bool far = kFar != 3 && dense_needs_far(g, limit2);
@@ -831,11 +856,8 @@ __device__ __forceinline__ Best nn_query_dense(const DenseDev &g, float qx, floa
     if (kDiag) dg->t_far = wall_clock64();
     // the lanes of a split query hold the bests of disjoint parts of the candidate set: the smallest
     // (distance, index) key among them is the query's (every lane of the group ends up with it)
-    for (uint32_t m = 1; m < (1u << sp.lg); m <<= 1) {
-        const unsigned long long mine = ((unsigned long long)__float_as_uint(b.d) << 32) | b.idx;
-        const unsigned long long other = (unsigned long long)__shfl_xor((long long)mine, (int)m);
-        if (other < mine) { b.d = __uint_as_float((uint32_t)(other >> 32)); b.idx = (uint32_t)other; }
-    }
+    for (uint32_t m = 1; m < (1u << sp.lg); m <<= 1)
+        b.key = min_key(b.key, __longlong_as_double(__shfl_xor(__double_as_longlong(b.key), (int)m)));
     return dense_result(g, b);
 }
 
