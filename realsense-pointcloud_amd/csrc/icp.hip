@@ -1004,6 +1004,7 @@ __global__ __launch_bounds__(kBlock) void k_recip_filter(const float4 *tgt, int 
                                                          const float4 *child_pts, const uint32_t *perm, const uint32_t *first)
 {
     const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (kDense) dense_ring1_setup(gd);
     if (u >= n) return;
     const int pos = corr_pos[u];
     if (pos < 0) return;

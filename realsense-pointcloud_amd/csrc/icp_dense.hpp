@@ -21,6 +21,7 @@
 #pragma once
 
 #include "icp_kernels.hpp"
+#include "ring1_offsets.hpp"
 
 namespace rsreg {
 
@@ -300,8 +301,6 @@ __global__ __launch_bounds__(kBlock) void k_dense_nbr(const uint32_t *cellslot, 
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float sel3(float a, float b, float c, int i) { return i == 0 ? a : (i == 1 ? b : c); }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -590,8 +589,36 @@ __device__ __forceinline__ uint32_t dense_own(const DenseDev &g, const DRes &rs,
     return occ;
 }
 
+// Where neighbour j of a cell lies in the padded table, in entries from the cell's own: 27 words of LDS (32 with the zeros
+// behind them), the same for every query of a grid, written once per workgroup (ring1_offset, ring1_offsets.hpp) and read with
+// one ds_read_b32 per cell a search moves to.  As arithmetic on j it was two 32-bit multiplies (quarter rate) and, the grid's
+// strides having been pushed out of the scalar registers, four lane reads per step; put together from +-sxy, +-sx, +-1 by
+// selects it needs the strides in vector registers and was slower than the multiplies.
+// EVERY kernel that searches calls dense_ring1_setup first, with all its threads, before any of them returns (it holds a
+// barrier); a workgroup has at least 32 threads.
+__device__ __forceinline__ int *dense_ring1_table()
+{
+    __shared__ int s_ring1_off[32];
+    return s_ring1_off;
+}
+
+__device__ __forceinline__ void dense_ring1_setup(const DenseDev &g)
+{
+    if (threadIdx.x < 32u) dense_ring1_table()[threadIdx.x] = threadIdx.x < 27u ? ring1_offset(ring1_cell((int)threadIdx.x), g.sx, g.sxy) : 0;
+    __syncthreads();
+}
+
 // ring 1, lane by lane: a flat loop -- a trip moves on to the next plausible cell and/or scores 4 candidates.  The range
 // of the cell after the current one is already in flight (nse) while the current one is scored.
+// A step to the next cell, as it now is (one divergent region, entered by the lanes whose walk has ended):
+//   * the pending range, if its bound still holds, is opened: its end to start from is the sign of nyz2 (the flag as a mask
+//     pair of its own was merged at the end of every region it crossed), its (y, z) distance |nyz2|;
+//   * j = lowest bit of the mask (v_ffbl; j = -1 with no cell left, and nothing of it is then used), the bit cleared;
+//   * ring1_cell(j): six compares (j against 9 and 18, j mod 9 against 3 and 6, j mod 3 against 1 and 2) that every select
+//     below shares -- no division of j, no multiply;
+//   * gx, gy, gz: two selects each; lb2 = ((gx + gy) + gz) * cell2, the same floats in the same order as ever;
+//   * the cell's range is asked for only if it is a cell and lb2 <= limit2 (one test, one region): table entry base + off[j],
+//     off[j] from the LDS table above; nyz2 = (gy + gz) * cell2 with the sign set for a cell that is read from its right end.
 template <bool kDiag = false>
 __device__ __forceinline__ void dense_ring1_lane(const DenseDev &g, const DRes &rs, const DQuery &q, const DRing1 &r1, uint32_t mask, DBest &b,
                                                  float &limit2, DSplit sp, DDiag *dg = nullptr)
@@ -599,33 +626,33 @@ __device__ __forceinline__ void dense_ring1_lane(const DenseDev &g, const DRes &
     if (!mask) return;
     const f32x2 qxy = {q.qx, q.qy};
     const float qz = q.qz, cell2 = g.cell * g.cell, x_slack = g.x_slack;
-    const float gx0 = r1.gx0, gx2 = r1.gx2, gy0 = r1.gy0, gy2 = r1.gy2, gz0 = r1.gz0, gz2 = r1.gz2, gx1 = 0.0f, gy1 = 0.0f, gz1 = 0.0f;
+    const float gx0 = r1.gx0, gx2 = r1.gx2, gy0 = r1.gy0, gy2 = r1.gy2, gz0 = r1.gz0, gz2 = r1.gz2;
     const int base = r1.base;
     const bool right_half = r1.right_half;
+    const int *off = dense_ring1_table();
     DWalk w;
     w.left = 0;
     u32x2 nse = {0u, 0u};
     float nlb2 = 0.0f, nyz2 = 0.0f;
-    bool nvalid = false, nback = false;
+    bool nvalid = false;
     for (;;) {
         if (w.left <= 0) {
             if (!nvalid && !mask) break;
-            if (nvalid && nlb2 <= limit2) dwalk_open(w, nse, nback, nyz2, sp);   // (the limit may have tightened since that range was asked for)
+            if (nvalid && nlb2 <= limit2) dwalk_open(w, nse, __float_as_int(nyz2) < 0, fabsf(nyz2), sp);   // (the limit may have tightened since that range was asked for)
             nvalid = false;
-            if (mask) {
-                if (kDiag) ++dg->r1_cells;
-                const int j = __ffs((int)mask) - 1;
-                mask &= mask - 1;
-                const int dz = j / 9, dy = (j - dz * 9) / 3, dx = j - dz * 9 - dy * 3;
-                const float lb2 = (sel3(gx0, gx1, gx2, dx) + sel3(gy0, gy1, gy2, dy) + sel3(gz0, gz1, gz2, dz)) * cell2;
-                if (lb2 <= limit2) {
-                    const int idx = base + (dz - 1) * g.sxy + (dy - 1) * g.sx + (dx - 1);
-                    nse = __builtin_amdgcn_raw_buffer_load_b64(rs.tab, (uint32_t)idx * 4u, 0, 0);
-                    nlb2 = lb2;
-                    nyz2 = (sel3(gy0, gy1, gy2, dy) + sel3(gz0, gz1, gz2, dz)) * cell2;
-                    nvalid = true;
-                    nback = dx == 0 ? true : (dx == 1 ? right_half : false);   // a cell to the left is read from its right end
-                }
+            if (kDiag && mask) ++dg->r1_cells;
+            const bool more = mask != 0;
+            const int j = __ffs((int)mask) - 1;
+            mask &= mask - 1;
+            const Ring1Cell c = ring1_cell(j);
+            const float gx = ring1_pick(c.x1, c.x2, gx0, 0.0f, gx2), gy = ring1_pick(c.y1, c.y2, gy0, 0.0f, gy2), gz = ring1_pick(c.z1, c.z2, gz0, 0.0f, gz2);
+            const float lb2 = ((gx + gy) + gz) * cell2;
+            if (more && lb2 <= limit2) {
+                nse = __builtin_amdgcn_raw_buffer_load_b64(rs.tab, (uint32_t)(base + off[j]) * 4u, 0, 0);
+                nlb2 = lb2;
+                const float yz2 = (gy + gz) * cell2;
+                nyz2 = (!c.x1 || (!c.x2 && right_half)) ? -yz2 : yz2;   // a cell to the left is read from its right end, the own column's as the own cell was
+                nvalid = true;
             }
         }
         if (w.left > 0) {
@@ -866,6 +893,7 @@ __global__ __launch_bounds__(kBlock) void k_nn_search_dense(const float4 *cur, u
                                                             int *corr_pos, float *corr_d2, int *seed)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    dense_ring1_setup(g);
     if (i >= n) return;
     const float4 q = cur[i];
     int pos = -1;
@@ -1002,6 +1030,7 @@ __global__ __launch_bounds__(kTile, kDiag == 1 ? 4 : 8) void k_icp_fused_dense(f
     if (item == 0xffffffffu) return;   // (a workgroup the schedule has nothing for)
     const uint32_t tile = item & 0xffffffu, lg = (item >> 28) & 3u;
     if (tile >= sched.n_tiles) return;   // (a carried schedule's tile that this source does not have)
+    dense_ring1_setup(g);                // (both returns above are the whole workgroup's)
     const uint32_t i = tile * kTile + threadIdx.x;
     if (dev && !restart) {   // device-resident loop: the increment comes from the previous k_icp_solve
         T = dev->t_inc;
