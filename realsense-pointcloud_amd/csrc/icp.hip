@@ -878,18 +878,16 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
     RSREG_HIP(ctx, ctx->d_first.reserve((n + 2) * 4));
     RSREG_HIP(ctx, ctx->d_partials.reserve((size_t)reduce_blocks(n) * RSREG_NUM_SUMS * 8));
     {
-        // the tile schedule's arrays (items | wave costs | done counters | ...) lie at offsets that depend on the buffer's capacity
-        // only, so that a schedule can be carried over to the next alignment (launch_fused); a new buffer starts from zero
-        // (the done counters go back to zero by themselves) and without a schedule
+        // the tile schedule's arrays lie at offsets that depend on the buffer's capacity only (tile_sched.hpp: sched_layout), so
+        // that a schedule can be carried over to the next alignment; a new buffer starts from zero (the done counters go back
+        // to zero by themselves) and without a schedule
         // (a larger buffer can come back at the address of the one just freed: the capacity says whether it is a new one)
         void *before = ctx->d_sched.ptr;
         const size_t cap_before = ctx->d_sched.cap;
-        RSREG_HIP(ctx, ctx->d_sched.reserve((size_t)reduce_blocks(n) * 15 * 4 + 256));
+        RSREG_HIP(ctx, ctx->d_sched.reserve(sched_layout(reduce_blocks(n)).words * 4));
         if (ctx->d_sched.ptr != before || ctx->d_sched.cap != cap_before) {
             RSREG_HIP(ctx, hipMemsetAsync(ctx->d_sched.ptr, 0, ctx->d_sched.cap, ctx->stream));
-            ctx->sched_cap_tiles = (uint32_t)((ctx->d_sched.cap - 256) / (15 * 4));
-            ctx->sched_keep_items = 0;
-            ctx->sched_first_items = 0;
+            sched_regrown(ctx->sched, sched_capacity(ctx->d_sched.cap));
         }
     }
     RSREG_HIP(ctx, ctx->d_sums.reserve(64 * 8));
@@ -1222,19 +1220,7 @@ int launch_plane_sums(rsreg_ctx *ctx, double *sums)
     return RSREG_OK;
 }
 
-// ---- tile schedule of the fused dense kernel (icp_dense.hpp: TileSched) -------------------------------------
-// A launch of ~14 k waves on 8 k wave slots ends with a long tail: a few waves run 3x longer than the mean,
-// they all sit on the same (near, densely sampled) surfaces in every iteration, and nothing is left to fill
-// the slots around them.  The second launch of an alignment times every wave; from then on the tiles
-// are launched longest first, and the longest few per cent are searched by 2 or 4 lanes per query.
-// What is summed, and in which order, does not change.
-struct SchedCfg {
-    bool on = true;
-    double f4 = 0.0, f2 = 0.10;    // fractions of the tiles searched with 4 and with 2 lanes per query (swept on the bench pair)
-    uint32_t min_tiles = 1024;     // below this a launch does not even fill the wave slots once
-    int at_launch = 1;             // the launch that is timed (0 = the first, which runs without seeds)
-};
-
+// ---- tile schedule of the fused dense kernel (tile_sched.hpp: what it is for, its layout, state and launch rule) ----------
 SchedCfg sched_cfg()
 {
     const Tunables &t = tunables();
@@ -1247,18 +1233,17 @@ SchedCfg sched_cfg()
     return c;
 }
 
-constexpr int kSchedKeepFor = 8;   // alignments a tile schedule serves before a launch is timed again
+static_assert(kSchedCostWords == kTileWaves, "the schedule buffer holds one cost word per wave of a tile");
 
 struct SchedBufs {
-    uint32_t *items, *cost, *done, *keys, *keys_alt, *vals, *vals_alt, *items_first;
+    uint32_t *items, *cost, *done, *items_first;
 };
 
-SchedBufs sched_bufs(const rsreg_ctx *ctx, uint32_t n_tiles)
+SchedBufs sched_bufs(const rsreg_ctx *ctx)
 {
     uint32_t *p = ctx->d_sched.as<uint32_t>();
-    (void)n_tiles;
-    const size_t t = ctx->sched_cap_tiles;   // (capacity, not this source's tiles: the arrays stay put from one alignment to the next)
-    return SchedBufs{p, p + 4 * t, p + 6 * t, p + 7 * t, p + 8 * t, p + 9 * t, p + 10 * t, p + 11 * t};
+    const SchedLayout l = sched_layout(ctx->sched.cap_tiles);   // (capacity, not this source's tiles: the arrays stay put from one alignment to the next)
+    return SchedBufs{p + l.items, p + l.cost, p + l.done, p + l.items_first};
 }
 
 // The whole schedule in one workgroup (7 k tiles at 10^6 points; three kernels and a device-wide radix sort of 10-bit
@@ -1266,112 +1251,39 @@ SchedBufs sched_bufs(const rsreg_ctx *ctx, uint32_t n_tiles)
 // wave ran in the timed launch, in steps of 0.64 us, longest first, then rank r -> its workgroups: the first n4 tiles
 // get four, the next n2 two, the others one.  Tiles of one step come in whatever order the atomics hand out: the order
 // of the workgroups decides when a tile runs, never what it computes.
-__global__ __launch_bounds__(1024) void k_sched_build(const uint32_t *cost, uint32_t n_tiles, uint32_t n4, uint32_t n2, uint32_t *items, uint32_t *done)
-{
-    __shared__ uint32_t bins[1024];
-    __shared__ uint32_t part[16];
-    bins[threadIdx.x] = 0;
-    __syncthreads();
-    auto key_of = [&](uint32_t t) {
-        uint32_t c = 0;
-        for (int w = 0; w < kTileWaves; ++w) c = max(c, cost[t * kTileWaves + w]);
-        return 1023u - min(c >> 6, 1023u);
-    };
-    for (uint32_t t = threadIdx.x; t < n_tiles; t += 1024u) {
-        atomicAdd(&bins[key_of(t)], 1u);
-        done[t] = 0u;
-    }
-    __syncthreads();
-    // exclusive scan of the 1024 bins: one per thread
-    const uint32_t mine = bins[threadIdx.x], lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off);
-        if ((int)lane >= off) incl += v;
-    }
-    if (lane == 63u) part[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w) before += part[w];
-    __syncthreads();
-    bins[threadIdx.x] = before + incl - mine;
-    __syncthreads();
-    for (uint32_t t = threadIdx.x; t < n_tiles; t += 1024u) {
-        const uint32_t r = atomicAdd(&bins[key_of(t)], 1u);
-        uint32_t lg, base;
-        if (r < n4) { lg = 2; base = 4 * r; }
-        else if (r < n4 + n2) { lg = 1; base = 4 * n4 + 2 * (r - n4); }
-        else { lg = 0; base = 4 * n4 + 2 * n2 + (r - n4 - n2); }
-        for (uint32_t p = 0; p < (1u << lg); ++p) items[base + p] = t | p << 24 | lg << 28;
-    }
-}
-
-// The same schedule, XCD-aware (RSREG_SCHED_XCD, default on): workgroups are dealt to the eight XCDs in turn (b and
-// b + 8 share one, MI355X_MICROARCH.md "Workgroup dispatch"), and every XCD has a 4 MiB L2 of its own.  The tiles are in
-// the source's Morton order, so a run of consecutive tiles is a compact piece of space: pieces of `deal` (32) consecutive
-// tiles are dealt to eight runs in turn, each run is sorted longest first by itself, and the runs are dealt out to the
-// workgroups in turn: workgroup b works on run b % 8 while that run lasts, so one XCD's L2 sees an eighth of the target's
-// cells instead of all of them.  When a run is used up the others close ranks (no empty workgroups; those last tiles land
-// on whatever XCD is next).  Which workgroup takes which tile never changes what a tile computes.
-// Measured (profiles/r03_experiments/xcd_schedule_*): 300 k points 53.6 -> 48.7 us per launch (the eighth of the index
-// fits the L2), 10^6 points level (96.9 against 96.5-98.3); pieces of 64+ tiles or eight contiguous runs of equal cost
-// (deal = 0) are slower at 10^6 (102-103 us: the heavy tiles of a crowded region then share one XCD's 256 workgroup
-// slots); a few cost classes with the Morton order kept inside a class are slower the coarser the classes (97 -> 117 us).
-__global__ __launch_bounds__(1024) void k_sched_build_xcd(const uint32_t *cost, uint32_t n_tiles, uint32_t n4, uint32_t n2, uint32_t total_items,
-                                                          uint32_t deal, uint32_t *items, uint32_t *done)
+// The list is XCD-aware: workgroups are dealt to the eight XCDs in turn (b and b + 8 share one, MI355X_MICROARCH.md
+// "Workgroup dispatch"), and every XCD has a 4 MiB L2 of its own.  The tiles are in the source's Morton order, so a run of
+// consecutive tiles is a compact piece of space: pieces of `deal` (RSREG_SCHED_XCD_DEAL, 32) consecutive tiles are dealt
+// to eight runs in turn, each run is sorted longest first by itself, and the runs are dealt out to the workgroups in turn:
+// workgroup b works on run b % 8 while that run lasts, so one XCD's L2 sees an eighth of the target's cells instead of all
+// of them.  When a run is used up the others close ranks (no empty workgroups; those last tiles land on whatever XCD is
+// next).  Which workgroup takes which tile never changes what a tile computes.
+// Measured (profiles/r03_experiments/xcd_schedule_*) against one longest-first list for all XCDs: 300 k points 53.6 ->
+// 48.7 us per launch (the eighth of the index fits the L2), 10^6 points level (96.9 against 96.5-98.3); pieces of 64+ tiles
+// or eight contiguous runs of equal cost are slower at 10^6 (102-103 us: the heavy tiles of a crowded region then share
+// one XCD's 256 workgroup slots); a few cost classes with the Morton order kept inside a class are slower the coarser the
+// classes (97 -> 117 us).  (The single list and the equal-cost runs were forms of this kernel up to 730cb2e.)
+__global__ __launch_bounds__(1024) void k_sched_build(const uint32_t *cost, uint32_t n_tiles, uint32_t n4, uint32_t n2, uint32_t total_items,
+                                                      uint32_t deal, uint32_t *items, uint32_t *done)
 {
     constexpr uint32_t kRuns = 8;
     __shared__ uint32_t bins[kRuns * 1024];
     __shared__ uint32_t part[16];
     __shared__ uint32_t run_first[kRuns + 1];   // rank, in run-major sorted order, of the first tile of a run
-    __shared__ uint32_t total_cost;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     for (uint32_t k = tid; k < kRuns * 1024u; k += 1024u) bins[k] = 0;
+    __syncthreads();
     auto bucket_of = [&](uint32_t t) {   // 0 .. 1023, steps of 0.64 us, longer = larger
         uint32_t c = 0;
         for (int w = 0; w < kTileWaves; ++w) c = max(c, cost[t * kTileWaves + w]);
         return min(c >> 6, 1023u);
     };
-    auto block_exclusive = [&](uint32_t mine, uint32_t *total) -> uint32_t {   // over the 1024 threads, in thread order
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t v = __shfl_up(incl, off);
-            if ((int)lane >= off) incl += v;
-        }
-        __syncthreads();
-        if (lane == 63u) part[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (uint32_t w = 0; w < 16u; ++w) {
-            if (w < wave) before += part[w];
-            all += part[w];
-        }
-        if (total) *total = all;
-        return before + incl - mine;
-    };
-    // every thread owns a contiguous share of the tiles: their cost before them, in natural order
+    auto run_of = [&](uint32_t t) { return (t / deal) % kRuns; };
+    // every thread owns a contiguous share of the tiles
     const uint32_t per = (n_tiles + 1023u) / 1024u, lo = min(n_tiles, tid * per), hi = min(n_tiles, lo + per);
-    uint32_t mine = 0;
-    for (uint32_t t = lo; t < hi; ++t) mine += bucket_of(t) + 1u;
-    uint32_t all = 0;
-    const uint32_t before = block_exclusive(mine, &all);
-    if (tid == 0) total_cost = all;
-    __syncthreads();
-    const uint32_t C = max(total_cost, 1u);
-    // deal == 0: eight contiguous runs of equal cost; deal > 0: pieces of `deal` consecutive tiles dealt to the runs in turn
-    auto run_of = [&](uint32_t t, uint32_t cost_before) {
-        return deal ? (t / deal) % kRuns : min(kRuns - 1u, (uint32_t)(((unsigned long long)cost_before * kRuns) / C));
-    };
-    {
-        uint32_t at = before;
-        for (uint32_t t = lo; t < hi; ++t) {
-            const uint32_t b = bucket_of(t);
-            atomicAdd(&bins[run_of(t, at) * 1024u + (1023u - b)], 1u);
-            at += b + 1u;
-            done[t] = 0u;
-        }
+    for (uint32_t t = lo; t < hi; ++t) {
+        atomicAdd(&bins[run_of(t) * 1024u + (1023u - bucket_of(t))], 1u);
+        done[t] = 0u;
     }
     __syncthreads();
     // exclusive scan of the 8 x 1024 bins, run-major: eight consecutive bins per thread
@@ -1379,7 +1291,16 @@ __global__ __launch_bounds__(1024) void k_sched_build_xcd(const uint32_t *cost, 
         uint32_t v[8], sum = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) { v[k] = bins[tid * 8u + k]; sum += v[k]; }
-        uint32_t at = block_exclusive(sum, nullptr);
+        uint32_t incl = sum;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t u = __shfl_up(incl, off);
+            if ((int)lane >= off) incl += u;
+        }
+        if (lane == 63u) part[wave] = incl;
+        __syncthreads();
+        uint32_t at = incl - sum;
+        for (uint32_t w = 0; w < wave; ++w) at += part[w];
         if ((tid & 127u) == 0) run_first[tid >> 7] = at;   // (bin x * 1024 is thread 128 x's first)
         if (tid == 0) run_first[kRuns] = n_tiles;
 #pragma unroll
@@ -1402,58 +1323,35 @@ __global__ __launch_bounds__(1024) void k_sched_build_xcd(const uint32_t *cost, 
         for (uint32_t y = 0; y < kRuns; ++y) pos += min(len[y], p + (y < x ? 1u : 0u));
         return pos;
     };
-    {
-        uint32_t at = before;
-        for (uint32_t t = lo; t < hi; ++t) {
-            const uint32_t b = bucket_of(t), x = run_of(t, at);
-            at += b + 1u;
-            const uint32_t r = atomicAdd(&bins[x * 1024u + (1023u - b)], 1u) - run_first[x];   // rank inside its run, longest first
-            uint32_t lg, p;
-            if (r < r4[x]) { lg = 2; p = 4u * r; }
-            else if (r < r4[x] + r2[x]) { lg = 1; p = 4u * r4[x] + 2u * (r - r4[x]); }
-            else { lg = 0; p = 4u * r4[x] + 2u * r2[x] + (r - r4[x] - r2[x]); }
-            for (uint32_t q = 0; q < (1u << lg); ++q) items[place(x, p + q)] = t | q << 24 | lg << 28;
-        }
+    for (uint32_t t = lo; t < hi; ++t) {
+        const uint32_t b = bucket_of(t), x = run_of(t);
+        const uint32_t r = atomicAdd(&bins[x * 1024u + (1023u - b)], 1u) - run_first[x];   // rank inside its run, longest first
+        uint32_t lg, p;
+        if (r < r4[x]) { lg = 2; p = 4u * r; }
+        else if (r < r4[x] + r2[x]) { lg = 1; p = 4u * r4[x] + 2u * (r - r4[x]); }
+        else { lg = 0; p = 4u * r4[x] + 2u * r2[x] + (r - r4[x] - r2[x]); }
+        for (uint32_t q = 0; q < (1u << lg); ++q) items[place(x, p + q)] = t | q << 24 | lg << 28;
     }
     for (uint32_t k = used + tid; k < total_items; k += 1024u) items[k] = 0xffffffffu;   // (a run shorter than its share of the splits: nothing to do)
 }
 
 // first: the schedule of the alignments' FIRST launches (from a timed first launch; kept beside the steady one)
-int build_schedule(rsreg_ctx *ctx, uint32_t n_tiles, bool first = false)
+int build_schedule(rsreg_ctx *ctx, uint32_t n_tiles, bool first)
 {
     const SchedCfg cfg = sched_cfg();
-    if (n_tiles > ctx->sched_cap_tiles) return fail(ctx, RSREG_ERR_STATE, "tile schedule: more tiles than the schedule buffer was laid out for");
-    const SchedBufs sb = sched_bufs(ctx, n_tiles);
-    hipStream_t st = ctx->stream;
+    if (n_tiles > ctx->sched.cap_tiles) return fail(ctx, RSREG_ERR_STATE, "tile schedule: more tiles than the schedule buffer was laid out for");
+    const SchedBufs sb = sched_bufs(ctx);
     uint32_t n4 = (uint32_t)(cfg.f4 * n_tiles), n2 = (uint32_t)(cfg.f2 * n_tiles);
-    const bool xcd = tunables().sched_xcd;
-    uint32_t *items = first ? sb.items_first : sb.items;
-    if (xcd) {
-        n4 -= n4 % 8u;   // (an eighth of the splits to every run)
-        n2 -= n2 % 8u;
-        const uint32_t deal = tunables().sched_xcd_deal;
-        k_sched_build_xcd<<<1, 1024, 0, st>>>(sb.cost, n_tiles, n4, n2, n_tiles + 3 * n4 + n2, deal, items, sb.done);
-    } else {
-        k_sched_build<<<1, 1024, 0, st>>>(sb.cost, n_tiles, n4, n2, items, sb.done);
-    }
-    RSREG_HIP(ctx, hipGetLastError());
+    n4 -= n4 % 8u;   // (an eighth of the splits to every run)
+    n2 -= n2 % 8u;
     const uint32_t n_items = n_tiles + 3 * n4 + n2;
-    if (first) {
-        ctx->sched_first_items = n_items;
-        ctx->sched_first_tiles = n_tiles;
-        ctx->sched_first_age = 0;
-        return RSREG_OK;
-    }
-    ctx->icp.sched_items = n_items;
-    ctx->sched_keep_items = ctx->icp.sched_items;   // (kept for the alignments to come: launch_fused)
-    ctx->sched_keep_tiles = n_tiles;
-    ctx->sched_keep_age = 0;
+    k_sched_build<<<1, 1024, 0, ctx->stream>>>(sb.cost, n_tiles, n4, n2, n_items, tunables().sched_xcd_deal, first ? sb.items_first : sb.items, sb.done);
+    RSREG_HIP(ctx, hipGetLastError());
+    sched_built(ctx->sched, ctx->icp.sched, first, n_items, n_tiles);
 #ifdef RSREG_DIAG
-    if (tunables().sched_verbose)
-        std::fprintf(stderr, "[rsreg] tile schedule: %u tiles, %u searched by 4 lanes per query, %u by 2, %u workgroups\n", n_tiles, n4, n2,
-                     ctx->icp.sched_items);
+    if (!first && tunables().sched_verbose)
+        std::fprintf(stderr, "[rsreg] tile schedule: %u tiles, %u searched by 4 lanes per query, %u by 2, %u workgroups\n", n_tiles, n4, n2, n_items);
 #endif
-    ctx->icp.sched_ready = true;
     return RSREG_OK;
 }
 
@@ -1468,7 +1366,7 @@ int launch_fused(rsreg_ctx *ctx, double *sums, bool want_corr, bool device_loop 
     // the first launch of an alignment over the dense index reads the source itself, applies the guess and starts without
     // seeds: k_restart_source's work, one launch and a pass over the working copy saved (never with a schedule of this
     // alignment's own in place: that is built from one of its launches; a carried one may serve it, below)
-    const bool restart_here = s.restart_pending && ctx->grid.dense && !s.sched_ready && !s.pending_transform;
+    const bool restart_here = s.restart_pending && ctx->grid.dense && !s.sched.ready && !s.pending_transform;
     if (restart_here) {
         s.restart_pending = false;
     } else {
@@ -1494,62 +1392,26 @@ int launch_fused(rsreg_ctx *ctx, double *sums, bool want_corr, bool device_loop 
 #endif
             const SchedCfg cfg = sched_cfg();
             const uint32_t n_tiles = reduce_blocks(n);
-            const bool sched_ok = cfg.on && (!wt || light) && n_tiles >= cfg.min_tiles && n_tiles < (1u << 24) &&
-                                  n_tiles <= ctx->sched_cap_tiles;   // (the arrays of sched_bufs are laid out for that many tiles)
+            const SchedLaunch l = sched_next(cfg, ctx->sched, s.sched, n_tiles, restart_here, wt && !light);
             TileSched sc{};
             sc.n_tiles = n_tiles;
-            uint32_t grid = n_tiles;
-            if (sched_ok) {
-                const SchedBufs sb = sched_bufs(ctx, n_tiles);
+            if (l.eligible) {
+                const SchedBufs sb = sched_bufs(ctx);
+                sc.items = l.from == SchedLaunch::first ? sb.items_first : l.from == SchedLaunch::steady ? sb.items : nullptr;
+                sc.cost = l.timed ? sb.cost : nullptr;
                 sc.done = sb.done;
                 sc.pos = ctx->d_corr_pos.as<int>();
                 sc.d2 = ctx->d_corr_d2.as<float>();
-                // The schedule of an earlier alignment of this context serves this one too, from the launch that would otherwise be
-                // timed: the long tiles sit on the same (near, densely sampled) surfaces from one frame to the next, a schedule is
-                // an order of work and never wrong, and the timed launch runs unscheduled (140 against 93 us at 10^6 points).
-                // Carried for at most kSchedKeepFor alignments and only to a source of about as many tiles; RSREG_SCHED_KEEP=0: never.
-                auto fits = [&](uint32_t tiles) { return n_tiles + n_tiles / 8 >= tiles && tiles + tiles / 8 >= n_tiles; };
-                const bool keep = tunables().sched_keep;
-                bool first_sched = false, time_first = false;
-                if (restart_here && keep) {
-                    // the FIRST launch (unseeded, from the source itself under the guess: the only launch the reference's
-                    // parameters ever run) has a cost profile of its own: it is timed once and scheduled from its own
-                    // kind's costs in the alignments that follow
-                    if (ctx->sched_first_items && ctx->sched_first_age < kSchedKeepFor && fits(ctx->sched_first_tiles)) {
-                        first_sched = true;
-                        ++ctx->sched_first_age;
-                    } else {
-                        time_first = true;
-                    }
-                }
-                if (!s.sched_ready && !restart_here && s.fused_launches >= cfg.at_launch && ctx->sched_keep_items && keep &&
-                    ctx->sched_keep_age < kSchedKeepFor && fits(ctx->sched_keep_tiles)) {
-                    s.sched_ready = true;
-                    s.sched_carried = true;
-                    s.sched_items = ctx->sched_keep_items + (n_tiles > ctx->sched_keep_tiles ? n_tiles - ctx->sched_keep_tiles : 0u);
-                    ++ctx->sched_keep_age;
-                }
-                if (first_sched) {
-                    sc.items = sb.items_first;
-                    sc.n_items = ctx->sched_first_items;
-                    sc.first_extra = ctx->sched_first_tiles;
-                    grid = ctx->sched_first_items + (n_tiles > ctx->sched_first_tiles ? n_tiles - ctx->sched_first_tiles : 0u);
-                } else if (s.sched_ready) {
-                    sc.items = sb.items;
-                    grid = s.sched_items;
-                    sc.n_items = s.sched_carried ? ctx->sched_keep_items : grid;
-                    sc.first_extra = ctx->sched_keep_tiles;
-                } else if (time_first || (!restart_here && s.fused_launches == cfg.at_launch)) {
-                    sc.cost = sb.cost;
-                }
+                sc.n_items = l.n_items;
+                sc.first_extra = l.first_extra;
             }
-            kern<<<grid, kTile, 0, ctx->stream>>>(
+            kern<<<l.grid, kTile, 0, ctx->stream>>>(
                 ctx->d_cur.as<float4>(), restart_here ? ctx->d_src.as<float4>() : nullptr, ctx->d_first.as<uint32_t>(), n, to_mat34(restart_here ? s.final_t : s.t_inc),
                 restart_here ? (s.final_t.is_identity() ? 0 : 1) : (s.pending_transform ? 1 : 0),
                 dense_dev(ctx, s.prm.max_correspondence_distance), gate2, want_corr ? ctx->d_corr_pos.as<int>() : nullptr,
                 ctx->d_corr_d2.as<float>(), ctx->d_partials.as<double>(), seed_ptr(ctx), wt, dev, sc);
             RSREG_HIP(ctx, hipGetLastError());
-            if (sc.cost) {
+            if (l.timed) {
                 int rc = build_schedule(ctx, n_tiles, restart_here);
                 if (rc) return rc;
                 if (restart_here && cfg.at_launch == 0) {   // (RSREG_SCHED_AT=0: the steady schedule from the first launch's costs too)
@@ -1557,7 +1419,7 @@ int launch_fused(rsreg_ctx *ctx, double *sums, bool want_corr, bool device_loop 
                     if (rc) return rc;
                 }
             }
-            s.fused_launches++;
+            s.sched.fused_launches++;
             if (sc.items) s.n_sched_launches++;
         }
         else
@@ -2215,7 +2077,7 @@ int icp_end(rsreg_ctx *ctx, rsreg_icp_result *result, void *aligned_out, size_t 
     if (const char *wt_path = tunables().wave_times) {
         if (ctx->grid.dense == 1 && ctx->n_work) {
             const bool light = tunables().wave_times_light;
-            const size_t nw = light ? (size_t)(ctx->icp.sched_ready ? ctx->icp.sched_items : reduce_blocks(ctx->n_work)) * kTileWaves
+            const size_t nw = light ? (size_t)(ctx->icp.sched.ready ? ctx->icp.sched.items : reduce_blocks(ctx->n_work)) * kTileWaves
                                     : (ctx->n_work + 63) / 64;
             std::vector<unsigned long long> h(16 * nw + (light ? 0 : (ctx->n_work + 1) / 2));   // wave records, then a uint32 of step counts per lane
             (void)hipMemcpy(h.data(), ctx->d_brick.ptr, h.size() * 8, hipMemcpyDeviceToHost);

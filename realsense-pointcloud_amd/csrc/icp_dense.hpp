@@ -22,6 +22,7 @@
 
 #include "icp_kernels.hpp"
 #include "ring1_offsets.hpp"
+#include "tile_sched.hpp"
 
 namespace rsreg {
 
@@ -910,23 +911,7 @@ __global__ __launch_bounds__(kBlock) void k_nn_search_dense(const float4 *cur, u
     corr_d2[i] = d2;
 }
 
-// How the workgroups of a fused launch map to tiles (icp.hip: build_schedule).  All null: workgroup b is tile b.
-// With a schedule, the tiles that took longest in an earlier iteration come first, and the longest of
-// them are split: 2 or 4 workgroups share the tile's 128 queries, 2 or 4 lanes search each query (DSplit),
-// and whichever of those workgroups finishes last adds up the tile's 17 sums in the usual order.
-struct TileSched {
-    const uint32_t *items;   // per workgroup: tile | part << 24 | log2(lanes per query) << 28
-    uint32_t *cost;          // per wave of an unsplit tile: how long it ran in this launch (100 MHz ticks), or null
-    uint32_t *done;          // per tile: parts finished so far (split tiles; goes back to 0 by itself)
-    int *pos;                // per query: where the parts of a split tile leave their matches
-    float *d2;
-    uint32_t n_tiles;        // slabs of `partials`
-    // A schedule carried over from an earlier alignment of this context (icp.hip: launch_fused) was built for another source:
-    // workgroups [0, n_items) take its items -- those of tiles this source does not have do nothing --, the workgroups
-    // behind them the tiles it did not know, first_extra + 0, 1, ..., unsplit.  (A schedule of this alignment's own: n_items =
-    // the grid, no extras.)
-    uint32_t n_items, first_extra;
-};
+// How the workgroups of a fused launch map to tiles: TileSched (tile_sched.hpp, with the rule that fills it in: sched_next).
 
 // device-wide visible accesses for what the parts of a split tile hand to each other inside one launch
 // (they may run on different XCDs, whose L2s are not coherent for ordinary accesses)

@@ -22,6 +22,7 @@
 #include "tunables.hpp"
 #include "owned.hpp"
 #include "workers.hpp"
+#include "tile_sched.hpp"
 
 namespace rsreg {
 
@@ -231,10 +232,7 @@ struct IcpState {
     double ms_nn = 0, ms_reduce = 0, ms_transform = 0;
     int n_nn_launches = 0;
     int n_sched_launches = 0;      // ... of them launched from a tile schedule
-    int fused_launches = 0;        // fused dense launches of this alignment so far
-    bool sched_ready = false;      // d_sched holds a tile schedule for this alignment
-    uint32_t sched_items = 0;      // workgroups of a scheduled launch
-    bool sched_carried = false;    // ... whose schedule an earlier alignment of the context built
+    SchedRun sched;                // the tile schedule of the fused dense launches, as this alignment sees it (tile_sched.hpp)
     bool idle_after_sums = false;  // the caller's thread has waited for the main stream (the sums) and queued nothing since: rsreg_icp_end need not wait again
 };
 
@@ -262,14 +260,8 @@ struct rsreg_ctx {
     rsreg::DevBuf d_cellpos;      // uint32[n_cells+1]: first sorted point of each occupied cell
     rsreg::DevBuf d_dense;        // dense mode: uint32[(nx+2)(ny+2)(nz+2)+1] first sorted point of EVERY cell, followed by one uint32 per cell: occupancy of its 27-cell neighbourhood
     rsreg::DevBuf d_pos_of;       // dense mode: uint32 per target record, its position in d_tgt_sorted
-    rsreg::DevBuf d_sched;        // tile schedule of the fused dense kernel: items (4 per tile) | wave costs | done counters | sort scratch
-    uint32_t sched_cap_tiles = 0;        // tiles the buffer was laid out for (the arrays' offsets)
-    uint32_t sched_keep_items = 0, sched_keep_tiles = 0;   // the last schedule built in it: workgroups, tiles of its source (0: none)
-    int sched_keep_age = 0;              // alignments it has served since
-    // the same for the FIRST launch of an alignment (unseeded, from the source itself: another cost profile), built from a timed
-    // first launch and kept beside the steady one
-    uint32_t sched_first_items = 0, sched_first_tiles = 0;
-    int sched_first_age = 0;
+    rsreg::DevBuf d_sched;        // tile schedule of the fused dense kernel, uint32 words: items (4 per tile) | wave costs (2) | done counters (1) | first-launch items (4): sched_layout
+    rsreg::SchedKept sched;       // what the buffer was laid out for and the schedules kept in it (tile_sched.hpp)
     rsreg::DevBuf d_keys, d_keys_alt, d_vals, d_vals_alt, d_flags, d_scan, d_brick, d_tmp;
     rsreg::DevBuf d_misc;         // small: bbox, counters
     rsreg::DevBuf d_cnt;          // counting build (cellsort.hpp): points per table slot, all zero between builds

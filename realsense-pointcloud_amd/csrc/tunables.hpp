@@ -41,9 +41,7 @@ struct Tunables {
     double sched_f4 = 0.0, sched_f2 = 0.10;   // RSREG_SCHED_F4 / _F2: fractions of the tiles searched by 4 / 2 lanes per query
     uint32_t sched_min_tiles = 1024;       // RSREG_SCHED_MIN_TILES
     int sched_at = 1;                      // RSREG_SCHED_AT: the launch that is timed
-    bool sched_xcd = true;                 // RSREG_SCHED_XCD=0
-    uint32_t sched_xcd_deal = 32;          // RSREG_SCHED_XCD_DEAL
-    bool sched_keep = true;                // RSREG_SCHED_KEEP=0: every alignment times a launch of its own and builds its own schedule
+    uint32_t sched_xcd_deal = 32;          // RSREG_SCHED_XCD_DEAL: consecutive tiles dealt to one XCD at a time (at least 1)
     // ---- clouds, NDT
     long long cloud_pool_mb = 4096;        // RSREG_CLOUD_POOL_MB
     bool ndt_watch = true;                 // RSREG_NDT_NO_WATCH: hipStreamSynchronize instead of watching the stamped pass number
@@ -87,9 +85,7 @@ template <typename Get> inline Tunables tunables_read(Get get)
     if (const char *e = get("RSREG_SCHED_AT")) v.sched_at = std::atoi(e);
     v.sched_f4 = std::min(std::max(v.sched_f4, 0.0), 1.0);
     v.sched_f2 = std::min(std::max(v.sched_f2, 0.0), 1.0 - v.sched_f4);   // (every tile at most once: up to 4 workgroups per tile)
-    v.sched_xcd = !off("RSREG_SCHED_XCD");
-    if (const char *e = get("RSREG_SCHED_XCD_DEAL")) v.sched_xcd_deal = (uint32_t)std::atoi(e);
-    v.sched_keep = !off("RSREG_SCHED_KEEP");
+    if (const char *e = get("RSREG_SCHED_XCD_DEAL")) v.sched_xcd_deal = (uint32_t)std::max(1, std::atoi(e));
     if (const char *e = get("RSREG_CLOUD_POOL_MB")) v.cloud_pool_mb = std::max(0ll, std::atoll(e));
     v.ndt_watch = !set("RSREG_NDT_NO_WATCH");
 #ifdef RSREG_DIAG

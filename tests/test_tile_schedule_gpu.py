@@ -1,4 +1,5 @@
-"""The tile schedule of the fused search kernel (csrc/icp.hip: build_schedule): tiles launched longest first,
+"""The tile schedule of the fused search kernel (csrc/tile_sched.hpp: the launch rule sched_next, whose cases run without a GPU in
+test_tile_sched_cpu.py; csrc/icp.hip: build_schedule, launch_fused): tiles launched longest first,
 the longest ones searched by 2 or 4 lanes per query.  It may change WHEN a query is searched and by how many
 lanes, never what is found or how the 17 sums are added up: every result must be bit-identical to the
 unscheduled launch."""
@@ -204,3 +205,37 @@ def test_carried_schedule_serves_the_first_launch(api, rs, monkeypatch):
             assert 0 < r.n_scheduled_launches < r.n_nn_launches    # built in this alignment: its first launches run unscheduled
         else:
             assert r.n_scheduled_launches == r.n_nn_launches, (k, r.n_scheduled_launches, r.n_nn_launches)
+
+
+def test_kept_schedules_expire_and_follow_the_tile_count(api, frames, monkeypatch):
+    """Twelve alignments of one context on the 50 k pair (391 tiles, every launch eligible, a quarter of the tiles split in
+    four and a quarter in two): the first times its first two launches and builds both schedules, the next eight are served
+    from their first launch on, the tenth finds both schedules expired (kSchedKeepFor = 8) and builds anew, a source of half
+    the tiles and then the full one again are each too far from the kept tile count (sched_fits) and build anew.  Every
+    alignment gives the bits of a fresh, unscheduled context."""
+    src, tgt = frames[("50k", "parity")]
+    n = len(src)
+    half = type(src)(src.points[: n // 2].copy(), width=n // 2, height=1, is_dense=False)
+    monkeypatch.setenv("RSREG_SCHED", "0")
+    base_full, kind = _run(api, src, tgt, 2, 4, 0.02)
+    if kind != 1:
+        pytest.skip("the schedule belongs to the dense-table search")
+    base_half, _ = _run(api, half, tgt, 2, 4, 0.02)
+    monkeypatch.setenv("RSREG_SCHED", "1")
+    monkeypatch.setenv("RSREG_SCHED_MIN_TILES", "1")
+    monkeypatch.setenv("RSREG_SCHED_F4", "0.25")
+    monkeypatch.setenv("RSREG_SCHED_F2", "0.25")
+    icp = api.IterativeClosestPoint(api.Context(0))
+    icp.params = api.icp_params(max_iterations=4, criteria_mode=1, pipeline_mode=2, max_correspondence_distance=0.02)
+    icp.setInputTarget(tgt)
+    unscheduled = []
+    for k in range(12):
+        icp.setInputSource(half if k == 10 else src)
+        out = icp.align()
+        r = icp.result
+        got = (bytes(r.transform), bytes(r.sums_last), r.n_correspondences, r.iterations, r.state, r.converged, r.mse,
+               np.stack([out.points[c] for c in "xyz"]).tobytes())
+        assert got == (base_half if k == 10 else base_full), k
+        unscheduled.append(r.n_nn_launches - r.n_scheduled_launches)
+    print("unscheduled launches per alignment:", unscheduled)
+    assert unscheduled == [2] + [0] * 8 + [2, 2, 2]
