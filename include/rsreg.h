@@ -553,6 +553,49 @@ int rsreg_cloud_knn(rsreg_ctx *ctx, const rsreg_cloud *in, int k, int32_t *index
  * (computeMeanAndCovarianceMatrix); this is the covariance the formula defines, in double, about the record.  A PCL build
  * agrees with it to PCL's own rounding. */
 int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const float viewpoint[3], rsreg_cloud *out);
+/* ---- pcl::FPFHEstimation with setKSearch(k), 2 <= k <= 64: the Simplified Point Feature Histogram of every record and the Fast
+ * Point Feature Histogram weighted from them.  PCL 1.9.1 features/impl/fpfh.hpp (computePointSPFHSignature,
+ * weightPointSPFHSignature) and pfh_tools.cpp (computePairFeatures), recalled; PCL is not available to check against, so what
+ * follows IS the contract.
+ * normals: n records (the same n as `in`, the same context), normal_x, normal_y, normal_z the first three floats of each, stride
+ * >= 12 and a multiple of 4: what rsreg_cloud_normals wrote is accepted as it is.  Another size or context, k outside 2 .. 64,
+ * fewer than k finite records: RSREG_ERR_INVALID_ARG, nothing launched.
+ * Neighbourhood N(i): the k neighbours of rsreg_cloud_knn, ascending by (d2, index), the record itself among them; d2(i, .) their
+ * float32 squared distances.
+ * Pair features of record i and neighbour j, in DOUBLE from the float inputs, no contraction.  Skipped when j == i.
+ *   dp = p_j - p_i; f4 = sqrt((dp.x^2 + dp.y^2) + dp.z^2); skipped when f4 == 0.
+ *   a1 = (n_i . dp) / f4, a2 = (n_j . dp) / f4, every dot product here summed as (x + y) + z.
+ *   fabs(a1) < fabs(a2): n1 = n_j, n2 = n_i, dp = -dp, f3 = -a2; otherwise n1 = n_i, n2 = n_j, f3 = a1.  (PCL's
+ *   acos(fabs(a1)) > acos(fabs(a2)), without the acos.)
+ *   v = dp x n1 = (dp.y n1.z - dp.z n1.y, dp.z n1.x - dp.x n1.z, dp.x n1.y - dp.y n1.x); |v| = sqrt((v.x^2 + v.y^2) + v.z^2);
+ *   skipped when |v| == 0; v = v / |v| (three divisions).
+ *   w = n1 x v (the same component formula); f2 = v . n2; f1 = atan2(w . n2, n1 . n2).
+ *   Skipped when n_i or n_j is not finite (a stated choice: PCL's behaviour there is undefined).
+ * Bins, 11 per feature: floor of 11 * ((f1 + pi) * (1 / (2 pi))), 11 * ((f2 + 1) * 0.5), 11 * ((f3 + 1) * 0.5), each clamped to
+ * [0, 10].
+ * SPFH row of record i: 33 floats, feature 1 first.  A bin hit by c pairs holds the float that adding
+ * hist_incr = 100.0f / (float)(k - 1) to 0.0f c times gives (PCL's sequential +=; the increments are equal, so the value depends
+ * on c alone).  A skipped pair adds nothing and hist_incr still uses k - 1.  A record that is not finite, or whose normal is not
+ * finite, has an all-zero row.
+ * FPFH row of record i, in float32, no contraction, in PCL's order:
+ *   for a in 0 .. k-1 (neighbour order): if d2[a] == 0 continue (the record itself, exact copies); w = 1.0f / d2[a];
+ *     for t in 0 .. 2: for b in 0 .. 10: val = SPFH[N(i)[a]][t][b] * w; sum_t += val; h[t][b] += val;
+ *   for t in 0 .. 2: if (sum_t != 0) sum_t = (float)(100.0 / (double)sum_t); h[t][b] *= sum_t.
+ * Two quirks of PCL are kept: the weight is 1 / SQUARED distance, and the record's own SPFH does not enter its FPFH.  A record
+ * with no neighbour at positive distance gives 33 zeros, never a division by zero.  A record that is not finite, or whose own
+ * normal is not finite, gets 33 quiet NaNs.
+ * DEVIATION FROM PCL 1.9.1, stated: PCL computes the pair features in float through Eigen; here they are computed in double.  A PCL
+ * build can differ where a feature lies within float rounding of a bin edge.
+ * The same cloud, normals and k give the same bytes whatever the context has indexed before: the counts are integers, every
+ * float sum runs in the order above.
+ * Not built: setRadiusSearch, setSearchSurface, setIndices, other bin counts, PFH, feature matching.
+ *
+ * rsreg_cloud_fpfh: out = n records of 132 bytes laid out as pcl::FPFHSignature33 (float histogram[33]); width, height as the
+ * input's; is_dense 0 if any record got NaNs, otherwise the input's.  out != in, out != normals.  Waits for the stream (whether a
+ * record got NaNs).
+ * rsreg_cloud_spfh: host_out = the n * 33 floats of the SPFH rows, the caller's record order. */
+int rsreg_cloud_fpfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, int k, rsreg_cloud *out);
+int rsreg_cloud_spfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, int k, float *host_out /* n*33 */);
 /* ---- radius search: every record's neighbours within a radius in its own cloud, EXACT.  Record j is a neighbour of the finite
  * record i when j is finite and d2(i, j) < r2, with d2 the float32 L2_Simple squared distance of every search here and
  * r2 = (float)((double)radius * (double)radius): KdTreeFLANN::radiusSearch's cast and the STRICT compare of FLANN's

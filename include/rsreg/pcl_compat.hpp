@@ -930,6 +930,55 @@ template <typename PointInT, typename PointOutT = Normal> class NormalEstimation
     std::shared_ptr<Context> ctx_;
 };
 
+// ---- pcl::FPFHSignature33: the 33 floats of a Fast Point Feature Histogram, three blocks of 11 bins
+struct FPFHSignature33 {
+    float histogram[33];
+    static int descriptorSize() { return 33; }
+};
+static_assert(sizeof(FPFHSignature33) == 132, "pcl::FPFHSignature33 is 33 floats");
+
+// ---- pcl::FPFHEstimation<PointInT, PointNT, PointOutT> on the GPU with setKSearch (2 .. 64) over the exact k-nearest-neighbour
+// search (csrc/fpfh_kernels.hpp, rsreg_cloud_fpfh; include/rsreg.h holds the contract).  PointNT: records that begin with
+// normal_x, normal_y, normal_z (pcl::Normal); PointOutT: 132-byte records laid out as pcl::FPFHSignature33.  PCL's two quirks are
+// kept (the weight is 1 / squared distance, the record's own SPFH does not enter); the pair features are computed in double, not
+// in float (the stated deviation).  setRadiusSearch is refused: it is not built.  No setSearchSurface, no setIndices.
+template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33> class FPFHEstimation {
+    static_assert(sizeof(PointOutT) == 132, "the output records are laid out as pcl::FPFHSignature33");
+    static_assert(sizeof(PointNT) >= 12 && sizeof(PointNT) % 4 == 0, "the normals' records begin with three floats");
+  public:
+    FPFHEstimation() = default;
+    explicit FPFHEstimation(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {}
+    void setInputCloud(const typename PointCloud<PointInT>::Ptr &cloud) { input_ = cloud; }
+    void setInputNormals(const typename PointCloud<PointNT>::Ptr &normals) { normals_ = normals; }
+    void setKSearch(int k) { k_ = k; }
+    int getKSearch() const { return k_; }
+    void setRadiusSearch(double radius)
+    {
+        if (radius != 0.0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: FPFHEstimation::setRadiusSearch is not built; use setKSearch");
+    }
+    void compute(PointCloud<PointOutT> &output)
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        if (!normals_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputNormals not called");
+        const std::shared_ptr<Context> ctx = ctx_ ? ctx_ : Context::Default();
+        DeviceCloud<PointInT> tmp(*input_, ctx);
+        DeviceCloud<PointNT> tmp_normals(*normals_, ctx);
+        DeviceCloud<PointOutT> features(ctx);
+        compute(tmp, tmp_normals, features);
+        features.download(output);
+    }
+    void compute(const DeviceCloud<PointInT> &input, const DeviceCloud<PointNT> &normals, DeviceCloud<PointOutT> &output)
+    {
+        if (k_ == 0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setKSearch not called");
+        check(rsreg_cloud_fpfh(input.context()->get(), input.handle(), normals.handle(), k_, output.handle()), input.context()->get());
+    }
+  private:
+    int k_ = 0;                            // PCL's default: no search set (compute() refuses it)
+    typename PointCloud<PointInT>::Ptr input_;
+    typename PointCloud<PointNT>::Ptr normals_;
+    std::shared_ptr<Context> ctx_;
+};
+
 // ---- pcl::IntegralImageNormalEstimation<PointInT, PointOutT> for organized clouds (csrc/iinormals_kernels.hpp,
 // rsreg_cloud_integral_normals), with the calls of src/edge_extractor.hpp:9-15.  AVERAGE_3D_GRADIENT, the IGNORE border policy
 // and no depth-dependent smoothing are what is implemented: compute() refuses anything else.  The window sums are the double

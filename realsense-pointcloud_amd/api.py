@@ -128,6 +128,13 @@ class NormalCloud:
         return len(self.points)
 
 
+FPFH_DTYPE = np.dtype([("histogram", np.float32, (33,))])   # pcl::FPFHSignature33
+
+
+class FPFHCloud(NormalCloud):
+    """width / height / is_dense / points like pcl::PointCloud<pcl::FPFHSignature33>; points: FPFH_DTYPE records."""
+
+
 class DeviceCloud:
     """A cloud resident in HBM (rsreg_cloud): whole records plus width / height / is_dense.  What the
     reference's frame loop hands from step to step (filter -> align -> transformPointCloud -> operator+,
@@ -248,6 +255,63 @@ class DeviceCloud:
         rec = out.download_normals().points
         out.close()
         return np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
+
+    def _normals_on_device(self, normals):
+        """(a DeviceCloud of this context that holds the normals, whether it was made here): a DeviceCloud as it is, a NormalCloud,
+        a structured array that starts with normal_x, normal_y, normal_z, or an (n, >= 3) float32 array uploaded."""
+        if isinstance(normals, DeviceCloud):
+            return normals, False
+        rec = normals.points if hasattr(normals, "points") else np.asarray(normals)
+        if rec.dtype.names is None:
+            rec = np.ascontiguousarray(rec, np.float32)
+            if rec.ndim != 2 or rec.shape[1] < 3:
+                raise ValueError("normals must be a DeviceCloud, a NormalCloud, a structured array that starts with normal_x or an (n, >=3) float32 array")
+            rec = rec.view(np.dtype((np.void, rec.shape[1] * 4))).reshape(-1)
+        elif rec.dtype.names[:3] != ("normal_x", "normal_y", "normal_z") or rec.dtype.fields["normal_x"][1] != 0:
+            raise ValueError("the normals' records must start with normal_x, normal_y, normal_z")
+        return DeviceCloud(NormalCloud(rec, len(rec), 1, True), ctx=self.ctx), True
+
+    def fpfh_cloud(self, normals, k):
+        """pcl::FPFHEstimation with setKSearch(k) (rsreg_cloud_fpfh; include/rsreg.h holds the contract): a DeviceCloud of 132-byte
+        pcl::FPFHSignature33 records.  normals: see fpfh()."""
+        nrm, made = self._normals_on_device(normals)
+        out = DeviceCloud(ctx=self.ctx)
+        rc = _l.lib().rsreg_cloud_fpfh(self.ctx.h, self.h, nrm.h, int(k), out.h)
+        if made:
+            nrm.close()
+        if rc:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out
+
+    def fpfh(self, normals, k):
+        """(n, 33) float32: the Fast Point Feature Histogram of every record over its k nearest neighbours, three blocks of 11 bins
+        that each sum to 100 (NaN for a record that is not finite or whose normal is not).  normals: a DeviceCloud of this context
+        (what normals_cloud() returns), a NormalCloud, or an (n, >= 3) float32 array."""
+        out = self.fpfh_cloud(normals, k)
+        hist = out.download_fpfh().points["histogram"]
+        out.close()
+        return hist
+
+    def spfh(self, normals, k):
+        """(n, 33) float32: the Simplified Point Feature Histogram of every record (rsreg_cloud_spfh), the first pass of fpfh():
+        zeros for a record that is not finite or whose normal is not."""
+        nrm, made = self._normals_on_device(normals)
+        out = np.zeros((self.info()[0], 33), np.float32)
+        rc = _l.lib().rsreg_cloud_spfh(self.ctx.h, self.h, nrm.h, int(k), out.ctypes.data)
+        if made:
+            nrm.close()
+        _l.check(rc, self.ctx.h)
+        return out
+
+    def download_fpfh(self):
+        """download() of a cloud of pcl::FPFHSignature33 records (what FPFHEstimation.compute returns): an FPFHCloud."""
+        n, stride, w, h, dense = self.info()
+        if n and stride != FPFH_DTYPE.itemsize:
+            raise ValueError("the device cloud does not hold 132-byte pcl::FPFHSignature33 records")
+        rec = np.zeros(n, FPFH_DTYPE)
+        _l.check(_l.lib().rsreg_cloud_download(self.h, rec.ctypes.data, n), self.ctx.h)
+        return FPFHCloud(rec, w, h, dense)
 
     def radius_count(self, radius):
         """radiusSearch of every record in its own cloud, counted (rsreg_cloud_radius_count, exact): uint32 per record, its
@@ -1241,6 +1305,54 @@ class NormalEstimation:
         try:
             dev = self._normals_cloud(tmp)
             out = dev.download_normals()
+            dev.close()
+        finally:
+            tmp.close()
+        return out
+
+
+class FPFHEstimation:
+    """pcl::FPFHEstimation<PointXYZRGB, Normal, FPFHSignature33> on the GPU with setKSearch, 2 <= k <= 64, over the exact
+    k-nearest-neighbour search (csrc/fpfh_kernels.hpp, rsreg_cloud_fpfh; include/rsreg.h holds the contract).  PCL's two quirks are
+    kept -- the weight is 1 / squared distance, the record's own SPFH does not enter -- and the pair features are computed in
+    double, not in float.  setRadiusSearch, setSearchSurface and setIndices are not built.  compute() of a DeviceCloud gives a
+    DeviceCloud of pcl::FPFHSignature33 records, of a host cloud an FPFHCloud."""
+
+    def __init__(self, ctx=None):
+        self.k = 0                                   # PCL's default: no search set
+        self._in = None
+        self._normals = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setInputNormals(self, normals):
+        self._normals = normals
+
+    def setKSearch(self, k):
+        self.k = int(k)
+
+    def getKSearch(self):
+        return self.k
+
+    def setRadiusSearch(self, radius):
+        if float(radius) != 0.0:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "FPFHEstimation: setRadiusSearch is not built; use setKSearch")
+
+    def compute(self):
+        if self._in is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCloud not called")
+        if self._normals is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputNormals not called")
+        if self.k == 0:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setKSearch not called")
+        if isinstance(self._in, DeviceCloud):
+            return self._in.fpfh_cloud(self._normals, self.k)
+        tmp = DeviceCloud(self._in, ctx=self.ctx or default_context())
+        try:
+            dev = tmp.fpfh_cloud(self._normals, self.k)
+            out = dev.download_fpfh()
             dev.close()
         finally:
             tmp.close()

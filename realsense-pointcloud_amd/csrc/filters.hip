@@ -5,7 +5,8 @@
 // PassThrough: one flag pass, a prefix sum of the flags (oscan.hpp), one ordered gather.  StatisticalOutlierRemoval: the exact
 // k-NN index and search of knn_kernels.hpp, the threshold's two sums in PCL's own order, then the same flag / scan / gather.
 // pcl::RadiusOutlierRemoval and NormalEstimation by radius: the exact radius search of radius_kernels.hpp over an index of its own
-// placement, then the same flag / scan / gather, or k_normals' tail.
+// placement, then the same flag / scan / gather, or k_normals' tail.  pcl::FPFHEstimation (setKSearch): the k-NN search once, with
+// the pair features of fpfh_kernels.hpp behind it, then the weighting pass over the neighbour rows the search left.
 // Everything runs on the context's stream with the index rsreg_ctx::knn and the scratch rsreg_ctx::filt (the radius search:
 // rsreg_ctx::rad too): nothing here reads or writes a buffer of the alignment's index or of the fitness indices.
 #include <cmath>
@@ -14,6 +15,7 @@
 #include "knn_kernels.hpp"
 #include "normals_kernels.hpp"
 #include "radius_kernels.hpp"
+#include "fpfh_kernels.hpp"
 
 using namespace rsreg;
 
@@ -192,6 +194,35 @@ int radius_count_device(rsreg_ctx *ctx, const CloudView &v, double radius)
     return RSREG_OK;
 }
 
+// The first pass of FPFHEstimation, not waited for: the index, then every finite record's neighbour rows (fs.d_nn_idx, fs.d_nn_d2)
+// and SPFH row (fs.d_spfh); the SPFH rows of non-finite records are zero.  v, nv: the views of the cloud and of its normals.
+int fpfh_spfh_device(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, const rsreg_cloud *out, int k, CloudView &v, CloudView &nv,
+                     uint32_t *nfin_out)
+{
+    if (!normals) return RSREG_ERR_INVALID_ARG;
+    int rc = view_of(ctx, in, out, v);
+    if (rc) return rc;
+    rc = view_of(ctx, normals, nullptr, nv);   // (a normal record: three floats first, the stride rule of every record here)
+    if (rc) return rc;
+    if (k < 2 || k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must be between 2 and 64");
+    if (nv.n != v.n) return fail(ctx, RSREG_ERR_INVALID_ARG, "the normals must hold one record per record of the cloud");
+    if (v.n < (size_t)k) return fail(ctx, RSREG_ERR_INVALID_ARG, "the cloud has fewer than k finite records");
+    rc = knn_index_device(ctx, v, k, "the cloud has fewer than k finite records", nfin_out);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    const size_t cells = v.n * (size_t)k;
+    RSREG_HIP(ctx, fs.d_nn_idx.reserve(cells * 4 + 16));
+    RSREG_HIP(ctx, fs.d_nn_d2.reserve(cells * 4 + 16));
+    RSREG_HIP(ctx, fs.d_spfh.reserve(v.n * kFpfhRow * 4 + 16));
+    if (*nfin_out < v.n) RSREG_HIP(ctx, hipMemsetAsync(fs.d_spfh.ptr, 0, v.n * kFpfhRow * 4, st));
+    const float hist_incr = 100.0f / (float)(k - 1);
+    k_fpfh_spfh<<<std::min<uint32_t>(*nfin_out, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), k, hist_incr, v.rec, v.stride, nv.rec, nv.stride,
+                                                                             fs.d_nn_idx.as<int32_t>(), fs.d_nn_d2.as<float>(), fs.d_spfh.as<float>());
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -331,6 +362,41 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
     RSREG_HIP(ctx, hipGetLastError());
     // a record that got NaNs makes the cloud not dense; otherwise it is what the input says
     return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kNormalBytes, v.width, v.height, nfin < n ? 0 : v.is_dense);
+}
+
+int rsreg_cloud_spfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, int k, float *host_out)
+{
+    CloudView v, nv;
+    if (!host_out) return RSREG_ERR_INVALID_ARG;
+    uint32_t nfin = 0;
+    int rc = fpfh_spfh_device(ctx, in, normals, nullptr, k, v, nv, &nfin);
+    if (rc) return rc;
+    RSREG_HIP(ctx, hipMemcpyAsync(host_out, ctx->filt.d_spfh.ptr, v.n * kFpfhRow * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RSREG_OK;
+}
+
+int rsreg_cloud_fpfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, int k, rsreg_cloud *out)
+{
+    CloudView v, nv;
+    if (!out || out == in || out == normals) return RSREG_ERR_INVALID_ARG;
+    uint32_t nfin = 0;
+    int rc = fpfh_spfh_device(ctx, in, normals, out, k, v, nv, &nfin);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)v.n;
+    constexpr size_t kFpfhBytes = kFpfhRow * 4;   // pcl::FPFHSignature33
+    RSREG_HIP(ctx, fs.d_out.reserve(v.n * kFpfhBytes + 16));
+    // a record that is not finite, or whose own normal is not, gets NaNs: whether one did comes back with the stream
+    uint32_t *d_any = ctx->knn.d_box.as<uint32_t>() + 8, *h_any = fs.host.as<uint32_t>() + 8;
+    RSREG_HIP(ctx, hipMemsetAsync(d_any, 0, 4, st));
+    k_fpfh_weight<<<std::min<uint32_t>(n, 1u << 16), kKnnWave, 0, st>>>(v.rec, v.stride, nv.rec, nv.stride, n, k, fs.d_nn_idx.as<int32_t>(),
+                                                                       fs.d_nn_d2.as<float>(), fs.d_spfh.as<float>(), fs.d_out.as<float>(), d_any);
+    RSREG_HIP(ctx, hipGetLastError());
+    RSREG_HIP(ctx, hipMemcpyAsync(h_any, d_any, 4, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kFpfhBytes, v.width, v.height, *h_any ? 0 : v.is_dense);
 }
 
 int rsreg_cloud_radius_count(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, uint32_t *host_out)

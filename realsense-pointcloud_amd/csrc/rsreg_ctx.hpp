@@ -190,7 +190,8 @@ struct FilterScratch {
     DevBuf d_flags, d_pos;         // uint32 per record: keep flag, position among the kept
     DevBuf d_sums;                 // the threshold's two f64 sums
     DevBuf d_out;                  // the kept records (the normals), before the output cloud takes them
-    DevBuf d_nn_idx, d_nn_d2;      // rsreg_cloud_knn: k original indices / k squared distances per record
+    DevBuf d_nn_idx, d_nn_d2;      // rsreg_cloud_knn, rsreg_cloud_fpfh: k original indices / k squared distances per record
+    DevBuf d_spfh;                 // rsreg_cloud_spfh, rsreg_cloud_fpfh: 33 floats per record, the SPFH rows between the two passes
     PinnedBuf host;
 };
 

@@ -47,6 +47,7 @@ EXPORTS = [
     "rsreg_icp_grid_info", "rsreg_ctx_host_timing", "rsreg_lzf_max_encoded_size", "rsreg_lzf_encode", "rsreg_lzf_decode",
     "rsreg_icp_fitness_score", "rsreg_icp_fitness_sums", "rsreg_ndt_fitness_score",
     "rsreg_cloud_passthrough", "rsreg_cloud_sor", "rsreg_cloud_knn_mean_distance", "rsreg_cloud_knn", "rsreg_cloud_normals",
+    "rsreg_cloud_fpfh", "rsreg_cloud_spfh",
     "rsreg_cloud_radius_count", "rsreg_cloud_radius_outlier_removal", "rsreg_cloud_normals_radius",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
@@ -307,6 +308,8 @@ def lib():
     L.rsreg_cloud_knn_mean_distance.argtypes = [vp, vp, i32, vp]
     L.rsreg_cloud_knn.argtypes = [vp, vp, i32, vp, vp]
     L.rsreg_cloud_normals.argtypes = [vp, vp, i32, vp, vp]
+    L.rsreg_cloud_fpfh.argtypes = [vp, vp, vp, i32, vp]
+    L.rsreg_cloud_spfh.argtypes = [vp, vp, vp, i32, vp]
     L.rsreg_cloud_radius_count.argtypes = [vp, vp, dbl, vp]
     L.rsreg_cloud_radius_outlier_removal.argtypes = [vp, vp, dbl, i32, i32, i32, vp, C.POINTER(C.c_uint64)]
     L.rsreg_cloud_normals_radius.argtypes = [vp, vp, dbl, vp, vp]
