@@ -20,6 +20,7 @@ The normals, every finite record of every input (h = 2^-22; C_ref, l0_ref .. l2_
     PassThrough leaves out 0.0 % and is asserted);
   * sign: where the reference has |cos_view| > 1e-6 * |v| (and a gap), n . n_ref > 0; everywhere, n does not point away from
     the viewpoint by more than float rounding.
+The search on thin, far, piled-up and cell-aligned clouds (the other rules of the grid's layout): tests/test_pointgrid_searches_gpu.py.
 """
 import functools
 import os

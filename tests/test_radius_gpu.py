@@ -24,6 +24,7 @@ reference alone) -- the bounds of tests/test_normals_gpu.py with m in place of k
   * the rows with m < 3 and the non-finite rows are NaN, and no other row is: exactly the reference's rows, no share granted;
   * sign: where the reference has |cos_view| > 1e-6 * |v| (and a gap), n . n_ref > 0; everywhere, n does not point away from
     the viewpoint by more than float rounding; a neighbourhood in one place (trace 0) gives (0, 0, 1) before the flip, curvature 0.
+The counts on thin, far, piled-up and cell-aligned clouds (the other rules of the grid's layout): tests/test_pointgrid_searches_gpu.py.
 """
 import ctypes as C
 import functools

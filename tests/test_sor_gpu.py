@@ -11,6 +11,7 @@ threshold, relative):
     render_frame(1, "50k")  raw 1.75e-05 (threshold 0.0596315,  895 removed)   after PassThrough 4.38e-06 (0.0549797, 1 726)
     render_frame(1, "N300") raw 6.78e-06 (threshold 0.0265525, 7 204 removed)  after PassThrough 1.74e-05 (0.0249845, 11 722)
     render_frame(0, "N300") raw 7.13e-06 (threshold 0.0266004, 7 136 removed)  after PassThrough 1.94e-05 (0.0250073, 11 840)
+Thin, far, piled-up and cell-aligned clouds (the other rules of the grid's layout): tests/test_pointgrid_searches_gpu.py.
 """
 import os
 import subprocess
