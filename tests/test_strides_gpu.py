@@ -1,6 +1,8 @@
 """GPU: the C ABI takes records of 12, 16 or 32 bytes (packed xyz, xyz + one float, PCL's PointXYZRGB; include/rsreg.h: every
-entry point has a `stride`).  The Python layer only ever hands 32-byte records over, so this file goes through ctypes: the same
-points in all three layouts must give the same correspondences, the same 4x4 and the same transformed coordinates, bit for
+entry point has a `stride`).  The other tests of the alignment hand 32-byte PointCloud records over (the Python layer itself takes
+any: DeviceCloud uploads whatever record type it is given, and tests/test_cloud_layouts_gpu.py goes that way for the searches and
+filters); this file goes through ctypes, where every way in -- host pointer, device pointer, handle -- takes a stride: the
+same points in all three layouts must give the same correspondences, the same 4x4 and the same transformed coordinates, bit for
 bit -- for host pointers, device pointers and cloud handles (12- and 16-byte clouds take the generic record kernels, 32-byte
 ones the two-lanes-per-record form of cloud.hip)."""
 import ctypes as C
