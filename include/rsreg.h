@@ -536,6 +536,9 @@ int rsreg_cloud_knn_mean_distance(rsreg_ctx *ctx, const rsreg_cloud *in, int mea
  * float32 L2_Simple squared distances, the record itself and exact copies counted like any other; ascending by
  * (d2, original record index), and among records whose d2 equals the k-th smallest value the lowest indices (the tie
  * rule of every search here).  1 <= k <= 64; fewer than k finite records: RSREG_ERR_INVALID_ARG.  Host outputs, each nullable.
+ * The range of every exact search here (this one, the mean distances, the radius search, getFitnessScore): any finite float32
+ * coordinates, of the cloud and, for getFitnessScore, of the source however far outside the target's box.  A squared distance that overflows is +inf and ties with every other +inf (lowest index first; a mean over one is
+ * +inf), one in the float32 denormals keeps the bits IEEE arithmetic gives it, one that underflows is 0.
  * index_out:    n*k int32 original record indices, ascending (d2, index); a non-finite record's row is all -1.
  * sqr_dist_out: n*k float; a non-finite record's row is all 0. */
 int rsreg_cloud_knn(rsreg_ctx *ctx, const rsreg_cloud *in, int k, int32_t *index_out, float *sqr_dist_out);

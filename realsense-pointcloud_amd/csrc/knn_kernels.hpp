@@ -97,21 +97,24 @@ template <typename Sel>
 __device__ __forceinline__ int knn_walk(const PointGridDev &g, const float4 q, int kept, typename Sel::Elem *buf, int lane)
 {
     using Elem = typename Sel::Elem;
-    const float inf = __int_as_float(0x7f800000), cell2 = g.cell * g.cell;
+    const float inf = __int_as_float(0x7f800000);
     const unsigned long long lt = (1ull << lane) - 1ull;
-    const float ux = cell_pos(q.x, g.ox, g.inv_cell), uy = cell_pos(q.y, g.oy, g.inv_cell), uz = cell_pos(q.z, g.oz, g.inv_cell);
+    const float ux = bound_pos(cell_pos(q.x, g.ox, g.inv_cell)), uy = bound_pos(cell_pos(q.y, g.oy, g.inv_cell)),
+                uz = bound_pos(cell_pos(q.z, g.oz, g.inv_cell));
     const int cx = axis_cell(q.x, g.ox, g.inv_cell, g.dx), cy = axis_cell(q.y, g.oy, g.inv_cell, g.dy), cz = axis_cell(q.z, g.oz, g.inv_cell, g.dz);
-    const int rmax = max(max(max(cx, g.dx - 1 - cx), max(cy, g.dy - 1 - cy)), max(cz, g.dz - 1 - cz));
     int count = 0;
     Elem bound = Sel::none();
     float bound_d2 = inf;
     bool done = false, dirty = false;   // done: Sel::kEndsAtZero only
-    for (int r = 0; r <= rmax && !done; ++r) {
-        const int side = 2 * r + 1, rows = side * side;
-        for (int base = 0; base < rows && !done; base += kKnnWave) {
+    // shell r holds a cell while one of the six faces of its cube is inside the grid
+    for (int r = 0; !done && (r <= cx || r <= cy || r <= cz || cx + r < g.dx || cy + r < g.dy || cz + r < g.dz); ++r) {
+        // the rows of the shell's square that lie inside the grid (the others hold nothing: a record alone at the end of a grid of
+        // 4 000 x 2 x 2 cells walks 4 000 shells of four rows each, not of (2 r + 1)^2)
+        const int ny = min(cy + r, g.dy - 1) - max(cy - r, 0) + 1, rows = (min(cz + r, g.dz - 1) - (cz - r) + 1) * ny;
+        for (int base = max(r - cz, 0) * ny; base < rows && !done; base += kKnnWave) {
             const int row = base + lane;
-            const int oy = row % side - r, oz = row / side - r, y = cy + oy, z = cz + oz;
-            const bool in = row < rows && y >= 0 && y < g.dy && z >= 0 && z < g.dz;
+            const int y = max(cy - r, 0) + row % ny, z = cz - r + row / ny, oy = y - cy, oz = z - cz;
+            const bool in = row < rows;
             const bool face = abs(oy) == r || abs(oz) == r;   // a face row: every cell of it; else its two ends
             const float gy = axis_gap(uy, y, y), gz = axis_gap(uz, z, z);
             for (int pass = 0; pass < 2 && !done; ++pass) {
@@ -125,7 +128,7 @@ __device__ __forceinline__ int knn_walk(const PointGridDev &g, const float4 q, i
                     x0 = x1 = pass == 0 ? cx - r : cx + r;
                     has = has && x0 >= 0 && x0 < g.dx;
                 }
-                const float lb = has ? grid_lb2(axis_gap(ux, x0, x1), gy, gz, cell2) : inf;
+                const float lb = has ? grid_lb2(axis_gap(ux, x0, x1), gy, gz, g.cell) : inf;
                 uint32_t s = 0, e = 0;
                 if (has && !(lb > bound_d2)) {
                     const size_t c0 = ((size_t)z * (size_t)g.dy + (size_t)y) * (size_t)g.dx;
@@ -176,12 +179,12 @@ __device__ __forceinline__ int knn_walk(const PointGridDev &g, const float4 q, i
             }
             // every cell not visited yet lies beyond one of the six faces of the cube of shell r
             float out = inf;
-            if (cx + r + 1 < g.dx) out = fminf(out, grid_lb2(axis_gap(ux, cx + r + 1, g.dx - 1), 0.0f, 0.0f, cell2));
-            if (cx - r - 1 >= 0) out = fminf(out, grid_lb2(axis_gap(ux, 0, cx - r - 1), 0.0f, 0.0f, cell2));
-            if (cy + r + 1 < g.dy) out = fminf(out, grid_lb2(0.0f, axis_gap(uy, cy + r + 1, g.dy - 1), 0.0f, cell2));
-            if (cy - r - 1 >= 0) out = fminf(out, grid_lb2(0.0f, axis_gap(uy, 0, cy - r - 1), 0.0f, cell2));
-            if (cz + r + 1 < g.dz) out = fminf(out, grid_lb2(0.0f, 0.0f, axis_gap(uz, cz + r + 1, g.dz - 1), cell2));
-            if (cz - r - 1 >= 0) out = fminf(out, grid_lb2(0.0f, 0.0f, axis_gap(uz, 0, cz - r - 1), cell2));
+            if (cx + r + 1 < g.dx) out = fminf(out, grid_lb2(axis_gap(ux, cx + r + 1, g.dx - 1), 0.0f, 0.0f, g.cell));
+            if (cx - r - 1 >= 0) out = fminf(out, grid_lb2(axis_gap(ux, 0, cx - r - 1), 0.0f, 0.0f, g.cell));
+            if (cy + r + 1 < g.dy) out = fminf(out, grid_lb2(0.0f, axis_gap(uy, cy + r + 1, g.dy - 1), 0.0f, g.cell));
+            if (cy - r - 1 >= 0) out = fminf(out, grid_lb2(0.0f, axis_gap(uy, 0, cy - r - 1), 0.0f, g.cell));
+            if (cz + r + 1 < g.dz) out = fminf(out, grid_lb2(0.0f, 0.0f, axis_gap(uz, cz + r + 1, g.dz - 1), g.cell));
+            if (cz - r - 1 >= 0) out = fminf(out, grid_lb2(0.0f, 0.0f, axis_gap(uz, 0, cz - r - 1), g.cell));
             if (out > bound_d2) break;   // (strictly: a record AT the bound's distance may still carry a lower index)
         }
     }

@@ -117,15 +117,35 @@ __device__ __forceinline__ uint32_t grid_block_id(const PointGridDev &g, int bx,
     return ((uint32_t)bz * (uint32_t)g.by + (uint32_t)by) * (uint32_t)g.bx + (uint32_t)bx;
 }
 
+// The position the bounds below measure from: cell_pos, or NaN where the position says nothing that float arithmetic can use --
+// (q - origin) has overflowed (a query at the far end of a box that spans most of the float range), or the query lies more than
+// kPosMax cells from the origin (a source record far outside a tiny target box: its gaps would square to +inf while its distances
+// are finite floats).  axis_gap of a NaN is 0 for every cell (fmaxf drops the NaN), the one bound that is always true: such a
+// query visits everything.  Below kPosMax the sum of three squared gaps stays under 3.1e36.  (axis_cell clamps the same
+// positions to the first or the last cell, for the points and the queries alike.)
+constexpr float kPosMax = 1e18f;
+__device__ __forceinline__ float bound_pos(float u)
+{
+    return fabsf(u) <= kPosMax ? u : __int_as_float(0x7fc00000);
+}
+
 // A lower bound on the squared FLOAT distance (l2_simple) to anything beyond the per-axis gaps (cells, from axis_gap): what
 // lets a search skip a cell, a block or everything outside a shell and still return the exact nearest float distance.
 // axis_gap's kCellMargin covers the rounding of the cell assignment inside the grid (kGridMaxAxis cells at most along an axis:
 // 1e-3 cells); the relative factor covers what grows with the distance -- the rounding of (q - origin) * inv_cell for a query far
-// outside the grid (3 ulp), that of this sum (4 ulp) and of cell * cell against 1 / inv_cell (2 ulp), and l2_simple's own
-// (5 ulp): 14 ulp of 2^-24, 1e-6 < 4e-6.
-__device__ __forceinline__ float grid_lb2(float gx, float gy, float gz, float cell2)
+// outside the grid (3 ulp), that of this sum and its three products (6 ulp) and of the cell against 1 / inv_cell (2 ulp), and
+// l2_simple's own (5 ulp): 16 ulp of 2^-24, 1e-6 < 4e-6.
+// The range is every finite float32 cloud and every finite query.  The sum (finite: bound_pos) is multiplied by the cell TWICE,
+// not by cell * cell: that float product is +inf for a cell above 1.8e19 and 0 or a denormal of a few bits for one below 1e-19,
+// while distances of a few cells are still finite floats, or still tell records apart.  Taken one after the other, a product
+// overflows only where the bound, and with it every float distance it stands for, is above FLT_MAX (the first one only for a cell
+// above 1e2: the sum is below 3.1e36); gaps of 0 give 0, never 0 * inf.  Where the result is a float denormal, so is d2: each of
+// l2_simple's three products is then rounded to a multiple of 2^-149 (their sums are exact) and d2 can lie 1.5 * 2^-149 below the
+// real value, the last two roundings here move the bound by 2^-149 at most (a denormal first product is multiplied by a cell
+// below 1e-19 once more), and 4 * 2^-149 comes off -- nothing against a normal float.
+__device__ __forceinline__ float grid_lb2(float gx, float gy, float gz, float cell)
 {
-    return (gx * gx + gy * gy + gz * gz) * cell2 * 0.999996f;
+    return __fsub_rn(__fmul_rn(__fmul_rn(__fmul_rn(gx * gx + gy * gy + gz * gz, 0.999996f), cell), cell), 0x1p-147f);
 }
 
 // ------------------------------------------------------------------------------ record readers

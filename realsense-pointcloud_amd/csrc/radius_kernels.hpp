@@ -79,12 +79,13 @@ inline RadiusQuery radius_query(double radius, const PointGrid &gx)
 
 // the cells lo .. hi along one axis that a ball around in-grid position u can touch.  A point's cell is floor(its position) clamped into
 // the grid, the query's too (axis_cell); clamping is monotone, so clamping both ends of [u - reach, u + reach] covers a ball that
-// reaches past a face as well as a query that lies outside the grid.
+// reaches past a face as well as a query that lies outside the grid.  A NaN (bound_pos: the position says nothing)
+// leaves lo = 0 and hi = d - 1, the whole axis: fmaxf and fminf drop it, and each end meets first the clamp it then falls to.
 __device__ __forceinline__ void radius_axis_cells(float u, float reach, int d, int &lo, int &hi)
 {
     const float top = (float)(d - 1);
     lo = (int)fminf(fmaxf(floorf(u - reach), 0.0f), top);
-    hi = (int)fminf(fmaxf(floorf(u + reach), 0.0f), top);
+    hi = (int)fmaxf(fminf(floorf(u + reach), top), 0.0f);
 }
 
 // One wave hands every point of the index with l2_simple(q, point) < r2 to f, each to ONE lane (f(point), under divergence).  It visits
@@ -95,8 +96,8 @@ __device__ __forceinline__ void radius_axis_cells(float u, float reach, int d, i
 template <typename F>
 __device__ __forceinline__ void radius_walk(const PointGridDev &g, const float4 q, const RadiusQuery rq, int lane, F &f)
 {
-    const float cell2 = g.cell * g.cell;
-    const float ux = cell_pos(q.x, g.ox, g.inv_cell), uy = cell_pos(q.y, g.oy, g.inv_cell), uz = cell_pos(q.z, g.oz, g.inv_cell);
+    const float ux = bound_pos(cell_pos(q.x, g.ox, g.inv_cell)), uy = bound_pos(cell_pos(q.y, g.oy, g.inv_cell)),
+                uz = bound_pos(cell_pos(q.z, g.oz, g.inv_cell));
     int x0, x1, y0, y1, z0, z1;
     radius_axis_cells(ux, rq.reach, g.dx, x0, x1);
     radius_axis_cells(uy, rq.reach, g.dy, y0, y1);
@@ -108,7 +109,7 @@ __device__ __forceinline__ void radius_walk(const PointGridDev &g, const float4 
         uint32_t s = 0, e = 0;
         if (row < rows) {
             const int y = y0 + row % ny, z = z0 + row / ny;
-            if (!(grid_lb2(gx, axis_gap(uy, y, y), axis_gap(uz, z, z), cell2) > rq.r2)) {
+            if (!(grid_lb2(gx, axis_gap(uy, y, y), axis_gap(uz, z, z), g.cell) > rq.r2)) {
                 const size_t c0 = ((size_t)z * (size_t)g.dy + (size_t)y) * (size_t)g.dx;
                 s = g.start[c0 + (size_t)x0];
                 e = g.start[c0 + (size_t)x1 + 1];

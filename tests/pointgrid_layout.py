@@ -22,6 +22,7 @@ import numpy as np
 POLICIES = {"knn": (64.0, 4096.0, 33554432.0, False), "radius": (64.0, 4096.0, 33554432.0, False), "fit": (4.0, 64.0, 16777216.0, True)}
 CELL_MARGIN = np.float32(0.03)      # kCellMargin
 LB_FACTOR = np.float32(0.999996)    # grid_lb2's relative factor
+LB_DENORMAL_SLACK = np.float32(2.0 ** -147)   # ... and what it takes off for a d2 in the float32 denormals
 GRID_MAX_AXIS = 4096                # kGridMaxAxis
 
 Layout = collections.namedtuple("Layout", "cell inv_cell dims branch origin capped")
@@ -89,31 +90,44 @@ def cell_pos(xyz, lay):
         return ((xyz - lay.origin).astype(np.float32) * lay.inv_cell).astype(np.float32)
 
 
+POS_MAX = np.float32(1e18)          # kPosMax: beyond it a position says nothing the bounds can use
+
+
+def bound_pos(u):
+    """bound_pos: the position the bounds measure from -- NaN where (p - origin) has overflowed or lies beyond kPosMax cells."""
+    u = np.asarray(u, np.float32)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.abs(u) <= POS_MAX, u, np.float32(np.nan)).astype(np.float32)
+
+
 def cells_of(xyz, lay):
-    """axis_cell along every axis: floor(cell_pos), clamped into the grid.  int32, the shape of xyz."""
+    """axis_cell along every axis: floor(cell_pos), clamped into the grid (fmaxf, then fminf: a NaN lands in cell 0, an overflowed
+    position in the last cell).  int32, the shape of xyz."""
     u = np.floor(cell_pos(xyz, lay))
     top = np.asarray(lay.dims, np.float32) - np.float32(1)
-    return np.minimum(np.maximum(u, np.float32(0)), top).astype(np.int32)
+    return np.fmin(np.fmax(u, np.float32(0)), top).astype(np.int32)
 
 
 def axis_gap(u, lo, hi):
-    """float32: max(max(lo - u, u - (hi + 1)) - kCellMargin, 0)."""
+    """float32: fmaxf(fmaxf(lo - u, u - (hi + 1)) - kCellMargin, 0): 0 for a NaN position."""
     u = np.asarray(u, np.float32)
-    a = (np.asarray(lo).astype(np.float32) - u).astype(np.float32)
-    b = (u - (np.asarray(hi) + 1).astype(np.float32)).astype(np.float32)
-    return np.maximum((np.maximum(a, b) - CELL_MARGIN).astype(np.float32), np.float32(0))
+    with np.errstate(invalid="ignore"):
+        a = (np.asarray(lo).astype(np.float32) - u).astype(np.float32)
+        b = (u - (np.asarray(hi) + 1).astype(np.float32)).astype(np.float32)
+        return np.fmax((np.fmax(a, b) - CELL_MARGIN).astype(np.float32), np.float32(0))
 
 
-def grid_lb2(gx, gy, gz, cell2):
-    """float32: (gx * gx + gy * gy + gz * gz) * cell2 * 0.999996, left to right."""
+def grid_lb2(gx, gy, gz, cell):
+    """float32: (((gx * gx + gy * gy + gz * gz) * 0.999996) * cell) * cell - 2^-147, left to right, every step rounded."""
     gx, gy, gz = (np.asarray(g, np.float32) for g in (gx, gy, gz))
-    s = ((gx * gx).astype(np.float32) + (gy * gy).astype(np.float32)).astype(np.float32)
-    s = (s + (gz * gz).astype(np.float32)).astype(np.float32)
-    return ((s * np.float32(cell2)).astype(np.float32) * LB_FACTOR).astype(np.float32)
-
-
-def cell2_of(lay):
-    return np.float32(lay.cell * lay.cell)
+    cell = np.float32(cell)
+    with np.errstate(over="ignore", under="ignore"):
+        s = ((gx * gx).astype(np.float32) + (gy * gy).astype(np.float32)).astype(np.float32)
+        s = (s + (gz * gz).astype(np.float32)).astype(np.float32)
+        s = (s * LB_FACTOR).astype(np.float32)
+        s = (s * cell).astype(np.float32)
+        s = (s * cell).astype(np.float32)
+        return (s - LB_DENORMAL_SLACK).astype(np.float32)
 
 
 def radius_reach(radius, lay):
@@ -123,9 +137,11 @@ def radius_reach(radius, lay):
 
 
 def radius_axis_cells(u, reach, d):
-    """radius_axis_cells: the cells lo .. hi along one axis that a ball around in-grid position u can touch (float32, clamped)."""
+    """radius_axis_cells: the cells lo .. hi along one axis that a ball around in-grid position u can touch (float32, clamped; a NaN
+    position: the whole axis)."""
     u = np.asarray(u, np.float32)
     top = np.float32(d - 1)
-    lo = np.minimum(np.maximum(np.floor((u - reach).astype(np.float32)), np.float32(0)), top).astype(np.int32)
-    hi = np.minimum(np.maximum(np.floor((u + reach).astype(np.float32)), np.float32(0)), top).astype(np.int32)
+    with np.errstate(invalid="ignore"):
+        lo = np.fmin(np.fmax(np.floor((u - reach).astype(np.float32)), np.float32(0)), top).astype(np.int32)
+        hi = np.fmax(np.fmin(np.floor((u + reach).astype(np.float32)), top), np.float32(0)).astype(np.int32)
     return lo, hi

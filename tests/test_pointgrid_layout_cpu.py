@@ -253,7 +253,8 @@ def _min_ratio(d2, lb):
     pos = lb > 0
     if not pos.any():
         return np.inf, True
-    return float((d2[pos].astype(np.float64) / lb[pos].astype(np.float64)).min()), bool((lb <= d2).all())
+    with np.errstate(invalid="ignore"):                      # (inf / inf where both have overflowed: fmin passes over it)
+        return float(np.fmin.reduce(d2[pos].astype(np.float64) / lb[pos].astype(np.float64))), bool((lb <= d2).all())
 
 
 def _bounds(xyz, lay, queries=None, chunk=256):
@@ -263,17 +264,18 @@ def _bounds(xyz, lay, queries=None, chunk=256):
     t = xyz[finite_rows(xyz)]
     qs = t if queries is None else queries[finite_rows(queries)]
     c = G.cells_of(t, lay)
-    u_all, c_all = G.cell_pos(qs, lay), G.cells_of(qs, lay)
-    cell2 = G.cell2_of(lay)
+    u_all, c_all = G.bound_pos(G.cell_pos(qs, lay)), G.cells_of(qs, lay)
+    cell = lay.cell
     zero = np.float32(0)
     top = np.asarray(lay.dims) - 1
     cell_ratio, face_ratio, holds = np.inf, np.inf, True
     for s in range(0, len(qs), chunk):
         q, uq, cq = qs[s:s + chunk, None, :], u_all[s:s + chunk, None, :], c_all[s:s + chunk, None, :]
-        d2 = d2_f32(q, t[None, :, :])
+        with np.errstate(over="ignore", under="ignore"):
+            d2 = d2_f32(q, t[None, :, :])
         cp = np.broadcast_to(c[None, :, :], (len(uq), len(t), 3))
         gaps = [G.axis_gap(uq[..., k], cp[..., k], cp[..., k]) for k in range(3)]
-        lb = np.where((cp != cq).any(axis=2), G.grid_lb2(gaps[0], gaps[1], gaps[2], cell2), zero)
+        lb = np.where((cp != cq).any(axis=2), G.grid_lb2(gaps[0], gaps[1], gaps[2], cell), zero)
         r, ok = _min_ratio(d2, lb)
         cell_ratio, holds = min(cell_ratio, r), holds and ok
         for k in range(3):
@@ -282,7 +284,7 @@ def _bounds(xyz, lay, queries=None, chunk=256):
             down = G.axis_gap(uq[..., k], np.zeros_like(cp[..., k]), cp[..., k])
             g = np.where(cp[..., k] > cq[..., k], up, np.where(cp[..., k] < cq[..., k], down, zero))
             parts = [g if j == k else zero for j in range(3)]
-            r, ok = _min_ratio(d2, G.grid_lb2(parts[0], parts[1], parts[2], cell2))
+            r, ok = _min_ratio(d2, G.grid_lb2(parts[0], parts[1], parts[2], cell))
             face_ratio, holds = min(face_ratio, r), holds and ok
     return cell_ratio, face_ratio, holds
 
@@ -311,8 +313,8 @@ def test_ball_box_holds_every_neighbour(name):
     zero = np.float32(0)
     for what, r in K.radii(name):
         lay = G.layout(mn, mx, nfin, "radius", r)
-        reach, r2, cell2 = G.radius_reach(r, lay), R.r2_f32(r), G.cell2_of(lay)
-        u, c = G.cell_pos(t, lay), G.cells_of(t, lay)
+        reach, r2, cell = G.radius_reach(r, lay), R.r2_f32(r), lay.cell
+        u, c = G.bound_pos(G.cell_pos(t, lay)), G.cells_of(t, lay)
         box = [G.radius_axis_cells(u[:, k], reach, lay.dims[k]) for k in range(3)]
         pairs = 0
         for s in range(0, len(t), 256):
@@ -325,7 +327,7 @@ def test_ball_box_holds_every_neighbour(name):
             gx = G.axis_gap(u[q, 0], box[0][0][q], box[0][1][q])[:, None]
             gy = G.axis_gap(u[q, None, 1], c[None, :, 1], c[None, :, 1])
             gz = G.axis_gap(u[q, None, 2], c[None, :, 2], c[None, :, 2])
-            row_lb = G.grid_lb2(np.broadcast_to(gx, gy.shape), gy, gz, cell2)
+            row_lb = G.grid_lb2(np.broadcast_to(gx, gy.shape), gy, gz, cell)
             assert (inside | ~nb).all(), (name, what, r)
             assert (~(row_lb > r2) | ~nb).all(), (name, what, r)
             pairs += int(nb.sum())
@@ -340,7 +342,10 @@ def test_restated_constants_are_the_headers():
             return fh.read()
     rec, grid, rad = text("records.hpp"), text("pointgrid.hpp"), text("radius_kernels.hpp")
     assert np.float32(re.search(r"constexpr float kCellMargin = ([0-9.]+)f;", rec).group(1)) == G.CELL_MARGIN
-    assert np.float32(re.search(r"\* cell2 \* ([0-9.]+)f;", grid).group(1)) == G.LB_FACTOR
+    m = re.search(r"__fsub_rn\(__fmul_rn\(__fmul_rn\(__fmul_rn\(gx \* gx \+ gy \* gy \+ gz \* gz, ([0-9.]+)f\), cell\), cell\), (0x[0-9a-fp.+-]+)f\);", grid)
+    assert np.float32(m.group(1)) == G.LB_FACTOR and float.fromhex(m.group(2)) == G.LB_DENORMAL_SLACK
+    assert "fabsf(u) <= kPosMax ? u : __int_as_float(0x7fc00000)" in grid
+    assert np.float32(re.search(r"constexpr float kPosMax = ([0-9.e+]+)f;", grid).group(1)) == G.POS_MAX
     assert int(re.search(r"constexpr int kGridMaxAxis = (\d+);", grid).group(1)) == G.GRID_MAX_AXIS
     for struct, policy in (("FitGridPolicy", "fit"), ("KnnGridPolicy", "knn"), ("RadiusGridPolicy", "radius")):
         m = re.search(r"struct %s \{.*?kCellsPerPoint = ([0-9.]+), kMinCells = ([0-9.]+), kMaxCells = ([0-9.]+);\s*static constexpr bool kBlocks = (true|false);" % struct,
