@@ -591,7 +591,7 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
  * build can differ where a feature lies within float rounding of a bin edge.
  * The same cloud, normals and k give the same bytes whatever the context has indexed before: the counts are integers, every
  * float sum runs in the order above.
- * Not built: setRadiusSearch, setSearchSurface, setIndices, other bin counts, PFH, feature matching.
+ * Not built: setRadiusSearch, setSearchSurface, setIndices, other bin counts, PFH.
  *
  * rsreg_cloud_fpfh: out = n records of 132 bytes laid out as pcl::FPFHSignature33 (float histogram[33]); width, height as the
  * input's; is_dense 0 if any record got NaNs, otherwise the input's.  out != in, out != normals.  Waits for the stream (whether a
@@ -599,6 +599,48 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
  * rsreg_cloud_spfh: host_out = the n * 33 floats of the SPFH rows, the caller's record order. */
 int rsreg_cloud_fpfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, int k, rsreg_cloud *out);
 int rsreg_cloud_spfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, int k, float *host_out /* n*33 */);
+/* ---- feature matching: the exact k-nearest-neighbour search of one cloud's descriptors among another cloud's, and
+ * pcl::registration::CorrespondenceEstimation<FPFHSignature33, FPFHSignature33> over it (determineCorrespondences,
+ * determineReciprocalCorrespondences).  PCL 1.9.1 registration/impl/correspondence_estimation.hpp, KdTreeFLANN and FLANN's
+ * L2_Simple<float>, recalled; PCL is not available to check against, so what follows IS the contract.
+ * A DESCRIPTOR CLOUD is a device cloud whose records start with 33 floats: stride >= 132 and a multiple of 4.  What
+ * rsreg_cloud_fpfh wrote is accepted as it is, and so are wider records with a payload behind the row, which nothing reads.  A row
+ * is VALID when all 33 floats are finite (DefaultPointRepresentation::isValid).
+ * Distance of source row s and target row t, float32, sequential in bin order, no contraction:
+ *   d2 = 0.0f; for b in 0 .. 32: diff = s[b] - t[b]; d2 += diff * diff.
+ * A sum that overflows is +inf, which ties with every other +inf.
+ * The search is exact: bit-equal to a brute force in that order, ties to the lowest target index, and the same bytes whatever the
+ * context has done before -- every pair is computed, the selection is a minimum of unique (d2, index) keys.
+ *
+ * rsreg_cloud_feature_knn: for every valid source row the k valid target rows with the smallest d2, ascending by (d2, target
+ * record index); among rows whose d2 equals the k-th smallest the lowest indices win.  Host outputs, ns * k each, each nullable; an
+ * invalid source row gets indices -1 and distances 0 (the convention of rsreg_cloud_knn).  1 <= k <= 16.  RSREG_ERR_INVALID_ARG with
+ * nothing searched and the outputs untouched: fewer than k valid target rows (the pass that counts them is all that has run), k out
+ * of range, a NULL cloud, a cloud of another context, a stride under 132 or not a multiple of 4, an empty source.  source == target is allowed: a row then finds itself, or a
+ * lower-indexed exact copy, at d2 = 0.  Waits for the stream.
+ *
+ * rsreg_correspondence: pcl::Correspondence, 12 bytes; distance is the SQUARED distance, as in PCL.
+ * rsreg_cloud_feature_correspondences:
+ *   max_dist_sqr = max_distance * max_distance in double: DBL_MAX gives +inf, which keeps everything.  max_distance negative or
+ *   NaN: RSREG_ERR_INVALID_ARG.
+ *   For every valid source row i in ascending order: j = its nearest valid target row (k = 1 as above), d2 their distance.  The row
+ *   is dropped when (double)d2 > max_dist_sqr -- a distance AT the bound is kept -- otherwise {i, j, d2} is emitted.
+ *   reciprocal != 0: i' = the nearest valid SOURCE row of target row j, d2' its distance, the same tie rule.  The row is also
+ *   dropped when (double)d2' > max_dist_sqr || i' != i.
+ *   The output is ordered by index_query.  *n_out = the number found; when it exceeds `capacity` the first `capacity` are written
+ *   and the call still returns RSREG_OK: the caller sees *n_out > capacity, nothing is hidden.  host_out may be NULL when capacity
+ *   is 0.  No valid target row, or (reciprocal) no valid source row, or an empty cloud: *n_out = 0, RSREG_OK.  Waits for the stream.
+ * Not built: setIndices, descriptors of other lengths, other metrics, CorrespondenceRejector*, SampleConsensusPrerejective /
+ * SampleConsensusInitialAlignment, a transformation estimated from a correspondence list. */
+typedef struct rsreg_correspondence {
+    int32_t index_query;   /* source row */
+    int32_t index_match;   /* target row */
+    float distance;        /* squared */
+} rsreg_correspondence;
+int rsreg_cloud_feature_knn(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, int k, int32_t *index_out /* ns*k */,
+                            float *sqr_dist_out /* ns*k */);
+int rsreg_cloud_feature_correspondences(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, double max_distance, int reciprocal,
+                                        rsreg_correspondence *host_out, size_t capacity, size_t *n_out);
 /* ---- radius search: every record's neighbours within a radius in its own cloud, EXACT.  Record j is a neighbour of the finite
  * record i when j is finite and d2(i, j) < r2, with d2 the float32 L2_Simple squared distance of every search here and
  * r2 = (float)((double)radius * (double)radius): KdTreeFLANN::radiusSearch's cast and the STRICT compare of FLANN's

@@ -979,6 +979,65 @@ template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignatur
     std::shared_ptr<Context> ctx_;
 };
 
+// ---- pcl::Correspondence / pcl::Correspondences: a source row, its match in the target and their SQUARED distance
+struct Correspondence {
+    int index_query = 0;
+    int index_match = -1;
+    float distance = std::numeric_limits<float>::max();
+    Correspondence() = default;
+    Correspondence(int query, int match, float d) : index_query(query), index_match(match), distance(d) {}
+};
+static_assert(sizeof(Correspondence) == 12 && sizeof(Correspondence) == sizeof(rsreg_correspondence), "pcl::Correspondence is 12 bytes");
+using Correspondences = std::vector<Correspondence>;
+
+namespace registration {
+
+// ---- pcl::registration::CorrespondenceEstimation<FPFHSignature33, FPFHSignature33> on the GPU: every valid source descriptor's
+// nearest valid target descriptor by an exact brute-force search in the 33-dimensional space (csrc/feature_kernels.hpp,
+// rsreg_cloud_feature_correspondences; include/rsreg.h holds the contract).  Records that start with 33 floats; a match AT
+// max_distance is kept; the list is ordered by index_query.  Host clouds are uploaded into temporaries; the overloads that take
+// DeviceClouds leave everything but the list in HBM.  No setIndices, no rejectors.
+template <typename PointSource = FPFHSignature33, typename PointTarget = FPFHSignature33> class CorrespondenceEstimation {
+    static_assert(sizeof(PointSource) >= 132 && sizeof(PointSource) % 4 == 0 && sizeof(PointTarget) >= 132 && sizeof(PointTarget) % 4 == 0,
+                  "descriptor records start with 33 floats");
+  public:
+    CorrespondenceEstimation() = default;
+    explicit CorrespondenceEstimation(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {}
+    void setInputSource(const typename PointCloud<PointSource>::Ptr &cloud) { source_ = cloud, dsource_ = nullptr; }
+    void setInputTarget(const typename PointCloud<PointTarget>::Ptr &cloud) { target_ = cloud, dtarget_ = nullptr; }
+    // engine extra: descriptors that are in HBM already (what FPFHEstimation::compute left there); the clouds must outlive the calls
+    void setInputSource(const DeviceCloud<PointSource> &cloud) { dsource_ = &cloud, source_.reset(); }
+    void setInputTarget(const DeviceCloud<PointTarget> &cloud) { dtarget_ = &cloud, target_.reset(); }
+    void determineCorrespondences(Correspondences &out, double max_distance = std::numeric_limits<double>::max()) { run(out, max_distance, 0); }
+    void determineReciprocalCorrespondences(Correspondences &out, double max_distance = std::numeric_limits<double>::max()) { run(out, max_distance, 1); }
+  private:
+    void run(Correspondences &out, double max_distance, int reciprocal)
+    {
+        if (!source_ && !dsource_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputSource not called");
+        if (!target_ && !dtarget_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputTarget not called");
+        const std::shared_ptr<Context> ctx = dsource_ ? dsource_->context() : dtarget_ ? dtarget_->context() : ctx_ ? ctx_ : Context::Default();
+        std::unique_ptr<DeviceCloud<PointSource>> tmp_source;
+        std::unique_ptr<DeviceCloud<PointTarget>> tmp_target;
+        if (!dsource_) tmp_source.reset(new DeviceCloud<PointSource>(*source_, ctx));
+        if (!dtarget_) tmp_target.reset(new DeviceCloud<PointTarget>(*target_, ctx));
+        const DeviceCloud<PointSource> &s = dsource_ ? *dsource_ : *tmp_source;
+        const DeviceCloud<PointTarget> &t = dtarget_ ? *dtarget_ : *tmp_target;
+        size_t n = 0, found = 0;
+        check(rsreg_cloud_info(s.handle(), &n, nullptr, nullptr, nullptr, nullptr), ctx->get());
+        out.resize(n);
+        check(rsreg_cloud_feature_correspondences(ctx->get(), s.handle(), t.handle(), max_distance, reciprocal,
+                                                  reinterpret_cast<rsreg_correspondence *>(out.data()), n, &found), ctx->get());
+        out.resize(found);
+    }
+    typename PointCloud<PointSource>::Ptr source_;
+    typename PointCloud<PointTarget>::Ptr target_;
+    const DeviceCloud<PointSource> *dsource_ = nullptr;
+    const DeviceCloud<PointTarget> *dtarget_ = nullptr;
+    std::shared_ptr<Context> ctx_;
+};
+
+}  // namespace registration
+
 // ---- pcl::IntegralImageNormalEstimation<PointInT, PointOutT> for organized clouds (csrc/iinormals_kernels.hpp,
 // rsreg_cloud_integral_normals), with the calls of src/edge_extractor.hpp:9-15.  AVERAGE_3D_GRADIENT, the IGNORE border policy
 // and no depth-dependent smoothing are what is implemented: compute() refuses anything else.  The window sums are the double

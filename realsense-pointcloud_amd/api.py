@@ -135,6 +135,10 @@ class FPFHCloud(NormalCloud):
     """width / height / is_dense / points like pcl::PointCloud<pcl::FPFHSignature33>; points: FPFH_DTYPE records."""
 
 
+# pcl::Correspondence (rsreg_correspondence): 12 bytes; distance is the squared distance
+CORRESPONDENCE_DTYPE = np.dtype([("index_query", np.int32), ("index_match", np.int32), ("distance", np.float32)])
+
+
 class DeviceCloud:
     """A cloud resident in HBM (rsreg_cloud): whole records plus width / height / is_dense.  What the
     reference's frame loop hands from step to step (filter -> align -> transformPointCloud -> operator+,
@@ -312,6 +316,30 @@ class DeviceCloud:
         rec = np.zeros(n, FPFH_DTYPE)
         _l.check(_l.lib().rsreg_cloud_download(self.h, rec.ctypes.data, n), self.ctx.h)
         return FPFHCloud(rec, w, h, dense)
+
+    def feature_knn(self, target, k):
+        """(index (ns, k) int32, sqr_dist (ns, k) float32): for every valid row of this descriptor cloud (records that start with 33
+        floats, what fpfh_cloud() returns) the k valid rows of `target`, a DeviceCloud of this context, with the smallest float32
+        squared distance, ascending by (d2, index) (rsreg_cloud_feature_knn, exact; include/rsreg.h holds the contract).  A row with
+        a float that is not finite gets -1 and 0.  1 <= k <= 16."""
+        ns = self.info()[0]
+        k = int(k)
+        idx = np.full((ns, max(k, 0)), -1, np.int32)
+        d2 = np.zeros((ns, max(k, 0)), np.float32)
+        _l.check(_l.lib().rsreg_cloud_feature_knn(self.ctx.h, self.h, target.h, k, idx.ctypes.data, d2.ctypes.data), self.ctx.h)
+        return idx, d2
+
+    def feature_correspondences(self, target, max_distance=None, reciprocal=False):
+        """pcl::registration::CorrespondenceEstimation's determineCorrespondences (reciprocal: determineReciprocalCorrespondences)
+        between this descriptor cloud and `target` (rsreg_cloud_feature_correspondences): a CORRESPONDENCE_DTYPE array ordered by
+        index_query; distance is the squared distance.  max_distance None: DBL_MAX, PCL's default, which keeps every match."""
+        ns = self.info()[0]
+        out = np.zeros(ns, CORRESPONDENCE_DTYPE)
+        found = C.c_size_t(0)
+        md = sys.float_info.max if max_distance is None else float(max_distance)
+        _l.check(_l.lib().rsreg_cloud_feature_correspondences(self.ctx.h, self.h, target.h, md, int(bool(reciprocal)), out.ctypes.data, ns,
+                                                              C.byref(found)), self.ctx.h)
+        return out[:found.value]
 
     def radius_count(self, radius):
         """radiusSearch of every record in its own cloud, counted (rsreg_cloud_radius_count, exact): uint32 per record, its
@@ -1357,6 +1385,51 @@ class FPFHEstimation:
         finally:
             tmp.close()
         return out
+
+
+class CorrespondenceEstimation:
+    """pcl::registration::CorrespondenceEstimation<FPFHSignature33, FPFHSignature33> on the GPU: every valid source descriptor's
+    nearest valid target descriptor by an exact brute-force search (csrc/feature_kernels.hpp,
+    rsreg_cloud_feature_correspondences; include/rsreg.h holds the contract).  setInputSource / setInputTarget take a DeviceCloud
+    of descriptor records (what FPFHEstimation.compute returns for a DeviceCloud) or a host FPFHCloud, which is uploaded into a
+    temporary.  Both calls return a CORRESPONDENCE_DTYPE array ordered by index_query; distance is the squared distance, a match AT
+    max_distance is kept.  setIndices and the rejectors are not built."""
+
+    def __init__(self, ctx=None):
+        self._src = None
+        self._tgt = None
+        self.ctx = ctx
+
+    def setInputSource(self, cloud):
+        self._src = cloud
+
+    def setInputTarget(self, cloud):
+        self._tgt = cloud
+
+    def _run(self, max_distance, reciprocal):
+        if self._src is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputSource not called")
+        if self._tgt is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputTarget not called")
+        ctx = next((c.ctx for c in (self._src, self._tgt) if isinstance(c, DeviceCloud)), None) or self.ctx or default_context()
+        made = []
+        try:
+            pair = []
+            for c in (self._src, self._tgt):
+                if not isinstance(c, DeviceCloud):
+                    c = DeviceCloud(c, ctx=ctx)
+                    made.append(c)
+                pair.append(c)
+            return pair[0].feature_correspondences(pair[1], max_distance, reciprocal)
+        finally:
+            for c in made:
+                c.close()
+
+    def determineCorrespondences(self, max_distance=sys.float_info.max):
+        return self._run(max_distance, False)
+
+    def determineReciprocalCorrespondences(self, max_distance=sys.float_info.max):
+        return self._run(max_distance, True)
 
 
 class IntegralImageNormalEstimation:

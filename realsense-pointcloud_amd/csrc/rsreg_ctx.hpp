@@ -202,6 +202,18 @@ struct RadiusScratch {
     DevBuf d_count;                // uint32 per record: its neighbours within the radius
 };
 
+// Scratch of feature matching (features.hip, feature_kernels.hpp), per row of the two descriptor clouds of a call; not part of an index
+struct FeatureScratch {
+    DevBuf d_valid[2];             // uint32 per row: all 33 floats finite; [0] the source's rows, [1] the target's (source == target: [1] alone)
+    DevBuf d_keys[2];              // uint64 per row, (d2 bits << 32 | index): [0] every source row's nearest target row, [1] every target row's nearest source row
+    DevBuf d_part;                 // k > 1: the K keys every (target slice, source row) leaves for the merge
+    DevBuf d_idx, d_d2;            // rsreg_cloud_feature_knn: k indices / k squared distances per source row, before they go home
+    DevBuf d_flags, d_pos, d_scan; // correspondences: keep flag per source row, its position among the kept, the prefix sum's scratch
+    DevBuf d_out;                  // the 12-byte correspondences, before they go home
+    DevBuf d_count;                // 16 bytes: valid rows of the source, of the target (uint32 each); correspondences found (uint64)
+    PinnedBuf host;                // where the target's count, or the number found, lands
+};
+
 // Scratch of IntegralImageNormalEstimation (iinormals.hip), per pixel of the organized frame it is given
 struct IinScratch {
     DevBuf d_dist0, d_dist1, d_dist2;   // float: the distance map as set up, after the forward pass, after the backward pass
@@ -446,6 +458,9 @@ struct rsreg_ctx {
     rsreg::PointGrid knn;            // rebuilt by every k-NN call from the cloud it is given
     rsreg::FilterScratch filt;
     rsreg::RadiusScratch rad;        // radius search: it indexes in `knn` too, with a placement of its own
+
+    // ---- feature matching (features.hip): scratch of its own
+    rsreg::FeatureScratch feat;
 
     // ---- IntegralImageNormalEstimation (iinormals.hip)
     rsreg::IinScratch iin;

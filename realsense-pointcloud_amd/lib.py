@@ -16,7 +16,7 @@ ROOT = os.path.dirname(_HERE)
 DIAG = os.environ.get("RSREG_DIAG", "") == "1"
 SO_PATH = (os.environ.get("RSREG_SO") if DIAG else None) or os.path.join(_HERE, "librsreg_diag.so" if DIAG else "librsreg.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip", "depthcloud.hip", "depth_host.cpp"]
+SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip", "depthcloud.hip", "depth_host.cpp", "features.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) if os.path.isdir(CSRC) else []
 NUM_SUMS = 17
 NUM_PLANE_SUMS = 32                                      # include/rsreg.h: RSREG_NUM_PLANE_SUMS
@@ -47,7 +47,7 @@ EXPORTS = [
     "rsreg_icp_grid_info", "rsreg_ctx_host_timing", "rsreg_lzf_max_encoded_size", "rsreg_lzf_encode", "rsreg_lzf_decode",
     "rsreg_icp_fitness_score", "rsreg_icp_fitness_sums", "rsreg_ndt_fitness_score",
     "rsreg_cloud_passthrough", "rsreg_cloud_sor", "rsreg_cloud_knn_mean_distance", "rsreg_cloud_knn", "rsreg_cloud_normals",
-    "rsreg_cloud_fpfh", "rsreg_cloud_spfh",
+    "rsreg_cloud_fpfh", "rsreg_cloud_spfh", "rsreg_cloud_feature_knn", "rsreg_cloud_feature_correspondences",
     "rsreg_cloud_radius_count", "rsreg_cloud_radius_outlier_removal", "rsreg_cloud_normals_radius",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
@@ -92,6 +92,10 @@ class IcpResult(C.Structure):
 
 class SorStats(C.Structure):   # rsreg_sor_stats
     _fields_ = [("n_valid", C.c_uint64), ("n_kept", C.c_uint64), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
+
+
+class Correspondence(C.Structure):   # rsreg_correspondence (pcl::Correspondence)
+    _fields_ = [("index_query", C.c_int32), ("index_match", C.c_int32), ("distance", C.c_float)]
 
 
 class IinParams(C.Structure):   # rsreg_iin_params
@@ -310,6 +314,8 @@ def lib():
     L.rsreg_cloud_normals.argtypes = [vp, vp, i32, vp, vp]
     L.rsreg_cloud_fpfh.argtypes = [vp, vp, vp, i32, vp]
     L.rsreg_cloud_spfh.argtypes = [vp, vp, vp, i32, vp]
+    L.rsreg_cloud_feature_knn.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.rsreg_cloud_feature_correspondences.argtypes = [vp, vp, vp, dbl, i32, vp, sz, C.POINTER(sz)]
     L.rsreg_cloud_radius_count.argtypes = [vp, vp, dbl, vp]
     L.rsreg_cloud_radius_outlier_removal.argtypes = [vp, vp, dbl, i32, i32, i32, vp, C.POINTER(C.c_uint64)]
     L.rsreg_cloud_normals_radius.argtypes = [vp, vp, dbl, vp, vp]
