@@ -586,7 +586,9 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
  *   for t in 0 .. 2: if (sum_t != 0) sum_t = (float)(100.0 / (double)sum_t); h[t][b] *= sum_t.
  * Two quirks of PCL are kept: the weight is 1 / SQUARED distance, and the record's own SPFH does not enter its FPFH.  A record
  * with no neighbour at positive distance gives 33 zeros, never a division by zero.  A record that is not finite, or whose own
- * normal is not finite, gets 33 quiet NaNs.
+ * normal is not finite, gets 33 quiet NaNs.  A finite record can get NaNs by the arithmetic above as well, when 1.0f / d2[a] or a
+ * product overflows (a denormal d2 gives w = +inf, and 0 * inf is NaN): the NaNs stand where the formula puts them, their sign
+ * and payload are not specified, and is_dense is 0 as for any other NaN.
  * DEVIATION FROM PCL 1.9.1, stated: PCL computes the pair features in float through Eigen; here they are computed in double.  A PCL
  * build can differ where a feature lies within float rounding of a bin edge.
  * The same cloud, normals and k give the same bytes whatever the context has indexed before: the counts are integers, every

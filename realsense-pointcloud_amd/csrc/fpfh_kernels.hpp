@@ -116,7 +116,7 @@ __global__ __launch_bounds__(kKnnWave) void k_fpfh_spfh(PointGridDev g, int k, f
 }
 
 // One workgroup of ONE wave per record, in record order.  out: record i's 33 floats; a record that is not finite or whose own
-// normal is not finite gets quiet NaNs and sets *any_nan.  PCL's order (include/rsreg.h): for a, for t, for b: val = SPFH * w,
+// normal is not finite gets quiet NaNs and sets *any_nan; so does every row the arithmetic leaves a NaN in.  PCL's order (include/rsreg.h): for a, for t, for b: val = SPFH * w,
 // sum_t += val, h[t][b] += val; then h *= 100 / sum_t.  Lane b adds its own h in neighbour order; lane t < 3 adds sum_t over
 // (a, b) from the products staged in LDS.
 __global__ __launch_bounds__(kKnnWave) void k_fpfh_weight(const char *rec, size_t stride, const char *nrm, size_t nstride, uint32_t n, int k,
@@ -165,7 +165,15 @@ __global__ __launch_bounds__(kKnnWave) void k_fpfh_weight(const char *rec, size_
             sums[lane] = s;
         }
         __syncthreads();
-        if (lane < kFpfhRow) out[(size_t)i * kFpfhRow + (size_t)lane] = __fmul_rn(h, sums[lane / kFpfhBins]);
+        // a finite record gets NaNs by the arithmetic too (1 / d2 = +inf for a denormal d2, and 0 * inf; inf - inf of overflowed
+        // products): the flag is raised for every row that holds one -- a ballot, one plain store of the same word by one lane
+        bool is_nan = false;
+        if (lane < kFpfhRow) {
+            const float r = __fmul_rn(h, sums[lane / kFpfhBins]);
+            out[(size_t)i * kFpfhRow + (size_t)lane] = r;
+            is_nan = r != r;
+        }
+        if (__ballot(is_nan) != 0ull && lane == 0) *any_nan = 1u;
         __syncthreads();   // (the staged products and the weights have been read: the next record may overwrite them)
     }
 }

@@ -13,7 +13,9 @@ import numpy as np
 DIM = 33
 TILE, QUERIES, FILL = 64, 64, 2048
 KS = (1, 2, 5, 16)
+KS_EDGE = (3, 4, 8, 9)        # the compile-time lists are 1, 2, 4, 8, 16: the first and the last k of the lists KS leaves out
 NS = (1, 63, 64, 65, 1000)
+EVERY_K_SIZES = ((65, 2500), (1000, 65))   # several slices and a second query block of one live lane; one slice, a full and a one-row tile
 
 
 def nts(k):
@@ -33,7 +35,7 @@ def slice_begin(s, slices, nt):
 
 
 # (ns, nt) the rule is tabulated on: every size of the tests, the corners of the rule, and sizes of real use
-PLAN_TABLE = sorted({(ns, nt) for ns in NS for k in KS for nt in nts(k)} |
+PLAN_TABLE = sorted({(ns, nt) for ns in NS for k in KS + KS_EDGE for nt in nts(k)} | set(EVERY_K_SIZES) |
                     {(1, 20000), (3000, 16), (65, 2500), (1, 1), (1, 127), (1, 128), (64, 64 * 2048), (64, 64 * 2048 + 63), (65, 64 * 2048), (2048 * 64, 5000),
                      (2048 * 64 + 1, 5000), (5000, 5000), (30000, 30000), (100000, 100000), (307200, 307200), (2 ** 31 - 17, 2 ** 31 - 17), (1, 2 ** 31 - 17)})
 
@@ -138,6 +140,70 @@ def few_valid(n_valid, nt=70, seed=106):
     tgt[bad[::2], 0] = np.nan
     tgt[bad[1::2], DIM - 1] = np.inf
     return tgt
+
+
+BIG = np.float32(3e38)
+OVERFLOW_BIN = 11
+OVERFLOW_PLUS_TARGETS = 5     # target rows that share the source's +3e38: fewer than 16, so a 16th answer lies at +inf
+
+
+@functools.lru_cache(maxsize=None)
+def overflow(ns=130, nt=200, seed=107):
+    """(source, target): every way a d2 becomes +inf, all rows finite floats.
+      * every fourth source row times -2^120, every third target row times 2^120: a square overflows.  Such a source row is at +inf
+        from EVERY target row: its k nearest are the k lowest valid target indices, against a list that starts empty;
+      * bin OVERFLOW_BIN holds +3e38 in source rows 1, 9, 17, .. and -3e38 in target rows 1, 8, 15, ..: the difference itself
+        overflows (3e38 - -3e38).  OVERFLOW_PLUS_TARGETS target rows hold +3e38 there instead: the only rows at a finite distance
+        from those source rows, so their nearest is finite and their 16th is +inf;
+      * the last source row is 1e19 in every bin: every square is finite and the SUM overflows at the fourth bin; the one before
+        is 1e15 in every bin: far from every target row, at a finite distance from the ones that are not scaled."""
+    src, tgt = order_rows(ns, seed), order_rows(nt, seed + 1)
+    with np.errstate(over="ignore"):
+        tgt[::3] = np.ldexp(tgt[::3], 120)
+        src[::4] = -np.ldexp(src[::4], 120)
+    src[1::8, OVERFLOW_BIN] = BIG
+    tgt[1::7, OVERFLOW_BIN] = -BIG
+    plus = np.arange(2, nt, 3)[-OVERFLOW_PLUS_TARGETS:]       # (not scaled, not among the -3e38 rows)
+    plus = plus[(plus % 7) != 1]
+    tgt[plus, OVERFLOW_BIN] = BIG
+    src[-1] = np.float32(1e19)
+    src[-2] = np.float32(1e15)
+    assert np.isfinite(src).all() and np.isfinite(tgt).all()
+    return _frozen(src, tgt)
+
+
+@functools.lru_cache(maxsize=None)
+def denormal(name):
+    """(source, target) whose squared distances are float32 denormals while every input is a normal float: the key of the search is
+    the float's bit pattern, so the answer is right only if no subtraction, product or sum of a pair flushes a denormal.
+      "order"  order_rows * 2^-70: most d2 are denormal, none is zero, the last bits depend on the summation order;
+      "exact"  exact_rows * 2^-73: every d2 is a denormal of a few bits (a difference of 0.25 squares to 2^-150, half of the
+               smallest denormal: it rounds to 0), a few hundred distinct values, ties everywhere;
+      "zeros"  rows of +0.0 and -0.0 alone: every d2 has the bits of +0, the lowest index wins."""
+    if name == "order":
+        src, tgt = np.ldexp(order_rows(200, 108), -70), np.ldexp(order_rows(300, 109), -70)
+    elif name == "exact":
+        src, tgt = exact_rows(200, 110), exact_rows(300, 111)
+        near = (np.abs(src[:, None, :] - tgt[None, :, :]) <= 0.25).all(axis=2).any(axis=0)
+        src, tgt = np.ldexp(src, -73), np.ldexp(tgt[~near], -73)          # (a target row 0.25 or less from a source row in every bin: d2 = 0, left out)
+    elif name == "zeros":
+        rng = np.random.default_rng(112)
+        src, tgt = (np.where(rng.random((n, DIM)) < 0.5, np.float32(0.0), np.float32(-0.0)).astype(np.float32) for n in (70, 130))
+    else:
+        raise KeyError(name)
+    assert src.dtype == np.float32 and tgt.dtype == np.float32
+    return _frozen(src, tgt)
+
+
+DENORMALS = ("order", "exact", "zeros")
+FLT_MIN = np.finfo(np.float32).tiny
+
+
+def self_rows():
+    """The rows of the `source == target` tests: the real case's target -- repeated rows everywhere -- with three rows made invalid."""
+    rows = real()[1].copy()
+    rows[[5, 1000, 2899], [0, 32, 7]] = [np.nan, np.inf, -np.inf]
+    return rows
 
 
 def records(rows, stride=132, seed=0):

@@ -87,3 +87,54 @@ def ref_normals(name, k=10):
     nrm = np.ascontiguousarray(N.normals(cloud(name), k).normal)
     nrm.setflags(write=False)
     return nrm
+
+
+# ---- hand-made normals: the contract normalises nothing, so its formulas hold for any finite normal.  Each case is (xyz, normals).
+ZEROED = (200, 585)           # zero_normals: record 200 and its nearest neighbour, whose nearest neighbour is record 200
+EVERY_K = tuple(range(2, 65))
+
+
+def _frozen(*arrays):
+    for a in arrays:
+        a.setflags(write=False)
+    return arrays
+
+
+@functools.lru_cache(maxsize=None)
+def non_unit(power=0):
+    """uniform() with its reference normals (k = 10), each times 2^e, e drawn from [-20, 20]: f2 and f3 leave [-1, 1] and the clamps
+    of the bins at 0 and 10 work.  power: all of them times 2^power more (100: still finite floats, products far outside)."""
+    e = np.random.default_rng(18).integers(-20, 21, len(cloud("uniform")))
+    nrm = np.ldexp(ref_normals("uniform"), (e + power)[:, None]).astype(np.float32)
+    assert np.isfinite(nrm).all()
+    return _frozen(cloud("uniform").copy(), nrm)
+
+
+@functools.lru_cache(maxsize=None)
+def parallel():
+    """lattice() with every normal (0, 0, 1): for the neighbours straight above and below dp is parallel to the source normal,
+    |v| = 0, the pair is skipped.  Every other feature sits at mid-bin or well inside one."""
+    xyz = lattice()
+    return _frozen(xyz, np.tile(np.float32([0.0, 0.0, 1.0]), (len(xyz), 1)))
+
+
+@functools.lru_cache(maxsize=None)
+def zero_normals():
+    """non_unit() with the normals of record ZEROED[0] and of its nearest neighbour set to (0, 0, 0): finite, so accepted.  One
+    side zero: f1 = atan2(+-0, +-0), on the sign of a zero; both sides zero: v = 0, the pair is skipped both ways."""
+    xyz, nrm = non_unit()
+    nrm = nrm.copy()
+    nrm[list(ZEROED)] = 0.0
+    return _frozen(xyz.copy(), nrm)
+
+
+@functools.lru_cache(maxsize=None)
+def every_k():
+    """200 records of the uniform box with their reference normals at k = 10: small enough to run every k from 2 to 64."""
+    import normals_ref as N
+    xyz = uniform(200, 3)
+    return _frozen(xyz, np.ascontiguousarray(N.normals(xyz, 10).normal))
+
+
+HAND_MADE = {"non_unit": non_unit, "non_unit_2^100": lambda: non_unit(100), "parallel": parallel, "zero_normals": zero_normals}
+FRAGILE_CAP = {"non_unit": 0.01, "non_unit_2^100": 0.01, "parallel": 0.01, "zero_normals": 0.04}

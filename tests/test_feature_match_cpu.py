@@ -108,7 +108,7 @@ def test_copies_case_lowest_index_wins(ns, nt):
     if nt > K.TILE:
         assert {0, K.TILE - 1, K.TILE} <= set(planted.tolist())
     assert len(planted) >= min(nt, 2) and (slices == 1 or len(planted) >= 2 * slices)
-    for k in K.KS:
+    for k in K.KS + K.KS_EDGE:
         if len(planted) < k:
             continue
         idx, d2 = R.knn(src, tgt, k)
@@ -126,11 +126,106 @@ def test_holes_case():
     assert not np.isin(idx[sv], np.flatnonzero(~tv)).any()                   # never a match
     pairs = R.correspondences(src, tgt)
     assert [p[0] for p in pairs] == np.flatnonzero(sv).tolist()              # never a query
-    for k in K.KS:
+    for k in K.KS + K.KS_EDGE:
         assert R.valid_rows(K.few_valid(k)).sum() == k
         R.knn(src, K.few_valid(k), k)
         with pytest.raises(ValueError):
             R.knn(src, K.few_valid(k - 1), k)
+
+
+def test_overflow_case():
+    """What the GPU test relies on, on the reference alone: +inf everywhere, never a NaN; source rows at +inf from every target row
+    get the lowest valid indices; rows whose nearest is finite and whose 16th is not."""
+    src, tgt = K.overflow()
+    assert R.valid_rows(src).all() and R.valid_rows(tgt).all() and 100 <= len(src) <= 500 and 100 <= len(tgt) <= 500
+    d2 = R.d2_matrix(src, tgt)
+    assert not np.isnan(d2).any()
+    share = np.isinf(d2).mean()
+    with np.errstate(over="ignore"):
+        diff = src[:, None, K.OVERFLOW_BIN] - tgt[None, :, K.OVERFLOW_BIN]
+    idx4, d4 = R.knn(src, tgt, 4)
+    all_inf = np.isinf(d4).all(axis=1)
+    idx16, d16 = R.knn(src, tgt, 16)
+    mixed = np.isfinite(d16[:, 0]) & np.isinf(d16[:, -1])
+    print("overflow: %d x %d, +inf share %.2f, pairs whose difference overflows %d, rows with all four nearest at +inf %d, with a finite nearest and a +inf 16th %d" %
+          (len(src), len(tgt), share, int(np.isinf(diff).sum()), int(all_inf.sum()), int(mixed.sum())))
+    assert 0.25 <= share <= 0.75
+    assert np.isinf(diff).sum() > 100                                        # 3e38 - -3e38: the difference itself
+    assert all_inf.sum() >= 10 and (idx4[all_inf] == np.arange(4)).all()     # every target row is valid: the four lowest indices
+    assert np.isinf(d2[all_inf]).all() and (idx16[all_inf] == np.arange(16)).all()
+    assert mixed.sum() >= 5
+    assert np.isinf(d2[-1]).all() and (src[-1].astype(np.float64) ** 2 < K.BIG).all()   # finite squares, a sum that overflows
+    assert np.isfinite(d2[-2]).any() and d2[-2].min() > 1e30                 # far from every target row, at a finite distance from some
+    # correspondences: +inf matches are kept at DBL_MAX with distance inf, and exactly they are dropped at 1e30 (1e60 > FLT_MAX)
+    sv, tv = R.valid_rows(src), R.valid_rows(tgt)
+    for reciprocal in (False, True):
+        kept = R.correspondences_from_d2(d2, sv, tv, R.DBL_MAX, reciprocal)
+        cut = R.correspondences_from_d2(d2, sv, tv, 1e30, reciprocal)
+        assert any(np.isinf(p[2]) for p in kept) and cut == [p for p in kept if np.isfinite(p[2])] and 0 < len(cut) < len(kept)
+    assert len(R.correspondences_from_d2(d2, sv, tv)) == len(src)
+
+
+def test_reciprocal_tie_at_infinity_on_a_hand_made_pair():
+    """Source rows at 3e38, 2e38, 0 and target rows at -3e38, -3e38, 1 along bin 0.  Every distance but the last pair's is +inf
+    (3e38 - -3e38 overflows in the difference, 2e38 - -3e38 too, 0 - -3e38 in the square), and +inf ties with +inf: every all-inf row
+    takes index 0.  Source row 1's forward match is target 0, whose nearest source is row 0: not reciprocal."""
+    def rows(xs):
+        out = np.zeros((len(xs), R.DIM), np.float32)
+        out[:, 0] = xs
+        return out
+    src, tgt = rows([3e38, 2e38, 0.0]), rows([-3e38, -3e38, 1.0])
+    inf = np.inf
+    assert R.d2_matrix(src, tgt).tolist() == [[inf, inf, inf], [inf, inf, inf], [inf, inf, 1.0]]
+    assert R.correspondences(src, tgt) == [(0, 0, inf), (1, 0, inf), (2, 2, 1.0)]
+    assert R.correspondences(src, tgt, reciprocal=True) == [(0, 0, inf), (2, 2, 1.0)]
+    assert R.correspondences(src, tgt, max_distance=1e30) == [(2, 2, 1.0)] == R.correspondences(src, tgt, max_distance=1e30, reciprocal=True)
+    assert R.knn(src, tgt, 3)[0].tolist() == [[0, 1, 2], [0, 1, 2], [2, 0, 1]]
+
+
+def test_denormal_cases():
+    """Squared distances below FLT_MIN from inputs that are all normal floats (or zeros): what is tested is the arithmetic of a
+    pair, not the upload."""
+    for name in K.DENORMALS:
+        src, tgt = K.denormal(name)
+        for rows in (src, tgt):
+            assert ((rows == 0) | (np.abs(rows) >= K.FLT_MIN)).all() and R.valid_rows(rows).all()
+        d2 = R.d2_matrix(src, tgt)
+        den = (d2 > 0) & (d2 < K.FLT_MIN)
+        _, d4 = R.knn(src, tgt, 4)
+        den4 = (d4 > 0) & (d4 < K.FLT_MIN)
+        print("denormal %s: %d x %d, denormal d2 %.1f %%, of the four nearest %.1f %%, zero %d, distinct values %d" %
+              (name, len(src), len(tgt), 100 * den.mean(), 100 * den4.mean(), int((d2 == 0).sum()), len(np.unique(d2))))
+        if name == "order":
+            assert den.mean() >= 0.5 and den4.mean() >= 0.5 and not (d2 == 0).any()
+            assert (src != 0).all() and (tgt != 0).all()
+        elif name == "exact":
+            assert den.all() and len(np.unique(d2)) < d2.size // 50
+            ties = (d2 == d2.min(axis=1)[:, None]).sum(axis=1)
+            assert (ties > 1).mean() > 0.1                                   # ties present, at the nearest itself
+            # a difference of 0.25 * 2^-73 squares to half the smallest denormal and rounds to 0 (to even): the bits are a matter of rounding there
+            assert np.float32(np.ldexp(np.float32(0.25), -73)) ** 2 == 0 and (np.ldexp(np.float32(0.5), -73) ** 2).view(np.uint32) == 2
+        else:
+            assert (d2.view(np.uint32) == 0).all() and np.signbit(src).any() and not np.signbit(src).all()
+            idx, _ = R.knn(src, tgt, 16)
+            assert (idx == np.arange(16)).all()
+
+
+def test_self_rows_case():
+    """source == target at k > 1 on the reference: column 0 is the lowest valid copy at d2 = 0, and the copies of a row come before
+    every other row, in index order."""
+    rows = K.self_rows()
+    valid = R.valid_rows(rows)
+    assert (~valid).sum() == 3
+    idx, d2 = R.knn(rows, rows, 16)
+    _, inverse = np.unique(rows, axis=0, return_inverse=True)
+    inverse = inverse.reshape(-1)
+    many = 0
+    for i in np.flatnonzero(valid)[::7]:
+        same = np.flatnonzero(valid & (inverse == inverse[i]))
+        m = min(len(same), 16)
+        assert idx[i, :m].tolist() == same[:m].tolist() and (d2[i, :m] == 0).all() and (m == 16 or d2[i, m] > 0)
+        many += 1 < len(same)
+    assert many > 20 and (idx[~valid] == -1).all()
 
 
 def test_records_keep_the_rows_and_fill_the_rest():

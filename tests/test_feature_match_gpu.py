@@ -75,7 +75,7 @@ def _check_knn(api, ctx, src, tgt, k, d2=None, dsrc=None, dtgt=None, label=""):
     return idx, dist
 
 
-@pytest.mark.parametrize("k", K.KS)
+@pytest.mark.parametrize("k", K.KS + K.KS_EDGE)
 @pytest.mark.parametrize("name", ["exact", "order"])
 def test_knn_bit_equal_on_the_size_grid(api, ctx, name, k):
     """ns in {1, 63, 64, 65, 1000} x nt in {k, tile - 1, tile, tile + 1, 2500}: prefixes of one pool, one reference matrix.  One
@@ -96,6 +96,19 @@ def test_knn_bit_equal_on_real_rows(api, ctx, k):
     _check_knn(api, ctx, src, tgt, k, _pool_d2("real"), _prefix(api, ctx, "real", 0, len(src)), _prefix(api, ctx, "real", 1, len(tgt)), "real")
 
 
+@pytest.mark.parametrize("name", ["exact", "order"])
+def test_knn_every_k(api, ctx, name):
+    """k = 1 .. 16, so every list length K in {1, 2, 4, 8, 16} runs with k at its first and at its last slot (k = K: the k-th answer
+    is the slot the guard and the eviction work on, no slack behind it).  (65, 2500): 39 slices and a second query block with one
+    live lane; (1000, 65): one slice, a full tile and a tile of one row."""
+    src, tgt = POOLS[name]()
+    d2 = _pool_d2(name)
+    for ns, nt in K.EVERY_K_SIZES:
+        assert (K.plan(ns, nt)[1] > 1) == (nt == 2500)
+        for k in range(1, 17):
+            _check_knn(api, ctx, src[:ns], tgt[:nt], k, d2[:ns, :nt], _prefix(api, ctx, name, 0, ns), _prefix(api, ctx, name, 1, nt), name)
+
+
 @pytest.mark.parametrize("ns,nt", K.COPIES_SIZES)
 def test_knn_copies_lowest_index_wins(api, ctx, ns, nt):
     """Equal rows at index 0, tile - 1, tile and at both ends of every slice: (1, 20 000) is one query block and 312 slices,
@@ -103,7 +116,7 @@ def test_knn_copies_lowest_index_wins(api, ctx, ns, nt):
     src, tgt, planted = K.copies(ns, nt, 200 + ns)
     dsrc, dtgt = _dev(api, ctx, src), _dev(api, ctx, tgt)
     d2 = R.d2_matrix(src, tgt)
-    for k in K.KS:
+    for k in K.KS + K.KS_EDGE:
         if k > nt:
             continue
         idx, dist = _check_knn(api, ctx, src, tgt, k, d2, dsrc, dtgt, "copies")
@@ -112,7 +125,7 @@ def test_knn_copies_lowest_index_wins(api, ctx, ns, nt):
             assert idx[ns // 2].tolist() == planted[:k].tolist()
 
 
-@pytest.mark.parametrize("k", K.KS)
+@pytest.mark.parametrize("k", K.KS + K.KS_EDGE)
 def test_knn_holes(api, ctx, k):
     """NaN, +inf, -inf in the first or last bin: never a match, never a query; a target with exactly k valid rows is searched, one
     with k - 1 refused."""
@@ -209,6 +222,95 @@ def test_reciprocal_tie_drops_a_good_forward_match(api, ctx):
     src, tgt = rows([0.0, 1.0, 10.0]), rows([0.5, 0.5, 9.0])
     fwd, rec = _check_lists(_dev(api, ctx, src), _dev(api, ctx, tgt), R.d2_matrix(src, tgt), R.valid_rows(src), R.valid_rows(tgt), None, "tie")
     assert fwd.tolist() == [(0, 0, 0.25), (1, 0, 0.25), (2, 2, 1.0)] and rec.tolist() == [(0, 0, 0.25), (2, 2, 1.0)]
+
+
+def test_overflowing_distances(api, ctx):
+    """A square, a difference and a sum that overflow: d2 = +inf, which ties with every other +inf.  Source rows at +inf from every
+    target row get the k lowest valid indices (against a list that starts at kFmNone); +inf matches are correspondences at DBL_MAX
+    with distance inf, and exactly they are dropped at max_distance = 1e30 (its square, 1e60, is above every finite float)."""
+    src, tgt = K.overflow()
+    d2, dsrc, dtgt = R.d2_matrix(src, tgt), _dev(api, ctx, src), _dev(api, ctx, tgt)
+    sv, tv = R.valid_rows(src), R.valid_rows(tgt)
+    for k in (1, 4, 16):
+        idx, dist = _check_knn(api, ctx, src, tgt, k, d2, dsrc, dtgt, "overflow")
+        all_inf = np.isinf(d2).all(axis=1)
+        assert all_inf.sum() >= 10 and (idx[all_inf] == np.arange(k)).all() and np.isinf(dist[all_inf]).all()
+        assert not np.isnan(dist).any()
+    assert (np.isfinite(dist[:, 0]) & np.isinf(dist[:, -1])).sum() >= 5
+    fwd, rec = _check_lists(dsrc, dtgt, d2, sv, tv, None, "overflow")
+    assert len(fwd) == len(src) and np.isinf(fwd["distance"]).sum() >= 10 and np.isinf(rec["distance"]).any()
+    assert (0, 0) in zip(rec["index_query"].tolist(), rec["index_match"].tolist())     # +inf both ways, the lowest index both ways
+    cut_fwd, cut_rec = _check_lists(dsrc, dtgt, d2, sv, tv, 1e30, "overflow, 1e30")
+    assert cut_fwd.tobytes() == fwd[np.isfinite(fwd["distance"])].tobytes() and cut_rec.tobytes() == rec[np.isfinite(rec["distance"])].tobytes()
+    assert 0 < len(cut_rec) < len(rec) and 0 < len(cut_fwd) < len(fwd)
+
+
+def test_reciprocal_tie_at_infinity(api, ctx):
+    """Source rows at 3e38, 2e38, 0 and target rows at -3e38, -3e38, 1 along bin 0: every d2 but the last pair's is +inf, the +inf
+    ties go to index 0 both ways, so source row 1 -- whose forward match is target 0 -- is not reciprocal.  At 1e30 the +inf matches
+    go, forward and reciprocal."""
+    def rows(xs):
+        out = np.zeros((len(xs), 33), np.float32)
+        out[:, 0] = xs
+        return out
+    src, tgt = rows([3e38, 2e38, 0.0]), rows([-3e38, -3e38, 1.0])
+    dsrc, dtgt = _dev(api, ctx, src), _dev(api, ctx, tgt)
+    d2, sv, tv = R.d2_matrix(src, tgt), R.valid_rows(src), R.valid_rows(tgt)
+    fwd, rec = _check_lists(dsrc, dtgt, d2, sv, tv, None, "tie at +inf")
+    inf = float("inf")
+    assert fwd.tolist() == [(0, 0, inf), (1, 0, inf), (2, 2, 1.0)] and rec.tolist() == [(0, 0, inf), (2, 2, 1.0)]
+    fwd, rec = _check_lists(dsrc, dtgt, d2, sv, tv, 1e30, "tie at +inf, 1e30")
+    assert fwd.tolist() == [(2, 2, 1.0)] and rec.tolist() == [(2, 2, 1.0)]
+    idx, dist = _check_knn(api, ctx, src, tgt, 3, d2, dsrc, dtgt, "tie at +inf")
+    assert idx.tolist() == [[0, 1, 2], [0, 1, 2], [2, 0, 1]]
+
+
+@pytest.mark.parametrize("name", K.DENORMALS)
+def test_denormal_distances(api, ctx, name):
+    """d2 below FLT_MIN from normal inputs: the key is the float's bit pattern, so one flushed difference, product or sum changes
+    an answer.  `zeros`: rows of +0.0 and -0.0, every d2 the bits of +0, the lowest index wins."""
+    src, tgt = K.denormal(name)
+    d2, dsrc, dtgt = R.d2_matrix(src, tgt), _dev(api, ctx, src), _dev(api, ctx, tgt)
+    for k in (1, 4, 16):
+        idx, dist = _check_knn(api, ctx, src, tgt, k, d2, dsrc, dtgt, "denormal " + name)
+        if name == "zeros":
+            assert (idx == np.arange(k)).all() and (dist.view(np.uint32) == 0).all()
+        else:
+            assert (dist[:, 0] > 0).all() and (dist[:, 0] < K.FLT_MIN).mean() > 0.9
+    sv, tv = R.valid_rows(src), R.valid_rows(tgt)
+    fwd, rec = _check_lists(dsrc, dtgt, d2, sv, tv, None, "denormal " + name)
+    assert len(fwd) == len(src) and 0 < len(rec) <= len(fwd)
+    middle = float(np.sqrt(np.float64(np.median(fwd["distance"]))))           # a bound among the denormals: the compare is in double
+    part, _ = _check_lists(dsrc, dtgt, d2, sv, tv, middle, "denormal " + name)
+    assert (0 < len(part) < len(fwd)) or name == "zeros"
+
+
+@pytest.mark.parametrize("k", [4, 16])
+def test_source_is_target_past_the_first(api, ctx, k):
+    """One cloud in both roles -- one validity array serves both -- at k > 1, on rows with copies and three invalid rows: column 0 is
+    the lowest valid copy at d2 = 0, and the copies of a row come before every other row, in index order."""
+    rows = K.self_rows()
+    valid = R.valid_rows(rows)
+    dc = _dev(api, ctx, rows)
+    idx, dist = _check_knn(api, ctx, rows, rows, k, _self_d2(), dc, dc, "source is target")
+    _, inverse = np.unique(rows, axis=0, return_inverse=True)
+    inverse = inverse.reshape(-1)
+    order = np.lexsort((np.arange(len(rows)), inverse))
+    order = order[valid[order]]                                                # the valid rows, grouped by distinct row, ascending index inside
+    starts = np.flatnonzero(np.r_[True, np.diff(inverse[order]) != 0])
+    several = 0
+    for a, b in zip(starts, np.r_[starts[1:], len(order)]):
+        same = order[a:b]
+        m = min(len(same), k)
+        assert (idx[same, :m] == same[:m]).all() and (dist[same, :m] == 0).all() and (m == k or (dist[same, m] > 0).all())
+        several += len(same) if len(same) > 1 else 0
+    assert several > 100 and (idx[~valid] == -1).all() and (dist[~valid] == 0).all()
+
+
+@functools.lru_cache(maxsize=None)
+def _self_d2():
+    rows = K.self_rows()
+    return R.d2_matrix(rows, rows)
 
 
 def test_capacity_smaller_than_found(api, ctx):

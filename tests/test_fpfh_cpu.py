@@ -111,6 +111,60 @@ def test_recorded_result():
     assert (r.fragile_nb == g["fragile_nb"]).all()
 
 
+@functools.lru_cache(maxsize=None)
+def _hand_made(name):
+    xyz, nrm = K.HAND_MADE[name]()
+    return F.fpfh(xyz, nrm, 10)
+
+
+def _clamped(r, t):
+    """The counted pairs whose scaled feature t lies outside [0, 11): the clamp moves them into bin 0 or bin 10."""
+    s = r.scaled[..., t]
+    return r.valid & ((s < 0.0) | (s >= float(F.BINS)))
+
+
+@pytest.mark.parametrize("name", sorted(K.HAND_MADE))
+def test_hand_made_normals(name):
+    """The cases with normals that are not unit vectors, on the reference alone: the branches each one is there for are taken, the
+    share of records the GPU test lets off stays under the cap (1 %; 4 % where two normals are zero and theta = +-pi hangs on the
+    sign of a zero), and no row holds a NaN."""
+    r = _hand_made(name)
+    n = len(r.idx)
+    own = np.arange(n)[:, None]
+    pairs, skipped = int(r.valid.sum()), int((~r.valid & (r.idx != own)).sum())
+    f2, f3 = int(_clamped(r, 1).sum()), int(_clamped(r, 2).sum())
+    share = r.fragile_nb.mean()
+    print("%s: %d records, %d pairs counted, %d skipped, clamped in f2 %d, in f3 %d, fragile %d, fragile or fragile neighbour %d (%.2f %%)" %
+          (name, n, pairs, skipped, f2, f3, int(r.fragile.sum()), int(r.fragile_nb.sum()), 100 * share))
+    assert n <= 2000 and share <= K.FRAGILE_CAP[name]
+    assert not r.nan_rows.any() and np.isfinite(r.fpfh).all() and F.blocks_ok(r.fpfh).all()
+    assert (r.counts.reshape(n, 3, 11).sum(axis=2) == r.valid.sum(axis=1)[:, None]).all()
+    if name.startswith("non_unit"):
+        assert f3 >= pairs / 4 and f2 > 0 and not r.fragile_nb.any() and skipped == 0
+        assert r.counts[:, 22].sum() > 1000 and r.counts[:, 32].sum() > 1000 and r.counts[:, 11].sum() > 100 and r.counts[:, 21].sum() > 100   # both clamps
+    if name == "parallel":
+        assert skipped > 3000 and not r.fragile.any() and f2 == 0 and f3 == 0
+        m = r.margin[r.valid]
+        assert m.min() > 0.3                                                   # mid-bin (5.5) or well inside one (1.61, 9.39; 2.32 at the rim)
+    if name == "zero_normals":
+        a, b = K.ZEROED
+        assert r.idx[a, 1] == b and r.idx[b, 1] == a                           # mutual nearest neighbours: v = 0 both ways
+        assert not r.valid[a, 1] and not r.valid[b, 1] and skipped == 2
+        assert r.fragile[a] and r.fragile[b] and 0 < r.fragile.sum() < 20      # theta = +-pi on the sign of a zero
+        s = r.scaled[[a, b]][r.valid[[a, b]]]
+        assert np.isin(s[:, 0], [0.0, 5.5, 11.0]).all() and (s[:, 1] == 5.5).all()   # atan2(+-0, +-0) is 0 or +-pi; f2 = v . 0 = 0
+
+
+def test_every_k_lets_no_record_off():
+    """uniform(200, 3) at every k from 2 to 64: no record is fragile at any k, so the GPU sweep compares every row."""
+    xyz, nrm = K.every_k()
+    assert len(xyz) == 200 and K.EVERY_K == tuple(range(2, 65))
+    for k in K.EVERY_K:
+        r = F.fpfh(xyz, nrm, k)
+        assert not r.fragile_nb.any() and not r.nan_rows.any() and F.blocks_ok(r.fpfh).all(), k
+        assert (r.valid.sum(axis=1) == k - 1).all()
+
+
 @pytest.mark.parametrize("name,k", [("uniform", 10), ("sphere", 16), ("corner", 10), ("plane", 9), ("lattice", 10)])
 def test_fragile_share(name, k):
     """The cap: at most 1 % of the records are fragile or have a fragile neighbour, on the reference alone.  The 12^3 lattice is

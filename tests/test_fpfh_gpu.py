@@ -5,6 +5,8 @@ The normals come from rsreg_cloud_normals at k = 10 (hand-made ones where a clou
 the GPU call and to the reference.  SPFH rows are EQUAL on every record that is not fragile, FPFH rows BIT-EQUAL on every record
 that is not fragile and has no fragile neighbour (fragile: a pair feature within 1e-9 bins of a bin edge, decided on the reference
 alone; tests/fpfh_ref.py derives the figure).  Every other record is finite and its blocks sum to 100 +- 1e-3 or are zero.
+The cases of fpfh_cases.HAND_MADE feed normals that are not unit vectors -- scaled, all (0, 0, 1), two of them zero -- through the
+same rule: the clamps of the bins, the |v| = 0 skip and atan2(+-0, +-0) are reached by nothing else.
 """
 import functools
 import os
@@ -126,6 +128,109 @@ def test_plane_lattice_ties(api, ctx):
     assert (ref.d2[inner, 1:5] == ref.d2[inner, 1]).all() and (ref.d2[inner, 5:9] == ref.d2[inner, 5]).all()   # four at H, four at H * sqrt(2)
     assert dc.fpfh(nd, 9).tobytes() == ref.fpfh.tobytes()
     assert dc.spfh(nd, 9).tobytes() == ref.spfh.tobytes()
+
+
+def _hand_made(api, ctx, name, k=10):
+    """(DeviceCloud, NormalCloud, reference) of a case of fpfh_cases.HAND_MADE: the same float32 normals go to both."""
+    xyz, nrm = K.HAND_MADE[name]()
+    return api.DeviceCloud(_cloud(xyz), ctx=ctx), _normal_cloud(api, nrm), F.fpfh(xyz, nrm, k)
+
+
+def _check_by_the_rule(dc, normals, ref, k, label):
+    """SPFH equal on the records that are not fragile, FPFH by _check_fpfh; returns both."""
+    spfh, got = dc.spfh(normals, k), dc.fpfh(normals, k)
+    np.testing.assert_array_equal(spfh[~ref.fragile], ref.spfh[~ref.fragile])
+    _check_fpfh(got, ref, label)
+    return spfh, got
+
+
+@pytest.mark.parametrize("name", ["non_unit", "non_unit_2^100"])
+def test_normals_that_are_not_unit_vectors(api, ctx, name):
+    """Normals times 2^e, e in [-20, 20] (and all times 2^100 more): the contract normalises nothing.  f2 and f3 leave [-1, 1], so
+    most pairs land in bin 0 or bin 10 through the clamps -- a clamp that is missing or differs moves a count."""
+    dc, normals, ref = _hand_made(api, ctx, name)
+    assert not ref.fragile_nb.any() and not ref.nan_rows.any()
+    s3 = ref.scaled[..., 2]
+    below, above = ref.valid & (s3 < 0), ref.valid & (s3 >= 11)
+    assert below.sum() > 1000 and above.sum() > 1000
+    spfh, got = _check_by_the_rule(dc, normals, ref, 10, name)
+    # a pair below 0 is counted in bin 0 of f3, one at 11 or above in bin 10: the counts of those two bins, through the table
+    tab = F.count_table(10)
+    want0 = np.bincount(np.nonzero(ref.valid & (s3 < 1))[0], minlength=len(spfh))
+    want10 = np.bincount(np.nonzero(ref.valid & (s3 >= 10))[0], minlength=len(spfh))
+    np.testing.assert_array_equal(spfh[:, 22], tab[want0])
+    np.testing.assert_array_equal(spfh[:, 32], tab[want10])
+    assert dc.fpfh_cloud(normals, 10).info() == (len(got), 132, len(got), 1, True)   # (finite normals of any length: nothing to flag)
+
+
+def test_dp_parallel_to_the_source_normal(api, ctx):
+    """The 12^3 lattice with every normal (0, 0, 1): the neighbours straight above and below give |v| = 0 and are skipped.  No
+    record is fragile, so every byte is the reference's.  Record (6, 6, 6) by hand: of its nine neighbours (six at H, the three of
+    lowest index at H * sqrt(2)) the two along z are skipped; the five in its own z-plane have f1 = f2 = f3 at mid-bin (bin 5);
+    (-1, 0, -1) and (-1, 0, +1) have f3 = -+0.7071 -> 11 * 0.1464 = 1.61 and 9.39, bins 1 and 9."""
+    dc, normals, ref = _hand_made(api, ctx, "parallel")
+    n = len(ref.idx)
+    own = np.arange(n)[:, None]
+    assert (~ref.valid & (ref.idx != own)).sum() > 3000 and not ref.fragile.any() and not ref.fragile_nb.any()
+    spfh, got = dc.spfh(normals, 10), dc.fpfh(normals, 10)
+    assert spfh.tobytes() == ref.spfh.tobytes()
+    assert got.tobytes() == ref.fpfh.tobytes()
+    inner = (6 * 12 + 6) * 12 + 6
+    assert ref.idx[inner].tolist() == [942, 798, 930, 941, 943, 954, 1086, 786, 797, 799]
+    tab = F.count_table(10)
+    want = np.zeros(33, np.float32)
+    want[5], want[11 + 5] = tab[7], tab[7]
+    want[22 + 1], want[22 + 5], want[22 + 9] = tab[1], tab[5], tab[1]
+    assert spfh[inner].tolist() == want.tolist() and tab[1] == np.float32(100.0) / np.float32(9.0) and 77.7777 < tab[7] < 77.7778
+
+
+def _block_fragile(ref, rows):
+    """(len(rows), 3) bool: whether a counted pair of the record lies within FRAGILE_BELOW bins of an edge of feature t"""
+    s = ref.scaled[rows]
+    edges = np.arange(1, F.BINS, dtype=np.float64)
+    m = np.abs(s[..., None] - edges).min(axis=-1)
+    m[..., 0] = np.minimum(m[..., 0], np.minimum(np.abs(s[..., 0]), np.abs(s[..., 0] - float(F.BINS))))
+    return ((m < F.FRAGILE_BELOW) & ref.valid[rows][..., None]).any(axis=1)
+
+
+def test_zero_normals(api, ctx):
+    """Two mutual nearest neighbours with the normal (0, 0, 0), which is finite: their own pair has v = 0 and is skipped both ways,
+    every other pair of theirs has theta = atan2(+-0, +-0) -- fragile by the reference's rule, in feature 1 alone.  The rule holds
+    on the rest, every row is finite, is_dense stays the input's, and their SPFH rows count exactly the pairs the reference counts."""
+    dc, normals, ref = _hand_made(api, ctx, "zero_normals")
+    zeroed = list(K.ZEROED)
+    assert ref.fragile[zeroed].all() and ref.fragile_nb.mean() <= K.FRAGILE_CAP["zero_normals"] and not ref.nan_rows.any()
+    spfh, got = _check_by_the_rule(dc, normals, ref, 10, "zero normals")
+    assert np.isfinite(got).all() and F.blocks_ok(got).all() and np.isfinite(spfh).all()
+    out = dc.fpfh_cloud(normals, 10)
+    assert out.info() == (len(got), 132, len(got), 1, True)
+    assert out.download_fpfh().points["histogram"].tobytes() == got.tobytes()
+    tab = F.count_table(10)
+    sound = ~_block_fragile(ref, zeroed)
+    assert sound[:, 1:].all() and not sound[:, 0].any()                      # f2 and f3 are sound, f1 hangs on the sign of a zero
+    for row, i in enumerate(zeroed):
+        pairs = int(ref.valid[i].sum())
+        assert pairs == 8                                                      # nine neighbours, one of them the other zero normal
+        for t in range(3):
+            block = spfh[i, 11 * t:11 * t + 11]
+            assert np.isin(block, tab[:10]).all()
+            counts = np.searchsorted(tab[:10], block)                          # (the table is increasing: the count behind each float)
+            assert (tab[counts] == block).all()
+            if sound[row, t]:
+                assert counts.tolist() == ref.counts[i, 11 * t:11 * t + 11].tolist()
+            assert counts.sum() == pairs == ref.counts[i, 11 * t:11 * t + 11].sum()
+
+
+def test_every_k(api, ctx):
+    """k = 2 .. 64 on 200 records: hist_incr, the table of counts and the `lane < k` masks at every k.  No record is fragile at any
+    k (tests/test_fpfh_cpu.py), so every SPFH and FPFH byte is compared."""
+    xyz, nrm = K.every_k()
+    dc, normals = api.DeviceCloud(_cloud(xyz), ctx=ctx), _normal_cloud(api, nrm)
+    knn = N.knn(xyz, 64)
+    for k in K.EVERY_K:
+        ref = F.fpfh(xyz, nrm, k, knn_result=(knn[0][:, :k], knn[1][:, :k]))
+        assert not ref.fragile_nb.any()
+        _check_by_the_rule(dc, normals, ref, k, "every k: k = %d" % k)
 
 
 def test_exact_copies(api, ctx):

@@ -19,6 +19,8 @@ point grid's float32 arithmetic does outside it (tests/scale_cases.py holds the 
     score that lie up to 1e32 cells outside a target box of any size (FAR_TARGETS: beyond kPosMax cells the position is a NaN).
   * The box of cells and the rows a radius search visits hold every neighbour on the same clouds, the record itself included
     where its position has overflowed (its box is then the whole axis).
+  * The FPFH contract outside the window, on `uniform` (FPFH_REGIME): all d2 zero or all +inf give all-zero rows; a denormal d2 gives
+    w = +inf and a row of NaNs in a finite record, which nan_rows does not name and is_dense has to.
   * The share of records the normals check leaves out (gap_ratio < 1e-3) is at most 5 % of uniform and sphere at scale 1, on the
     reference; inside the window it is the same share by invariance.
 """
@@ -255,6 +257,35 @@ def test_share_left_out_by_the_gap_condition(name):
         out = 1.0 - float((ref.gap[ref.finite] >= 1e-3).mean())
         print("%s k=%d: %.2f %% of the records left out by gap_ratio >= 1e-3" % (name, k, 100 * out))
         assert out <= 0.05
+
+
+# uniform at 2^e, k = 10, the scale-1 normals: (rows with a denormal d2, rows with a +inf d2, rows with a NaN, all-zero rows)
+FPFH_REGIME = {-120: (0, 0, 0, 1500), -70: (1500, 0, 1500, 0), -62: (1500, 0, 1500, 0), 62: (0, 0, 0, 0), 66: (0, 4, 0, 0), 70: (0, 1500, 0, 1484),
+               100: (0, 1500, 0, 1500)}
+
+
+def test_fpfh_regimes_outside_the_window():
+    """What the FPFH contract gives where a d2 is not a finite normal float, on the reference alone.  All d2 zero: every neighbour is
+    skipped, 33 zeros.  A denormal d2: w = 1.0f / d2 = +inf, val = SPFH * w is +inf or 0 * inf = NaN, and the row of a FINITE record
+    with finite normals holds NaNs -- nan_rows (non-finite records and normals) does not name it, is_dense has to.  A +inf d2:
+    w = 0, the neighbour adds nothing, no NaN; all ten at +inf (or 0, the record itself): 33 zeros."""
+    assert sorted(FPFH_REGIME) == sorted(C.EXTREME)
+    nrm = np.ascontiguousarray(fpfh_cases.ref_normals("uniform"))
+    for e in C.EXTREME:
+        xyz = C.cloud_of(("uniform", e))
+        r = fpfh_ref.fpfh(xyz, nrm, 10, knn_result=C.knn_ref(C.brute("uniform", e), 10))
+        denormal = ((r.d2 > 0) & (r.d2 < C.FLT_MIN)).any(axis=1)
+        inf = np.isinf(r.d2).any(axis=1)
+        nan = np.isnan(r.fpfh).any(axis=1)
+        zero = (r.fpfh == 0).all(axis=1)
+        got = (int(denormal.sum()), int(inf.sum()), int(nan.sum()), int(zero.sum()))
+        print("uniform*2^%d: rows with a denormal d2 %d, with a +inf d2 %d, with a NaN %d, all zero %d" % ((e,) + got))
+        assert got == FPFH_REGIME[e], (e, got)
+        assert not r.nan_rows.any() and not r.fragile_nb.any()
+        assert (nan == denormal).all() and (np.isnan(r.fpfh).all(axis=1) == nan).all()   # a NaN anywhere in a row is a NaN everywhere in it
+        assert fpfh_ref.blocks_ok(r.fpfh[~nan]).all()
+        if e == -120:
+            assert (r.d2 == 0).all() and (r.spfh != 0).any()                  # (the pair features are doubles: the SPFH rows are not zero)
 
 
 def test_fpfh_condition_holds_at_2_to_the_62():

@@ -12,8 +12,10 @@ scaling by 2^e commutes with all of them, and names the regime of the point grid
     and mean distances bit-equal, +inf rows and +inf means included; radius counts equal (at a radius drawn from the cloud and at
     1e30, whose float32 square is +inf); the fitness count exact and the score within 1e-12 relative (tests/test_plane_icp_gpu.py's
     rule); the normals through tests/test_normals_gpu.py's checker (its bounds are relative to the trace); FPFH through
-    tests/test_fpfh_gpu.py's rule where every d2 is a finite normal float (at 2^62: test_scale_cpu.py).  On the denormal cloud
-    every d2 is 0: the answer is the reference's, the k lowest indices.
+    tests/test_fpfh_gpu.py's rule where every d2 is a finite normal float (at 2^62: test_scale_cpu.py) and through
+    _check_fpfh_outside elsewhere: a denormal d2 puts NaNs into the rows of finite records, in the reference's places, and the
+    cloud is then not dense (test_scale_cpu.py has the table of regimes).  On the denormal cloud every d2 is 0: the answer is the
+    reference's, the k lowest indices.
     The sources of a fitness score also lie far outside the target's box (FAR_TARGETS: up to 1e32 cells of a box of any size).
 (c) One EXTREME case gives the same bytes from a fresh context that indexed a metre-scale cloud first.
 
@@ -24,6 +26,7 @@ import numpy as np
 import pytest
 
 import fitness_ref as F
+import fpfh_cases
 import fpfh_ref
 import normals_ref as N
 import radius_cases
@@ -226,6 +229,27 @@ def test_window_gives_the_bytes_of_scale_one(api, ctx, name, e):
 
 
 # ------------------------------------------------------------------------------------------------ (b) outside the window: the references
+def _check_fpfh_outside(got, spfh, ref, label):
+    """tests/test_fpfh_gpu.py's rule where a d2 among the ten nearest is a denormal or +inf.  A denormal d2 gives w = 1 / d2 = +inf
+    and 0 * inf = NaN in a finite record's row (include/rsreg.h says so); a +inf d2 gives w = 0.  NaNs stand in exactly the
+    reference's places on every record -- with w = +inf every block's sum is a NaN, whatever the bins: a neighbour's SPFH block holds
+    a zero bin -- and their sign and payload are not compared; every other float is bit-equal on the records that are not fragile
+    and have no fragile neighbour; the rows of non-finite records are the quiet NaN 0x7fc00000; blocks sum to 100 or are zero on the
+    rows without a NaN whose d2 are all finite normal floats (or 0)."""
+    want_nan = np.isnan(ref.fpfh)
+    ok = ~ref.fragile_nb & ~ref.nan_rows
+    differ = (got.view(np.uint32) != ref.fpfh.view(np.uint32)) & ~want_nan
+    bad = np.flatnonzero(differ[ok].any(axis=1))
+    print("%s: records %d, fragile or fragile neighbour %d, rows with a NaN %d (of them non-finite records or normals %d), all-zero rows %d, rows that differ %d" %
+          (label, len(got), int(ref.fragile_nb.sum()), int(want_nan.any(axis=1).sum()), int(ref.nan_rows.sum()), int((ref.fpfh == 0).all(axis=1).sum()), len(bad)))
+    assert (np.isnan(got) == want_nan).all(), np.flatnonzero((np.isnan(got) != want_nan).any(axis=1))[:8]
+    assert len(bad) == 0, (np.flatnonzero(ok)[bad[:4]], got[ok][bad[:4]], ref.fpfh[ok][bad[:4]])
+    assert (got.view(np.uint32)[ref.nan_rows] == 0x7fc00000).all()
+    np.testing.assert_array_equal(spfh[~ref.fragile], ref.spfh[~ref.fragile])
+    sound = ~want_nan.any(axis=1) & (np.isfinite(ref.d2) & ((ref.d2 == 0) | (ref.d2 >= C.FLT_MIN))).all(axis=1)
+    assert fpfh_ref.blocks_ok(got[sound]).all()
+
+
 def _outside_outputs(api, ctx, dc, xyz, cloud, case):
     out = {"xyz": xyz, "cloud": cloud}
     out["knn"] = {k: dc.knn(k) for k in C.KS}
@@ -283,16 +307,43 @@ def _outside_case(api, ctx, dc, xyz, cloud, case):
         ref = N.normals(xyz, k, knn_result=C.knn_ref(b, k))
         _check_normals(got["normals"][k], cloud, ref, (0.0, 0.0, 0.0), False, "%s k=%d" % (C.label(case), k))
     d10 = b.d2[fin][:, :10]
+    name = case if isinstance(case, str) else case[0]
+    nrm = _fpfh_normals(name, got["normals"][10])
+    ref = fpfh_ref.fpfh(xyz, nrm, 10, knn_result=C.knn_ref(b, 10))
     if (np.isfinite(d10) & ((d10 == 0) | (d10 >= C.FLT_MIN))).all():        # every d2 a finite normal float (or 0: a copy)
-        name = case if isinstance(case, str) else case[0]
-        nrm = _fpfh_normals(name, got["normals"][10])
-        ref = fpfh_ref.fpfh(xyz, nrm, 10, knn_result=C.knn_ref(b, 10))
         _check_fpfh(dc.fpfh(nrm, 10), ref, "fpfh %s" % C.label(case))
         np.testing.assert_array_equal(dc.spfh(nrm, 10)[~ref.fragile], ref.spfh[~ref.fragile])
+    else:                                                                   # a denormal or +inf d2: 1 / d2 is +inf or 0
+        _check_fpfh_outside(dc.fpfh(nrm, 10), dc.spfh(nrm, 10), ref, "fpfh %s" % C.label(case))
     if case == "denormal":                                                  # every d2 is 0: the k lowest indices, for every record
         assert (b.d2 == 0).all() and (b.idx[:, :10] == np.arange(10)).all()
         assert (got["knn"][10][0] == np.arange(10)).all() and (got["mean"][10] == 0).all()
         assert (got["counts"][0] == len(xyz)).all()
+
+
+@pytest.mark.parametrize("e,dense", [(-62, False), (-70, False), (70, True), (100, True)])
+def test_fpfh_cloud_is_dense_only_without_nans(api, ctx, e, dense):
+    """include/rsreg.h: "is_dense 0 if any record got NaNs".  At 2^-62 and 2^-70 every d2 of the uniform box is a denormal, 1 / d2 is
+    +inf and every row of every (finite) record holds NaNs: the cloud is not dense, and matching it against itself finds no valid
+    row.  At 2^70 and 2^100 the weights are 0, the rows zeros: no NaN, dense.  (tests/test_scale_cpu.py has the table.)"""
+    xyz = C.cloud_of(("uniform", e))
+    nrm = np.ascontiguousarray(fpfh_cases.ref_normals("uniform"))
+    ref = fpfh_ref.fpfh(xyz, nrm, 10, knn_result=C.knn_ref(C.brute("uniform", e), 10))
+    assert not ref.nan_rows.any() and np.isnan(ref.fpfh).any() == (not dense)
+    dc = api.DeviceCloud(radius_cases.cloud(xyz, is_dense=True), ctx=ctx)
+    out = dc.fpfh_cloud(nrm, 10)
+    try:
+        rows = out.download_fpfh().points["histogram"]
+        assert (np.isnan(rows) == np.isnan(ref.fpfh)).all()
+        assert out.info() == (len(xyz), 132, len(xyz), 1, dense)
+        found = out.feature_correspondences(out)
+        if dense:
+            assert (rows == 0).all(axis=1).sum() >= 1400 and len(found) == len(xyz)
+        else:
+            assert np.isnan(rows).any(axis=1).all() and len(found) == 0 and len(out.feature_correspondences(out, reciprocal=True)) == 0
+    finally:
+        out.close()
+        dc.close()
 
 
 @pytest.mark.parametrize("case", C.FAR_TARGETS, ids=C.label)
