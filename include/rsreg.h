@@ -216,7 +216,7 @@ int rsreg_ctx_destroy(rsreg_ctx *ctx);
 int rsreg_ctx_synchronize(rsreg_ctx *ctx);
 /* What a frame loop is about to need, requested ahead of the need (engine extra; the schemes call it when registration() starts:
  * types.hpp:19, main.cpp:85 -- the first registration() of a process otherwise creates these one by one on its critical
- * path): the context's upload / source / download streams and, with RSREG_PREPARE_SIDE_STREAMS, the three side streams
+ * path): the context's upload / source / download streams and, with RSREG_PREPARE_SIDE_STREAMS, the four side streams
  * (hardware queues: ~12 ms each for a process's first four), the pinned staging buffers of the upload and download workers
  * for frames of `frame_bytes` (0: none), and one device buffer of `model_bytes` for a cloud that will grow to that size
  * (0: none; the merged model of IncrementalICP then grows without re-allocation).  Returns at once: a thread of the context

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "records.hpp"
+#include "cloud_ops.hpp"
 
 using namespace rsreg;
 
@@ -44,18 +45,22 @@ struct rsreg_cloud {
     mutable uint64_t box_version = ~0ull;
 };
 
-extern "C" int rsreg_icp_set_target_scan_(rsreg_ctx *ctx, const void *d_points, size_t n, size_t stride, double max_correspondence_distance);   // icp.hip
-constexpr size_t kScanSourceLimit = 64;       // (= kScanMaxSource of icp_kernels.hpp) source points at most, and ...
-constexpr size_t kScanTargetFloor = 32768;    // ... target points at least, for the search without an index
-
-namespace rsreg {
-int edge_features_device(rsreg_ctx *ctx, const char *d_rec, size_t stride, uint32_t width, uint32_t height, uint32_t *n_out, int side_set);   // edges.hip
-int voxel_filter_device(rsreg_ctx *ctx, const char *d_in, uint32_t N, size_t stride, const float leaf[3], uint32_t *n_out, int side_set);   // voxel.hip
-}
+constexpr size_t kScanTargetFloor = 32768;    // the search without an index: kScanMaxSource source points at most, so many target points at least
 
 namespace {
 
-inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+// The records of `c` have been rewritten and this is their shape: the ONLY code that moves a cloud's version.  What is kept
+// per (id, version) -- the ICP target index (rsreg_icp_target_is_cloud), the source cloud of rsreg_icp_align_cloud, the
+// bounding box -- is stale from here on.
+void cloud_rewritten(rsreg_cloud *c, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense)
+{
+    c->version++;
+    c->n = n;
+    c->stride = stride;
+    c->width = width;
+    c->height = height;
+    c->is_dense = is_dense;
+}
 
 // pcl::transformPointCloud / the aligned cloud of icp.align(): whole records copied, xyz <- T * xyz for
 // finite points; set_w: data[3] = 1 like Registration::align does.  in == out allowed.
@@ -240,6 +245,19 @@ void cloud_pool_clear(rsreg_ctx *ctx)
     pool.slots.clear();
     pool.held = 0;
 }
+
+int cloud_view(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *out, const CloudRule &rule, CloudView &v)
+{
+    if (!ctx || !in || in->ctx != ctx || (out && out->ctx != ctx)) return RSREG_ERR_INVALID_ARG;
+    int rc = rsreg_cloud_info(in, &v.n, &v.stride, &v.width, &v.height, &v.is_dense);
+    if (rc) return rc;
+    if (v.stride < rule.min_stride || (rule.stride_mult4 && v.stride % 4 != 0)) return fail(ctx, RSREG_ERR_INVALID_ARG, rule.bad_stride);
+    if (v.n > rule.max_n) return fail(ctx, RSREG_ERR_INVALID_ARG, rule.too_large);
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    v.rec = static_cast<const char *>(rsreg_cloud_device_ptr(in));
+    if (v.n && !v.rec) return fail(ctx, RSREG_ERR_STATE, "the cloud's records are not available");
+    return RSREG_OK;
+}
 }  // namespace rsreg
 
 void rsreg_ctx::prep_join()
@@ -328,12 +346,7 @@ int rsreg_cloud_upload(rsreg_cloud *c, const void *points, size_t n, size_t stri
         RSREG_HIP(ctx, hipMemcpyAsync(c->buf.ptr, stage, n * stride, hipMemcpyHostToDevice, ctx->stream));
         RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the staging buffer is reused by the next call
     }
-    c->version++;
-    c->n = n;
-    c->stride = stride;
-    c->width = width;
-    c->height = height;
-    c->is_dense = is_dense;
+    cloud_rewritten(c, n, stride, width, height, is_dense);
     return RSREG_OK;
 }
 
@@ -385,12 +398,7 @@ int upload_on_worker(rsreg_cloud *c, const void *points, size_t n, size_t stride
         });
         c->filling = true;
     }
-    c->version++;
-    c->n = n;
-    c->stride = stride;
-    c->width = width;
-    c->height = height;
-    c->is_dense = is_dense;
+    cloud_rewritten(c, n, stride, width, height, is_dense);
     if (n && wait_staged) {
         const int e = ctx->up.worker->wait(c->up_ticket);
         if (e) return fail(ctx, RSREG_ERR_HIP, "an asynchronous upload failed", (hipError_t)e);
@@ -469,19 +477,18 @@ const void *rsreg_cloud_device_ptr(const rsreg_cloud *c)
     return c->buf.ptr;
 }
 
-// (internal, edges.hip) the cloud takes a copy of the first n records of `buf`
+// (cloud_ops.hpp) the cloud takes a copy of the first n records of `buf`
 int rsreg_cloud_adopt_(rsreg_cloud *c, DevBuf *buf, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense)
 {
     rsreg_ctx *ctx = c->ctx;
     RSREG_HIP(ctx, settle(c));
     RSREG_HIP(ctx, cloud_reserve(ctx, c->buf, n * stride + 16));
     if (n) RSREG_HIP(ctx, hipMemcpyAsync(c->buf.ptr, buf->ptr, n * stride, hipMemcpyDeviceToDevice, ctx->stream));
-    c->version++;
-    c->n = n; c->stride = stride; c->width = width; c->height = height; c->is_dense = is_dense;
+    cloud_rewritten(c, n, stride, width, height, is_dense);
     return RSREG_OK;
 }
 
-// (internal: depthcloud.hip) a kernel on the context's stream is about to write n records of `stride` bytes straight into
+// (cloud_ops.hpp) a kernel on the context's stream is about to write n records of `stride` bytes straight into
 // `c`: what rsreg_cloud_upload does before its copy, and after it
 int rsreg_cloud_begin_write_(rsreg_cloud *c, size_t n, size_t stride, void **d_records)
 {
@@ -494,8 +501,7 @@ int rsreg_cloud_begin_write_(rsreg_cloud *c, size_t n, size_t stride, void **d_r
 
 int rsreg_cloud_end_write_(rsreg_cloud *c, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense)
 {
-    c->version++;
-    c->n = n; c->stride = stride; c->width = width; c->height = height; c->is_dense = is_dense;
+    cloud_rewritten(c, n, stride, width, height, is_dense);
     return RSREG_OK;
 }
 
@@ -509,8 +515,7 @@ int rsreg_cloud_copy(rsreg_ctx *ctx, const rsreg_cloud *in, rsreg_cloud *out)
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     RSREG_HIP(ctx, cloud_reserve(ctx, out->buf, in->n * in->stride + 16));
     if (in->n) RSREG_HIP(ctx, hipMemcpyAsync(out->buf.ptr, in->buf.ptr, in->n * in->stride, hipMemcpyDeviceToDevice, ctx->stream));
-    out->version++;
-    out->n = in->n; out->stride = in->stride; out->width = in->width; out->height = in->height; out->is_dense = in->is_dense;
+    cloud_rewritten(out, in->n, in->stride, in->width, in->height, in->is_dense);
     return RSREG_OK;
 }
 
@@ -531,8 +536,7 @@ int rsreg_cloud_filter(rsreg_ctx *ctx, const rsreg_cloud *in, const float leaf[3
     if (rc) return rc;
     RSREG_HIP(ctx, cloud_reserve(ctx, out->buf, (size_t)nr * stride + 16));   // (in == out: the input has been consumed by now)
     if (nr) RSREG_HIP(ctx, hipMemcpyAsync(out->buf.ptr, ctx->d_vox_out.ptr, (size_t)nr * stride, hipMemcpyDeviceToDevice, ctx->stream));
-    out->version++;
-    out->n = nr; out->stride = stride; out->width = nr; out->height = 1; out->is_dense = 0;
+    cloud_rewritten(out, nr, stride, nr, 1, 0);
     return RSREG_OK;
 }
 
@@ -616,8 +620,7 @@ int rsreg_cloud_filter_async(rsreg_ctx *ctx, const rsreg_cloud *in, const float 
     RSREG_HIP(ctx, cloud_reserve(ctx, out->buf, (chained ? in->buf.cap : in->n * stride) + 16));
     RSREG_HIP(ctx, out->ev_filled.ensure());
     const float l0 = leaf[0], l1 = leaf[1], l2 = leaf[2];
-    out->version++;
-    out->n = 0; out->stride = stride; out->width = 0; out->height = 1; out->is_dense = 0;
+    cloud_rewritten(out, 0, stride, 0, 1, 0);   // (n and width: the job fills them in when it has run)
     out->filter_rc = 0;
     out->filter_worker = worker;
     out->filter_ticket = ctx->side_workers[worker]->post([ctx, in, out, chained, stride, l0, l1, l2, set]() -> int {
@@ -668,8 +671,7 @@ int rsreg_cloud_edge_features_async(rsreg_ctx *ctx, const rsreg_cloud *in, rsreg
     RSREG_HIP(ctx, out->ev_filled.ensure());
     const InFlight inf = in_flight_of(in);
     const char *src = in->buf.as<char>();
-    out->version++;
-    out->n = 0; out->stride = stride; out->width = 0; out->height = 1; out->is_dense = in->is_dense;
+    cloud_rewritten(out, 0, stride, 0, 1, in->is_dense);
     out->filter_rc = 0;
     out->filter_worker = worker;
     out->filter_ticket = ctx->side_workers[worker]->post([ctx, out, src, stride, w, h, inf, set]() -> int {
@@ -708,8 +710,7 @@ int rsreg_cloud_transform(rsreg_ctx *ctx, const rsreg_cloud *in, const float tra
         RSREG_HIP(ctx, launch_records_transform(ctx->stream, in->buf.as<char>(), out->buf.as<char>(), (uint32_t)in->n, in->stride, to_mat34(T), 0));
     }
     const rsreg::CloudBox moved_box = (in->box.valid && in->box_version == in->version) ? rsreg::transformed_box(in->box, transform) : rsreg::CloudBox{};
-    out->version++;
-    out->n = in->n; out->stride = in->stride; out->width = in->width; out->height = in->height; out->is_dense = in->is_dense;
+    cloud_rewritten(out, in->n, in->stride, in->width, in->height, in->is_dense);
     if (moved_box.valid && rsreg::tunables().box_cache) {   // (a box around the moved points, not measured on them: CloudBox::exact)
         out->box = moved_box;
         out->box_version = out->version;
@@ -719,7 +720,7 @@ int rsreg_cloud_transform(rsreg_ctx *ctx, const rsreg_cloud *in, const float tra
 
 // pcl::PointCloud::operator+ / += (incremental_icp.hpp:64, icp_edge...hpp:119-120): out = a followed by b;
 // out may be a (the append of `target += transformed` then costs only the copy of b) or b
-const rsreg_ctx *rsreg_cloud_ctx_(const rsreg_cloud *c) { return c ? c->ctx : nullptr; }   // (internal: edges.hip)
+const rsreg_ctx *rsreg_cloud_ctx_(const rsreg_cloud *c) { return c ? c->ctx : nullptr; }   // (cloud_ops.hpp)
 
 // rsreg_cloud_download that returns at once: the records as they are when the main stream gets here are copied to a pinned
 // staging buffer on a download stream and from there to `out` by a thread of the context; the cloud may be rewritten
@@ -823,8 +824,7 @@ int rsreg_cloud_concat(rsreg_ctx *ctx, const rsreg_cloud *a, const rsreg_cloud *
         cloud_drop(ctx, out->buf);   // (a or b may be `out`: its old buffer is reused only by work queued after these copies)
         out->buf = std::move(fresh);
     }
-    out->version++;
-    out->n = total; out->stride = stride; out->width = (uint32_t)total; out->height = 1; out->is_dense = dense;
+    cloud_rewritten(out, total, stride, (uint32_t)total, 1, dense);
     if (merged_box.valid && total && rsreg::tunables().box_cache) {
         out->box = merged_box;
         out->box_version = out->version;
@@ -867,7 +867,7 @@ int rsreg_icp_set_target_cloud(rsreg_ctx *ctx, const rsreg_cloud *c, double max_
     // IncrementalICP aligns the ten or twenty points a 1 m voxel filter leaves of a frame against the whole merged model
     // (incremental_icp.hpp:54-59): for so few queries the index is not worth building (icp.hip: scan_target).  The
     // source is set before the target in the reference; if it is not, or changes, rsreg_icp_begin builds the index.
-    const bool few_queries = ctx->have_source && ctx->n_source > 0 && ctx->n_source <= kScanSourceLimit && c->n >= kScanTargetFloor &&
+    const bool few_queries = ctx->have_source && ctx->n_source > 0 && ctx->n_source <= kScanMaxSource && c->n >= kScanTargetFloor &&
                              rsreg::tunables().scan_target;
     // (a cloud that has grown since its index was built -- icp_edge_based_registration.hpp:119-120: *target = *icp_aligned +
     // *target, then the next frame's setInputTarget -- is indexed afresh: rounds 3-4 merged the new records into the index
@@ -889,7 +889,6 @@ int rsreg_icp_set_target_cloud(rsreg_ctx *ctx, const rsreg_cloud *c, double max_
 
 // the normals of the ICP target from a device cloud (what rsreg_cloud_normals wrote: 32-byte pcl::Normal records; any stride
 // whose first 12 bytes are the normal): one per target record
-extern "C" int rsreg_icp_set_target_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride);   // icp.hip
 int rsreg_icp_set_target_normals_cloud(rsreg_ctx *ctx, const rsreg_cloud *c)
 {
     if (!ctx || !c || c->ctx != ctx) return RSREG_ERR_INVALID_ARG;
@@ -945,9 +944,7 @@ int rsreg_icp_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_icp_pa
         RSREG_HIP(ctx, launch_records_transform(ctx->stream, src->buf.as<char>(), aligned_out->buf.as<char>(), (uint32_t)src->n, src->stride, to_mat34(T), 1));
     }
     const rsreg::CloudBox moved_box = (src->box.valid && src->box_version == src->version) ? rsreg::transformed_box(src->box, result->transform) : rsreg::CloudBox{};
-    aligned_out->version++;
-    aligned_out->n = src->n; aligned_out->stride = src->stride; aligned_out->width = src->width; aligned_out->height = src->height;
-    aligned_out->is_dense = src->is_dense;
+    cloud_rewritten(aligned_out, src->n, src->stride, src->width, src->height, src->is_dense);
     if (moved_box.valid && rsreg::tunables().box_cache) {
         aligned_out->box = moved_box;
         aligned_out->box_version = aligned_out->version;
@@ -956,10 +953,6 @@ int rsreg_icp_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_icp_pa
 }
 
 // ---- NDT on cloud handles
-int rsreg_ndt_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, size_t stride, int is_dense, double resolution);
-int rsreg_ndt_align_device(rsreg_ctx *ctx, const void *d_source, size_t n, size_t stride, int is_dense, const float *guess,
-                           const rsreg_ndt_params *params, rsreg_ndt_result *result, void *d_aligned_out);
-
 int rsreg_ndt_set_target_cloud(rsreg_ctx *ctx, const rsreg_cloud *c, double resolution)
 {
     if (!ctx || !c || c->ctx != ctx) return RSREG_ERR_INVALID_ARG;
@@ -985,9 +978,7 @@ int rsreg_ndt_align_cloud(rsreg_ctx *ctx, const rsreg_cloud *source, const float
     int rc = rsreg_ndt_align_device(ctx, source->n ? source->buf.ptr : nullptr, source->n, source->stride, source->is_dense, guess, params,
                                     result, aligned_out ? aligned_out->buf.ptr : nullptr);
     if (rc || !aligned_out) return rc;
-    aligned_out->version++;
-    aligned_out->n = source->n; aligned_out->stride = source->stride; aligned_out->width = source->width;
-    aligned_out->height = source->height; aligned_out->is_dense = source->is_dense;
+    cloud_rewritten(aligned_out, source->n, source->stride, source->width, source->height, source->is_dense);
     return RSREG_OK;
 }
 

@@ -13,7 +13,7 @@
 #include <cstring>
 #include <mutex>
 
-#include "rsreg_ctx.hpp"
+#include "cloud_ops.hpp"
 
 using namespace rsreg;
 

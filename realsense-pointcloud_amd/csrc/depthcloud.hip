@@ -9,16 +9,9 @@
 #include <cstring>
 
 #include "depthcloud_kernels.hpp"
+#include "cloud_ops.hpp"
 
 using namespace rsreg;
-
-struct rsreg_cloud;
-extern "C" {
-// cloud.hip: room for n records of `stride` bytes in `c`, about to be rewritten on the context's stream; and the rewrite done
-int rsreg_cloud_begin_write_(rsreg_cloud *c, size_t n, size_t stride, void **d_records);
-int rsreg_cloud_end_write_(rsreg_cloud *c, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense);
-const rsreg_ctx *rsreg_cloud_ctx_(const rsreg_cloud *c);
-}
 
 namespace {
 

@@ -23,24 +23,15 @@
 
 #include "records.hpp"
 #include "compact.hpp"
+#include "cloud_ops.hpp"
 
 using namespace rsreg;
-
-struct rsreg_cloud;
-extern "C" {
-const void *rsreg_cloud_device_ptr(const rsreg_cloud *c);
-int rsreg_cloud_info(const rsreg_cloud *c, size_t *n, size_t *stride, uint32_t *width, uint32_t *height, int *is_dense);
-int rsreg_cloud_adopt_(rsreg_cloud *c, DevBuf *buf, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense);   // cloud.hip
-const rsreg_ctx *rsreg_cloud_ctx_(const rsreg_cloud *c);   // cloud.hip: the context a handle belongs to
-}
 
 namespace {
 
 struct Kernel3 {
     float k[9];
 };
-
-inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
@@ -436,16 +427,10 @@ int rsreg_extract_edge_features(rsreg_ctx *ctx, const void *points, uint32_t wid
     *n_out = 0;
     if (n == 0) return RSREG_OK;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    RSREG_HIP(ctx, ctx->d_vox_in.reserve(n * stride));
-    RSREG_HIP(ctx, ctx->h_stage.reserve(n * stride));
-    {
-        char *stage = ctx->h_stage.as<char>();
-        const char *src = static_cast<const char *>(points);
-        host_parallel_for(n, [=](size_t lo, size_t hi) { rsreg::stream_copy(stage + lo * stride, src + lo * stride, (hi - lo) * stride); });
-    }
-    RSREG_HIP(ctx, hipMemcpyAsync(ctx->d_vox_in.ptr, ctx->h_stage.ptr, n * stride, hipMemcpyHostToDevice, ctx->stream));
+    int rc = stage_up(ctx, points, n, stride);
+    if (rc) return rc;
     uint32_t ne = 0;
-    int rc = rsreg::edge_features_device(ctx, ctx->d_vox_in.as<char>(), stride, width, height, &ne, -1);
+    rc = rsreg::edge_features_device(ctx, ctx->d_vox_in.as<char>(), stride, width, height, &ne, -1);
     if (rc || ne == 0) return rc;
     RSREG_HIP(ctx, hipMemcpyAsync(ctx->h_stage.ptr, ctx->d_vox_out.ptr, (size_t)ne * stride, hipMemcpyDeviceToHost, ctx->stream));
     if (indices_out) RSREG_HIP(ctx, hipMemcpyAsync(indices_out, ctx->d_vals_alt.ptr, (size_t)ne * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -459,20 +444,18 @@ int rsreg_extract_edge_features(rsreg_ctx *ctx, const void *points, uint32_t wid
 // (pcl::copyPointCloud (cloud, indices, out))
 int rsreg_cloud_edge_features(rsreg_ctx *ctx, const rsreg_cloud *in, rsreg_cloud *out)
 {
-    if (!ctx || !in || !out) return RSREG_ERR_INVALID_ARG;
-    // like every other rsreg_cloud_* operation: both handles belong to THIS context (its stream, scratch and device)
-    if (rsreg_cloud_ctx_(in) != ctx || rsreg_cloud_ctx_(out) != ctx) return RSREG_ERR_INVALID_ARG;
-    size_t n = 0, stride = 0;
-    uint32_t w = 0, h = 0;
-    int dense = 0;
-    int rc = rsreg_cloud_info(in, &n, &stride, &w, &h, &dense);
+    if (!out) return RSREG_ERR_INVALID_ARG;
+    // (a record's colour word: one message for the stride and the shape; the image's own limit is edge_features_device's)
+    constexpr const char *kNeeds = "edge extraction needs an organized XYZRGB cloud";
+    constexpr CloudRule rule{20, false, kNeeds, kAnyCount, nullptr};
+    CloudView v;
+    int rc = cloud_view(ctx, in, out, rule, v);
     if (rc) return rc;
-    if ((size_t)w * h != n || stride < 20) return fail(ctx, RSREG_ERR_INVALID_ARG, "edge extraction needs an organized XYZRGB cloud");
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    if ((size_t)v.width * v.height != v.n) return fail(ctx, RSREG_ERR_INVALID_ARG, kNeeds);
     uint32_t ne = 0;
-    rc = rsreg::edge_features_device(ctx, static_cast<const char *>(rsreg_cloud_device_ptr(in)), stride, w, h, &ne, -1);
+    rc = rsreg::edge_features_device(ctx, v.rec, v.stride, v.width, v.height, &ne, -1);
     if (rc) return rc;
-    return rsreg_cloud_adopt_(out, &ctx->d_vox_out, ne, stride, ne, 1, dense);
+    return rsreg_cloud_adopt_(out, &ctx->d_vox_out, ne, v.stride, ne, 1, v.is_dense);
 }
 
 }  // extern "C"

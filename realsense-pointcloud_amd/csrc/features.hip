@@ -8,44 +8,23 @@
 // rule of feature_plan.hpp, the merge of the slices.  The correspondences are the K = 1 search forwards and, if reciprocal, the
 // same launch with the roles swapped, then one flag / scan (oscan.hpp) / gather over the source rows, ONE 8-byte count read back
 // and one download.  Everything runs on the context's stream with the scratch rsreg_ctx::feat and touches no other buffer.
-#include "rsreg_ctx.hpp"
+#include "records.hpp"
+#include "cloud_ops.hpp"
 #include "oscan.hpp"
 #include "feature_kernels.hpp"
 
 using namespace rsreg;
 
-struct rsreg_cloud;
-extern "C" {
-const rsreg_ctx *rsreg_cloud_ctx_(const rsreg_cloud *c);   // cloud.hip: the context a handle belongs to
-}
-
 namespace {
 
-inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
-
-struct DescView {
-    const char *rec = nullptr;
-    size_t n = 0, stride = 0;
-};
+constexpr CloudRule kDescRule{(size_t)kFmDim * 4, true, "a descriptor cloud's records start with 33 floats: a stride of at least 132 that is a multiple of 4",
+                              0x7ffffff0ull, "cloud too large"};
 
 // a descriptor cloud's records on the context's stream (an upload or a queued filter of it has been waited for)
-int desc_view(rsreg_ctx *ctx, const rsreg_cloud *c, DescView &v)
-{
-    if (!ctx || !c) return RSREG_ERR_INVALID_ARG;
-    if (rsreg_cloud_ctx_(c) != ctx) return RSREG_ERR_INVALID_ARG;
-    int rc = rsreg_cloud_info(c, &v.n, &v.stride, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    if (v.stride < (size_t)kFmDim * 4 || v.stride % 4 != 0)
-        return fail(ctx, RSREG_ERR_INVALID_ARG, "a descriptor cloud's records start with 33 floats: a stride of at least 132 that is a multiple of 4");
-    if (v.n > 0x7ffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    v.rec = static_cast<const char *>(rsreg_cloud_device_ptr(c));
-    if (v.n && !v.rec) return fail(ctx, RSREG_ERR_STATE, "the cloud's records are not available");
-    return RSREG_OK;
-}
+int desc_view(rsreg_ctx *ctx, const rsreg_cloud *c, CloudView &v) { return cloud_view(ctx, c, nullptr, kDescRule, v); }
 
 // fs.d_valid[which][i] = row i is valid; the count of valid rows into word `which` of fs.d_count (zeroed by the caller)
-int valid_rows(rsreg_ctx *ctx, const DescView &v, int which)
+int valid_rows(rsreg_ctx *ctx, const CloudView &v, int which)
 {
     FeatureScratch &fs = ctx->feat;
     RSREG_HIP(ctx, fs.d_valid[which].reserve(v.n * 4 + 16));
@@ -56,7 +35,7 @@ int valid_rows(rsreg_ctx *ctx, const DescView &v, int which)
     return RSREG_OK;
 }
 
-template <int K> int launch_search(rsreg_ctx *ctx, const DescView &q, const uint32_t *qvalid, const DescView &t, const uint32_t *tvalid, const FeaturePlan &p,
+template <int K> int launch_search(rsreg_ctx *ctx, const CloudView &q, const uint32_t *qvalid, const CloudView &t, const uint32_t *tvalid, const FeaturePlan &p,
                                    unsigned long long *out)
 {
     k_fm_search<K><<<p.qblocks * p.slices, kFmLanes, 0, ctx->stream>>>(q.rec, q.stride, qvalid, (uint32_t)q.n, t.rec, t.stride, tvalid, (uint32_t)t.n, p.slices, out);
@@ -73,7 +52,7 @@ template <int K> int launch_merge(rsreg_ctx *ctx, const unsigned long long *keys
 
 // keys[i] = the nearest valid row of t to the valid row i of q (kFmNone: q's row is not valid, or t has no valid row): the K = 1
 // search, not waited for.  q.n >= 1.
-int nearest_keys(rsreg_ctx *ctx, const DescView &q, const uint32_t *qvalid, const DescView &t, const uint32_t *tvalid, DevBuf &keys)
+int nearest_keys(rsreg_ctx *ctx, const CloudView &q, const uint32_t *qvalid, const CloudView &t, const uint32_t *tvalid, DevBuf &keys)
 {
     RSREG_HIP(ctx, keys.reserve(q.n * 8 + 16));
     RSREG_HIP(ctx, hipMemsetAsync(keys.ptr, 0xff, q.n * 8, ctx->stream));
@@ -87,7 +66,7 @@ extern "C" {
 
 int rsreg_cloud_feature_knn(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, int k, int32_t *index_out, float *sqr_dist_out)
 {
-    DescView sv, tv;
+    CloudView sv, tv;
     int rc = desc_view(ctx, source, sv);
     if (rc) return rc;
     rc = desc_view(ctx, target, tv);
@@ -161,7 +140,7 @@ int rsreg_cloud_feature_knn(rsreg_ctx *ctx, const rsreg_cloud *source, const rsr
 int rsreg_cloud_feature_correspondences(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, double max_distance, int reciprocal,
                                         rsreg_correspondence *host_out, size_t capacity, size_t *n_out)
 {
-    DescView sv, tv;
+    CloudView sv, tv;
     int rc = desc_view(ctx, source, sv);
     if (rc) return rc;
     rc = desc_view(ctx, target, tv);

@@ -16,39 +16,26 @@
 #include "normals_kernels.hpp"
 #include "radius_kernels.hpp"
 #include "fpfh_kernels.hpp"
+#include "cloud_ops.hpp"
 
 using namespace rsreg;
 
-struct rsreg_cloud;
-extern "C" {
-int rsreg_cloud_adopt_(rsreg_cloud *c, DevBuf *buf, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense);   // cloud.hip
-const rsreg_ctx *rsreg_cloud_ctx_(const rsreg_cloud *c);   // cloud.hip: the context a handle belongs to
-}
-
 namespace {
 
-inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 inline uint32_t div_up64(unsigned long long a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
 
-struct CloudView {
-    const char *rec = nullptr;
-    size_t n = 0, stride = 0;
-    uint32_t width = 0, height = 0;
-    int is_dense = 0;
-};
-
-// the input's records on the context's stream (an upload or a queued filter of it has been waited for)
-int view_of(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *out, CloudView &v)
+// One launch leaves one word -- a count, or a flag it only ever sets (`clear`: zeroed first) -- and the word comes home with the
+// stream: launch(d_word) queues the kernel.  The slot: kFiltWord of the index's box buffer and of the pinned scratch.
+template <typename Launch> int word_home(rsreg_ctx *ctx, bool clear, Launch launch, uint32_t *word_out)
 {
-    if (!ctx || !in) return RSREG_ERR_INVALID_ARG;
-    if (rsreg_cloud_ctx_(in) != ctx || (out && rsreg_cloud_ctx_(out) != ctx)) return RSREG_ERR_INVALID_ARG;
-    int rc = rsreg_cloud_info(in, &v.n, &v.stride, &v.width, &v.height, &v.is_dense);
-    if (rc) return rc;
-    if (v.stride < 12 || v.stride % 4 != 0) return fail(ctx, RSREG_ERR_INVALID_ARG, "records need x, y, z floats and a stride that is a multiple of 4");
-    if (v.n > 0x7ffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    v.rec = static_cast<const char *>(rsreg_cloud_device_ptr(in));
-    if (v.n && !v.rec) return fail(ctx, RSREG_ERR_STATE, "the cloud's records are not available");
+    hipStream_t st = ctx->stream;
+    uint32_t *d_word = ctx->knn.d_box.as<uint32_t>() + kFiltWord, *h_word = ctx->filt.host.as<uint32_t>() + kFiltWord;
+    if (clear) RSREG_HIP(ctx, hipMemsetAsync(d_word, 0, 4, st));
+    launch(d_word);
+    RSREG_HIP(ctx, hipGetLastError());
+    RSREG_HIP(ctx, hipMemcpyAsync(h_word, d_word, 4, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    *word_out = *h_word;
     return RSREG_OK;
 }
 
@@ -96,13 +83,11 @@ int compact_into(rsreg_ctx *ctx, const CloudView &v, rsreg_cloud *out, int is_de
         RSREG_HIP(ctx, kx.d_box.reserve(64));
         RSREG_HIP(ctx, fs.host.reserve(256));
         RSREG_HIP(ctx, oscan<uint32_t>(fs.d_flags.as<uint32_t>(), fs.d_pos.as<uint32_t>(), v.n, 0u, kx.d_scan.ptr, st));
-        uint32_t *d_kept = kx.d_box.as<uint32_t>() + 8;
-        k_filter_gather<<<div_up64((unsigned long long)n * (v.stride / 4), kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, fs.d_flags.as<uint32_t>(),
-                                                                                                   fs.d_pos.as<uint32_t>(), fs.d_out.as<char>(), d_kept);
-        RSREG_HIP(ctx, hipGetLastError());
-        RSREG_HIP(ctx, hipMemcpyAsync(fs.host.as<uint32_t>() + 8, d_kept, 4, hipMemcpyDeviceToHost, st));
-        RSREG_HIP(ctx, hipStreamSynchronize(st));
-        kept = fs.host.as<uint32_t>()[8];
+        const int rc = word_home(ctx, false, [&](uint32_t *d_kept) {
+            k_filter_gather<<<div_up64((unsigned long long)n * (v.stride / 4), kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, fs.d_flags.as<uint32_t>(),
+                                                                                                       fs.d_pos.as<uint32_t>(), fs.d_out.as<char>(), d_kept);
+        }, &kept);
+        if (rc) return rc;
     }
     *n_kept_out = kept;
     return rsreg_cloud_adopt_(out, &fs.d_out, kept, v.stride, kept, 1, is_dense);   // (in == out: the input has been consumed by now)
@@ -126,9 +111,9 @@ int organized_into(rsreg_ctx *ctx, const CloudView &v, rsreg_cloud *out, uint32_
         k_filter_organized<<<div_up64((unsigned long long)n * (v.stride / 4), kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, fs.d_flags.as<uint32_t>(),
                                                                                                       fs.d_out.as<char>());
         RSREG_HIP(ctx, hipGetLastError());
-        RSREG_HIP(ctx, hipMemcpyAsync(fs.host.as<uint32_t>() + 8, fs.d_pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        RSREG_HIP(ctx, hipMemcpyAsync(fs.host.as<uint32_t>() + kFiltWord, fs.d_pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, st));
         RSREG_HIP(ctx, hipStreamSynchronize(st));
-        removed = n - fs.host.as<uint32_t>()[8];
+        removed = n - fs.host.as<uint32_t>()[kFiltWord];
     }
     *n_kept_out = n - removed;
     return rsreg_cloud_adopt_(out, &fs.d_out, v.n, v.stride, v.width, v.height, removed ? 0 : v.is_dense);
@@ -200,9 +185,9 @@ int fpfh_spfh_device(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *n
                      uint32_t *nfin_out)
 {
     if (!normals) return RSREG_ERR_INVALID_ARG;
-    int rc = view_of(ctx, in, out, v);
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
     if (rc) return rc;
-    rc = view_of(ctx, normals, nullptr, nv);   // (a normal record: three floats first, the stride rule of every record here)
+    rc = cloud_view(ctx, normals, nullptr, kXyzRule, nv);   // (a normal record: three floats first, the stride rule of every record here)
     if (rc) return rc;
     if (k < 2 || k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must be between 2 and 64");
     if (nv.n != v.n) return fail(ctx, RSREG_ERR_INVALID_ARG, "the normals must hold one record per record of the cloud");
@@ -223,6 +208,29 @@ int fpfh_spfh_device(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *n
     return RSREG_OK;
 }
 
+// The tail of a normals call, behind the index over `nfin` finite records: room for the pcl::Normal records, NaNs for the
+// records that are not finite, the search -- launch(vp, d_normals, &any_nan) with PCL's default viewpoint if there is none,
+// left out when nothing is finite -- and the records handed to `out`: a record that got NaNs makes the cloud not dense;
+// otherwise it is what the input says.
+constexpr size_t kNormalBytes = 32;   // pcl::Normal
+template <typename Launch> int normals_into(rsreg_ctx *ctx, const CloudView &v, uint32_t nfin, const float viewpoint[3], rsreg_cloud *out, Launch launch)
+{
+    FilterScratch &fs = ctx->filt;
+    const uint32_t n = (uint32_t)v.n;
+    RSREG_HIP(ctx, fs.d_out.reserve(v.n * kNormalBytes + 16));
+    if (nfin < n) {
+        k_normals_not_finite<<<div_up(n, kBlock), kBlock, 0, ctx->stream>>>(v.rec, v.stride, n, fs.d_out.as<float>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    const float vp[3] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f, viewpoint ? viewpoint[2] : 0.0f};
+    uint32_t any_nan = 0;
+    if (nfin) {
+        const int rc = launch(vp, fs.d_out.as<float>(), &any_nan);
+        if (rc) return rc;
+    }
+    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kNormalBytes, v.width, v.height, (nfin < n || any_nan) ? 0 : v.is_dense);
+}
+
 }  // namespace
 
 extern "C" {
@@ -232,7 +240,7 @@ int rsreg_cloud_passthrough(rsreg_ctx *ctx, const rsreg_cloud *in, int field, fl
 {
     CloudView v;
     if (!out) return RSREG_ERR_INVALID_ARG;
-    int rc = view_of(ctx, in, out, v);
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
     if (rc) return rc;
     // (PCL warns about a field it does not find and returns an empty cloud: here the call is refused)
     if (field < 0 || field > 2) return fail(ctx, RSREG_ERR_INVALID_ARG, "PassThrough filters on field 0 (x), 1 (y) or 2 (z)");
@@ -253,7 +261,7 @@ int rsreg_cloud_knn_mean_distance(rsreg_ctx *ctx, const rsreg_cloud *in, int mea
 {
     CloudView v;
     if (!host_out) return RSREG_ERR_INVALID_ARG;
-    int rc = view_of(ctx, in, nullptr, v);
+    int rc = cloud_view(ctx, in, nullptr, kXyzRule, v);
     if (rc) return rc;
     uint32_t nfin = 0;
     rc = knn_mean_distance_device(ctx, v, mean_k, &nfin);
@@ -267,7 +275,7 @@ int rsreg_cloud_sor(rsreg_ctx *ctx, const rsreg_cloud *in, int mean_k, double st
 {
     CloudView v;
     if (!out) return RSREG_ERR_INVALID_ARG;
-    int rc = view_of(ctx, in, out, v);
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
     if (rc) return rc;
     uint32_t nfin = 0;
     rc = knn_mean_distance_device(ctx, v, mean_k, &nfin);
@@ -308,7 +316,7 @@ int rsreg_cloud_sor(rsreg_ctx *ctx, const rsreg_cloud *in, int mean_k, double st
 int rsreg_cloud_knn(rsreg_ctx *ctx, const rsreg_cloud *in, int k, int32_t *index_out, float *sqr_dist_out)
 {
     CloudView v;
-    int rc = view_of(ctx, in, nullptr, v);
+    int rc = cloud_view(ctx, in, nullptr, kXyzRule, v);
     if (rc) return rc;
     if (k < 1 || k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must be between 1 and 64");
     uint32_t nfin = 0;
@@ -342,26 +350,17 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
 {
     CloudView v;
     if (!out || out == in) return RSREG_ERR_INVALID_ARG;
-    int rc = view_of(ctx, in, out, v);
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
     if (rc) return rc;
     if (k < 3 || k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must be between 3 and 64");
     uint32_t nfin = 0;
     rc = knn_index_device(ctx, v, k, "the cloud has fewer than k finite records", &nfin);
     if (rc) return rc;
-    FilterScratch &fs = ctx->filt;
-    hipStream_t st = ctx->stream;
-    const uint32_t n = (uint32_t)v.n;
-    constexpr size_t kNormalBytes = 32;   // pcl::Normal
-    RSREG_HIP(ctx, fs.d_out.reserve(v.n * kNormalBytes + 16));
-    if (nfin < n) {
-        k_normals_not_finite<<<div_up(n, kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, fs.d_out.as<float>());
+    return normals_into(ctx, v, nfin, viewpoint, out, [&](const float vp[3], float *d_normals, uint32_t *) {
+        k_normals<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, ctx->stream>>>(grid_dev(ctx->knn), k, v.rec, v.stride, vp[0], vp[1], vp[2], d_normals);
         RSREG_HIP(ctx, hipGetLastError());
-    }
-    const float vp[3] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f, viewpoint ? viewpoint[2] : 0.0f};
-    k_normals<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), k, v.rec, v.stride, vp[0], vp[1], vp[2], fs.d_out.as<float>());
-    RSREG_HIP(ctx, hipGetLastError());
-    // a record that got NaNs makes the cloud not dense; otherwise it is what the input says
-    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kNormalBytes, v.width, v.height, nfin < n ? 0 : v.is_dense);
+        return (int)RSREG_OK;
+    });
 }
 
 int rsreg_cloud_spfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, int k, float *host_out)
@@ -389,21 +388,20 @@ int rsreg_cloud_fpfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *n
     constexpr size_t kFpfhBytes = kFpfhRow * 4;   // pcl::FPFHSignature33
     RSREG_HIP(ctx, fs.d_out.reserve(v.n * kFpfhBytes + 16));
     // a record that is not finite, or whose own normal is not, gets NaNs: whether one did comes back with the stream
-    uint32_t *d_any = ctx->knn.d_box.as<uint32_t>() + 8, *h_any = fs.host.as<uint32_t>() + 8;
-    RSREG_HIP(ctx, hipMemsetAsync(d_any, 0, 4, st));
-    k_fpfh_weight<<<std::min<uint32_t>(n, 1u << 16), kKnnWave, 0, st>>>(v.rec, v.stride, nv.rec, nv.stride, n, k, fs.d_nn_idx.as<int32_t>(),
-                                                                       fs.d_nn_d2.as<float>(), fs.d_spfh.as<float>(), fs.d_out.as<float>(), d_any);
-    RSREG_HIP(ctx, hipGetLastError());
-    RSREG_HIP(ctx, hipMemcpyAsync(h_any, d_any, 4, hipMemcpyDeviceToHost, st));
-    RSREG_HIP(ctx, hipStreamSynchronize(st));
-    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kFpfhBytes, v.width, v.height, *h_any ? 0 : v.is_dense);
+    uint32_t any_nan = 0;
+    rc = word_home(ctx, true, [&](uint32_t *d_any) {
+        k_fpfh_weight<<<std::min<uint32_t>(n, 1u << 16), kKnnWave, 0, st>>>(v.rec, v.stride, nv.rec, nv.stride, n, k, fs.d_nn_idx.as<int32_t>(),
+                                                                           fs.d_nn_d2.as<float>(), fs.d_spfh.as<float>(), fs.d_out.as<float>(), d_any);
+    }, &any_nan);
+    if (rc) return rc;
+    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kFpfhBytes, v.width, v.height, any_nan ? 0 : v.is_dense);
 }
 
 int rsreg_cloud_radius_count(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, uint32_t *host_out)
 {
     CloudView v;
     if (!host_out) return RSREG_ERR_INVALID_ARG;
-    int rc = view_of(ctx, in, nullptr, v);
+    int rc = cloud_view(ctx, in, nullptr, kXyzRule, v);
     if (rc) return rc;
     rc = radius_count_device(ctx, v, radius);
     if (rc || !v.n) return rc;
@@ -417,7 +415,7 @@ int rsreg_cloud_radius_outlier_removal(rsreg_ctx *ctx, const rsreg_cloud *in, do
 {
     CloudView v;
     if (!out) return RSREG_ERR_INVALID_ARG;
-    int rc = view_of(ctx, in, out, v);
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
     if (rc) return rc;
     if (min_neighbors < 0) return fail(ctx, RSREG_ERR_INVALID_ARG, "min_neighbors must not be negative");
     rc = radius_count_device(ctx, v, radius);
@@ -441,36 +439,21 @@ int rsreg_cloud_normals_radius(rsreg_ctx *ctx, const rsreg_cloud *in, double rad
 {
     CloudView v;
     if (!out || out == in) return RSREG_ERR_INVALID_ARG;
-    int rc = view_of(ctx, in, out, v);
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
     if (rc) return rc;
     if (!(radius > 0.0) || !std::isfinite(radius)) return fail(ctx, RSREG_ERR_INVALID_ARG, "the radius must be finite and above 0");
-    FilterScratch &fs = ctx->filt;
-    hipStream_t st = ctx->stream;
-    const uint32_t n = (uint32_t)v.n;
-    constexpr size_t kNormalBytes = 32;   // pcl::Normal
-    RSREG_HIP(ctx, fs.d_out.reserve(v.n * kNormalBytes + 16));
-    uint32_t nfin = 0, any_nan = 0;
-    if (n) {
-        RadiusQuery rq;
+    uint32_t nfin = 0;
+    RadiusQuery rq;
+    if (v.n) {
         rc = radius_index_device(ctx, v, radius, nullptr, &rq, &nfin);
         if (rc) return rc;
-        if (nfin < n) {
-            k_normals_not_finite<<<div_up(n, kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, fs.d_out.as<float>());
-            RSREG_HIP(ctx, hipGetLastError());
-        }
-        if (nfin) {
-            // a record with fewer than three neighbours gets NaNs too: whether one did comes back with the stream
-            uint32_t *d_any = ctx->knn.d_box.as<uint32_t>() + 8, *h_any = fs.host.as<uint32_t>() + 8;
-            RSREG_HIP(ctx, hipMemsetAsync(d_any, 0, 4, st));
-            const float vp[3] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f, viewpoint ? viewpoint[2] : 0.0f};
-            k_normals_radius<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), rq, vp[0], vp[1], vp[2], fs.d_out.as<float>(), d_any);
-            RSREG_HIP(ctx, hipGetLastError());
-            RSREG_HIP(ctx, hipMemcpyAsync(h_any, d_any, 4, hipMemcpyDeviceToHost, st));
-            RSREG_HIP(ctx, hipStreamSynchronize(st));
-            any_nan = *h_any;
-        }
     }
-    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kNormalBytes, v.width, v.height, (nfin < n || any_nan) ? 0 : v.is_dense);
+    // a record with fewer than three neighbours gets NaNs too: whether one did comes back with the stream
+    return normals_into(ctx, v, nfin, viewpoint, out, [&](const float vp[3], float *d_normals, uint32_t *any_nan) {
+        return word_home(ctx, true, [&](uint32_t *d_any) {
+            k_normals_radius<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, ctx->stream>>>(grid_dev(ctx->knn), rq, vp[0], vp[1], vp[2], d_normals, d_any);
+        }, any_nan);
+    });
 }
 
 }  // extern "C"

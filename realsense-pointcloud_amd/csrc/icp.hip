@@ -22,14 +22,13 @@
 #include "oscan.hpp"
 #include "fitness_kernels.hpp"
 #include "plane_kernels.hpp"
+#include "cloud_ops.hpp"
 
 using namespace rsreg;
 
 namespace {
 
 inline uint32_t reduce_blocks(size_t n) { return (uint32_t)std::max<size_t>((n + kTile - 1) / kTile, 1); }  // depends on n only
-
-inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 hipEvent_t take_event(rsreg_ctx *ctx)
 {
@@ -1142,8 +1141,6 @@ int launch_search(rsreg_ctx *ctx)
     return RSREG_OK;
 }
 
-extern "C" int rsreg_comm_allreduce_device_(rsreg_ctx *ctx, double *d_buf, int count);  // comm.cpp
-
 // where k_final_reduce leaves the 17 sums the host is about to read: without a communicator straight in the pinned
 // host buffer (no copy to queue behind the kernel), otherwise in HBM (the all-reduce works there)
 double *host_sums_target(rsreg_ctx *ctx) { return ctx->comm ? ctx->d_sums.as<double>() : ctx->h_sums.as<double>(); }
@@ -1691,8 +1688,6 @@ int rsreg_ctx_create(int device_id, void *stream, rsreg_ctx **out)
     *out = ctx;
     return RSREG_OK;
 }
-
-int rsreg_comm_destroy(rsreg_ctx *ctx);
 
 int rsreg_ctx_destroy(rsreg_ctx *ctx)
 {

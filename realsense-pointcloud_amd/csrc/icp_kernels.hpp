@@ -1243,10 +1243,9 @@ __global__ __launch_bounds__(kReduceBlock) void k_final_reduce_solve(const doubl
 // ------------------------------------------------------------------------ no index: a handful of queries
 // IncrementalICP aligns what a 1 m voxel filter leaves of a frame -- ten or twenty points -- against everything merged so
 // far (incremental_icp.hpp:54-59; the leaf is never set, PCL's default applies).  Building an index over millions of
-// target points for twenty queries costs fifty times the search: with at most kScanMaxSource distinct source points every
-// target point is scored against every query instead.  Same float32 distance in the same operation order, same gate
+// target points for twenty queries costs fifty times the search: with at most kScanMaxSource (rsreg_ctx.hpp) distinct source
+// points every target point is scored against every query instead.  Same float32 distance in the same operation order, same gate
 // test, lowest index among equals (the minimum of (distance, index) keys does not depend on the order they arrive in).
-constexpr uint32_t kScanMaxSource = 64;
 
 // (x, y, index, z) records in the caller's order: position == index.  A non-finite point is infinitely far from
 // every query.

@@ -9,14 +9,9 @@
 #include <cstring>
 
 #include "iinormals_kernels.hpp"
+#include "cloud_ops.hpp"
 
 using namespace rsreg;
-
-struct rsreg_cloud;
-extern "C" {
-int rsreg_cloud_adopt_(rsreg_cloud *c, DevBuf *buf, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense);   // cloud.hip
-const rsreg_ctx *rsreg_cloud_ctx_(const rsreg_cloud *c);   // cloud.hip: the context a handle belongs to
-}
 
 extern "C" {
 
@@ -33,17 +28,18 @@ void rsreg_iin_params_default(rsreg_iin_params *p)
 
 int rsreg_cloud_integral_normals(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_iin_params *prm, rsreg_cloud *out, uint8_t *rect_out)
 {
-    if (!ctx || !in || !out || out == in) return RSREG_ERR_INVALID_ARG;
-    if (rsreg_cloud_ctx_(in) != ctx || rsreg_cloud_ctx_(out) != ctx) return RSREG_ERR_INVALID_ARG;
+    if (!out || out == in) return RSREG_ERR_INVALID_ARG;
     rsreg_iin_params p;
     rsreg_iin_params_default(&p);
     if (prm) p = *prm;
-    size_t n = 0, stride = 0;
-    uint32_t width = 0, height = 0;
-    int is_dense = 0;
-    int rc = rsreg_cloud_info(in, &n, &stride, &width, &height, &is_dense);
+    // (the frame's own limit, width and count at once, is below: the rule has none)
+    constexpr CloudRule rule{kXyzRule.min_stride, kXyzRule.stride_mult4, kXyzRule.bad_stride, kAnyCount, nullptr};
+    CloudView v;
+    const int rc = cloud_view(ctx, in, out, rule, v);
     if (rc) return rc;
-    if (stride < 12 || stride % 4 != 0) return fail(ctx, RSREG_ERR_INVALID_ARG, "records need x, y, z floats and a stride that is a multiple of 4");
+    const char *rec = v.rec;
+    const size_t n = v.n, stride = v.stride;
+    const uint32_t width = v.width, height = v.height;
     if (height <= 1 || width == 0 || (size_t)width * (size_t)height != n)
         return fail(ctx, RSREG_ERR_INVALID_ARG, "IntegralImageNormalEstimation needs an organized cloud (height > 1)");
     if (width > (uint32_t)kIinMaxWidth || n > 0x7ffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "frames wider than 8192 pixels are not supported");
@@ -54,9 +50,6 @@ int rsreg_cloud_integral_normals(rsreg_ctx *ctx, const rsreg_cloud *in, const rs
         return fail(ctx, RSREG_ERR_INVALID_ARG, "normal_smoothing_size must be in (0, 64]");
     if (!(std::isfinite(p.max_depth_change_factor) && p.max_depth_change_factor >= 0.0f))
         return fail(ctx, RSREG_ERR_INVALID_ARG, "max_depth_change_factor must be finite and not negative");
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    const char *rec = static_cast<const char *>(rsreg_cloud_device_ptr(in));
-    if (!rec) return fail(ctx, RSREG_ERR_STATE, "the cloud's records are not available");
 
     IinScratch &sc = ctx->iin;
     hipStream_t st = ctx->stream;

@@ -15,10 +15,9 @@
 
 #include "ndt_kernels.hpp"
 #include "pointgrid.hpp"
+#include "cloud_ops.hpp"
 
 using namespace rsreg;
-
-extern "C" int rsreg_comm_allreduce_device_(rsreg_ctx *ctx, double *d_buf, int count);  // comm.cpp
 
 namespace {
 
@@ -29,8 +28,6 @@ constexpr int kPassBlocks = RSREG_NDT_PASS_BLOCKS;   // fixed: the summation ord
                                    // 36 k points against 23 voxels: 0.61-0.62 ms per alignment, 1024: 0.65-0.68, 256: 0.62-0.63)
 constexpr int kMinPointsPerVoxel = 6;
 constexpr double kMinCovarEigMult = 0.01;
-
-inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 struct Pose {
     double p[6];

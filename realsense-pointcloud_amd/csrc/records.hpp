@@ -13,6 +13,8 @@ namespace rsreg {
 
 constexpr int kBlock = 256;            // 4 waves of 64
 
+inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }   // (host: the blocks of a launch)
+
 struct Mat34 {  // rows of the 3x4 part of a column-major Mat4f, passed by value to kernels
     float r0[4], r1[4], r2[4];
 };

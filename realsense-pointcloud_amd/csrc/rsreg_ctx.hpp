@@ -58,6 +58,9 @@ constexpr uint32_t kHsCounts = 40;                  // [40, 43) the target build
 constexpr uint32_t kHsCountWords = 3;
 constexpr uint32_t kHsPlainBox = 48;                // [48, 56) k_source_plain's box and stamp: harvest_source_box (caller)
 constexpr uint32_t kHsWords = 64;
+// knn.d_box and filt.host (pinned), the cloud filters' (filters.hip): the word behind the box is where one launch leaves a
+// flag or a count and where it lands at home
+constexpr uint32_t kFiltWord = kBoxWords;
 // the target's box borrows its scratch: the head of h_sums (pinned double[64]) is where the box, or the head of d_misc, lands;
 // d_comm holds the partials behind the 64 doubles of an allreduce
 constexpr size_t kSumsBytes = 64 * sizeof(double);
@@ -156,6 +159,9 @@ struct GridParams {
     int table_sparse;      // dense: only the table entries of occupied cells (and the slot behind each) are valid
     int have_nbr;          // dense: the neighbourhood occupancy words are built (0: a counting build for a small source left them out, icp.hip)
 };
+// dense == 2: so many source points at most -- one workgroup's lanes and LDS slots (icp_kernels.hpp: k_scan_*); cloud.hip
+// picks that search by it
+constexpr uint32_t kScanMaxSource = 64;
 
 struct BrickEntry {          // 32 B, one hash-table slot
     unsigned long long key;  // packed brick coordinate, ~0 = empty

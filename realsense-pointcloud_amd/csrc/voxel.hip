@@ -34,6 +34,7 @@
 #include "osort.hpp"
 #include "oscan.hpp"
 #include "pointgrid.hpp"
+#include "cloud_ops.hpp"
 
 namespace rsreg {
 namespace {
@@ -669,6 +670,28 @@ int voxel_filter_device(rsreg_ctx *ctx, const char *d_in, uint32_t N, size_t str
     return RSREG_OK;
 }
 
+// through pinned staging, copied by a few threads: a pageable hipMemcpy of 10-30 MB is several times slower
+int stage_up(rsreg_ctx *ctx, const void *in, size_t n, size_t stride)
+{
+    RSREG_HIP(ctx, ctx->d_vox_in.reserve(n * stride));
+    RSREG_HIP(ctx, ctx->h_stage.reserve(n * stride));
+    char *stage = ctx->h_stage.as<char>();
+    const char *src = static_cast<const char *>(in);
+    host_parallel_for(n, [=](size_t lo, size_t hi) { rsreg::stream_copy(stage + lo * stride, src + lo * stride, (hi - lo) * stride); });
+    RSREG_HIP(ctx, hipMemcpyAsync(ctx->d_vox_in.ptr, ctx->h_stage.ptr, n * stride, hipMemcpyHostToDevice, ctx->stream));
+    return RSREG_OK;
+}
+
+int stage_down(rsreg_ctx *ctx, void *out, size_t n, size_t stride)
+{
+    RSREG_HIP(ctx, hipMemcpyAsync(ctx->h_stage.ptr, ctx->d_vox_out.ptr, n * stride, hipMemcpyDeviceToHost, ctx->stream));
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const char *stage = ctx->h_stage.as<char>();
+    char *dst = static_cast<char *>(out);
+    host_parallel_for(n, [=](size_t lo, size_t hi) { std::memcpy(dst + lo * stride, stage + lo * stride, (hi - lo) * stride); });
+    return RSREG_OK;
+}
+
 }  // namespace rsreg
 
 extern "C" int rsreg_approx_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_t n, size_t stride, const float leaf[3], void *out,
@@ -680,26 +703,13 @@ extern "C" int rsreg_approx_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_
     *n_out = 0;
     if (n == 0) return RSREG_OK;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    RSREG_HIP(ctx, ctx->d_vox_in.reserve(n * stride));
-    // through pinned staging, copied by a few threads: a pageable hipMemcpy of 10-30 MB is several times slower
-    RSREG_HIP(ctx, ctx->h_stage.reserve(n * stride));
-    {
-        char *stage = ctx->h_stage.as<char>();
-        const char *src = static_cast<const char *>(in);
-        host_parallel_for(n, [=](size_t lo, size_t hi) { rsreg::stream_copy(stage + lo * stride, src + lo * stride, (hi - lo) * stride); });
-    }
-    RSREG_HIP(ctx, hipMemcpyAsync(ctx->d_vox_in.ptr, ctx->h_stage.ptr, n * stride, hipMemcpyHostToDevice, st));
+    int rc = stage_up(ctx, in, n, stride);
+    if (rc) return rc;
     uint32_t nr = 0;
-    int rc = voxel_filter_device(ctx, ctx->d_vox_in.as<char>(), (uint32_t)n, stride, leaf, &nr, -1);
+    rc = voxel_filter_device(ctx, ctx->d_vox_in.as<char>(), (uint32_t)n, stride, leaf, &nr, -1);
     if (rc || nr == 0) return rc;
-    RSREG_HIP(ctx, hipMemcpyAsync(ctx->h_stage.ptr, ctx->d_vox_out.ptr, (size_t)nr * stride, hipMemcpyDeviceToHost, st));
-    RSREG_HIP(ctx, hipStreamSynchronize(st));
-    {
-        const char *stage = ctx->h_stage.as<char>();
-        char *dst = static_cast<char *>(out);
-        host_parallel_for(nr, [=](size_t lo, size_t hi) { std::memcpy(dst + lo * stride, stage + lo * stride, (hi - lo) * stride); });
-    }
+    rc = stage_down(ctx, out, nr, stride);
+    if (rc) return rc;
     *n_out = nr;
     return RSREG_OK;
 }
@@ -989,32 +999,21 @@ int voxel_grid_device(rsreg_ctx *ctx, const char *d_in, uint32_t N, size_t strid
 
 }  // namespace rsreg
 
-struct rsreg_cloud;
-extern "C" int rsreg_cloud_adopt_(rsreg_cloud *c, DevBuf *buf, size_t n, size_t stride, uint32_t width, uint32_t height, int is_dense);   // cloud.hip
-extern "C" const rsreg_ctx *rsreg_cloud_ctx_(const rsreg_cloud *c);                                                                      // cloud.hip
-
 extern "C" int rsreg_cloud_voxel_grid(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_voxel_grid_params *params, rsreg_cloud *out,
                                       rsreg_voxel_grid_info *info)
 {
-    if (!ctx || !in || !out || rsreg_cloud_ctx_(in) != ctx || rsreg_cloud_ctx_(out) != ctx) return RSREG_ERR_INVALID_ARG;
-    if (!vg_params_ok(params)) return RSREG_ERR_INVALID_ARG;
-    size_t n = 0, stride = 0;
-    uint32_t width = 0, height = 0;
-    int is_dense = 0;
-    int rc = rsreg_cloud_info(in, &n, &stride, &width, &height, &is_dense);
+    if (!out || !vg_params_ok(params)) return RSREG_ERR_INVALID_ARG;
+    constexpr CloudRule rule{20, true, "records need rgb at byte 16 and a stride that is a multiple of 4", 0x3ffffff0ull, "cloud too large"};
+    CloudView v;
+    int rc = cloud_view(ctx, in, out, rule, v);
     if (rc) return rc;
-    if (stride < 20 || (stride & 3)) return fail(ctx, RSREG_ERR_INVALID_ARG, "records need rgb at byte 16 and a stride that is a multiple of 4");
-    if (n > 0x3ffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    const char *rec = static_cast<const char *>(rsreg_cloud_device_ptr(in));
-    if (n && !rec) return fail(ctx, RSREG_ERR_STATE, "the cloud's records are not available");
     rsreg_voxel_grid_info nfo;
     uint32_t n_out = 0;
-    rc = voxel_grid_device(ctx, rec, (uint32_t)n, stride, *params, &n_out, &nfo);
+    rc = voxel_grid_device(ctx, v.rec, (uint32_t)v.n, v.stride, *params, &n_out, &nfo);
     if (rc) return rc;
     if (info) *info = nfo;
     if (nfo.overflowed) return in == out ? RSREG_OK : rsreg_cloud_copy(ctx, in, out);
-    return rsreg_cloud_adopt_(out, &ctx->d_vox_out, n_out, stride, n_out, 1, 1);   // (in == out: the input has been consumed by now)
+    return rsreg_cloud_adopt_(out, &ctx->d_vox_out, n_out, v.stride, n_out, 1, 1);   // (in == out: the input has been consumed by now)
 }
 
 extern "C" int rsreg_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_t n, size_t stride, const rsreg_voxel_grid_params *params, void *out,
@@ -1029,17 +1028,10 @@ extern "C" int rsreg_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_t n, si
     if (info) *info = nfo;
     if (n == 0) return RSREG_OK;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    RSREG_HIP(ctx, ctx->d_vox_in.reserve(n * stride));
-    RSREG_HIP(ctx, ctx->h_stage.reserve(n * stride));
-    {
-        char *stage = ctx->h_stage.as<char>();
-        const char *src = static_cast<const char *>(in);
-        host_parallel_for(n, [=](size_t lo, size_t hi) { rsreg::stream_copy(stage + lo * stride, src + lo * stride, (hi - lo) * stride); });
-    }
-    RSREG_HIP(ctx, hipMemcpyAsync(ctx->d_vox_in.ptr, ctx->h_stage.ptr, n * stride, hipMemcpyHostToDevice, st));
+    int rc = stage_up(ctx, in, n, stride);
+    if (rc) return rc;
     uint32_t nr = 0;
-    int rc = voxel_grid_device(ctx, ctx->d_vox_in.as<char>(), (uint32_t)n, stride, *params, &nr, &nfo);
+    rc = voxel_grid_device(ctx, ctx->d_vox_in.as<char>(), (uint32_t)n, stride, *params, &nr, &nfo);
     if (rc) return rc;
     if (info) *info = nfo;
     if (nfo.overflowed) {   // the output is the input
@@ -1048,13 +1040,8 @@ extern "C" int rsreg_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_t n, si
         return RSREG_OK;
     }
     if (nr == 0) return RSREG_OK;
-    RSREG_HIP(ctx, hipMemcpyAsync(ctx->h_stage.ptr, ctx->d_vox_out.ptr, (size_t)nr * stride, hipMemcpyDeviceToHost, st));
-    RSREG_HIP(ctx, hipStreamSynchronize(st));
-    {
-        const char *stage = ctx->h_stage.as<char>();
-        char *dst = static_cast<char *>(out);
-        host_parallel_for(nr, [=](size_t lo, size_t hi) { std::memcpy(dst + lo * stride, stage + lo * stride, (hi - lo) * stride); });
-    }
+    rc = stage_down(ctx, out, nr, stride);
+    if (rc) return rc;
     *n_out = nr;
     return RSREG_OK;
 }
