@@ -344,7 +344,19 @@ int rsreg_transform_cloud(rsreg_ctx *ctx, const void *in, void *out, size_t n, s
 /* incremental_icp.hpp:54-55, icp_edge...hpp:47,59-60,75-76, ndt_edge...hpp:45,57-58,68-69.
  * Order-dependent streaming hash-history centroiding; this entry point runs it sequentially
  * on the host (no context needed), record for record like PCL.  Records must be PointXYZRGB (stride >= 20, rgb
- * at byte 16).  out must hold n records; *n_out receives the count.  in == out allowed. */
+ * at byte 16).  out must hold n records; *n_out receives the count.  in == out allowed.
+ * The contract, the same for this entry point, the GPU filter and the oracle (float32, one IEEE operation at a time):
+ * (1) The stream: a history of 512 slots.  A record whose slot holds another voxel flushes that voxel's centroid to the
+ *     output and takes the slot; at the end the occupied slots are flushed in slot order.
+ * (2) The centroid: the sums of x, y, z and of the r, g, b bytes (each converted to float first), from +0.0f on in input
+ *     order, divided by (float)count.  The colour is (int) of the three byte means, r << 16 | g << 8 | b; the fourth float is
+ *     1.0f; everything else in the record is zero.
+ * (3) A record with a non-finite x, y or z takes no part.
+ * (4) The cell index of a coordinate: c = floorf(x * inv) with inv = 1.0f / leaf; it is INT32_MIN when c is a NaN or
+ *     outside [-2^31, 2^31), otherwise the integer c.  That is what the conversion delivers on x86, and therefore what PCL
+ *     computes there; every implementation here writes it out.  So a leaf whose reciprocal is +inf is accepted (every cell
+ *     index of that axis is INT32_MIN), and coordinates of either sign past int32 share one voxel.
+ * (5) The slot: (ix * 7171 + iy * 3079 + iz * 4231) modulo 2^32, & 511. */
 int rsreg_approx_voxel_grid(const void *in, size_t n, size_t stride, const float leaf[3],
                             void *out, size_t *n_out);
 /* The same filter on the GPU, same output record for record: the points of one hash slot are

@@ -772,6 +772,9 @@ static size_t avg_flush(char *ob, size_t op, size_t stride, avg_he *h)
     return op + 1;
 }
 
+/* the cell index of the contract (include/rsreg.h): INT_MIN for a NaN and for anything outside [-2^31, 2^31), as x86 converts */
+static int avg_cell(float c) { return (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : (-2147483647 - 1); }
+
 int orc_approx_voxel_grid(const void *in, size_t n, size_t stride, const float *leaf, void *out,
                           size_t *n_out)
 {
@@ -789,10 +792,10 @@ int orc_approx_voxel_grid(const void *in, size_t n, size_t stride, const float *
         memcpy(&p[3], ib + cp * stride + 16, 4); /* the 'rgb' field read as a float */
         memcpy(rgba, ib + cp * stride + 16, 4);  /* b g r a */
         if (!finite3(p)) continue; /* PCL: undefined (float->int of NaN); oracle skips them */
-        int ix = (int)floorf(p[0] * inv_leaf[0]);
-        int iy = (int)floorf(p[1] * inv_leaf[1]);
-        int iz = (int)floorf(p[2] * inv_leaf[2]);
-        unsigned int hash = (unsigned int)((ix * 7171 + iy * 3079 + iz * 4231) & (HIST - 1));
+        int ix = avg_cell(floorf(p[0] * inv_leaf[0]));
+        int iy = avg_cell(floorf(p[1] * inv_leaf[1]));
+        int iz = avg_cell(floorf(p[2] * inv_leaf[2]));
+        unsigned int hash = ((unsigned int)ix * 7171u + (unsigned int)iy * 3079u + (unsigned int)iz * 4231u) & (HIST - 1);
         avg_he *h = &hist[hash];
         if (h->count && (ix != h->ix || iy != h->iy || iz != h->iz)) {
             op = avg_flush(tmp, op, stride, h);

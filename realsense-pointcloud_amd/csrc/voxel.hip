@@ -47,21 +47,26 @@ struct VoxelOf {
     bool ok;
 };
 
+// The cell index of the contract (include/rsreg.h): the integer c, or INT32_MIN when c is a NaN or outside [-2^31, 2^31) -- what
+// x86's conversion, and therefore PCL, delivers for a leaf coordinate past int32 (a leaf whose reciprocal is +inf included).  The
+// device's own (int) saturates and turns a NaN into 0: other voxels, other slots.
+__device__ __forceinline__ int vox_cell_i32(float c) { return (c >= -2147483648.0f && c < 2147483648.0f) ? (int)c : (int)0x80000000; }
+
 __device__ __forceinline__ VoxelOf voxel_of(const char *rec, float ivx, float ivy, float ivz)
 {
     const float *p = reinterpret_cast<const float *>(rec);
     const float x = p[0], y = p[1], z = p[2];
     VoxelOf v;
     v.ok = isfinite(x) && isfinite(y) && isfinite(z);
-    v.ix = (int)floorf(__fmul_rn(x, ivx));
-    v.iy = (int)floorf(__fmul_rn(y, ivy));
-    v.iz = (int)floorf(__fmul_rn(z, ivz));
+    v.ix = vox_cell_i32(floorf(__fmul_rn(x, ivx)));
+    v.iy = vox_cell_i32(floorf(__fmul_rn(y, ivy)));
+    v.iz = vox_cell_i32(floorf(__fmul_rn(z, ivz)));
     return v;
 }
 
-__device__ __forceinline__ uint32_t slot_of(const VoxelOf &v)
+__device__ __forceinline__ uint32_t slot_of(const VoxelOf &v)   // (modulo 2^32)
 {
-    return (uint32_t)(v.ix * 7171 + v.iy * 3079 + v.iz * 4231) & (kHist - 1);
+    return ((uint32_t)v.ix * 7171u + (uint32_t)v.iy * 3079u + (uint32_t)v.iz * 4231u) & (kHist - 1);
 }
 
 // key = slot (non-finite points: kHist, sorted behind everything), value = input position; the filter's four counters
@@ -723,7 +728,8 @@ extern "C" int rsreg_approx_voxel_grid_gpu(rsreg_ctx *ctx, const void *in, size_
 //   k_vox_runs<true> / k_vox_long_runs<true> / k_vox_huge_runs<true>: the sums of a leaf in ascending input index
 //   (min_points_per_voxel > 1: k_vg_keep / oscan) k_vg_emit: the records, in key order
 // Keys are 32 bits wide unless the leaf indices use all 32 bits (div_b's product passes 2^31 although d's does not: the box
-// is measured twice, by a difference and by two floors): then the sentinel is bit 32 and the keys are 64 bits wide.
+// is measured twice, by a difference and by two floors; or a box bound saturated, and the indices are whatever the float
+// difference gives: vg_leaf_grid): then the sentinel is bit 32 and the keys are 64 bits wide.
 namespace rsreg {
 namespace {
 
@@ -831,7 +837,11 @@ inline int32_t vg_host_sat_i32(float f)
 }
 
 // What the host makes of the box: 1 = the leaf size is too small for it (PCL: the output is the input); else the leaf grid,
-// the info fields and the largest key a finite record can get.
+// the info fields and the largest key a finite record can get.  That is not prod(div_b) - 1: ijk is the float difference
+// floorf(p * inv) - (float)min_b, which is monotonic in p, so on every axis the record at max_p has the largest -- but where a
+// bound has saturated div_b says nothing about it (a compact box at 3e9: div_b = 1, ijk = 852516352), and where the
+// difference rounds up it is div_b itself (a box from -1 to 33554430).  A bound that saturated, or a sum of 2^32 and more
+// (idx wraps): the keys may be any 32-bit value.
 int vg_leaf_grid(const float mn[3], const float mx[3], const float leaf[3], LeafGrid &g, rsreg_voxel_grid_info &nfo, uint32_t &max_key)
 {
     unsigned long long cells = 1;
@@ -843,21 +853,26 @@ int vg_leaf_grid(const float mn[3], const float mx[3], const float leaf[3], Leaf
         cells *= (unsigned long long)((int64_t)v + 1);   // (a factor is 2^31 at the most and `cells` below 2^31 before it)
         if (cells > (unsigned long long)INT32_MAX) return 1;
     }
-    unsigned long long span = 1;   // the product of the divisions as it is, saturated at 2^32
+    bool saturated = false;
+    unsigned long long top[3];   // the ijk of max_p, by k_vg_keys' arithmetic
     for (int a = 0; a < 3; ++a) {
-        const float lo = mn[a] * g.inv[a], hi = mx[a] * g.inv[a];
-        nfo.min_b[a] = vg_host_sat_i32(std::floor(lo));
-        nfo.max_b[a] = vg_host_sat_i32(std::floor(hi));
-        const long long div = (long long)nfo.max_b[a] - (long long)nfo.min_b[a] + 1;   // (1 .. 2^32)
-        nfo.div_b[a] = (int32_t)(uint32_t)div;
-        if (span < (1ull << 32)) span = std::min(span * (unsigned long long)div, 1ull << 32);   // (span < 2^32, div <= 2^32: no overflow of 64 bits)
+        const float lo = std::floor(mn[a] * g.inv[a]), hi = std::floor(mx[a] * g.inv[a]);
+        nfo.min_b[a] = vg_host_sat_i32(lo);
+        nfo.max_b[a] = vg_host_sat_i32(hi);
+        if (lo < -2147483648.0f || lo >= 2147483648.0f || hi < -2147483648.0f || hi >= 2147483648.0f) saturated = true;
+        nfo.div_b[a] = (int32_t)((uint32_t)nfo.max_b[a] - (uint32_t)nfo.min_b[a] + 1u);
         g.min_b[a] = nfo.min_b[a];
+        top[a] = (uint32_t)vg_host_sat_i32(hi - (float)nfo.min_b[a]);
     }
     g.mul[0] = 1u;
     g.mul[1] = (uint32_t)nfo.div_b[0];
     g.mul[2] = (uint32_t)nfo.div_b[0] * (uint32_t)nfo.div_b[1];
     for (int a = 0; a < 3; ++a) nfo.divb_mul[a] = (int32_t)g.mul[a];
-    max_key = (uint32_t)(span - 1);   // (2^32 leaves or more: the indices wrap and may be any 32-bit value)
+    // the largest idx in 64 bits (every factor is below 2^32, and each term is looked at before it is added)
+    const unsigned long long m1 = (uint32_t)nfo.div_b[0], m2 = m1 * (unsigned long long)(uint32_t)nfo.div_b[1];
+    const bool any_key = saturated || (m2 >> 32) || ((top[1] * m1) >> 32) || ((top[2] * m2) >> 32);
+    const unsigned long long top_key = any_key ? 0ull : top[0] + top[1] * m1 + top[2] * m2;
+    max_key = (any_key || (top_key >> 32)) ? 0xffffffffu : (uint32_t)top_key;
     return 0;
 }
 

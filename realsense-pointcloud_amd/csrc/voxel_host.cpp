@@ -24,6 +24,10 @@ struct Slot {
     float acc[7] = {0, 0, 0, 0, 0, 0, 0};  // x y z rgb-as-float r g b
 };
 
+// The cell index of the contract (include/rsreg.h): the integer c, or INT32_MIN when c is a NaN or outside [-2^31, 2^31).  That is
+// what x86's conversion instruction delivers, and therefore PCL; written out, because in C++ the plain cast is undefined there.
+inline int32_t cell_i32(float c) { return (c >= -2147483648.0f && c < 2147483648.0f) ? static_cast<int32_t>(c) : INT32_MIN; }
+
 void emit(unsigned char *out, size_t &n_out, size_t stride, const Slot &s)
 {
     const float n = static_cast<float>(s.count);
@@ -68,10 +72,10 @@ extern "C" int rsreg_approx_voxel_grid(const void *in, size_t n, size_t stride, 
         std::memcpy(&rgbf, rec + 16, 4);
         std::memcpy(bgra, rec + 16, 4);
         if (!std::isfinite(xyz[0]) || !std::isfinite(xyz[1]) || !std::isfinite(xyz[2])) continue;
-        const int ix = static_cast<int>(std::floor(xyz[0] * inv[0]));
-        const int iy = static_cast<int>(std::floor(xyz[1] * inv[1]));
-        const int iz = static_cast<int>(std::floor(xyz[2] * inv[2]));
-        const unsigned h = static_cast<unsigned>((ix * 7171 + iy * 3079 + iz * 4231) & (kHist - 1));
+        const int32_t ix = cell_i32(std::floor(xyz[0] * inv[0]));
+        const int32_t iy = cell_i32(std::floor(xyz[1] * inv[1]));
+        const int32_t iz = cell_i32(std::floor(xyz[2] * inv[2]));
+        const uint32_t h = (static_cast<uint32_t>(ix) * 7171u + static_cast<uint32_t>(iy) * 3079u + static_cast<uint32_t>(iz) * 4231u) & (kHist - 1);
         Slot &s = hist[h];
         if (s.count && (s.ix != ix || s.iy != iy || s.iz != iz)) {
             emit(result, count, stride, s);

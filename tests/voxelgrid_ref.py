@@ -112,7 +112,7 @@ def voxel_grid(points, leaf, downsample_all_data=True, min_points=0, reverse_lea
         if reverse_leaves:
             members = members[::-1]
         cnt = F(n)
-        mean = {k: F(np.cumsum(v[members], dtype=F)[-1] / cnt) for k, v in comps.items()}
+        mean = {k: F(np.cumsum(np.r_[F(0.0), v[members]], dtype=F)[-1] / cnt) for k, v in comps.items()}     # (a sum starts at +0.0f: a leaf of -0.0f alone gives +0.0f)
         rec = out[kept:kept + 1]
         rec["x"], rec["y"], rec["z"] = mean["x"], mean["y"], mean["z"]
         rec.view(np.uint8).reshape(-1)[12:16] = np.frombuffer(F(1.0).tobytes(), np.uint8)
