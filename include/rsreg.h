@@ -242,7 +242,23 @@ void rsreg_ndt_params_reference(rsreg_ndt_params *p);
  * taken over at the next call that waits for the stream): a host buffer has been read by then (a second
  * rsreg_icp_set_target first waits for the queued build that still reads the staged records); a DEVICE buffer
  * (d_points) must stay alive and unchanged until the next synchronising call on the context -- rsreg_icp_align /
- * rsreg_icp_begin, rsreg_icp_grid_info or rsreg_ctx_synchronize -- has returned. */
+ * rsreg_icp_begin, rsreg_icp_grid_info or rsreg_ctx_synchronize -- has returned.
+ * RANGE.  The grid is decided by csrc/icp_grid_plan.hpp from the box of the finite records, their number and the gate; its
+ * constants are metres (a cell cap of 14 .. 42 mm, at most 60 000 cells along the longest axis, at least 1e-6 m a cell), so a
+ * cloud at another scale gets another grid.  A target is SERVED when that grid's cell is at most 2^60 m (1.15e18) and the box
+ * is no wider than a finite float along any axis; every other target -- a cloud of extent 6.9e22 m or more, a bounded gate of
+ * 8.9e18 m or more, records at +-3e38 -- is taken (its records and box serve rsreg_icp_fitness_score, which searches an index
+ * of its own over the whole float range) but every correspondence search over it -- rsreg_icp_search, rsreg_icp_align* -- is
+ * REFUSED with RSREG_ERR_INVALID_ARG: on such a grid cell * cell is not a normal float and the searches' bounds would skip cells
+ * that hold the answer.  Nothing is refused for being small: a cloud of denormal coordinates lies in one cell and is searched
+ * point by point.
+ * COST.  A search looks at nothing farther than the gate.  With an UNBOUNDED gate (PCL's default, sqrt(DBL_MAX)) or one wider
+ * than the cloud, a query with no target point near it walks the grid outwards until the grid is exhausted: up to
+ * (longest axis in cells / 2)^3 bricks of the brick hash, or (2 * longest axis)^2 rows of the dense table.  For a cloud of a few
+ * metres that is a few thousand steps; for a cloud wider than about 2.5 km the cell is extent / 60 000 whatever the number of
+ * points, and one such query costs up to 10^13 steps -- in practice the call does not return.  Give a cloud of that extent a
+ * gate below a quarter of its extent: the cell then follows the gate, and a query costs a few thousand steps at most
+ * (tests/icp_grid_layout.py: cost_bound, the model; tests/icp_scale_cases.py: OVER_CAP, the cases left out for it). */
 int rsreg_icp_set_target(rsreg_ctx *ctx, const void *points, size_t n, size_t stride,
                          int is_dense, double max_correspondence_distance);
 int rsreg_icp_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, size_t stride,
@@ -278,7 +294,15 @@ int rsreg_icp_align_records(rsreg_ctx *ctx, const float *guess, const rsreg_icp_
 int rsreg_icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params);
 /* CorrespondenceEstimation::determineCorrespondences: nearest target per current source
  * point.  Outputs (host, each nullable, n_source entries): index into the ORIGINAL target
- * array (-1: no target within the gate / non-finite source point), squared distance. */
+ * array (-1: no target within the gate / non-finite source point), squared distance.
+ * The contract is a float32 brute force: d2 = (dx * dx + dy * dy) + dz * dz, every operation rounded once (a difference that
+ * overflows gives +inf, a square that underflows a denormal or 0); the lowest target index among the smallest d2 (+inf ties
+ * with +inf); a pair is rejected iff (double)d2 > gate * gate.  It holds, index for index and d2 bit for bit, over every served
+ * target (rsreg_icp_set_target: RANGE) for every finite query, wherever it lies -- tests/test_icp_scale_gpu.py: clouds from 2^-140
+ * to 2^66, offsets up to 2^23 m, queries 2^5 .. 2^100 m outside the box, a gate of +inf under which pairs at d2 = +inf are accepted,
+ * on both kinds of index.  A query more than 1 024 cells outside the target's box (its position in cell units then carries a
+ * rounding the bounds' margin is not argued for) is searched without bounds: nothing when the gate cannot reach the box from
+ * there, else every target point -- n points a query. */
 int rsreg_icp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out);
 /* The 17 sums over the accepted correspondences of the last search (this rank's block). */
 int rsreg_icp_sums(rsreg_ctx *ctx, double sums[RSREG_NUM_SUMS]);

@@ -23,6 +23,7 @@
 #include "fitness_kernels.hpp"
 #include "plane_kernels.hpp"
 #include "cloud_ops.hpp"
+#include "icp_grid_plan.hpp"
 
 using namespace rsreg;
 
@@ -95,17 +96,8 @@ GridDev grid_dev(const rsreg_ctx *ctx, double max_dist)
     g.bricks = ctx->d_table.as<BrickEntry>();
     g.cellpos = ctx->d_cellpos.as<uint32_t>();
     g.pts = ctx->d_tgt_sorted.as<float4>();
+    g.n_pts = p.dense ? 0u : p.n_points;   // (the brick hash's own count; a dense index is never searched through a GridDev)
     return g;
-}
-
-// host mirror of cell_coord (same IEEE operations, no contraction)
-int host_cell_coord(float p, float origin, float inv_cell)
-{
-    volatile float d = p - origin;
-    volatile float v = d * inv_cell;
-    float f = std::floor(v);
-    f = std::min(std::max(f, -4.0f), 70000.0f);
-    return (int)f;
 }
 
 // bounding box + count of the finite points of a device-resident cloud (one host sync), on the given stream with
@@ -145,6 +137,11 @@ int device_bbox(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, floa
     return device_bbox_on(ctx, ctx->stream, ctx->d_misc.as<uint32_t>(), ctx->h_sums.as<uint32_t>(),
                           reinterpret_cast<uint32_t *>(ctx->d_comm.as<char>() + kCommPartialsAt), d_pts, n, stride, mn, mx, nfin);
 }
+
+// max_ring counts the rings that cover the gate (icp_grid_plan.hpp) -- unless that is the whole grid, where it says nothing about the
+// gate.  True: the gate is at most max_ring cells.  The searches built for gates of at most four cells (the blocks search of the
+// fused kernel, the sparse table) are chosen by max_ring <= 4 AND this: they carry no far path (icp_dense.hpp: nn_query_dense).
+bool gate_in_rings(const GridParams &p) { return p.max_ring < std::max(p.dims[0], std::max(p.dims[1], p.dims[2])) + 1; }
 
 DenseDev dense_dev(const rsreg_ctx *ctx, double max_dist)
 {
@@ -368,7 +365,9 @@ int build_dense(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doub
     gp.xbits = narrow ? std::min(16, 32 - id_bits) : 16;
     // the searches of gates up to four cells go through the occupancy words only (icp_dense.hpp: dense_far_blocks);
     // the row search of wider or unbounded gates reads table entries of empty cells too and needs all of them
-    gp.table_sparse = (gp.max_ring <= 4 && !full_table && !tunables().far_rows) ? 1 : 0;
+    // (... a gate of at most four cells, that is: max_ring of a grid of three cells a side is the whole grid, whatever the gate, and a
+    //  far query's scan of every point reads the first and the last table entry -- icp_dense.hpp: nn_query_dense)
+    gp.table_sparse = (gp.max_ring <= 4 && gate_in_rings(gp) && !full_table && !tunables().far_rows) ? 1 : 0;
     const uint32_t *h_counts = ctx->h_smisc.as<uint32_t>() + kHsCounts;
     const bool counted = count_sort_pays(n, total);
     if (counted) {
@@ -478,49 +477,27 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
         return RSREG_OK;
     }
 
-    // ---- cell size: a whole fraction of the gate, no larger than the cap; an unbounded
-    // gate searches outward until the grid is exhausted.  `refine` (second pass only) shrinks
-    // the cells of a dense cloud towards ~8 points per occupied cell.
-    // the cap is tuned on 10^6-point D435i-like frames; sparser clouds (lower resolution of the same
-    // scene: sample spacing ~ n^-1/2) do best with somewhat larger cells (swept at 50 k and 300 k points)
-    const double cap = tunables().cell_cap * std::min(3.0, std::max(1.0, std::pow(1.0e6 / std::max<double>(nfin, 1.0e4), 0.28)));
-    double extent = 0;
-    for (int k = 0; k < 3; ++k) extent = std::max(extent, (double)mx[k] - (double)mn[k]);
-    double cell;
-    const bool bounded = std::isfinite(max_dist) && max_dist > 0 && max_dist < 0.25 * extent + 1e-3;
-    if (bounded) {
-        const double padded = max_dist * 1.04;
-        int parts = std::max(1, (int)std::ceil(padded / (cap * refine)));
-        parts = std::min(parts, 8);   // the far phase walks (2*parts/4+3)^3 bricks for an unmatched query
-        cell = padded / parts;
-        // a gate below the cap (the reference's 1 cm on sparse edge clouds): cells as large as the cap still need one
-        // ring only, and the table (cleared and scanned on every build) shrinks with the cube of the cell
-        const bool wide = tunables().wide_cells;
-        if (wide && parts == 1 && cap * refine > padded) cell = cap * refine;
-    } else {
-        cell = cap * refine;
-    }
-    cell = std::max(cell, extent / 60000.0);  // 16 bits per axis in the cell key
-    cell = std::max(cell, 1e-6);
+    // ---- the grid: cell, origin, dims, rings and the kind of index, decided by the host-only rule of icp_grid_plan.hpp.
+    // `refine` (second pass only) shrinks the cells of a dense cloud towards ~8 points per occupied cell.
+    static_assert(kIcpPlanMargin == kCellMargin, "icp_grid_plan.hpp counts the rings of a gate with the searches' margin");
+    IcpGridInput plan_in;
+    for (int k = 0; k < 3; ++k) { plan_in.mn[k] = mn[k]; plan_in.mx[k] = mx[k]; }
+    plan_in.nfin = nfin;
+    plan_in.max_dist = max_dist;
+    plan_in.refine = refine;
+    plan_in.cell_cap = tunables().cell_cap;
+    plan_in.wide_cells = tunables().wide_cells;
+    plan_in.dense_max_cells = tunables().dense_max_cells;
+    const IcpGridPlan plan = icp_grid_plan(plan_in);
     GridParams &gp = ctx->grid;
-    gp.cell = (float)cell;
-    gp.inv_cell = 1.0f / gp.cell;
-    for (int k = 0; k < 3; ++k) {
-        gp.origin[k] = mn[k];
-        gp.dims[k] = host_cell_coord(mx[k], gp.origin[k], gp.inv_cell) + 2;
-    }
-    const int max_dim = std::max(gp.dims[0], std::max(gp.dims[1], gp.dims[2]));
-    int max_ring = max_dim + 1;
-    if (std::isfinite(max_dist) && max_dist >= 0) {
-        const double rings = std::ceil(max_dist / (double)gp.cell + kCellMargin);   // smallest R with (R - margin) * cell >= gate
-        if (rings < (double)(max_dim + 1)) max_ring = std::max(1, (int)rings);
-    }
-    gp.max_ring = max_ring;
-    {
-        const long long padded = (long long)(gp.dims[0] + 2) * (gp.dims[1] + 2) * (gp.dims[2] + 2);
-        // (the dense search addresses points by 32-bit byte offsets: 16 B x 2^28)
-        if (padded <= tunables().dense_max_cells && (unsigned long long)nfin + 4ull < (1ull << 28)) return build_dense(ctx, d_pts, n, stride, max_dist, nfin, ev0, ev1);
-    }
+    // a grid on which the searches' float32 bounds do not hold (a cell above 2^60 m, a box wider than a float) is built as before --
+    // the target's box and records serve the fitness score, which has an index of its own -- and never searched (refuse_unserved)
+    gp.unserved = plan.served ? 0 : 1;
+    gp.cell = plan.cell;
+    gp.inv_cell = plan.inv_cell;
+    for (int k = 0; k < 3; ++k) { gp.origin[k] = plan.origin[k]; gp.dims[k] = plan.dims[k]; }
+    gp.max_ring = plan.max_ring;
+    if (plan.index_kind == 1) return build_dense(ctx, d_pts, n, stride, max_dist, nfin, ev0, ev1);
 
     // ---- sort by (brick, cell in brick, xyz hash)
     // (the brick path counts with atomics in the words k_bbox_final clears; the dense table's kernels only store there)
@@ -609,16 +586,13 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
     // dense cloud: rebuild once with smaller cells (fewer candidates per query)
     const bool adaptive = tunables().adaptive_cell;
     if (adaptive && refine == 1.0 && n_cells > 0) {
-        const double per_cell = (double)n_unique / (double)n_cells;
-        if (per_cell > 14.0) {
+        const double r = icp_refine_factor(n_unique, n_cells);
+        if (r != 1.0) {
             const double ms_first = gi.ms_build;
-            const double r = std::max(0.2, std::sqrt(8.0 / per_cell));
-            const float cell_before = gp.cell;
             ctx->next_tgt_box = ctx->last_tgt_box;   // (the same records: no second measurement)
             int rc2 = build_grid(ctx, d_pts, n, stride, max_dist, r);
             if (rc2) return rc2;
             ctx->grid_info.ms_build += ms_first;
-            (void)cell_before;
         }
     }
     return RSREG_OK;
@@ -1014,6 +988,8 @@ __global__ __launch_bounds__(kBlock) void k_recip_filter(const float4 *tgt, int 
     if (!ok) corr_pos[u] = -1;
 }
 
+int refuse_unserved(rsreg_ctx *ctx, const rsreg_ctx *grid_of);   // (below, with launch_search)
+
 // the optional filters PCL's ICP applies between determineCorrespondences and the transformation estimate:
 // reciprocal correspondences (CorrespondenceEstimation::determineReciprocalCorrespondences) and the trimmed rejector
 int apply_filters(rsreg_ctx *ctx)
@@ -1048,6 +1024,7 @@ int apply_filters(rsreg_ctx *ctx)
             }
             return fail(ctx, rc, why.c_str());
         }
+        if (int rcu = refuse_unserved(ctx, c)) return rcu;   // (the index over the source: the same range)
         if (c->grid.n_points) {   // (a bound while the child's counting build has not been waited for: never 0 for a cloud with a finite point)
             const DenseDev gd = c->grid.dense ? dense_dev(c, s.prm.max_correspondence_distance) : DenseDev{};
             const GridDev gh = grid_dev(c, s.prm.max_correspondence_distance);
@@ -1097,8 +1074,17 @@ int apply_filters(rsreg_ctx *ctx)
     return RSREG_OK;
 }
 
+// Every correspondence search starts with this: a target whose grid is outside the served range (build_grid: unserved) is refused
+// here, before a launch, not answered wrongly.  (One host comparison per launch; the kernels are the ones of every other grid.)
+int refuse_unserved(rsreg_ctx *ctx, const rsreg_ctx *grid_of)
+{
+    if (!grid_of->grid.unserved) return RSREG_OK;
+    return fail(ctx, RSREG_ERR_INVALID_ARG, "target outside the range the ICP search serves: cell above 2^60 m or box wider than a float (rsreg.h: rsreg_icp_set_target)");
+}
+
 int launch_search(rsreg_ctx *ctx)
 {
+    if (int rcu = refuse_unserved(ctx, ctx)) return rcu;
     ctx->icp.idle_after_sums = false;   // (something is queued on the main stream from here on)
     IcpState &s = ctx->icp;
     {
@@ -1355,6 +1341,7 @@ int build_schedule(rsreg_ctx *ctx, uint32_t n_tiles, bool first)
 // fused pass: applies the pending increment (if any), searches, gates and reduces
 int launch_fused(rsreg_ctx *ctx, double *sums, bool want_corr, bool device_loop = false)
 {
+    if (int rcu = refuse_unserved(ctx, ctx)) return rcu;
     ctx->icp.idle_after_sums = false;   // (something is queued on the main stream from here on)
     IcpState &s = ctx->icp;
     const uint32_t n = (uint32_t)ctx->n_work;
@@ -1376,7 +1363,7 @@ int launch_fused(rsreg_ctx *ctx, double *sums, bool want_corr, bool device_loop 
         if (ctx->grid.dense) {
             unsigned long long *wt = wave_times_ptr(ctx, n);
             // (the search beyond ring 1 comes in two forms; each instantiation carries only the one its grid uses)
-            const bool blocks = ctx->grid.max_ring <= 4 && !tunables().far_rows;
+            const bool blocks = ctx->grid.max_ring <= 4 && gate_in_rings(ctx->grid) && !tunables().far_rows;
 #ifdef RSREG_DIAG
             const bool light = tunables().wave_times_light;
             const bool tab = !ctx->grid.have_nbr;   // (an index without occupancy words: read off the table)

@@ -874,14 +874,30 @@ __device__ __forceinline__ Best nn_query_dense(const DenseDev &g, float qx, floa
     const DQuery q = dense_query(g, qx, qy, qz);
     float limit2 = g.prune2;
     DBest b = dbest_none();
-    dense_near<kDiag, kFar == 3>(g, rs, q, seed_pos, b, limit2, sp, dg);
-    if (kDiag) dg->t_near = wall_clock64();
-    const bool far = kFar != 3 && dense_needs_far(g, limit2);
-    if (far) {
-        if (kFar == 1 || (kFar == 0 && g.max_ring <= 4)) dense_far_blocks<kDiag>(g, rs, q, b, limit2, sp, dg);
-        else dense_far<kDiag>(g, rs, q, b, limit2, sp, dg);
+    // kFar 1 and 3 -- the host's choice for a gate of at most four cells (icp.hip: gate_in_rings) -- carry no far path, and need
+    // none: nothing is within such a gate of a query 1 024 cells outside, so whatever the bounds skip out there was no match, and
+    // whatever they do not skip is scored exactly and rejected by the gate.  (Compiled into those too, the scan cost the fused
+    // kernel nine spilled VGPRs of its 64 and a 10^6-point launch 5 us.)
+    if ((kFar == 0 || kFar == 2) && far_query(q.ux, q.uy, q.uz, g.nx, g.ny, g.nz)) {
+        // (icp_kernels.hpp: kFarCells) no bound holds out there: nothing, or every point -- the sorted points of all cells are one run,
+        // from the start of the first cell to the start of the border cell behind the last.  A gate that reaches this far spans more
+        // than four cells, or the grid is a few cells in all: the table then has every entry (build_dense: table_sparse).
+        if (!far_unreachable(q.ux, q.uy, q.uz, g.nx, g.ny, g.nz, g.cell, g.prune2)) {
+            const uint32_t s = __builtin_amdgcn_raw_buffer_load_b32(rs.tab, dense_cell_id(g, 0, 0, 0) * 4u, 0, 0);
+            const uint32_t e = __builtin_amdgcn_raw_buffer_load_b32(rs.tab, (dense_cell_id(g, g.nx - 1, g.ny - 1, g.nz - 1) + 1u) * 4u, 0, 0);
+            dscan_range(b, rs.pts, s * 16u, e * 16u, f32x2{q.qx, q.qy}, q.qz, sp);
+        }
+        if (kDiag) dg->t_near = dg->t_far = wall_clock64();
+    } else {
+        dense_near<kDiag, kFar == 3>(g, rs, q, seed_pos, b, limit2, sp, dg);
+        if (kDiag) dg->t_near = wall_clock64();
+        const bool far = kFar != 3 && dense_needs_far(g, limit2);
+        if (far) {
+            if (kFar == 1 || (kFar == 0 && g.max_ring <= 4)) dense_far_blocks<kDiag>(g, rs, q, b, limit2, sp, dg);
+            else dense_far<kDiag>(g, rs, q, b, limit2, sp, dg);
+        }
+        if (kDiag) dg->t_far = wall_clock64();
     }
-    if (kDiag) dg->t_far = wall_clock64();
     // the lanes of a split query hold the bests of disjoint parts of the candidate set: the smallest
     // (distance, index) key among them is the query's (every lane of the group ends up with it)
     for (uint32_t m = 1; m < (1u << sp.lg); m <<= 1)

@@ -43,7 +43,35 @@ struct GridDev {
     const BrickEntry *bricks;
     const uint32_t *cellpos;
     const float4 *pts;
+    uint32_t n_pts;          // sorted target points: what a far query's exhaustive scan reads (nn_query)
 };
+
+// A query more than so many cells outside the grid along an axis -- or whose position in cell units is not a finite float -- is a
+// FAR query.  The bounds every search skips cells by measure from the query's position u = (q - origin) * inv_cell, which carries
+// a rounding of 2^-23 |u|; the fixed margins (kCellMargin 0.03, the dense search's 0.004 .. 0.03) cover it for |u| up to the
+// grid + 1 024 cells with room for the rounding of the bounds' own products, and not at 10^6 cells.  A far query therefore takes no
+// bound at all: nothing when the gate cannot reach the box from there (far_unreachable), else every target point, scored like any
+// other candidate (lowest index among equal d2).  That costs a query n points, whatever the grid.
+constexpr float kFarCells = 1024.0f;
+
+// |u - h| <= h + kFarCells along every axis, h = half the grid: written so that a NaN or infinite position is far
+__device__ __forceinline__ bool far_query(float ux, float uy, float uz, int nx, int ny, int nz)
+{
+    const float hx = 0.5f * (float)nx, hy = 0.5f * (float)ny, hz = 0.5f * (float)nz;
+    return !(fabsf(ux - hx) <= hx + kFarCells && fabsf(uy - hy) <= hy + kFarCells && fabsf(uz - hz) <= hz + kFarCells);
+}
+
+// A far query is at least o cells outside the box along some axis, o what its rounded position says (true: within 2^-22 of it), so
+// every target point is farther than 0.99 * o * cell, and every float d2 above the square of that (each of its roundings is 2^-24).
+// prune2 is the gate's square rounded up (+inf: unbounded): below that square, every pair would be rejected -- as the brute force does.
+// (o = +inf, a position that overflowed: every finite gate is out of reach, and every d2 is +inf.)
+__device__ __forceinline__ bool far_unreachable(float ux, float uy, float uz, int nx, int ny, int nz, float cell, float prune2)
+{
+    const float hx = 0.5f * (float)nx, hy = 0.5f * (float)ny, hz = 0.5f * (float)nz;
+    const float o = fmaxf(fmaxf(fabsf(ux - hx) - hx, fabsf(uy - hy) - hy), fabsf(uz - hz) - hz);
+    const float r = (o * 0.99f) * cell;
+    return prune2 < r * r;
+}
 
 // State of the device-resident loop (RSREG_PIPELINE_DEVICE_LOOP): what update_from_sums keeps
 // on the host, kept in HBM so that iteration k+1 can be queued before iteration k has run.
@@ -783,6 +811,10 @@ __device__ __forceinline__ Best nn_query(const GridDev &g, float qx, float qy, f
     Best b{~0ull, -1, FLT_MAX};
     if (g.dx <= 0) return b;
     const QueryGeom qg = query_geom(g, qx, qy, qz);
+    if (far_query(qg.ux, qg.uy, qg.uz, g.dx, g.dy, g.dz)) {   // no bound holds out there: nothing, or every point
+        if (!far_unreachable(qg.ux, qg.uy, qg.uz, g.dx, g.dy, g.dz, g.cell, g.prune2)) scan_points(g.pts, 0u, g.n_pts, qx, qy, qz, b);
+        return b;
+    }
     float limit2 = g.prune2;  // nothing farther than this can be accepted or improve the best
     if (seed_pos >= 0) {
         const float4 t = g.pts[seed_pos];

@@ -158,6 +158,7 @@ struct GridParams {
     int xbits;             // dense: bits of the x position inside a cell in the sort key (16, or what a 32-bit key leaves)
     int table_sparse;      // dense: only the table entries of occupied cells (and the slot behind each) are valid
     int have_nbr;          // dense: the neighbourhood occupancy words are built (0: a counting build for a small source left them out, icp.hip)
+    int unserved;          // 1: a grid the searches' float32 bounds do not hold on (icp_grid_plan.hpp: served) -- built, never searched
 };
 // dense == 2: so many source points at most -- one workgroup's lanes and LDS slots (icp_kernels.hpp: k_scan_*); cloud.hip
 // picks that search by it
