@@ -668,8 +668,7 @@ int rsreg_cloud_spfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *n
  *   The output is ordered by index_query.  *n_out = the number found; when it exceeds `capacity` the first `capacity` are written
  *   and the call still returns RSREG_OK: the caller sees *n_out > capacity, nothing is hidden.  host_out may be NULL when capacity
  *   is 0.  No valid target row, or (reciprocal) no valid source row, or an empty cloud: *n_out = 0, RSREG_OK.  Waits for the stream.
- * Not built: setIndices, descriptors of other lengths, other metrics, CorrespondenceRejector*, SampleConsensusPrerejective /
- * SampleConsensusInitialAlignment, a transformation estimated from a correspondence list. */
+ * Not built: setIndices, descriptors of other lengths, other metrics.  What turns the list into a pose is the next section. */
 typedef struct rsreg_correspondence {
     int32_t index_query;   /* source row */
     int32_t index_match;   /* target row */
@@ -679,6 +678,96 @@ int rsreg_cloud_feature_knn(rsreg_ctx *ctx, const rsreg_cloud *source, const rsr
                             float *sqr_dist_out /* ns*k */);
 int rsreg_cloud_feature_correspondences(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, double max_distance, int reciprocal,
                                         rsreg_correspondence *host_out, size_t capacity, size_t *n_out);
+/* ---- pose from correspondences: pcl::registration::CorrespondenceRejectorSampleConsensus (RANSAC over a correspondence list, its
+ * model pcl::SampleConsensusModelRegistration) and pcl::registration::TransformationEstimationSVD over a correspondence list.  PCL
+ * 1.9.1 registration/impl/correspondence_rejection_sample_consensus.hpp, sample_consensus/impl/sac_model_registration.hpp and
+ * sample_consensus/impl/ransac.hpp, recalled; PCL is not available to check against, so what follows IS the contract, and where it
+ * leaves PCL it says DEVIATION.
+ * Inputs of every entry point: two device clouds of the context whose records start with x, y, z floats (stride >= 12 and a multiple
+ * of 4; source == target is allowed) and a HOST array of n rsreg_correspondence: index_query names a source record, index_match a
+ * target record, distance is ignored.  An index outside its cloud, a NULL cloud, a cloud of another context or such a stride:
+ * RSREG_ERR_INVALID_ARG, checked on the host before anything is launched.  The list goes to the device once a call and is gathered
+ * into six coordinate planes there.  A pair is FINITE when its six coordinates are.  All calls wait for the stream.
+ * The score of one pair (p the source point, q the target point) under a transform T (m = its rows), float32, every operation rounded
+ * once, no contraction:
+ *   p'.x = ((m0[0] * p.x + m0[1] * p.y) + m0[2] * p.z) + m0[3], p'.y and p'.z alike (transformPointCloud's order);
+ *   dx = p'.x - q.x, ...; d2 = (dx * dx + dy * dy) + dz * dz (L2_Simple, as every search here).
+ * The pair is an INLIER iff it is finite and (double)d2 < threshold * threshold: strictly, as in PCL's countWithinDistance.  NaN
+ * compares false.  threshold negative or NaN: RSREG_ERR_INVALID_ARG.
+ *
+ * rsreg_cloud_count_inliers: counts_out[h] = the inliers of transforms[16 * h .. 16 * h + 15] (column-major 4 x 4, host; the last
+ *   row is not read), h < H.  Any floats are allowed in a transform; a pair whose d2 is NaN or +inf is not an inlier.  H == 0: nothing
+ *   is written.  n == 0: zeros.
+ *
+ * rsreg_cloud_estimate_rigid_svd: TransformationEstimationSVD::estimateRigidTransformation(source, target, correspondences).
+ *   sums_out = the RSREG_NUM_SUMS sums of the finite pairs in the layout above ([0] their number, [1..3] sum p, [4..6] sum q,
+ *   [7 + 3 r + c] sum q[r] * p[c], [16] sum of d2 of the pairs as they stand, d2 the float32 L2_Simple of p and q), in double.  The
+ *   products of two floats are exact in double; the additions run in a fixed tree that is a function of n alone: pair i is term
+ *   i % 64 of wave (i / 64) % 2 of group i / 128; a wave's 64 terms meet pairwise across lane bit 5, 4, 3, 2, 1, 0; a group is wave 0 +
+ *   wave 1; groups g, g + 256, g + 512, .. are added in ascending order into one of 256 strands, strand t meets strands t + 32, + 16, ..,
+ *   + 1 within its 64, and the four 64s are added in order.  A pair that is not finite, or left out, is a term of +0.
+ *   t_out is exactly rsreg_umeyama_from_sums(sums_out).  Fewer than three finite pairs: RSREG_ERR_INVALID_ARG.  Either output may be NULL.
+ *
+ * rsreg_cloud_sac_correspondences: the rejector.  params NULL: rsreg_sac_params_default (PCL's defaults: inlier_threshold 0.05,
+ *   max_iterations 1000, probability 0.99; refit_rounds 0, min_sample_distance 0, seed 0).  probability outside (0, 1),
+ *   min_sample_distance negative or NaN, max_iterations or refit_rounds negative: RSREG_ERR_INVALID_ARG.
+ *   HYPOTHESIS h (h = 0, 1, ...) draws from a counter-based generator, all in uint64 arithmetic modulo 2^64:
+ *     z = seed + (64 * h + draw) * 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     z = z ^ (z >> 31); index(h, draw) = ((z >> 32) * n) >> 32.
+ *   Try t = 0 .. 15 takes the pairs i0, i1, i2 = index(h, 3 t), index(h, 3 t + 1), index(h, 3 t + 2).  The try is GOOD when the three
+ *   indices differ, the three pairs are finite, the three source points are pairwise apart by (double)d2 > min_sample_distance^2 (d2
+ *   their float32 L2_Simple; with 0 this refuses coincident points), and rsreg_umeyama_from_sums succeeds on the three pairs' sums
+ *   (double, each sum 0.0 + the term of i0 + that of i1 + that of i2).  The first good try gives the hypothesis its T; sixteen bad
+ *   tries make it INVALID: its count is 0 and the stopping rule passes over it.
+ *   DEVIATION: PCL's rand()-driven sampler, its isSampleGood threshold derived from the cloud's covariance and its skipped-sample
+ *   counter are not reproduced; min_sample_distance is the explicit stand-in for that threshold.
+ *   count[h] = the inliers of T(h) at inlier_threshold.
+ *   THE STOPPING RULE is PCL's (ransac.hpp), replayed sequentially in double over the counts:
+ *     k = 1; best = -1 (PCL's -INT_MAX: the first valid hypothesis always sets k); for h = 0, 1, .. while h < k and h < max_iterations:
+ *       if h is valid and count[h] > best: best = count[h]; winner = h; w = (double)best / (double)n; q = 1 - w * w * w;
+ *         q = min(max(q, DBL_EPSILON), 1 - DBL_EPSILON); k = log(1 - probability) / log(q).
+ *   The device scores the hypotheses in batches and may score more than the replay consumes; the result does not depend on the batches.
+ *   DEVIATION: PCL's iterations_ > max_iterations_ off-by-one (one more iteration than asked) is not kept.
+ *   The winner is the FIRST h that reached the final best.  NO MODEL when n < 3 or best < 3: found = 0, transform the identity,
+ *   best_hypothesis and sample -1, n_inliers 0, and all n correspondences remain (host_out = the input list) -- what PCL does when
+ *   computeModel fails.
+ *   Otherwise transform = T(winner), the kept pairs are its inliers, and refit_rounds = r refits up to r times: T = the fit of
+ *   rsreg_cloud_estimate_rigid_svd over the current inliers -- the tree of the WHOLE list, every pair that is not an inlier a term of
+ *   +0 in its place -- (a round does not start with fewer than three), then the inliers are
+ *   selected again under T; the rounds end early when no pair's flag changed.  DEVIATION: this is not PCL's refineModel (its
+ *   variance-driven threshold loop is not built).
+ *   host_out: the kept correspondences in input order, their records unchanged.  *n_out = their number; when it exceeds `capacity`
+ *   the first `capacity` are written and the call still returns RSREG_OK (the convention of rsreg_cloud_feature_correspondences).
+ *   Every output is a function of the two clouds, the list and the parameters alone: the counts are integers, the generator is a
+ *   function of (seed, h, draw), every float sum has its order written above.
+ * Not built: SampleConsensusPrerejective, SampleConsensusInitialAlignment, the other CorrespondenceRejector*, refineModel. */
+typedef struct rsreg_sac_params {
+    double inlier_threshold;      /* 0.05 */
+    double probability;           /* 0.99 */
+    double min_sample_distance;   /* 0 */
+    int32_t max_iterations;       /* 1000 */
+    int32_t refit_rounds;         /* 0 */
+    uint64_t seed;                /* 0 */
+} rsreg_sac_params;
+typedef struct rsreg_sac_result {
+    float transform[16];          /* column-major */
+    int32_t found;
+    int32_t best_hypothesis;
+    int32_t sample[3];            /* the winner's three pairs (positions in the input list) */
+    int32_t iterations;           /* hypotheses the replay consumed */
+    uint64_t n_inliers;
+    int32_t refit_rounds_run;
+    int32_t reserved0;
+    double sums[RSREG_NUM_SUMS];  /* the last refit's sums; zeros when there was none */
+} rsreg_sac_result;
+void rsreg_sac_params_default(rsreg_sac_params *p);
+int rsreg_cloud_count_inliers(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const rsreg_correspondence *corr, size_t n,
+                              const float *transforms /* H*16 */, size_t H, double threshold, uint32_t *counts_out /* H */);
+int rsreg_cloud_estimate_rigid_svd(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const rsreg_correspondence *corr, size_t n,
+                                   float t_out[16], double sums_out[RSREG_NUM_SUMS]);
+int rsreg_cloud_sac_correspondences(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const rsreg_correspondence *corr, size_t n,
+                                    const rsreg_sac_params *params /* may be NULL */, rsreg_correspondence *host_out, size_t capacity, size_t *n_out,
+                                    rsreg_sac_result *result /* may be NULL */);
 /* ---- radius search: every record's neighbours within a radius in its own cloud, EXACT.  Record j is a neighbour of the finite
  * record i when j is finite and d2(i, j) < r2, with d2 the float32 L2_Simple squared distance of every search here and
  * r2 = (float)((double)radius * (double)radius): KdTreeFLANN::radiusSearch's cast and the STRICT compare of FLANN's

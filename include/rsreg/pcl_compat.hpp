@@ -1036,6 +1036,97 @@ template <typename PointSource = FPFHSignature33, typename PointTarget = FPFHSig
     std::shared_ptr<Context> ctx_;
 };
 
+// a host cloud or a cloud in HBM as the DeviceCloud a call takes: host clouds are uploaded into a temporary that lives as long as this
+template <typename PointT> struct DeviceInput {
+    DeviceInput(const typename PointCloud<PointT>::Ptr &host, const DeviceCloud<PointT> *dev, const std::shared_ptr<Context> &ctx)
+    {
+        if (!dev) tmp_.reset(new DeviceCloud<PointT>(*host, ctx));
+        cloud_ = dev ? dev : tmp_.get();
+    }
+    rsreg_cloud *handle() const { return cloud_->handle(); }
+  private:
+    std::unique_ptr<DeviceCloud<PointT>> tmp_;
+    const DeviceCloud<PointT> *cloud_ = nullptr;
+};
+
+// ---- pcl::registration::CorrespondenceRejectorSampleConsensus<PointT> on the GPU: RANSAC over a correspondence list, thousands of
+// hypotheses each scored against every pair (csrc/sac_kernels.hpp, rsreg_cloud_sac_correspondences; include/rsreg.h holds the
+// contract and the stated deviations from PCL: the sampler, the stopping rule's off-by-one, the refit).  setRefineModel(true) is ONE
+// refit round over the inliers, not PCL's refineModel.  Engine extras: setSeed, setProbability, setMinSampleDistance, getResult.
+template <typename PointT> class CorrespondenceRejectorSampleConsensus {
+    static_assert(sizeof(PointT) >= 12 && sizeof(PointT) % 4 == 0, "records start with x, y, z floats");
+  public:
+    CorrespondenceRejectorSampleConsensus() { rsreg_sac_params_default(&prm_); std::memset(&res_, 0, sizeof res_); }
+    explicit CorrespondenceRejectorSampleConsensus(std::shared_ptr<Context> ctx) : CorrespondenceRejectorSampleConsensus() { ctx_ = std::move(ctx); }
+    void setInputSource(const typename PointCloud<PointT>::Ptr &cloud) { source_ = cloud, dsource_ = nullptr; }
+    void setInputTarget(const typename PointCloud<PointT>::Ptr &cloud) { target_ = cloud, dtarget_ = nullptr; }
+    void setInputSource(const DeviceCloud<PointT> &cloud) { dsource_ = &cloud, source_.reset(); }   // (the clouds must outlive the calls)
+    void setInputTarget(const DeviceCloud<PointT> &cloud) { dtarget_ = &cloud, target_.reset(); }
+    void setInlierThreshold(double threshold) { prm_.inlier_threshold = threshold; }
+    double getInlierThreshold() const { return prm_.inlier_threshold; }
+    void setMaximumIterations(int n) { prm_.max_iterations = n; }
+    int getMaximumIterations() const { return prm_.max_iterations; }
+    void setRefineModel(bool on) { prm_.refit_rounds = on ? 1 : 0; }
+    void setSeed(uint64_t seed) { prm_.seed = seed; }
+    void setProbability(double p) { prm_.probability = p; }
+    void setMinSampleDistance(double d) { prm_.min_sample_distance = d; }
+    void setInputCorrespondences(const std::shared_ptr<const Correspondences> &corr) { input_ = corr; }
+    void getCorrespondences(Correspondences &out)
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCorrespondences not called");
+        getRemainingCorrespondences(*input_, out);
+    }
+    void getRemainingCorrespondences(const Correspondences &in, Correspondences &out)
+    {
+        if (!source_ && !dsource_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputSource not called");
+        if (!target_ && !dtarget_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputTarget not called");
+        const std::shared_ptr<Context> ctx = dsource_ ? dsource_->context() : dtarget_ ? dtarget_->context() : ctx_ ? ctx_ : Context::Default();
+        const DeviceInput<PointT> s(source_, dsource_, ctx), t(target_, dtarget_, ctx);
+        Correspondences kept(in.size());
+        size_t found = 0;
+        check(rsreg_cloud_sac_correspondences(ctx->get(), s.handle(), t.handle(), reinterpret_cast<const rsreg_correspondence *>(in.data()), in.size(), &prm_,
+                                              reinterpret_cast<rsreg_correspondence *>(kept.data()), kept.size(), &found, &res_), ctx->get());
+        kept.resize(found);
+        out.swap(kept);
+    }
+    Matrix4f getBestTransformation() const
+    {
+        Matrix4f T = Matrix4f::Identity();
+        if (res_.found) std::memcpy(T.data(), res_.transform, sizeof res_.transform);
+        return T;
+    }
+    const rsreg_sac_result &getResult() const { return res_; }
+  private:
+    rsreg_sac_params prm_;
+    rsreg_sac_result res_;
+    std::shared_ptr<const Correspondences> input_;
+    typename PointCloud<PointT>::Ptr source_, target_;
+    const DeviceCloud<PointT> *dsource_ = nullptr, *dtarget_ = nullptr;
+    std::shared_ptr<Context> ctx_;
+};
+
+// ---- pcl::registration::TransformationEstimationSVD<PointSource, PointTarget>::estimateRigidTransformation with a
+// correspondence list (rsreg_cloud_estimate_rigid_svd): the fit over the finite pairs, summed in double in a fixed order on the GPU
+template <typename PointSource, typename PointTarget = PointSource> class TransformationEstimationSVD {
+  public:
+    TransformationEstimationSVD() = default;
+    explicit TransformationEstimationSVD(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {}
+    void estimateRigidTransformation(const PointCloud<PointSource> &source, const PointCloud<PointTarget> &target, const Correspondences &corr, Matrix4f &T) const
+    {
+        const std::shared_ptr<Context> ctx = ctx_ ? ctx_ : Context::Default();
+        const DeviceCloud<PointSource> s(source, ctx);
+        const DeviceCloud<PointTarget> t(target, ctx);
+        estimateRigidTransformation(s, t, corr, T);
+    }
+    void estimateRigidTransformation(const DeviceCloud<PointSource> &source, const DeviceCloud<PointTarget> &target, const Correspondences &corr, Matrix4f &T) const
+    {
+        check(rsreg_cloud_estimate_rigid_svd(source.context()->get(), source.handle(), target.handle(), reinterpret_cast<const rsreg_correspondence *>(corr.data()),
+                                             corr.size(), T.data(), nullptr), source.context()->get());
+    }
+  private:
+    std::shared_ptr<Context> ctx_;
+};
+
 }  // namespace registration
 
 // ---- pcl::IntegralImageNormalEstimation<PointInT, PointOutT> for organized clouds (csrc/iinormals_kernels.hpp,

@@ -341,6 +341,41 @@ class DeviceCloud:
                                                               C.byref(found)), self.ctx.h)
         return out[:found.value]
 
+    def count_inliers(self, target, corr, transforms, threshold):
+        """uint32 per transform: the pairs of `corr` (a CORRESPONDENCE_DTYPE array; index_query a record of this cloud, index_match
+        one of `target`) within `threshold` of their match once the transform has moved the source point
+        (rsreg_cloud_count_inliers; include/rsreg.h holds the arithmetic).  transforms: (H, 4, 4), or one 4 x 4."""
+        corr = np.ascontiguousarray(corr, CORRESPONDENCE_DTYPE)
+        t = np.asarray(transforms, np.float32)
+        t = t.reshape(-1, 4, 4)
+        packed = np.ascontiguousarray(t.transpose(0, 2, 1))   # column-major, one after the other
+        out = np.zeros(len(t), np.uint32)
+        _l.check(_l.lib().rsreg_cloud_count_inliers(self.ctx.h, self.h, target.h, corr.ctypes.data, len(corr), packed.ctypes.data, len(t), float(threshold),
+                                                    out.ctypes.data), self.ctx.h)
+        return out
+
+    def estimate_rigid_svd(self, target, corr):
+        """(T 4 x 4 float32, the 17 sums float64): TransformationEstimationSVD over the finite pairs of `corr`
+        (rsreg_cloud_estimate_rigid_svd); T is umeyama_from_sums of the sums."""
+        corr = np.ascontiguousarray(corr, CORRESPONDENCE_DTYPE)
+        t, sums = np.zeros(16, np.float32), np.zeros(_l.NUM_SUMS, np.float64)
+        _l.check(_l.lib().rsreg_cloud_estimate_rigid_svd(self.ctx.h, self.h, target.h, corr.ctypes.data, len(corr), t.ctypes.data, sums.ctypes.data), self.ctx.h)
+        return _rowmajor(t), sums
+
+    def sac_correspondences(self, target, corr, capacity=None, **params):
+        """pcl::registration::CorrespondenceRejectorSampleConsensus over `corr` (rsreg_cloud_sac_correspondences): (the kept
+        correspondences in input order, SacResult).  params: inlier_threshold, max_iterations, probability, refit_rounds,
+        min_sample_distance, seed (sac_params()).  capacity: room for so many records (None: all); the result's n_out is the
+        number kept, however many were written."""
+        corr = np.ascontiguousarray(corr, CORRESPONDENCE_DTYPE)
+        p = sac_params(**params)
+        room = len(corr) if capacity is None else int(capacity)
+        out = np.zeros(room, CORRESPONDENCE_DTYPE)
+        found, res = C.c_size_t(0), _l.SacResult()
+        _l.check(_l.lib().rsreg_cloud_sac_correspondences(self.ctx.h, self.h, target.h, corr.ctypes.data, len(corr), C.byref(p), out.ctypes.data, room,
+                                                          C.byref(found), C.byref(res)), self.ctx.h)
+        return out[:min(found.value, room)], SacResult(res, found.value)
+
     def radius_count(self, radius):
         """radiusSearch of every record in its own cloud, counted (rsreg_cloud_radius_count, exact): uint32 per record, its
         neighbours with float32 d2 < (float)(radius * radius) -- strictly, itself and exact copies among them; 0 for a non-finite
@@ -1430,6 +1465,118 @@ class CorrespondenceEstimation:
 
     def determineReciprocalCorrespondences(self, max_distance=sys.float_info.max):
         return self._run(max_distance, True)
+
+
+def sac_params(**kw):
+    """rsreg_sac_params: PCL's defaults (rsreg_sac_params_default) with the given fields replaced."""
+    p = _l.SacParams()
+    _l.lib().rsreg_sac_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(p._fields_):
+            raise TypeError("rsreg_sac_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class SacResult:
+    """rsreg_sac_result: transform (4 x 4), found, best_hypothesis, sample, iterations, n_inliers, refit_rounds_run, sums; n_out: the
+    correspondences kept (which may exceed the capacity that was given)."""
+
+    def __init__(self, r, n_out):
+        self.transform = _rowmajor(list(r.transform))
+        self.found, self.best_hypothesis, self.sample = bool(r.found), int(r.best_hypothesis), tuple(r.sample)
+        self.iterations, self.n_inliers, self.refit_rounds_run = int(r.iterations), int(r.n_inliers), int(r.refit_rounds_run)
+        self.sums = np.array(list(r.sums), np.float64)
+        self.n_out = int(n_out)
+
+
+def _as_device_pair(src, tgt, ctx):
+    """(source, target, made): both as DeviceClouds of one context; made: the temporaries uploaded for host clouds"""
+    ctx = next((c.ctx for c in (src, tgt) if isinstance(c, DeviceCloud)), None) or ctx or default_context()
+    pair, made = [], []
+    for c in (src, tgt):
+        if not isinstance(c, DeviceCloud):
+            c = DeviceCloud(c, ctx=ctx)
+            made.append(c)
+        pair.append(c)
+    return pair[0], pair[1], made
+
+
+class CorrespondenceRejectorSampleConsensus:
+    """pcl::registration::CorrespondenceRejectorSampleConsensus on the GPU: RANSAC over a correspondence list, thousands of
+    hypotheses each scored against every pair (csrc/sac_kernels.hpp, rsreg_cloud_sac_correspondences; include/rsreg.h holds the
+    contract and the stated deviations from PCL).  setInputSource / setInputTarget take a DeviceCloud or a host PointCloud (uploaded
+    into a temporary).  setRefineModel(True) is one refit round over the inliers, not PCL's refineModel."""
+
+    def __init__(self, ctx=None):
+        self._src = self._tgt = self._corr = None
+        self.ctx = ctx
+        self.params = sac_params()
+        self._result = None
+
+    def setInputSource(self, cloud):
+        self._src = cloud
+
+    def setInputTarget(self, cloud):
+        self._tgt = cloud
+
+    def setInlierThreshold(self, threshold):
+        self.params.inlier_threshold = float(threshold)
+
+    def getInlierThreshold(self):
+        return self.params.inlier_threshold
+
+    def setMaximumIterations(self, n):
+        self.params.max_iterations = int(n)
+
+    def getMaximumIterations(self):
+        return self.params.max_iterations
+
+    def setRefineModel(self, on):
+        self.params.refit_rounds = 1 if on else 0
+
+    def setInputCorrespondences(self, corr):
+        self._corr = np.ascontiguousarray(corr, CORRESPONDENCE_DTYPE)
+
+    def getRemainingCorrespondences(self, corr):
+        """The correspondences of `corr` that RANSAC keeps, in input order; getBestTransformation() is theirs afterwards."""
+        if self._src is None or self._tgt is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputSource / setInputTarget not called")
+        src, tgt, made = _as_device_pair(self._src, self._tgt, self.ctx)
+        try:
+            kept, self._result = src.sac_correspondences(tgt, corr, **{k: getattr(self.params, k) for k, _ in self.params._fields_})
+        finally:
+            for c in made:
+                c.close()
+        return kept
+
+    def getCorrespondences(self):
+        if self._corr is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCorrespondences not called")
+        return self.getRemainingCorrespondences(self._corr)
+
+    def getBestTransformation(self):
+        return np.eye(4, dtype=np.float32) if self._result is None else self._result.transform
+
+    @property
+    def result(self):
+        return self._result
+
+
+class TransformationEstimationSVD:
+    """pcl::registration::TransformationEstimationSVD with a correspondence list (rsreg_cloud_estimate_rigid_svd): the fit over
+    the finite pairs, the sums in double in a fixed order on the GPU."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx
+
+    def estimateRigidTransformation(self, source, target, correspondences):
+        src, tgt, made = _as_device_pair(source, target, self.ctx)
+        try:
+            return src.estimate_rigid_svd(tgt, correspondences)[0]
+        finally:
+            for c in made:
+                c.close()
 
 
 class IntegralImageNormalEstimation:

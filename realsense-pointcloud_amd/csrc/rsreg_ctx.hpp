@@ -221,6 +221,22 @@ struct FeatureScratch {
     PinnedBuf host;                // where the target's count, or the number found, lands
 };
 
+// Scratch of RANSAC over a correspondence list (sac.hip, sac_kernels.hpp), per pair of the list and per hypothesis of a launch; not part of an index
+struct SacScratch {
+    PinnedBuf h_corr;              // the caller's 12-byte correspondences, staged for the link ...
+    DevBuf d_corr;                 // ... and in HBM
+    DevBuf d_planes;               // float, six planes of (pairs rounded up to whole tiles): source x y z, target x y z; NaN where a pair is not finite
+    DevBuf d_table;                // 12 floats per hypothesis of a launch: the rows of its transform
+    DevBuf d_sample;               // 4 int32 per hypothesis of a launch: its three pairs and the try that gave them
+    DevBuf d_counts;               // uint32 per hypothesis of a launch: its inliers
+    DevBuf d_flags[2];             // uint32 per pair: inlier under the current transform; the two take turns over the refit rounds
+    DevBuf d_pos, d_scan;          // the kept pairs' positions, the prefix sum's scratch
+    DevBuf d_out;                  // the kept correspondences, before they go home
+    DevBuf d_partials, d_sums;     // the 17 sums: a slab per workgroup, the totals
+    DevBuf d_word;                 // 32 bytes: flags set, flags changed (uint32 each); correspondences kept (uint64 at byte 8)
+    PinnedBuf host;                // counts, samples, rows, sums and words on their way home; a caller's transforms on their way out
+};
+
 // Scratch of IntegralImageNormalEstimation (iinormals.hip), per pixel of the organized frame it is given
 struct IinScratch {
     DevBuf d_dist0, d_dist1, d_dist2;   // float: the distance map as set up, after the forward pass, after the backward pass
@@ -468,6 +484,9 @@ struct rsreg_ctx {
 
     // ---- feature matching (features.hip): scratch of its own
     rsreg::FeatureScratch feat;
+
+    // ---- pose from correspondences (sac.hip): scratch of its own
+    rsreg::SacScratch sac;
 
     // ---- IntegralImageNormalEstimation (iinormals.hip)
     rsreg::IinScratch iin;
