@@ -693,7 +693,9 @@ int rsreg_cloud_feature_correspondences(rsreg_ctx *ctx, const rsreg_cloud *sourc
  *   p'.x = ((m0[0] * p.x + m0[1] * p.y) + m0[2] * p.z) + m0[3], p'.y and p'.z alike (transformPointCloud's order);
  *   dx = p'.x - q.x, ...; d2 = (dx * dx + dy * dy) + dz * dz (L2_Simple, as every search here).
  * The pair is an INLIER iff it is finite and (double)d2 < threshold * threshold: strictly, as in PCL's countWithinDistance.  NaN
- * compares false.  threshold negative or NaN: RSREG_ERR_INVALID_ARG.
+ * compares false.  threshold negative or NaN: RSREG_ERR_INVALID_ARG.  Every float32 operation is IEEE: denormals are kept, an
+ * overflow is +-inf and inf - inf is NaN.  threshold * threshold is a double product: when it is +inf or above FLT_MAX every finite
+ * pair with a finite d2 is an inlier, when it is at most 2^-149 only d2 == 0 is, and when it is 0 (a threshold below 1.5e-162) none.
  *
  * rsreg_cloud_count_inliers: counts_out[h] = the inliers of transforms[16 * h .. 16 * h + 15] (column-major 4 x 4, host; the last
  *   row is not read), h < H.  Any floats are allowed in a transform; a pair whose d2 is NaN or +inf is not an inlier.  H == 0: nothing
@@ -719,6 +721,9 @@ int rsreg_cloud_feature_correspondences(rsreg_ctx *ctx, const rsreg_cloud *sourc
  *   their float32 L2_Simple; with 0 this refuses coincident points), and rsreg_umeyama_from_sums succeeds on the three pairs' sums
  *   (double, each sum 0.0 + the term of i0 + that of i1 + that of i2).  The first good try gives the hypothesis its T; sixteen bad
  *   tries make it INVALID: its count is 0 and the stopping rule passes over it.
+ *   The d2 of two source points is a float32 like any other: a cloud whose squared point distances underflow float32 (points less
+ *   than about 2^-75 apart, denormal clouds) has no valid sample at min_sample_distance 0 and the call reports NO MODEL after one
+ *   iteration; a d2 that overflowed to +inf is above the square of every min_sample_distance whose own square is finite.
  *   DEVIATION: PCL's rand()-driven sampler, its isSampleGood threshold derived from the cloud's covariance and its skipped-sample
  *   counter are not reproduced; min_sample_distance is the explicit stand-in for that threshold.
  *   count[h] = the inliers of T(h) at inlier_threshold.

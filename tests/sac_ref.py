@@ -3,6 +3,8 @@ hypothesis's three-pair sums in float64 in the contract's order with the solve t
 which is not code under test), the scores in numpy.float32 in the contract's order, and the stopping rule replayed with math.log.
 
 Nothing here knows about batches, tiles or slices: a hypothesis is a function of (seed, h), a count a function of (T, pairs).
+Trace (at the end) runs the float32 operations once more and classifies every intermediate: tests/test_sac_edges_cpu.py reads from it
+in which regime of the float32 range a scaled case lies.
 """
 import math
 
@@ -142,7 +144,7 @@ def sac(api, src_xyz, tgt_xyz, corr, inlier_threshold=0.05, max_iterations=1000,
     else:
         counts, valid = counts
     best, winner, r.iterations, r.ks = replay(counts, n, probability, max_iterations, valid=valid)
-    r.counts, r.valid = counts, valid
+    r.counts, r.valid, r.best = counts, valid, best
     if best < 3:
         return r
     T, ids, _ = hypothesis(api, P, Q, finite, seed, winner, min_sample_distance)
@@ -190,3 +192,47 @@ def exact_terms(P, Q, finite):
     t[16] = l2_simple(P, Q).astype(np.float64)
     t[:, ~finite] = 0.0
     return t
+
+
+class Trace:
+    """The float32 operations of the contract once more, with every result classified: `inf` counts the results that overflowed
+    (+-inf from finite operands), `nan` the NaNs, `denormal` the results that are non-zero denormals, `underflow` the products that
+    are 0 although neither factor is.  (A float32 sum or difference cannot underflow: a denormal result of an addition is exact.)
+    A run in which all four stay 0 commutes with a scaling of every input by a power of two."""
+    FLT_MIN = np.float32(np.finfo(np.float32).tiny)
+
+    def __init__(self):
+        self.inf = self.nan = self.denormal = self.underflow = 0
+
+    def _note(self, r, a, b):
+        self.inf += int((np.isinf(r) & np.isfinite(a) & np.isfinite(b)).sum())
+        self.nan += int(np.isnan(r).sum())
+        self.denormal += int(((r != 0) & (np.abs(r) < self.FLT_MIN)).sum())
+        return r
+
+    def mul(self, a, b):
+        with np.errstate(all="ignore"):
+            a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+            r = (a * b).astype(np.float32)
+            self.underflow += int(((r == 0) & (a != 0) & (b != 0)).sum())
+        return self._note(r, a, b)
+
+    def add(self, a, b, sign=1):
+        with np.errstate(all="ignore"):
+            a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+            r = (a + b if sign > 0 else a - b).astype(np.float32)
+        return self._note(r, a, b)
+
+    def l2_simple(self, a, b):
+        """l2_simple() of two (.., 3) arrays, traced"""
+        d = [self.add(a[..., c], b[..., c], -1) for c in range(3)]
+        return self.add(self.add(self.mul(d[0], d[0]), self.mul(d[1], d[1])), self.mul(d[2], d[2]))
+
+    def score(self, T, P, Q):
+        """the float32 d2 of every pair under ONE transform T, traced: what within() compares with the threshold"""
+        m = np.asarray(T, np.float32).reshape(4, 4)
+        moved = []
+        for r in range(3):
+            a = self.add(self.mul(m[r, 0], P[:, 0]), self.mul(m[r, 1], P[:, 1]))
+            moved.append(self.add(self.add(a, self.mul(m[r, 2], P[:, 2])), m[r, 3]))
+        return self.l2_simple(np.stack(moved, axis=1), Q)
