@@ -745,7 +745,8 @@ int rsreg_cloud_feature_correspondences(rsreg_ctx *ctx, const rsreg_cloud *sourc
  *   the first `capacity` are written and the call still returns RSREG_OK (the convention of rsreg_cloud_feature_correspondences).
  *   Every output is a function of the two clouds, the list and the parameters alone: the counts are integers, the generator is a
  *   function of (seed, h, draw), every float sum has its order written above.
- * Not built: SampleConsensusPrerejective, SampleConsensusInitialAlignment, the other CorrespondenceRejector*, refineModel. */
+ * Not built: SampleConsensusInitialAlignment, the other CorrespondenceRejector*, refineModel.  (SampleConsensusPrerejective: the
+ * section after this one.) */
 typedef struct rsreg_sac_params {
     double inlier_threshold;      /* 0.05 */
     double probability;           /* 0.99 */
@@ -773,6 +774,99 @@ int rsreg_cloud_estimate_rigid_svd(rsreg_ctx *ctx, const rsreg_cloud *source, co
 int rsreg_cloud_sac_correspondences(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const rsreg_correspondence *corr, size_t n,
                                     const rsreg_sac_params *params /* may be NULL */, rsreg_correspondence *host_out, size_t capacity, size_t *n_out,
                                     rsreg_sac_result *result /* may be NULL */);
+/* ---- pose from descriptor neighbours: pcl::SampleConsensusPrerejective -- three source records, each paired with a random one of
+ * its k nearest descriptors, a cheap edge-length test (pcl::registration::CorrespondenceRejectorPoly), and the surviving poses scored
+ * against the WHOLE target cloud by a nearest-point search.  PCL 1.9.1 registration/impl/sample_consensus_prerejective.hpp and
+ * correspondence_rejection_poly.hpp, recalled; PCL is not available to check against, so what follows IS the contract, and where it
+ * leaves PCL it says DEVIATION.
+ * Inputs of both entry points: two device clouds of the context whose records start with x, y, z floats (stride >= 12 and a multiple
+ * of 4; source == target is allowed).  A NULL cloud, a cloud of another context or such a stride: RSREG_ERR_INVALID_ARG.  Both calls
+ * index the target once (a round trip to the host for its box) and wait for the stream.
+ *
+ * THE SCORE of a transform T (m = its rows) over the source: for every source record i whose x, y, z are finite,
+ *   p' = the float32 transform of the pair score above: p'.x = ((m0[0] * p.x + m0[1] * p.y) + m0[2] * p.z) + m0[3], p'.y and p'.z
+ *   alike (transformPointCloud's order), every operation rounded once, no contraction;
+ *   if p' is finite, d2 = the EXACT nearest float32 L2_Simple squared distance from p' to the finite target records, d2 = the
+ *   minimum over the target records q of (dx * dx + dy * dy) + dz * dz with dx = p'.x - q.x, ... (the search of getFitnessScore);
+ *   the record is an INLIER iff (double)d2 < max_range * max_range: strictly, PCL's getFitness.  The product is a double: when it is
+ *   +inf or above FLT_MAX every record with a finite d2 is an inlier, when it is at most 2^-149 only d2 == 0 is, and when it is 0 none.
+ *   A record that is not finite, a p' that is not finite, a d2 that is +inf or NaN, an empty or all-non-finite target: no inlier.
+ * count = the number of inliers.  sum = the sum of the inliers' d2 in double, in a tree that is a function of the source's record
+ * count ns alone: record i is term i % 64 of wave (i / 64) % 2 of group i / 128; a record that is not an inlier is a term of +0.0,
+ * and so is every term behind record ns - 1 of the last group; a wave's 64 terms meet pairwise across lane bit 5, 4, 3, 2, 1, 0
+ * (term t + term t + 32, then those 32 sums t + t + 16, ..); a group is wave 0 + wave 1; the groups are added in ascending order,
+ * starting from group 0's value: ((g0 + g1) + g2) + ...  No float atomics anywhere: the same clouds, transforms and range give the
+ * same bytes for any batch, slice, launch order or context.
+ *
+ * rsreg_cloud_score_transforms: the scoring stage on its own, the counterpart of rsreg_cloud_count_inliers with a search in place of
+ *   a list.  counts_out[h] and sums_out[h] = the count and the sum of transforms[16 * h .. 16 * h + 15] (column-major 4 x 4, host; the
+ *   last row is not read), h < H; either may be NULL.  Any floats are allowed in a transform.  H == 0: nothing is written.  An empty
+ *   source, an empty or all-non-finite target: zeros.  max_range negative or NaN: RSREG_ERR_INVALID_ARG.
+ *
+ * rsreg_cloud_prerejective: neighbor_index is a HOST table of ns rows of k int32, exactly what
+ *   rsreg_cloud_feature_knn(source_features, target_features, k) wrote: row i holds the k target records nearest to source record i in
+ *   descriptor space; a row of -1 makes record i INELIGIBLE.  1 <= k <= 16.  An entry >= nt, a negative one other than -1, or a row
+ *   that is -1 only in part: RSREG_ERR_INVALID_ARG, checked on the host before anything is launched.  The table (ns * k * 4 bytes) goes
+ *   to the device once a call; a device-resident table is not built.
+ *   params NULL: rsreg_prerej_params_default (similarity_threshold 0.9, inlier_fraction 0, select_by_inliers 0, seed 0; max_iterations
+ *   10 and max_correspondence_distance sqrt(DBL_MAX), pcl::Registration's own defaults).  max_iterations negative,
+ *   similarity_threshold outside [0, 1) or NaN, inlier_fraction outside [0, 1] or NaN, max_correspondence_distance negative or NaN:
+ *   RSREG_ERR_INVALID_ARG.  DEVIATION: nr_samples is 3 and nothing else (setNumberOfSamples is not built).
+ *   HYPOTHESIS h, h = 0 .. max_iterations - 1, makes ONE try (PCL's iteration: a rejected sample spends its iteration), with the
+ *   generator of the section above, index(h, draw, n) = ((z >> 32) * n) >> 32 over z = the splitmix64 finaliser of
+ *   seed + (64 * h + draw) * 0x9E3779B97F4A7C15: s_d = index(h, d, ns) for d = 0, 1, 2 are its source records, and
+ *   t_d = neighbor_index[s_d * k + index(h, 3 + d, k)] their target records.
+ *   h is VALID when s_0, s_1, s_2 differ, each is eligible, all six points are finite, the polygon test passes and
+ *   rsreg_umeyama_from_sums succeeds on the three pairs' sums (double, each sum 0.0 + the term of pair 0 + that of pair 1 + that of
+ *   pair 2, as the rejector above forms them); T(h) is that solve's result.
+ *   THE POLYGON TEST, float32: for each of the three edges (a, b), ds = the L2_Simple squared distance of source points a and b, dt
+ *   that of their target points; sim = ds < dt ? ds / dt : dt / ds, one IEEE float32 division; the edge passes iff
+ *   sim >= similarity_threshold * similarity_threshold, the product rounded to float32.  A NaN sim, which 0 / 0 gives, fails: coincident
+ *   points are refused without a further rule.
+ *   DEVIATION: PCL's rand()-driven sampler is not reproduced.
+ *   A valid hypothesis is scored as above at max_range = max_correspondence_distance; an invalid one is never searched.
+ *   SELECTION, replayed on the host in hypothesis order: h QUALIFIES when it is valid, count >= 1 and
+ *   (double)count / (double)ns >= inlier_fraction, ns EVERY source record (input_->size()); error = sum / count in double.
+ *   select_by_inliers == 0: the winner is the first h with the strictly lowest error among the qualifying (PCL's error < lowest_error).
+ *   DEVIATION: PCL keeps the error in float and accumulates the fitness in float in point order.
+ *   select_by_inliers == 1, an EXTENSION: the winner is the qualifying h with the highest count, then the lowest error, then the lowest
+ *   h.  PCL's rule with inlier_fraction 0 crowns any three-point pose whose samples happen to sit on target points (a count of 3
+ *   and an error near 0 beats every better-supported pose); this rule is what asks for support first.
+ *   No early stop (PCL 1.9.1 has none): every h < max_iterations is generated, and the result does not depend on the batches.
+ *   result: found = 0 when no hypothesis qualifies (also: an empty cloud, max_iterations 0): transform the identity, n_inliers 0,
+ *   fitness 0, best_hypothesis, sample and match -1, *n_out = 0.  Otherwise transform = T(winner), sample / match its s_d / t_d,
+ *   n_inliers its count, fitness its error.  n_valid: the valid hypotheses, i.e. the ones that were scored.
+ *   inliers_out: the winner's inlier source records in ascending order.  *n_out = their number; when it exceeds `capacity` the first
+ *   `capacity` are written and the call still returns RSREG_OK (the convention of rsreg_cloud_feature_correspondences).  inliers_out
+ *   may be NULL when capacity is 0.
+ *   Every output is a function of the two clouds, the table and the parameters alone.
+ * Not built: SampleConsensusInitialAlignment, nr_samples other than 3, a device-resident neighbour table, a refit over the winner's
+ * inliers. */
+typedef struct rsreg_prerej_params {
+    double max_correspondence_distance;   /* sqrt(DBL_MAX) */
+    double inlier_fraction;               /* 0 */
+    float similarity_threshold;           /* 0.9 */
+    int32_t max_iterations;               /* 10 */
+    int32_t select_by_inliers;            /* 0: PCL's rule */
+    int32_t reserved0;
+    uint64_t seed;                        /* 0 */
+} rsreg_prerej_params;
+typedef struct rsreg_prerej_result {
+    float transform[16];                  /* column-major */
+    int32_t found;
+    int32_t best_hypothesis;
+    int32_t sample[3];                    /* the winner's three source records */
+    int32_t match[3];                     /* ... and their target records */
+    uint64_t n_valid;                     /* hypotheses that were scored */
+    uint64_t n_inliers;
+    double fitness;                       /* the winner's error: sum / count */
+} rsreg_prerej_result;
+void rsreg_prerej_params_default(rsreg_prerej_params *p);
+int rsreg_cloud_score_transforms(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const float *transforms /* H*16 */, size_t H,
+                                 double max_range, uint32_t *counts_out /* H, may be NULL */, double *sums_out /* H, may be NULL */);
+int rsreg_cloud_prerejective(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const int32_t *neighbor_index /* ns*k */, int k,
+                             const rsreg_prerej_params *params /* may be NULL */, int32_t *inliers_out, size_t capacity, size_t *n_out,
+                             rsreg_prerej_result *result /* may be NULL */);
 /* ---- radius search: every record's neighbours within a radius in its own cloud, EXACT.  Record j is a neighbour of the finite
  * record i when j is finite and d2(i, j) < r2, with d2 the float32 L2_Simple squared distance of every search here and
  * r2 = (float)((double)radius * (double)radius): KdTreeFLANN::radiusSearch's cast and the STRICT compare of FLANN's

@@ -1188,6 +1188,119 @@ template <typename PointT> void transformPointCloud(const DeviceCloud<PointT> &i
     check(rsreg_cloud_transform(in.context()->get(), in.handle(), T.data(), out.handle()), in.context()->get());
 }
 
+// ---- pcl::SampleConsensusPrerejective<PointSource, PointTarget, FeatureT> on the GPU: poses from three source records and a random
+// one of each one's k nearest descriptors (setCorrespondenceRandomness), pre-rejected on their edge lengths, the survivors scored
+// against the whole target cloud by an exact nearest-point search (csrc/prerej_kernels.hpp, rsreg_cloud_prerejective; include/rsreg.h
+// holds the contract and the stated deviations from PCL: the sampler, the double error, three samples and nothing else).  align()
+// makes two calls, rsreg_cloud_feature_knn and rsreg_cloud_prerejective, and writes the source moved by the final transformation.
+// Engine extras: setSeed, setSelectByInliers (the winner by support first, not PCL's lowest error), getResult, the device overloads.
+template <typename PointSource, typename PointTarget = PointSource, typename FeatureT = FPFHSignature33> class SampleConsensusPrerejective {
+    static_assert(sizeof(PointSource) >= 12 && sizeof(PointSource) % 4 == 0 && sizeof(PointTarget) >= 12 && sizeof(PointTarget) % 4 == 0,
+                  "records start with x, y, z floats");
+    static_assert(sizeof(FeatureT) >= 132 && sizeof(FeatureT) % 4 == 0, "descriptor records start with 33 floats");
+  public:
+    SampleConsensusPrerejective() { rsreg_prerej_params_default(&prm_); reset(); }
+    explicit SampleConsensusPrerejective(std::shared_ptr<Context> ctx) : SampleConsensusPrerejective() { ctx_ = std::move(ctx); }
+    void setInputSource(const typename PointCloud<PointSource>::Ptr &cloud) { source_ = cloud, dsource_ = nullptr; }
+    void setInputTarget(const typename PointCloud<PointTarget>::Ptr &cloud) { target_ = cloud, dtarget_ = nullptr; }
+    void setSourceFeatures(const typename PointCloud<FeatureT>::Ptr &features) { sfeat_ = features, dsfeat_ = nullptr; }
+    void setTargetFeatures(const typename PointCloud<FeatureT>::Ptr &features) { tfeat_ = features, dtfeat_ = nullptr; }
+    void setInputSource(const DeviceCloud<PointSource> &cloud) { dsource_ = &cloud, source_.reset(); }   // (the clouds must outlive the calls)
+    void setInputTarget(const DeviceCloud<PointTarget> &cloud) { dtarget_ = &cloud, target_.reset(); }
+    void setSourceFeatures(const DeviceCloud<FeatureT> &features) { dsfeat_ = &features, sfeat_.reset(); }
+    void setTargetFeatures(const DeviceCloud<FeatureT> &features) { dtfeat_ = &features, tfeat_.reset(); }
+    void setMaximumIterations(int n) { prm_.max_iterations = n; }
+    int getMaximumIterations() const { return prm_.max_iterations; }
+    void setNumberOfSamples(int n)
+    {
+        if (n != 3) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: SampleConsensusPrerejective: only three samples are built");
+    }
+    int getNumberOfSamples() const { return 3; }
+    void setCorrespondenceRandomness(int k) { k_ = k; }
+    int getCorrespondenceRandomness() const { return k_; }
+    void setSimilarityThreshold(float t) { prm_.similarity_threshold = t; }
+    float getSimilarityThreshold() const { return prm_.similarity_threshold; }
+    void setMaxCorrespondenceDistance(double d) { prm_.max_correspondence_distance = d; }
+    double getMaxCorrespondenceDistance() const { return prm_.max_correspondence_distance; }
+    void setInlierFraction(float f) { prm_.inlier_fraction = f; }
+    float getInlierFraction() const { return (float)prm_.inlier_fraction; }
+    void setSeed(uint64_t seed) { prm_.seed = seed; }
+    void setSelectByInliers(bool on) { prm_.select_by_inliers = on ? 1 : 0; }
+    void align(PointCloud<PointSource> &output)
+    {
+        const std::shared_ptr<Context> ctx = context();
+        run(ctx);
+        if (source_) {
+            transformPointCloud(*source_, output, getFinalTransformation(), ctx);
+        } else {
+            DeviceCloud<PointSource> moved(ctx);
+            transformPointCloud(*dsource_, moved, getFinalTransformation());
+            moved.download(output);
+        }
+    }
+    void align(DeviceCloud<PointSource> &output)
+    {
+        if (!dsource_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputSource (device cloud) not called");
+        run(context());
+        transformPointCloud(*dsource_, output, getFinalTransformation());
+    }
+    bool hasConverged() const { return res_.found != 0; }
+    Matrix4f getFinalTransformation() const
+    {
+        Matrix4f T = Matrix4f::Identity();
+        if (res_.found) std::memcpy(T.data(), res_.transform, sizeof res_.transform);
+        return T;
+    }
+    const std::vector<int> &getInliers() const { return inliers_; }
+    double getFitnessScore() const { return res_.fitness; }   // the winner's error: the sum of its inliers' squared distances / their number
+    const rsreg_prerej_result &getResult() const { return res_; }
+  private:
+    void reset()
+    {
+        std::memset(&res_, 0, sizeof res_);
+        res_.best_hypothesis = -1;
+        inliers_.clear();
+    }
+    std::shared_ptr<Context> context() const
+    {
+        return dsource_ ? dsource_->context() : dtarget_ ? dtarget_->context() : dsfeat_ ? dsfeat_->context() : dtfeat_ ? dtfeat_->context()
+             : ctx_ ? ctx_ : Context::Default();
+    }
+    void run(const std::shared_ptr<Context> &ctx)
+    {
+        if (!source_ && !dsource_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputSource not called");
+        if (!target_ && !dtarget_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputTarget not called");
+        if (!sfeat_ && !dsfeat_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setSourceFeatures not called");
+        if (!tfeat_ && !dtfeat_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setTargetFeatures not called");
+        reset();
+        const registration::DeviceInput<PointSource> s(source_, dsource_, ctx);
+        const registration::DeviceInput<PointTarget> t(target_, dtarget_, ctx);
+        const registration::DeviceInput<FeatureT> fs(sfeat_, dsfeat_, ctx), ft(tfeat_, dtfeat_, ctx);
+        size_t n = 0, nf = 0, found = 0;
+        check(rsreg_cloud_info(s.handle(), &n, nullptr, nullptr, nullptr, nullptr), ctx->get());
+        check(rsreg_cloud_info(fs.handle(), &nf, nullptr, nullptr, nullptr, nullptr), ctx->get());
+        if (n != nf) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: the source and its features differ in size");
+        if (k_ < 1 || k_ > 16) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setCorrespondenceRandomness needs 1 .. 16");
+        std::vector<int32_t> nbr(n * (size_t)k_, -1);
+        check(rsreg_cloud_feature_knn(ctx->get(), fs.handle(), ft.handle(), k_, nbr.data(), nullptr), ctx->get());
+        std::vector<int> in(n);
+        check(rsreg_cloud_prerejective(ctx->get(), s.handle(), t.handle(), nbr.data(), k_, &prm_, in.data(), in.size(), &found, &res_), ctx->get());
+        in.resize(found);
+        inliers_.swap(in);
+    }
+    rsreg_prerej_params prm_;
+    rsreg_prerej_result res_;
+    int k_ = 2;                            // PCL's default
+    std::vector<int> inliers_;
+    typename PointCloud<PointSource>::Ptr source_;
+    typename PointCloud<PointTarget>::Ptr target_;
+    typename PointCloud<FeatureT>::Ptr sfeat_, tfeat_;
+    const DeviceCloud<PointSource> *dsource_ = nullptr;
+    const DeviceCloud<PointTarget> *dtarget_ = nullptr;
+    const DeviceCloud<FeatureT> *dsfeat_ = nullptr, *dtfeat_ = nullptr;
+    std::shared_ptr<Context> ctx_;
+};
+
 // ---- extract_edge_features (src/edge_extractor.hpp:7-39): the RGB-Canny edge points of an organized cloud
 inline std::shared_ptr<PointCloud<PointXYZRGB>> extract_edge_features(const std::shared_ptr<PointCloud<PointXYZRGB>> &cloud,
                                                                       const std::shared_ptr<Context> &ctx = Context::Default())

@@ -376,6 +376,35 @@ class DeviceCloud:
                                                           C.byref(found), C.byref(res)), self.ctx.h)
         return out[:min(found.value, room)], SacResult(res, found.value)
 
+    def score_transforms(self, target, transforms, max_range):
+        """(counts uint32, sums float64), one of each per transform: the records of this cloud whose exact nearest record of `target`
+        lies within `max_range` once the transform has moved them, and the sum of those squared distances
+        (rsreg_cloud_score_transforms; include/rsreg.h holds the arithmetic and the order of the sum).  transforms: (H, 4, 4), or one
+        4 x 4."""
+        t = np.asarray(transforms, np.float32).reshape(-1, 4, 4)
+        packed = np.ascontiguousarray(t.transpose(0, 2, 1))   # column-major, one after the other
+        counts, sums = np.zeros(len(t), np.uint32), np.zeros(len(t), np.float64)
+        _l.check(_l.lib().rsreg_cloud_score_transforms(self.ctx.h, self.h, target.h, packed.ctypes.data, len(t), float(max_range), counts.ctypes.data,
+                                                       sums.ctypes.data), self.ctx.h)
+        return counts, sums
+
+    def prerejective(self, target, neighbor_index, capacity=None, **params):
+        """pcl::SampleConsensusPrerejective (rsreg_cloud_prerejective): (the winner's inlier records of this cloud in ascending order,
+        PrerejResult).  neighbor_index: (ns, k) int32, what source_features.feature_knn(target_features, k)[0] returned.  params:
+        max_iterations, similarity_threshold, max_correspondence_distance, inlier_fraction, select_by_inliers, seed (prerej_params()).
+        capacity: room for so many records (None: all); the result's n_out is the number of inliers, however many were written."""
+        nbr = np.ascontiguousarray(neighbor_index, np.int32)
+        ns = self.info()[0]
+        if nbr.ndim != 2 or nbr.shape[0] != ns:
+            raise ValueError("neighbor_index must be (%d, k) int32" % ns)
+        p = prerej_params(**params)
+        room = ns if capacity is None else int(capacity)
+        out = np.zeros(room, np.int32)
+        found, res = C.c_size_t(0), _l.PrerejResult()
+        _l.check(_l.lib().rsreg_cloud_prerejective(self.ctx.h, self.h, target.h, nbr.ctypes.data, nbr.shape[1], C.byref(p), out.ctypes.data, room,
+                                                   C.byref(found), C.byref(res)), self.ctx.h)
+        return out[:min(found.value, room)], PrerejResult(res, found.value)
+
     def radius_count(self, radius):
         """radiusSearch of every record in its own cloud, counted (rsreg_cloud_radius_count, exact): uint32 per record, its
         neighbours with float32 d2 < (float)(radius * radius) -- strictly, itself and exact copies among them; 0 for a non-finite
@@ -1557,6 +1586,129 @@ class CorrespondenceRejectorSampleConsensus:
 
     def getBestTransformation(self):
         return np.eye(4, dtype=np.float32) if self._result is None else self._result.transform
+
+    @property
+    def result(self):
+        return self._result
+
+
+def prerej_params(**kw):
+    """rsreg_prerej_params: the defaults (rsreg_prerej_params_default) with the given fields replaced."""
+    p = _l.PrerejParams()
+    _l.lib().rsreg_prerej_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(p._fields_):
+            raise TypeError("rsreg_prerej_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class PrerejResult:
+    """rsreg_prerej_result: transform (4 x 4), found, best_hypothesis, sample (source records), match (target records), n_valid,
+    n_inliers, fitness; n_out: the winner's inliers (which may exceed the capacity that was given)."""
+
+    def __init__(self, r, n_out):
+        self.transform = _rowmajor(list(r.transform))
+        self.found, self.best_hypothesis = bool(r.found), int(r.best_hypothesis)
+        self.sample, self.match = tuple(r.sample), tuple(r.match)
+        self.n_valid, self.n_inliers, self.fitness = int(r.n_valid), int(r.n_inliers), float(r.fitness)
+        self.n_out = int(n_out)
+
+
+class SampleConsensusPrerejective:
+    """pcl::SampleConsensusPrerejective on the GPU: poses from three source records and a random one of each one's k nearest
+    descriptors, pre-rejected on their edge lengths, the survivors scored against the whole target cloud by an exact nearest-point
+    search (csrc/prerej_kernels.hpp, rsreg_cloud_prerejective; include/rsreg.h holds the contract and the stated deviations from
+    PCL).  The clouds are DeviceClouds or host PointClouds, the features DeviceClouds of descriptor records (what
+    FPFHEstimation.compute returns for a DeviceCloud) or host FPFHClouds; host inputs are uploaded into temporaries.  align() makes two
+    calls, rsreg_cloud_feature_knn and rsreg_cloud_prerejective, and returns the source moved by the final transformation.
+    params.select_by_inliers = 1 and params.seed are this library's own."""
+
+    def __init__(self, ctx=None):
+        self._src = self._tgt = self._src_feat = self._tgt_feat = None
+        self.ctx = ctx
+        self.params = prerej_params()
+        self.k = 2                                   # PCL's default correspondence randomness
+        self._result = None
+        self._inliers = np.zeros(0, np.int32)
+
+    def setInputSource(self, cloud):
+        self._src = cloud
+
+    def setInputTarget(self, cloud):
+        self._tgt = cloud
+
+    def setSourceFeatures(self, features):
+        self._src_feat = features
+
+    def setTargetFeatures(self, features):
+        self._tgt_feat = features
+
+    def setMaximumIterations(self, n):
+        self.params.max_iterations = int(n)
+
+    def setNumberOfSamples(self, n):
+        if int(n) != 3:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "SampleConsensusPrerejective: only three samples are built")
+
+    def getNumberOfSamples(self):
+        return 3
+
+    def setCorrespondenceRandomness(self, k):
+        self.k = int(k)
+
+    def getCorrespondenceRandomness(self):
+        return self.k
+
+    def setSimilarityThreshold(self, t):
+        self.params.similarity_threshold = float(t)
+
+    def getSimilarityThreshold(self):
+        return self.params.similarity_threshold
+
+    def setMaxCorrespondenceDistance(self, d):
+        self.params.max_correspondence_distance = float(d)
+
+    def setInlierFraction(self, f):
+        self.params.inlier_fraction = float(f)
+
+    def getInlierFraction(self):
+        return self.params.inlier_fraction
+
+    def align(self):
+        for what, v in (("setInputSource", self._src), ("setInputTarget", self._tgt), ("setSourceFeatures", self._src_feat),
+                        ("setTargetFeatures", self._tgt_feat)):
+            if v is None:
+                raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, what + " not called")
+        ctx = next((c.ctx for c in (self._src, self._tgt, self._src_feat, self._tgt_feat) if isinstance(c, DeviceCloud)), None) or self.ctx or default_context()
+        src, tgt, made = _as_device_pair(self._src, self._tgt, ctx)
+        try:
+            fs, ft, more = _as_device_pair(self._src_feat, self._tgt_feat, ctx)
+            made += more
+            nbr, _ = fs.feature_knn(ft, self.k)
+            self._inliers, self._result = src.prerejective(tgt, nbr, **{k: getattr(self.params, k) for k, _ in self.params._fields_})
+            moved = transformPointCloud(src, self._result.transform)
+            if isinstance(self._src, DeviceCloud):
+                return moved
+            out = moved.download()
+            moved.close()
+            return out
+        finally:
+            for c in made:
+                c.close()
+
+    def hasConverged(self):
+        return self._result is not None and self._result.found
+
+    def getFinalTransformation(self):
+        return np.eye(4, dtype=np.float32) if self._result is None else self._result.transform
+
+    def getInliers(self):
+        return self._inliers
+
+    def getFitnessScore(self):
+        """the winner's error, sum of its inliers' squared distances / their number (0.0 without a winner)"""
+        return 0.0 if self._result is None else self._result.fitness
 
     @property
     def result(self):

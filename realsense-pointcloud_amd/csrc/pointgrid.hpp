@@ -1,6 +1,6 @@
 // pointgrid.hpp — the dense point grid of the exact searches (rsreg_ctx.hpp: PointGrid): its layout, its
 // build, its device view, and the bounds both searches prune with.  Included by icp.hip (through fitness_kernels.hpp),
-// filters.hip (through knn_kernels.hpp) and ndt.hip (the box kernel).  Everything here is a template or inline: the header is
+// filters.hip (through knn_kernels.hpp), ndt.hip (the box kernel) and prerej.hip.  Everything here is a template or inline: the header is
 // shared by several translation units.
 //
 // A build is: the box and number of the finite points (one kernel, one round trip), the cell size from them (grid_layout),
@@ -146,6 +146,75 @@ __device__ __forceinline__ float bound_pos(float u)
 __device__ __forceinline__ float grid_lb2(float gx, float gy, float gz, float cell)
 {
     return __fsub_rn(__fmul_rn(__fmul_rn(__fmul_rn(gx * gx + gy * gy + gz * gz, 0.999996f), cell), cell), 0x1p-147f);
+}
+
+// ------------------------------------------------------------------------------ the nearest point (block-major grids)
+// A search walks shells of BLOCKS around the query's block (clamped into the grid), skips empty blocks on their word and cells on a
+// lower bound, and stops when the six slabs beyond the last shell are all farther than the best distance found (or the range):
+// fitness_kernels.hpp (getFitnessScore) and prerej_kernels.hpp (the score of a pose hypothesis) both call it.
+__device__ __forceinline__ void fit_visit_block(const PointGridDev &g, int bx, int by, int bz, float ux, float uy, float uz, float cell,
+                                                float qx, float qy, float qz, float &best, float &limit2)
+{
+    const uint32_t b = grid_block_id(g, bx, by, bz);
+    unsigned long long m = g.mask[b];
+    while (m) {
+        const int bit = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const int x = (bx << 2) | (bit & 3), y = (by << 2) | ((bit >> 2) & 3), z = (bz << 2) | (bit >> 4);
+        if (grid_lb2(axis_gap(ux, x, x), axis_gap(uy, y, y), axis_gap(uz, z, z), cell) > limit2) continue;
+        const uint32_t c = b * 64u + (uint32_t)bit;
+        const uint32_t e = g.start[c + 1];
+        for (uint32_t p = g.start[c]; p < e; ++p) {
+            const float4 t = g.pts[p];
+            best = fminf(best, l2_simple(qx, qy, qz, t.x, t.y, t.z));
+        }
+        limit2 = fminf(limit2, best);
+    }
+}
+
+// The nearest squared float distance from q to the indexed points (+inf: none within limit2).  limit2: nothing farther is wanted
+// (+inf: unbounded).  Every cell that could hold a point at least as close as the best so far is opened.
+__device__ __forceinline__ float fit_nearest(const PointGridDev &g, float qx, float qy, float qz, float limit2)
+{
+    float best = __int_as_float(0x7f800000);
+    if (g.dx <= 0) return best;
+    const float ux = bound_pos(cell_pos(qx, g.ox, g.inv_cell)), uy = bound_pos(cell_pos(qy, g.oy, g.inv_cell)),
+                uz = bound_pos(cell_pos(qz, g.oz, g.inv_cell));
+    const int qbx = axis_cell(qx, g.ox, g.inv_cell, g.dx) >> 2, qby = axis_cell(qy, g.oy, g.inv_cell, g.dy) >> 2,
+              qbz = axis_cell(qz, g.oz, g.inv_cell, g.dz) >> 2;
+    // gaps to the whole grid along each axis: what a slab beyond a shell is at least away along the other two
+    const float hx = axis_gap(ux, 0, g.dx - 1), hy = axis_gap(uy, 0, g.dy - 1), hz = axis_gap(uz, 0, g.dz - 1);
+    const int rb_max = max(max(max(qbx, g.bx - 1 - qbx), max(qby, g.by - 1 - qby)), max(qbz, g.bz - 1 - qbz));
+    for (int rb = 0; rb <= rb_max; ++rb) {
+        const int z0 = max(qbz - rb, 0), z1 = min(qbz + rb, g.bz - 1);
+        const int y0 = max(qby - rb, 0), y1 = min(qby + rb, g.by - 1);
+        for (int bz = z0; bz <= z1; ++bz) {
+            const float gz = axis_gap(uz, bz << 2, (bz << 2) + 3);
+            if (grid_lb2(0.0f, 0.0f, gz, g.cell) > limit2) continue;
+            for (int by = y0; by <= y1; ++by) {
+                const float gy = axis_gap(uy, by << 2, (by << 2) + 3);
+                if (grid_lb2(0.0f, gy, gz, g.cell) > limit2) continue;
+                const bool face = abs(bz - qbz) == rb || abs(by - qby) == rb;   // a face row: every block of it; else its two ends
+                const int xa = qbx - rb, xb = qbx + rb;
+                for (int bx = face ? max(xa, 0) : xa; bx <= (face ? min(xb, g.bx - 1) : xb); bx += face ? 1 : max(2 * rb, 1)) {
+                    if (bx < 0 || bx >= g.bx) continue;
+                    const float gx = axis_gap(ux, bx << 2, (bx << 2) + 3);
+                    if (grid_lb2(gx, gy, gz, g.cell) > limit2) continue;
+                    fit_visit_block(g, bx, by, bz, ux, uy, uz, g.cell, qx, qy, qz, best, limit2);
+                }
+            }
+        }
+        // every block not visited yet lies in one of the six slabs beyond this shell
+        float lb = __int_as_float(0x7f800000);
+        if (qbx + rb + 1 < g.bx) lb = fminf(lb, grid_lb2(axis_gap(ux, (qbx + rb + 1) << 2, g.dx - 1), hy, hz, g.cell));
+        if (qbx - rb - 1 >= 0) lb = fminf(lb, grid_lb2(axis_gap(ux, 0, ((qbx - rb - 1) << 2) + 3), hy, hz, g.cell));
+        if (qby + rb + 1 < g.by) lb = fminf(lb, grid_lb2(hx, axis_gap(uy, (qby + rb + 1) << 2, g.dy - 1), hz, g.cell));
+        if (qby - rb - 1 >= 0) lb = fminf(lb, grid_lb2(hx, axis_gap(uy, 0, ((qby - rb - 1) << 2) + 3), hz, g.cell));
+        if (qbz + rb + 1 < g.bz) lb = fminf(lb, grid_lb2(hx, hy, axis_gap(uz, (qbz + rb + 1) << 2, g.dz - 1), g.cell));
+        if (qbz - rb - 1 >= 0) lb = fminf(lb, grid_lb2(hx, hy, axis_gap(uz, 0, ((qbz - rb - 1) << 2) + 3), g.cell));
+        if (lb > limit2) break;
+    }
+    return best;
 }
 
 // ------------------------------------------------------------------------------ record readers

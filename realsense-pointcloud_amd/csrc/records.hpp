@@ -44,6 +44,17 @@ __device__ __forceinline__ const float *rec_xyz(const char *base, size_t stride,
     return reinterpret_cast<const float *>(base + i * stride);
 }
 
+// the generator of the pose hypotheses (include/rsreg.h, "pose from correspondences"; sac_kernels.hpp, prerej_kernels.hpp): the
+// splitmix64 finaliser over a counter, then a multiply-shift onto [0, n)
+__device__ __forceinline__ uint32_t sac_draw(unsigned long long seed, unsigned long long h, uint32_t draw, uint32_t n)
+{
+    unsigned long long z = seed + (64ull * h + draw) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (uint32_t)(((z >> 32) * (unsigned long long)n) >> 32);
+}
+
 constexpr float kCellMargin = 0.03f;   // slack (in cells) on every geometric lower bound: covers
                                        // the float rounding of the point -> cell assignment
 

@@ -237,6 +237,23 @@ struct SacScratch {
     PinnedBuf host;                // counts, samples, rows, sums and words on their way home; a caller's transforms on their way out
 };
 
+// Index and scratch of SampleConsensusPrerejective (prerej.hip, prerej_kernels.hpp): the target's point grid, rebuilt by every call,
+// and what a round of hypotheses leaves; shares no buffer with another index or with the correspondence rejector
+struct PrerejScratch {
+    PointGrid grid;                // the target of the call, block-major (FitGridPolicy)
+    DevBuf d_nbr;                  // int32, ns * k: the caller's table of descriptor neighbours
+    DevBuf d_table;                // 12 floats per hypothesis of a round: the rows of its transform
+    DevBuf d_valid;                // uint32 per hypothesis of a round: it has a transform
+    DevBuf d_sample;               // 8 int32 per hypothesis of a round: its three source records, its three target records, two spare words
+    DevBuf d_counts;               // uint32 per hypothesis of a round: its inliers
+    DevBuf d_sums;                 // double per hypothesis of a round: the sum of its inliers' d2
+    DevBuf d_partials;             // two doubles per (hypothesis of a launch, group of the source): the two waves' sums
+    DevBuf d_flags, d_pos, d_scan; // the winner's inlier flag per source record, its position among the inliers, the prefix sum's scratch
+    DevBuf d_out;                  // the winner's inliers (int32 record numbers), before they go home
+    DevBuf d_word;                 // the number of inliers (uint64)
+    PinnedBuf host;                // the box of the grid build; tables on their way out; counts, sums, flags, samples and rows on their way home
+};
+
 // Scratch of IntegralImageNormalEstimation (iinormals.hip), per pixel of the organized frame it is given
 struct IinScratch {
     DevBuf d_dist0, d_dist1, d_dist2;   // float: the distance map as set up, after the forward pass, after the backward pass
@@ -487,6 +504,9 @@ struct rsreg_ctx {
 
     // ---- pose from correspondences (sac.hip): scratch of its own
     rsreg::SacScratch sac;
+
+    // ---- pose from descriptor neighbours, scored against the whole target (prerej.hip): index and scratch of its own
+    rsreg::PrerejScratch prerej;
 
     // ---- IntegralImageNormalEstimation (iinormals.hip)
     rsreg::IinScratch iin;

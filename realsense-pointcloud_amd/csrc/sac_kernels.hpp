@@ -21,15 +21,7 @@ constexpr int kSacLanes = 256;        // the one-item-a-lane kernels' workgroup
 constexpr int kSacSumTile = 128;      // pairs a workgroup of k_sac_sums adds: two waves, the tree of the ICP sums (icp_kernels.hpp)
 constexpr int kSacFinalBlock = 256;
 
-// the contract's generator: the splitmix64 finaliser over a counter, then a multiply-shift onto [0, n)
-__device__ __forceinline__ uint32_t sac_draw(unsigned long long seed, unsigned long long h, uint32_t draw, uint32_t n)
-{
-    unsigned long long z = seed + (64ull * h + draw) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (uint32_t)(((z >> 32) * (unsigned long long)n) >> 32);
-}
+// (the contract's generator, sac_draw: records.hpp)
 
 __global__ __launch_bounds__(kSacLanes) void k_sac_gather(const rsreg_correspondence *corr, uint32_t n, const char *src, size_t sstride, const char *tgt,
                                                           size_t tstride, float *planes, uint32_t pitch)

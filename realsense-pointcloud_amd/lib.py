@@ -16,7 +16,7 @@ ROOT = os.path.dirname(_HERE)
 DIAG = os.environ.get("RSREG_DIAG", "") == "1"
 SO_PATH = (os.environ.get("RSREG_SO") if DIAG else None) or os.path.join(_HERE, "librsreg_diag.so" if DIAG else "librsreg.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip", "depthcloud.hip", "depth_host.cpp", "features.hip", "sac.hip"]
+SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip", "depthcloud.hip", "depth_host.cpp", "features.hip", "sac.hip", "prerej.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) if os.path.isdir(CSRC) else []
 NUM_SUMS = 17
 NUM_PLANE_SUMS = 32                                      # include/rsreg.h: RSREG_NUM_PLANE_SUMS
@@ -49,6 +49,7 @@ EXPORTS = [
     "rsreg_cloud_passthrough", "rsreg_cloud_sor", "rsreg_cloud_knn_mean_distance", "rsreg_cloud_knn", "rsreg_cloud_normals",
     "rsreg_cloud_fpfh", "rsreg_cloud_spfh", "rsreg_cloud_feature_knn", "rsreg_cloud_feature_correspondences",
     "rsreg_sac_params_default", "rsreg_cloud_count_inliers", "rsreg_cloud_estimate_rigid_svd", "rsreg_cloud_sac_correspondences",
+    "rsreg_prerej_params_default", "rsreg_cloud_score_transforms", "rsreg_cloud_prerejective",
     "rsreg_cloud_radius_count", "rsreg_cloud_radius_outlier_removal", "rsreg_cloud_normals_radius",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
@@ -108,6 +109,16 @@ class SacResult(C.Structure):   # rsreg_sac_result
     _fields_ = [("transform", C.c_float * 16), ("found", C.c_int32), ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 3),
                 ("iterations", C.c_int32), ("n_inliers", C.c_uint64), ("refit_rounds_run", C.c_int32), ("reserved0", C.c_int32),
                 ("sums", C.c_double * NUM_SUMS)]
+
+
+class PrerejParams(C.Structure):   # rsreg_prerej_params
+    _fields_ = [("max_correspondence_distance", C.c_double), ("inlier_fraction", C.c_double), ("similarity_threshold", C.c_float),
+                ("max_iterations", C.c_int32), ("select_by_inliers", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64)]
+
+
+class PrerejResult(C.Structure):   # rsreg_prerej_result
+    _fields_ = [("transform", C.c_float * 16), ("found", C.c_int32), ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 3),
+                ("match", C.c_int32 * 3), ("n_valid", C.c_uint64), ("n_inliers", C.c_uint64), ("fitness", C.c_double)]
 
 
 class IinParams(C.Structure):   # rsreg_iin_params
@@ -333,6 +344,10 @@ def lib():
     L.rsreg_cloud_count_inliers.argtypes = [vp, vp, vp, vp, sz, vp, sz, dbl, vp]
     L.rsreg_cloud_estimate_rigid_svd.argtypes = [vp, vp, vp, vp, sz, vp, vp]
     L.rsreg_cloud_sac_correspondences.argtypes = [vp, vp, vp, vp, sz, C.POINTER(SacParams), vp, sz, C.POINTER(sz), C.POINTER(SacResult)]
+    L.rsreg_prerej_params_default.argtypes = [C.POINTER(PrerejParams)]
+    L.rsreg_prerej_params_default.restype = None
+    L.rsreg_cloud_score_transforms.argtypes = [vp, vp, vp, vp, sz, dbl, vp, vp]
+    L.rsreg_cloud_prerejective.argtypes = [vp, vp, vp, vp, i32, C.POINTER(PrerejParams), vp, sz, C.POINTER(sz), C.POINTER(PrerejResult)]
     L.rsreg_cloud_radius_count.argtypes = [vp, vp, dbl, vp]
     L.rsreg_cloud_radius_outlier_removal.argtypes = [vp, vp, dbl, i32, i32, i32, vp, C.POINTER(C.c_uint64)]
     L.rsreg_cloud_normals_radius.argtypes = [vp, vp, dbl, vp, vp]
