@@ -822,7 +822,10 @@ int rsreg_cloud_sac_correspondences(rsreg_ctx *ctx, const rsreg_cloud *source, c
  *   THE POLYGON TEST, float32: for each of the three edges (a, b), ds = the L2_Simple squared distance of source points a and b, dt
  *   that of their target points; sim = ds < dt ? ds / dt : dt / ds, one IEEE float32 division; the edge passes iff
  *   sim >= similarity_threshold * similarity_threshold, the product rounded to float32.  A NaN sim, which 0 / 0 gives, fails: coincident
- *   points are refused without a further rule.
+ *   points are refused without a further rule.  A denormal ds or dt is divided as IEEE: nothing is flushed to zero.  A cloud whose
+ *   squared edge lengths all underflow to 0 (0 / 0), or overflow to +inf (inf / inf, a NaN as well), has no valid hypothesis.  At
+ *   similarity_threshold 0 an edge with exactly one zero length passes (sim = 0 / x = 0 >= 0): three source records matched to ONE
+ *   target record then reach the solve, which decides.
  *   DEVIATION: PCL's rand()-driven sampler is not reproduced.
  *   A valid hypothesis is scored as above at max_range = max_correspondence_distance; an invalid one is never searched.
  *   SELECTION, replayed on the host in hypothesis order: h QUALIFIES when it is valid, count >= 1 and

@@ -99,6 +99,33 @@ def polygon_ok(P, Q, similarity_threshold):
     return True
 
 
+def polygon_edges(P, Q):
+    """(3, 3) float32, a row (ds, dt, sim) per edge as polygon_ok forms them -- all three edges, whether or not an earlier one fails;
+    for tests/test_prerej_edges_cpu.py, which classifies them (a denormal, 0, +inf, a NaN sim)"""
+    out = np.zeros((3, 3), np.float32)
+    with np.errstate(all="ignore"):
+        for e, (a, b) in enumerate(((0, 1), (1, 2), (2, 0))):
+            ds, dt = S.l2_simple(P[a], P[b]), S.l2_simple(Q[a], Q[b])
+            sim = ds / dt if ds < dt else dt / ds
+            assert np.asarray(sim).dtype == np.float32
+            out[e] = ds, dt, sim
+    return out
+
+
+def sample_edges(src, tgt, nbr, seed, h):
+    """polygon_edges of hypothesis h's sample, or None when its draws do not give three distinct eligible records that are finite on
+    both sides (hypothesis() ends before the polygon test there)"""
+    ns, k = nbr.shape
+    ids = [int(S.draw_index(seed, h, d, ns)) for d in range(3)]
+    if any(nbr[i, 0] < 0 for i in ids) or len(set(ids)) < 3:
+        return None
+    match = [int(nbr[ids[d], int(S.draw_index(seed, h, 3 + d, k))]) for d in range(3)]
+    P, Q = src[ids], tgt[match]
+    if not (np.isfinite(P).all() and np.isfinite(Q).all()):
+        return None
+    return polygon_edges(P, Q)
+
+
 def hypothesis(api, src, tgt, nbr, seed, h, similarity_threshold):
     """(T 4 x 4 float32 or None, the three source records, the three target records or None): hypothesis h of the contract"""
     ns, k = nbr.shape
