@@ -629,7 +629,7 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
  * build can differ where a feature lies within float rounding of a bin edge.
  * The same cloud, normals and k give the same bytes whatever the context has indexed before: the counts are integers, every
  * float sum runs in the order above.
- * Not built: setRadiusSearch, setSearchSurface, setIndices, other bin counts, PFH.
+ * Not built: setSearchSurface, setIndices, other bin counts, PFH.  setRadiusSearch: rsreg_cloud_fpfh_radius, below.
  *
  * rsreg_cloud_fpfh: out = n records of 132 bytes laid out as pcl::FPFHSignature33 (float histogram[33]); width, height as the
  * input's; is_dense 0 if any record got NaNs, otherwise the input's.  out != in, out != normals.  Waits for the stream (whether a
@@ -904,6 +904,45 @@ int rsreg_cloud_radius_outlier_removal(rsreg_ctx *ctx, const rsreg_cloud *in, do
  * (computeMeanAndCovarianceMatrix); this is the covariance the formula defines, in double, about the record.  A PCL build
  * agrees with it to PCL's own rounding. */
 int rsreg_cloud_normals_radius(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, const float viewpoint[3], rsreg_cloud *out);
+/* ---- pcl::FPFHEstimationOMP with setRadiusSearch(radius): SPFH and FPFH over the radius search above -- a support of fixed
+ * metric size, any number of neighbours.  PCL 1.9.1 features/impl/fpfh.hpp (computePointSPFHSignature, weightPointSPFHSignature)
+ * and pfh_tools.cpp (computePairFeatures), recalled; PCL is not available to check against, so what follows IS the contract.
+ * normals: as for rsreg_cloud_fpfh (n records of the same context, three floats first, stride >= 12 and a multiple of 4).
+ * Neighbourhood N_r(i): exactly the radius search's -- the finite records j with float32 d2(i, j) < (float)((double)radius *
+ * (double)radius), strictly; the record itself and exact copies among them; no cap.  m(i) = their number = what
+ * rsreg_cloud_radius_count gives.
+ * Pair features and bins: those of rsreg_cloud_fpfh above, unchanged (double, no contraction).  A pair is skipped when j == i,
+ * when f4 == 0 (exact copies), when |v| == 0, or when n_i or n_j is not finite.
+ * SPFH row of record i: a bin hit by c pairs holds the float that adding hist_incr = 100.0f / (float)(m - 1) to 0.0f c times
+ * gives (PCL's sequential +=), for any c up to m - 1.  m == 1: no pair, no addition, a row of zeros -- the infinite increment is
+ * never used.  A record that is not finite, or whose own normal is not finite, has an all-zero row (and is a neighbour of others
+ * with that row).
+ * FPFH row of record i.  The weights and the products are PCL's float32:
+ *   for every j in N_r(i) with d2(i, j) != 0:  w = 1.0f / d2;  val[b] = SPFH[j][b] * w  (float32, no contraction);
+ *     H[b] += (double)val[b]
+ *   S_t = ((H[11t] + H[11t + 1]) + ...) + H[11t + 10] in double;  out[b] = (float)(H[b] * (S_t != 0 ? 100.0 / S_t : 0.0)).
+ * Both quirks of PCL are kept: the weight is 1 / SQUARED distance, and the record's own SPFH does not enter.  A record with no
+ * neighbour at positive distance gives 33 zeros.  A record that is not finite, or whose own normal is not finite, gets 33 quiet
+ * NaNs.  NaNs the arithmetic makes (a denormal d2 gives w = +inf, and 0 * inf is NaN) stand where it puts them, sign and payload
+ * not specified.  is_dense is 0 if any row holds a NaN, otherwise the input's.
+ * DEVIATION FROM PCL 1.9.1, stated: H is accumulated in DOUBLE, in an order that is a function of the cloud and the radius alone
+ * (inside a cell of the index the points lie in ascending record index) -- the deviation rsreg_cloud_normals_radius makes.  PCL
+ * adds the float products in float in FLANN's distance-sorted order; that is not reproduced: it would need a per-record sort of a
+ * list without a bound, and FLANN leaves the order of equal distances open anyway.  A PCL build agrees to float rounding of the
+ * sums (and to the pair features' deviation stated above).
+ * radius not finite or <= 0, normals of another size or context, out == in, out == normals, a null argument:
+ * RSREG_ERR_INVALID_ARG, nothing launched, `out` untouched.  An empty cloud gives an empty cloud of 132-byte records; a cloud
+ * without a finite record gives NaN rows, zero SPFH rows and zero counts.  The same cloud, normals and radius give the same bytes
+ * whatever the context has indexed before.  Every call builds its index and walks it twice; no neighbour list is stored.
+ * Not built: setSearchSurface, setIndices, other bin counts, PFH.
+ *
+ * rsreg_cloud_fpfh_radius: out = n records of 132 bytes laid out as pcl::FPFHSignature33, width and height as the input's.  Waits
+ * for the stream (whether a row holds a NaN).
+ * rsreg_cloud_spfh_radius: host_out = the n * 33 floats of the SPFH rows, count_out[i] = m(i) (0 for a non-finite record), the
+ * caller's record order. */
+int rsreg_cloud_fpfh_radius(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, double radius, rsreg_cloud *out);
+int rsreg_cloud_spfh_radius(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, double radius, float *host_out /* n*33 */,
+                            uint32_t *count_out /* n, may be NULL */);
 /* pcl::IntegralImageNormalEstimation on an ORGANIZED cloud of w x h records P[r][c] (src/edge_extractor.hpp:9-15 runs it with
  * AVERAGE_3D_GRADIENT, setMaxDepthChangeFactor(0.02f), setNormalSmoothingSize(10.0f) on every frame): a cost per pixel that
  * does not depend on the scene, and no index.  PCL 1.9.1 features/impl/integral_image_normal.hpp, recalled; PCL is not

@@ -941,7 +941,8 @@ static_assert(sizeof(FPFHSignature33) == 132, "pcl::FPFHSignature33 is 33 floats
 // search (csrc/fpfh_kernels.hpp, rsreg_cloud_fpfh; include/rsreg.h holds the contract).  PointNT: records that begin with
 // normal_x, normal_y, normal_z (pcl::Normal); PointOutT: 132-byte records laid out as pcl::FPFHSignature33.  PCL's two quirks are
 // kept (the weight is 1 / squared distance, the record's own SPFH does not enter); the pair features are computed in double, not
-// in float (the stated deviation).  setRadiusSearch is refused: it is not built.  No setSearchSurface, no setIndices.
+// in float (the stated deviation).  setRadiusSearch is refused here: FPFHEstimationOMP, below, takes either search.  No
+// setSearchSurface, no setIndices.
 template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33> class FPFHEstimation {
     static_assert(sizeof(PointOutT) == 132, "the output records are laid out as pcl::FPFHSignature33");
     static_assert(sizeof(PointNT) >= 12 && sizeof(PointNT) % 4 == 0, "the normals' records begin with three floats");
@@ -974,6 +975,58 @@ template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignatur
     }
   private:
     int k_ = 0;                            // PCL's default: no search set (compute() refuses it)
+    typename PointCloud<PointInT>::Ptr input_;
+    typename PointCloud<PointNT>::Ptr normals_;
+    std::shared_ptr<Context> ctx_;
+};
+
+// ---- pcl::FPFHEstimationOMP<PointInT, PointNT, PointOutT> on the GPU: with setKSearch (2 .. 64) the bytes of FPFHEstimation
+// (rsreg_cloud_fpfh), with setRadiusSearch over the exact radius search (csrc/fpfh_radius_kernels.hpp, rsreg_cloud_fpfh_radius;
+// include/rsreg.h holds the contract): a support of fixed metric size, any number of neighbours, the histogram sums in double (the
+// stated deviation).  As in PCL exactly one of the two is set: compute() refuses both and neither before any device call;
+// setKSearch(0) / setRadiusSearch(0) unset them.  setNumberOfThreads is accepted and ignored.  No setSearchSurface, no setIndices.
+template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33> class FPFHEstimationOMP {
+    static_assert(sizeof(PointOutT) == 132, "the output records are laid out as pcl::FPFHSignature33");
+    static_assert(sizeof(PointNT) >= 12 && sizeof(PointNT) % 4 == 0, "the normals' records begin with three floats");
+  public:
+    explicit FPFHEstimationOMP(unsigned int nr_threads = 0) : threads_(nr_threads) {}
+    explicit FPFHEstimationOMP(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {}
+    void setInputCloud(const typename PointCloud<PointInT>::Ptr &cloud) { input_ = cloud; }
+    void setInputNormals(const typename PointCloud<PointNT>::Ptr &normals) { normals_ = normals; }
+    void setKSearch(int k) { k_ = k; }
+    int getKSearch() const { return k_; }
+    void setRadiusSearch(double radius) { radius_ = radius; }
+    double getRadiusSearch() const { return radius_; }
+    void setNumberOfThreads(unsigned int nr_threads = 0) { threads_ = nr_threads; }
+    void compute(PointCloud<PointOutT> &output)
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        if (!normals_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputNormals not called");
+        check_search();
+        const std::shared_ptr<Context> ctx = ctx_ ? ctx_ : Context::Default();
+        DeviceCloud<PointInT> tmp(*input_, ctx);
+        DeviceCloud<PointNT> tmp_normals(*normals_, ctx);
+        DeviceCloud<PointOutT> features(ctx);
+        compute(tmp, tmp_normals, features);
+        features.download(output);
+    }
+    void compute(const DeviceCloud<PointInT> &input, const DeviceCloud<PointNT> &normals, DeviceCloud<PointOutT> &output)
+    {
+        check_search();
+        if (radius_ != 0.0)
+            check(rsreg_cloud_fpfh_radius(input.context()->get(), input.handle(), normals.handle(), radius_, output.handle()), input.context()->get());
+        else
+            check(rsreg_cloud_fpfh(input.context()->get(), input.handle(), normals.handle(), k_, output.handle()), input.context()->get());
+    }
+  private:
+    void check_search() const
+    {
+        if (k_ != 0 && radius_ != 0.0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: both setKSearch and setRadiusSearch are set: set one of them to 0");
+        if (k_ == 0 && radius_ == 0.0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: neither setKSearch nor setRadiusSearch is set");
+    }
+    int k_ = 0;                            // PCL's defaults: no search set (compute() refuses it)
+    double radius_ = 0.0;
+    unsigned int threads_ = 0;
     typename PointCloud<PointInT>::Ptr input_;
     typename PointCloud<PointNT>::Ptr normals_;
     std::shared_ptr<Context> ctx_;

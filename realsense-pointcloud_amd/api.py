@@ -308,6 +308,42 @@ class DeviceCloud:
         _l.check(rc, self.ctx.h)
         return out
 
+    def fpfh_radius_cloud(self, normals, radius):
+        """pcl::FPFHEstimationOMP with setRadiusSearch(radius) (rsreg_cloud_fpfh_radius; include/rsreg.h holds the contract): a
+        DeviceCloud of 132-byte pcl::FPFHSignature33 records over the exact radius search, any number of neighbours.  normals: see
+        fpfh()."""
+        nrm, made = self._normals_on_device(normals)
+        out = DeviceCloud(ctx=self.ctx)
+        rc = _l.lib().rsreg_cloud_fpfh_radius(self.ctx.h, self.h, nrm.h, float(radius), out.h)
+        if made:
+            nrm.close()
+        if rc:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out
+
+    def fpfh_radius(self, normals, radius):
+        """(n, 33) float32: the Fast Point Feature Histogram of every record over its neighbours within `radius`, three blocks of 11
+        bins that each sum to 100 or are all zero (NaN for a record that is not finite or whose normal is not)."""
+        out = self.fpfh_radius_cloud(normals, radius)
+        hist = out.download_fpfh().points["histogram"]
+        out.close()
+        return hist
+
+    def spfh_radius(self, normals, radius, counts=False):
+        """(n, 33) float32: the Simplified Point Feature Histogram of every record over its neighbours within `radius`
+        (rsreg_cloud_spfh_radius), the first pass of fpfh_radius(): zeros for a record that is not finite or whose normal is not.
+        counts: (rows, m) with m (n,) uint32, every record's number of neighbours -- what radius_count() gives."""
+        nrm, made = self._normals_on_device(normals)
+        n = self.info()[0]
+        out = np.zeros((n, 33), np.float32)
+        m = np.zeros(n, np.uint32)
+        rc = _l.lib().rsreg_cloud_spfh_radius(self.ctx.h, self.h, nrm.h, float(radius), out.ctypes.data, m.ctypes.data if counts else None)
+        if made:
+            nrm.close()
+        _l.check(rc, self.ctx.h)
+        return (out, m) if counts else out
+
     def download_fpfh(self):
         """download() of a cloud of pcl::FPFHSignature33 records (what FPFHEstimation.compute returns): an FPFHCloud."""
         n, stride, w, h, dense = self.info()
@@ -1407,8 +1443,9 @@ class FPFHEstimation:
     """pcl::FPFHEstimation<PointXYZRGB, Normal, FPFHSignature33> on the GPU with setKSearch, 2 <= k <= 64, over the exact
     k-nearest-neighbour search (csrc/fpfh_kernels.hpp, rsreg_cloud_fpfh; include/rsreg.h holds the contract).  PCL's two quirks are
     kept -- the weight is 1 / squared distance, the record's own SPFH does not enter -- and the pair features are computed in
-    double, not in float.  setRadiusSearch, setSearchSurface and setIndices are not built.  compute() of a DeviceCloud gives a
-    DeviceCloud of pcl::FPFHSignature33 records, of a host cloud an FPFHCloud."""
+    double, not in float.  setRadiusSearch is refused here: FPFHEstimationOMP, below, takes either search.  setSearchSurface and
+    setIndices are not built.  compute() of a DeviceCloud gives a DeviceCloud of pcl::FPFHSignature33 records, of a host cloud an
+    FPFHCloud."""
 
     def __init__(self, ctx=None):
         self.k = 0                                   # PCL's default: no search set
@@ -1444,6 +1481,67 @@ class FPFHEstimation:
         tmp = DeviceCloud(self._in, ctx=self.ctx or default_context())
         try:
             dev = tmp.fpfh_cloud(self._normals, self.k)
+            out = dev.download_fpfh()
+            dev.close()
+        finally:
+            tmp.close()
+        return out
+
+
+class FPFHEstimationOMP:
+    """pcl::FPFHEstimationOMP<PointXYZRGB, Normal, FPFHSignature33> on the GPU: with setKSearch, 2 <= k <= 64, the bytes of
+    FPFHEstimation (rsreg_cloud_fpfh); with setRadiusSearch over the exact radius search (csrc/fpfh_radius_kernels.hpp,
+    rsreg_cloud_fpfh_radius; include/rsreg.h holds the contract), any number of neighbours, the histogram sums in double.  As in
+    PCL exactly one of the two is set: compute() refuses both and neither before any device call; setKSearch(0) /
+    setRadiusSearch(0) unset them.  setNumberOfThreads is accepted and ignored.  compute() of a DeviceCloud gives a DeviceCloud of
+    pcl::FPFHSignature33 records, of a host cloud an FPFHCloud."""
+
+    def __init__(self, ctx=None):
+        self.k = 0                                   # PCL's default: no search set
+        self.radius = 0.0
+        self.threads = 0
+        self._in = None
+        self._normals = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setInputNormals(self, normals):
+        self._normals = normals
+
+    def setKSearch(self, k):
+        self.k = int(k)
+
+    def getKSearch(self):
+        return self.k
+
+    def setRadiusSearch(self, radius):
+        self.radius = float(radius)
+
+    def getRadiusSearch(self):
+        return self.radius
+
+    def setNumberOfThreads(self, threads=0):
+        self.threads = int(threads)
+
+    def _fpfh_cloud(self, dev):
+        return dev.fpfh_radius_cloud(self._normals, self.radius) if self.radius != 0.0 else dev.fpfh_cloud(self._normals, self.k)
+
+    def compute(self):
+        if self._in is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCloud not called")
+        if self._normals is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputNormals not called")
+        if self.k != 0 and self.radius != 0.0:   # (before any device call, as PCL's initCompute)
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "both setKSearch and setRadiusSearch are set: set one of them to 0")
+        if self.k == 0 and self.radius == 0.0:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "neither setKSearch nor setRadiusSearch is set")
+        if isinstance(self._in, DeviceCloud):
+            return self._fpfh_cloud(self._in)
+        tmp = DeviceCloud(self._in, ctx=self.ctx or default_context())
+        try:
+            dev = self._fpfh_cloud(tmp)
             out = dev.download_fpfh()
             dev.close()
         finally:

@@ -6,7 +6,8 @@
 // k-NN index and search of knn_kernels.hpp, the threshold's two sums in PCL's own order, then the same flag / scan / gather.
 // pcl::RadiusOutlierRemoval and NormalEstimation by radius: the exact radius search of radius_kernels.hpp over an index of its own
 // placement, then the same flag / scan / gather, or k_normals' tail.  pcl::FPFHEstimation (setKSearch): the k-NN search once, with
-// the pair features of fpfh_kernels.hpp behind it, then the weighting pass over the neighbour rows the search left.
+// the pair features of fpfh_kernels.hpp behind it, then the weighting pass over the neighbour rows the search left.  pcl::FPFHEstimationOMP
+// (setRadiusSearch): fpfh_radius_kernels.hpp's two walks of the radius index, no neighbour list between them.
 // Everything runs on the context's stream with the index rsreg_ctx::knn and the scratch rsreg_ctx::filt (the radius search:
 // rsreg_ctx::rad too): nothing here reads or writes a buffer of the alignment's index or of the fitness indices.
 #include <cmath>
@@ -16,6 +17,7 @@
 #include "normals_kernels.hpp"
 #include "radius_kernels.hpp"
 #include "fpfh_kernels.hpp"
+#include "fpfh_radius_kernels.hpp"
 #include "cloud_ops.hpp"
 
 using namespace rsreg;
@@ -208,6 +210,39 @@ int fpfh_spfh_device(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *n
     return RSREG_OK;
 }
 
+// The first pass of FPFHEstimationOMP by radius, not waited for: the radius index, then every finite record's SPFH row
+// (fs.d_spfh) and neighbour count (rs.d_count); the rows and counts of non-finite records are zero.  v, nv: the views of the cloud
+// and of its normals.  An empty cloud: nothing is reserved or launched, *nfin_out = 0.
+int fpfh_radius_spfh_device(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, const rsreg_cloud *out, double radius, CloudView &v,
+                            CloudView &nv, RadiusQuery *rq, uint32_t *nfin_out)
+{
+    if (!normals) return RSREG_ERR_INVALID_ARG;
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
+    if (rc) return rc;
+    rc = cloud_view(ctx, normals, nullptr, kXyzRule, nv);
+    if (rc) return rc;
+    if (!(radius > 0.0) || !std::isfinite(radius)) return fail(ctx, RSREG_ERR_INVALID_ARG, "the radius must be finite and above 0");
+    if (nv.n != v.n) return fail(ctx, RSREG_ERR_INVALID_ARG, "the normals must hold one record per record of the cloud");
+    *nfin_out = 0;
+    if (!v.n) return RSREG_OK;
+    FilterScratch &fs = ctx->filt;
+    RadiusScratch &rs = ctx->rad;
+    hipStream_t st = ctx->stream;
+    RSREG_HIP(ctx, rs.d_count.reserve(v.n * 4 + 16));
+    RSREG_HIP(ctx, fs.d_spfh.reserve(v.n * kFpfhRow * 4 + 16));
+    rc = radius_index_device(ctx, v, radius, rs.d_count.as<uint32_t>(), rq, nfin_out);
+    if (rc) return rc;
+    if (*nfin_out < v.n) RSREG_HIP(ctx, hipMemsetAsync(fs.d_spfh.ptr, 0, v.n * kFpfhRow * 4, st));
+    if (!*nfin_out) {   // (the build stops at the box: nothing has written the counts)
+        RSREG_HIP(ctx, hipMemsetAsync(rs.d_count.ptr, 0, v.n * 4, st));
+        return RSREG_OK;
+    }
+    k_fpfh_radius_spfh<<<std::min<uint32_t>(*nfin_out, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), *rq, nv.rec, nv.stride, fs.d_spfh.as<float>(),
+                                                                                    rs.d_count.as<uint32_t>());
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
 // The tail of a normals call, behind the index over `nfin` finite records: room for the pcl::Normal records, NaNs for the
 // records that are not finite, the search -- launch(vp, d_normals, &any_nan) with PCL's default viewpoint if there is none,
 // left out when nothing is finite -- and the records handed to `out`: a record that got NaNs makes the cloud not dense;
@@ -395,6 +430,49 @@ int rsreg_cloud_fpfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *n
     }, &any_nan);
     if (rc) return rc;
     return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kFpfhBytes, v.width, v.height, any_nan ? 0 : v.is_dense);
+}
+
+int rsreg_cloud_spfh_radius(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, double radius, float *host_out, uint32_t *count_out)
+{
+    CloudView v, nv;
+    if (!host_out) return RSREG_ERR_INVALID_ARG;
+    uint32_t nfin = 0;
+    RadiusQuery rq;
+    int rc = fpfh_radius_spfh_device(ctx, in, normals, nullptr, radius, v, nv, &rq, &nfin);
+    if (rc || !v.n) return rc;
+    RSREG_HIP(ctx, hipMemcpyAsync(host_out, ctx->filt.d_spfh.ptr, v.n * kFpfhRow * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (count_out) RSREG_HIP(ctx, hipMemcpyAsync(count_out, ctx->rad.d_count.ptr, v.n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RSREG_OK;
+}
+
+int rsreg_cloud_fpfh_radius(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, double radius, rsreg_cloud *out)
+{
+    CloudView v, nv;
+    if (!out || out == in || out == normals) return RSREG_ERR_INVALID_ARG;
+    uint32_t nfin = 0;
+    RadiusQuery rq;
+    int rc = fpfh_radius_spfh_device(ctx, in, normals, out, radius, v, nv, &rq, &nfin);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)v.n;
+    constexpr size_t kFpfhBytes = kFpfhRow * 4;   // pcl::FPFHSignature33
+    RSREG_HIP(ctx, fs.d_out.reserve(v.n * kFpfhBytes + 16));
+    if (nfin < n) {
+        k_fpfh_radius_not_finite<<<div_up64((unsigned long long)n * kFpfhRow, kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, fs.d_out.as<float>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    // a record whose own normal is not finite gets NaNs too, and the arithmetic can make some: whether it did comes back with the stream
+    uint32_t any_nan = 0;
+    if (nfin) {
+        rc = word_home(ctx, true, [&](uint32_t *d_any) {
+            k_fpfh_radius_weight<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), rq, nv.rec, nv.stride, fs.d_spfh.as<float>(),
+                                                                                         fs.d_out.as<float>(), d_any);
+        }, &any_nan);
+        if (rc) return rc;
+    }
+    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kFpfhBytes, v.width, v.height, (nfin < n || any_nan) ? 0 : v.is_dense);
 }
 
 int rsreg_cloud_radius_count(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, uint32_t *host_out)

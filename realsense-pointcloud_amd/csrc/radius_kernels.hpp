@@ -131,6 +131,51 @@ __device__ __forceinline__ void radius_walk(const PointGridDev &g, const float4 
     }
 }
 
+// The same walk for a consumer that works as a WAVE: f(point, hit) runs in uniform control flow after every 64-point read, every
+// lane with the point it read (unspecified where there was none) and whether it is a neighbour, so f may ballot, shuffle and meet
+// a barrier.  The rows, the reads and a read's lanes are those of radius_walk: the ascending (row, point) order of the hits is a
+// function of the index alone.
+template <typename F>
+__device__ __forceinline__ void radius_walk_wave(const PointGridDev &g, const float4 q, const RadiusQuery rq, int lane, F &f)
+{
+    const float ux = bound_pos(cell_pos(q.x, g.ox, g.inv_cell)), uy = bound_pos(cell_pos(q.y, g.oy, g.inv_cell)),
+                uz = bound_pos(cell_pos(q.z, g.oz, g.inv_cell));
+    int x0, x1, y0, y1, z0, z1;
+    radius_axis_cells(ux, rq.reach, g.dx, x0, x1);
+    radius_axis_cells(uy, rq.reach, g.dy, y0, y1);
+    radius_axis_cells(uz, rq.reach, g.dz, z0, z1);
+    const int ny = y1 - y0 + 1, rows = ny * (z1 - z0 + 1);
+    const float gx = axis_gap(ux, x0, x1);
+    for (int base = 0; base < rows; base += kKnnWave) {
+        const int row = base + lane;
+        uint32_t s = 0, e = 0;
+        if (row < rows) {
+            const int y = y0 + row % ny, z = z0 + row / ny;
+            if (!(grid_lb2(gx, axis_gap(uy, y, y), axis_gap(uz, z, z), g.cell) > rq.r2)) {
+                const size_t c0 = ((size_t)z * (size_t)g.dy + (size_t)y) * (size_t)g.dx;
+                s = g.start[c0 + (size_t)x0];
+                e = g.start[c0 + (size_t)x1 + 1];
+            }
+        }
+        unsigned long long todo = __ballot(e > s);
+        while (todo) {
+            const int l = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const uint32_t ss = __shfl(s, l), ee = __shfl(e, l);
+            for (uint32_t p = ss; p < ee; p += kKnnWave) {
+                const uint32_t i = p + (uint32_t)lane;
+                float4 t = q;
+                bool hit = false;
+                if (i < ee) {
+                    t = g.pts[i];
+                    hit = l2_simple(q.x, q.y, q.z, t.x, t.y, t.z) < rq.r2;
+                }
+                f(t, hit);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------ counts
 struct RadiusCount {
     uint32_t n = 0;
