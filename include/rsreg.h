@@ -629,7 +629,8 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
  * build can differ where a feature lies within float rounding of a bin edge.
  * The same cloud, normals and k give the same bytes whatever the context has indexed before: the counts are integers, every
  * float sum runs in the order above.
- * Not built: setSearchSurface, setIndices, other bin counts, PFH.  setRadiusSearch: rsreg_cloud_fpfh_radius, below.
+ * Not built: setSearchSurface with setKSearch, setIndices, other bin counts, PFH.  setRadiusSearch: rsreg_cloud_fpfh_radius,
+ * below; setSearchSurface with it: rsreg_cloud_fpfh_radius_surface.
  *
  * rsreg_cloud_fpfh: out = n records of 132 bytes laid out as pcl::FPFHSignature33 (float histogram[33]); width, height as the
  * input's; is_dense 0 if any record got NaNs, otherwise the input's.  out != in, out != normals.  Waits for the stream (whether a
@@ -934,7 +935,7 @@ int rsreg_cloud_normals_radius(rsreg_ctx *ctx, const rsreg_cloud *in, double rad
  * RSREG_ERR_INVALID_ARG, nothing launched, `out` untouched.  An empty cloud gives an empty cloud of 132-byte records; a cloud
  * without a finite record gives NaN rows, zero SPFH rows and zero counts.  The same cloud, normals and radius give the same bytes
  * whatever the context has indexed before.  Every call builds its index and walks it twice; no neighbour list is stored.
- * Not built: setSearchSurface, setIndices, other bin counts, PFH.
+ * Not built: setIndices, other bin counts, PFH.  setSearchSurface: rsreg_cloud_fpfh_radius_surface, below.
  *
  * rsreg_cloud_fpfh_radius: out = n records of 132 bytes laid out as pcl::FPFHSignature33, width and height as the input's.  Waits
  * for the stream (whether a row holds a NaN).
@@ -943,6 +944,51 @@ int rsreg_cloud_normals_radius(rsreg_ctx *ctx, const rsreg_cloud *in, double rad
 int rsreg_cloud_fpfh_radius(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, double radius, rsreg_cloud *out);
 int rsreg_cloud_spfh_radius(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, double radius, float *host_out /* n*33 */,
                             uint32_t *count_out /* n, may be NULL */);
+/* ---- setSearchSurface with setRadiusSearch(radius): the records of one cloud (the QUERIES: PCL's setInputCloud, nq of them) are
+ * searched for in another (the SURFACE: PCL's setSearchSurface, ns records), as PCL users compute normals and descriptors AT
+ * keypoints OVER the dense frame.  PCL 1.9.1 features/impl/feature.hpp (initCompute, searchForNeighbors) and fpfh.hpp
+ * (computeSPFHSignatures, computeFeature), recalled; PCL is not available to check against, so what follows IS the contract.
+ * Every cloud is a cloud of the context with records as above (x, y, z floats first, stride >= 12 and a multiple of 4); queries
+ * and surface may be the same handle.
+ * Neighbourhood: surface record j is a neighbour of finite query record i when j is finite and float32 d2(i, j) < (float)((double)
+ * radius * (double)radius), strictly -- the rule above, unchanged.  A query is not a neighbour of anything; a surface record that
+ * coincides with the query counts like any other.  m(i) = their number; it may be 0; a non-finite query has m = 0.
+ * Order: every sum runs in the order of the index over the SURFACE -- a function of the surface and the radius alone, not of the
+ * queries, their order, or what the context indexed before.  With queries == surface the counts and the normals are therefore the
+ * bytes of rsreg_cloud_radius_count and rsreg_cloud_normals_radius, and the FPFH rows are the bytes of rsreg_cloud_fpfh_radius on
+ * every record whose own normal is finite (the in-cloud call's NaN rule for a record's own normal does not exist here: the query has
+ * no normal and none is looked at).
+ * radius not finite or <= 0, normals whose size is not the surface's, a cloud of another context, `out` equal to an input, a null
+ * argument: RSREG_ERR_INVALID_ARG, nothing launched, `out` untouched.  Empty queries give an empty `out` of the right stride; an
+ * empty surface, or one without a finite record, gives every count 0, every row NaN and *n_spfh = 0.  Every call builds its own
+ * index over the surface.  Not built: setKSearch with a search surface (the k nearest samples of a dense surface are a support of
+ * a few millimetres), setIndices, neighbour lists as an output, PFH.
+ *
+ * rsreg_cloud_radius_count_surface: host_out[i] = m(i), nq uint32 in the queries' record order.
+ * rsreg_cloud_normals_radius_surface: the covariance of rsreg_cloud_normals_radius, unchanged -- C from d = neighbour - query
+ * record in double over the m surface neighbours; eigenvector, curvature, the flip (towards the viewpoint FROM THE QUERY RECORD)
+ * and the trace-0 case as they are.  m < 3 or a non-finite query: four quiet NaNs.  out: nq pcl::Normal records, width and height
+ * the queries'; is_dense 0 if any row got NaNs, otherwise the queries' own.  Waits for the stream.
+ * rsreg_cloud_fpfh_radius_surface, rsreg_cloud_spfh_radius_surface: surface_normals holds one record per surface record.
+ *   The SPFH row of a surface record is EXACTLY the row rsreg_cloud_spfh_radius(surface, surface_normals, radius) gives it: its
+ *   neighbourhood in the surface, the surface's normals, the same bytes.  A row is computed only for the surface records that are
+ *   a neighbour of at least one finite query (PCL's spfh_indices set): *n_spfh is the size of that set, needed_out[j] is 1 or 0,
+ *   and a host_out row that is not needed is zero.
+ *   The FPFH row of query i is the weighting above over its surface neighbours j with d2(i, j) != 0: w = 1.0f / d2 and
+ *   SPFH[j][b] * w in float32, H in double in the order of the surface's index, the block sums and the scaling as they are.
+ *   33 quiet NaNs for a non-finite query AND FOR A QUERY WITH m = 0 (PCL's searchForNeighbors(...) == 0 branch, recalled); 33
+ *   zeros when m > 0 but every neighbour is at distance 0.  out: nq records of 132 bytes, width and height the queries'; is_dense
+ *   0 if any row holds a NaN, otherwise the queries' own.  Both wait for the stream (the number of needed records).
+ *   count_out[i] = m(i) in the queries' record order. */
+int rsreg_cloud_radius_count_surface(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface, double radius,
+                                     uint32_t *host_out /* nq */);
+int rsreg_cloud_normals_radius_surface(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface, double radius,
+                                       const float viewpoint[3], rsreg_cloud *out);
+int rsreg_cloud_fpfh_radius_surface(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface,
+                                    const rsreg_cloud *surface_normals, double radius, rsreg_cloud *out, uint64_t *n_spfh /* may be NULL */);
+int rsreg_cloud_spfh_radius_surface(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface,
+                                    const rsreg_cloud *surface_normals, double radius, float *host_out /* ns*33 */,
+                                    uint32_t *needed_out /* ns, may be NULL */, uint32_t *count_out /* nq, may be NULL */);
 /* pcl::IntegralImageNormalEstimation on an ORGANIZED cloud of w x h records P[r][c] (src/edge_extractor.hpp:9-15 runs it with
  * AVERAGE_3D_GRADIENT, setMaxDepthChangeFactor(0.02f), setNormalSmoothingSize(10.0f) on every frame): a cost per pixel that
  * does not depend on the scene, and no index.  PCL 1.9.1 features/impl/integral_image_normal.hpp, recalled; PCL is not

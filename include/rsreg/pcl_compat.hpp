@@ -886,7 +886,10 @@ template <typename PointT> class RadiusOutlierRemoval {
 // rsreg_cloud_normals_radius; any number of neighbours, fewer than three give NaNs).  As in PCL exactly one of the two is set:
 // compute() refuses both and neither before any device call; setKSearch(0) / setRadiusSearch(0) unset them.  PointOutT: 32-byte
 // records laid out as pcl::Normal.  The covariance is the one the formula defines, in double about the query point -- PCL's float
-// accumulation about the origin is not reproduced (include/rsreg.h states the deviation).  No setSearchSurface, no setIndices.
+// accumulation about the origin is not reproduced (include/rsreg.h states the deviation).  setSearchSurface (a host cloud, or a
+// DeviceCloud that must outlive the calls): the neighbours come from that cloud (csrc/surface_kernels.hpp,
+// rsreg_cloud_normals_radius_surface), with setRadiusSearch only -- setKSearch with a surface is not built and compute() says so.
+// No setIndices.
 template <typename PointInT, typename PointOutT = Normal> class NormalEstimation {
     static_assert(sizeof(PointOutT) == 32, "the output records are laid out as pcl::Normal");
   public:
@@ -899,11 +902,13 @@ template <typename PointInT, typename PointOutT = Normal> class NormalEstimation
     double getRadiusSearch() const { return radius_; }
     void setViewPoint(float vx, float vy, float vz) { vp_[0] = vx; vp_[1] = vy; vp_[2] = vz; }
     void getViewPoint(float &vx, float &vy, float &vz) const { vx = vp_[0]; vy = vp_[1]; vz = vp_[2]; }
+    void setSearchSurface(const typename PointCloud<PointInT>::Ptr &surface) { surface_ = surface, dsurface_ = nullptr; }
+    void setSearchSurface(const DeviceCloud<PointInT> &surface) { dsurface_ = &surface, surface_.reset(); }
     void compute(PointCloud<PointOutT> &output)
     {
         if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
         check_search();
-        const std::shared_ptr<Context> ctx = ctx_ ? ctx_ : Context::Default();
+        const std::shared_ptr<Context> ctx = dsurface_ ? dsurface_->context() : ctx_ ? ctx_ : Context::Default();
         DeviceCloud<PointInT> tmp(*input_, ctx);
         DeviceCloud<PointOutT> normals(ctx);
         compute(tmp, normals);
@@ -912,21 +917,30 @@ template <typename PointInT, typename PointOutT = Normal> class NormalEstimation
     void compute(const DeviceCloud<PointInT> &input, DeviceCloud<PointOutT> &output)
     {
         check_search();
-        if (radius_ != 0.0)
-            check(rsreg_cloud_normals_radius(input.context()->get(), input.handle(), radius_, vp_, output.handle()), input.context()->get());
+        rsreg_ctx *c = input.context()->get();
+        if (surface_) {
+            DeviceCloud<PointInT> tmp(*surface_, input.context());
+            check(rsreg_cloud_normals_radius_surface(c, input.handle(), tmp.handle(), radius_, vp_, output.handle()), c);
+        } else if (dsurface_)
+            check(rsreg_cloud_normals_radius_surface(c, input.handle(), dsurface_->handle(), radius_, vp_, output.handle()), c);
+        else if (radius_ != 0.0)
+            check(rsreg_cloud_normals_radius(c, input.handle(), radius_, vp_, output.handle()), c);
         else
-            check(rsreg_cloud_normals(input.context()->get(), input.handle(), k_, vp_, output.handle()), input.context()->get());
+            check(rsreg_cloud_normals(c, input.handle(), k_, vp_, output.handle()), c);
     }
   private:
     void check_search() const
     {
         if (k_ != 0 && radius_ != 0.0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: both setKSearch and setRadiusSearch are set: set one of them to 0");
         if (k_ == 0 && radius_ == 0.0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: neither setKSearch nor setRadiusSearch is set");
+        if ((surface_ || dsurface_) && k_ != 0)
+            throw Error(RSREG_ERR_INVALID_ARG, "rsreg: NormalEstimation: setKSearch with setSearchSurface is not built; use setRadiusSearch");
     }
     int k_ = 0;                            // PCL's defaults: no search set (compute() refuses it)
     double radius_ = 0.0;
     float vp_[3] = {0.f, 0.f, 0.f};
-    typename PointCloud<PointInT>::Ptr input_;
+    typename PointCloud<PointInT>::Ptr input_, surface_;
+    const DeviceCloud<PointInT> *dsurface_ = nullptr;
     std::shared_ptr<Context> ctx_;
 };
 
@@ -941,8 +955,8 @@ static_assert(sizeof(FPFHSignature33) == 132, "pcl::FPFHSignature33 is 33 floats
 // search (csrc/fpfh_kernels.hpp, rsreg_cloud_fpfh; include/rsreg.h holds the contract).  PointNT: records that begin with
 // normal_x, normal_y, normal_z (pcl::Normal); PointOutT: 132-byte records laid out as pcl::FPFHSignature33.  PCL's two quirks are
 // kept (the weight is 1 / squared distance, the record's own SPFH does not enter); the pair features are computed in double, not
-// in float (the stated deviation).  setRadiusSearch is refused here: FPFHEstimationOMP, below, takes either search.  No
-// setSearchSurface, no setIndices.
+// in float (the stated deviation).  setRadiusSearch is refused here: FPFHEstimationOMP, below, takes either search and,
+// with a radius, a search surface.  No setSearchSurface, no setIndices.
 template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33> class FPFHEstimation {
     static_assert(sizeof(PointOutT) == 132, "the output records are laid out as pcl::FPFHSignature33");
     static_assert(sizeof(PointNT) >= 12 && sizeof(PointNT) % 4 == 0, "the normals' records begin with three floats");
@@ -984,7 +998,10 @@ template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignatur
 // (rsreg_cloud_fpfh), with setRadiusSearch over the exact radius search (csrc/fpfh_radius_kernels.hpp, rsreg_cloud_fpfh_radius;
 // include/rsreg.h holds the contract): a support of fixed metric size, any number of neighbours, the histogram sums in double (the
 // stated deviation).  As in PCL exactly one of the two is set: compute() refuses both and neither before any device call;
-// setKSearch(0) / setRadiusSearch(0) unset them.  setNumberOfThreads is accepted and ignored.  No setSearchSurface, no setIndices.
+// setKSearch(0) / setRadiusSearch(0) unset them.  setNumberOfThreads is accepted and ignored.  setSearchSurface (a host cloud, or a
+// DeviceCloud that must outlive the calls): the descriptors of the input cloud's records over that cloud, whose normals
+// setInputNormals must then hold, as in PCL (csrc/surface_kernels.hpp, rsreg_cloud_fpfh_radius_surface) -- with setRadiusSearch
+// only: setKSearch with a surface is not built and compute() says so.  No setIndices.
 template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignature33> class FPFHEstimationOMP {
     static_assert(sizeof(PointOutT) == 132, "the output records are laid out as pcl::FPFHSignature33");
     static_assert(sizeof(PointNT) >= 12 && sizeof(PointNT) % 4 == 0, "the normals' records begin with three floats");
@@ -998,36 +1015,48 @@ template <typename PointInT, typename PointNT, typename PointOutT = FPFHSignatur
     void setRadiusSearch(double radius) { radius_ = radius; }
     double getRadiusSearch() const { return radius_; }
     void setNumberOfThreads(unsigned int nr_threads = 0) { threads_ = nr_threads; }
+    void setSearchSurface(const typename PointCloud<PointInT>::Ptr &surface) { surface_ = surface, dsurface_ = nullptr; }
+    void setSearchSurface(const DeviceCloud<PointInT> &surface) { dsurface_ = &surface, surface_.reset(); }
     void compute(PointCloud<PointOutT> &output)
     {
         if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
         if (!normals_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputNormals not called");
         check_search();
-        const std::shared_ptr<Context> ctx = ctx_ ? ctx_ : Context::Default();
+        const std::shared_ptr<Context> ctx = dsurface_ ? dsurface_->context() : ctx_ ? ctx_ : Context::Default();
         DeviceCloud<PointInT> tmp(*input_, ctx);
         DeviceCloud<PointNT> tmp_normals(*normals_, ctx);
         DeviceCloud<PointOutT> features(ctx);
         compute(tmp, tmp_normals, features);
         features.download(output);
     }
+    // normals: the input's, or with a search surface the surface's
     void compute(const DeviceCloud<PointInT> &input, const DeviceCloud<PointNT> &normals, DeviceCloud<PointOutT> &output)
     {
         check_search();
-        if (radius_ != 0.0)
-            check(rsreg_cloud_fpfh_radius(input.context()->get(), input.handle(), normals.handle(), radius_, output.handle()), input.context()->get());
+        rsreg_ctx *c = input.context()->get();
+        if (surface_) {
+            DeviceCloud<PointInT> tmp(*surface_, input.context());
+            check(rsreg_cloud_fpfh_radius_surface(c, input.handle(), tmp.handle(), normals.handle(), radius_, output.handle(), nullptr), c);
+        } else if (dsurface_)
+            check(rsreg_cloud_fpfh_radius_surface(c, input.handle(), dsurface_->handle(), normals.handle(), radius_, output.handle(), nullptr), c);
+        else if (radius_ != 0.0)
+            check(rsreg_cloud_fpfh_radius(c, input.handle(), normals.handle(), radius_, output.handle()), c);
         else
-            check(rsreg_cloud_fpfh(input.context()->get(), input.handle(), normals.handle(), k_, output.handle()), input.context()->get());
+            check(rsreg_cloud_fpfh(c, input.handle(), normals.handle(), k_, output.handle()), c);
     }
   private:
     void check_search() const
     {
         if (k_ != 0 && radius_ != 0.0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: both setKSearch and setRadiusSearch are set: set one of them to 0");
         if (k_ == 0 && radius_ == 0.0) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: neither setKSearch nor setRadiusSearch is set");
+        if ((surface_ || dsurface_) && k_ != 0)
+            throw Error(RSREG_ERR_INVALID_ARG, "rsreg: FPFHEstimationOMP: setKSearch with setSearchSurface is not built; use setRadiusSearch");
     }
     int k_ = 0;                            // PCL's defaults: no search set (compute() refuses it)
     double radius_ = 0.0;
     unsigned int threads_ = 0;
-    typename PointCloud<PointInT>::Ptr input_;
+    typename PointCloud<PointInT>::Ptr input_, surface_;
+    const DeviceCloud<PointInT> *dsurface_ = nullptr;
     typename PointCloud<PointNT>::Ptr normals_;
     std::shared_ptr<Context> ctx_;
 };

@@ -344,6 +344,73 @@ class DeviceCloud:
         _l.check(rc, self.ctx.h)
         return (out, m) if counts else out
 
+    # ---- setSearchSurface: this cloud's records are the queries, `surface` (a DeviceCloud of this context; this one is allowed) is
+    # searched (include/rsreg.h holds the contract)
+    def radius_count_surface(self, surface, radius):
+        """radiusSearch of every record of this cloud in `surface`, counted (rsreg_cloud_radius_count_surface, exact): uint32 per
+        record, the finite surface records with float32 d2 < (float)(radius * radius), strictly; 0 for a non-finite record."""
+        out = np.zeros(self.info()[0], np.uint32)
+        _l.check(_l.lib().rsreg_cloud_radius_count_surface(self.ctx.h, self.h, surface.h, float(radius), out.ctypes.data), self.ctx.h)
+        return out
+
+    def normals_radius_surface_cloud(self, surface, radius, viewpoint=None):
+        """pcl::NormalEstimation with setSearchSurface(surface) and setRadiusSearch(radius) (rsreg_cloud_normals_radius_surface): a
+        DeviceCloud of one 32-byte pcl::Normal record per record of this cloud, from its neighbours in `surface`; fewer than three:
+        NaNs."""
+        out = DeviceCloud(ctx=self.ctx)
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float32).reshape(3)
+        rc = _l.lib().rsreg_cloud_normals_radius_surface(self.ctx.h, self.h, surface.h, float(radius), None if vp is None else vp.ctypes.data, out.h)
+        if rc:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out
+
+    def normals_radius_surface(self, surface, radius, viewpoint=None):
+        """(n, 4) float32: normal_x, normal_y, normal_z, curvature of every record of this cloud over its neighbours in `surface`."""
+        out = self.normals_radius_surface_cloud(surface, radius, viewpoint)
+        rec = out.download_normals().points
+        out.close()
+        return np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
+
+    def fpfh_radius_surface_cloud(self, surface, normals, radius, n_spfh=False):
+        """pcl::FPFHEstimationOMP with setSearchSurface(surface), setInputNormals(normals: the SURFACE's, see fpfh()) and
+        setRadiusSearch(radius) (rsreg_cloud_fpfh_radius_surface): a DeviceCloud of one 132-byte pcl::FPFHSignature33 record per
+        record of this cloud.  n_spfh: (cloud, the number of surface records whose SPFH row was computed)."""
+        nrm, made = surface._normals_on_device(normals)
+        out = DeviceCloud(ctx=self.ctx)
+        n = C.c_uint64(0)
+        rc = _l.lib().rsreg_cloud_fpfh_radius_surface(self.ctx.h, self.h, surface.h, nrm.h, float(radius), out.h, C.byref(n))
+        if made:
+            nrm.close()
+        if rc:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return (out, int(n.value)) if n_spfh else out
+
+    def fpfh_radius_surface(self, surface, normals, radius):
+        """(n, 33) float32: the Fast Point Feature Histogram of every record of this cloud over its neighbours in `surface` (NaN
+        for a record that is not finite or has no neighbour)."""
+        out = self.fpfh_radius_surface_cloud(surface, normals, radius)
+        hist = out.download_fpfh().points["histogram"]
+        out.close()
+        return hist
+
+    def spfh_radius_surface(self, surface, normals, radius):
+        """(rows, needed, m): the (ns, 33) float32 SPFH rows of `surface` (rsreg_cloud_spfh_radius_surface) -- the rows
+        surface.spfh_radius(normals, radius) gives where needed[j] (ns, uint32) is 1, a neighbour of a record of this cloud, zero
+        elsewhere -- and m (n, uint32), every record's number of neighbours in `surface`."""
+        nrm, made = surface._normals_on_device(normals)
+        ns = surface.info()[0]
+        out = np.zeros((ns, 33), np.float32)
+        needed = np.zeros(ns, np.uint32)
+        m = np.zeros(self.info()[0], np.uint32)
+        rc = _l.lib().rsreg_cloud_spfh_radius_surface(self.ctx.h, self.h, surface.h, nrm.h, float(radius), out.ctypes.data, needed.ctypes.data,
+                                                      m.ctypes.data)
+        if made:
+            nrm.close()
+        _l.check(rc, self.ctx.h)
+        return out, needed, m
+
     def download_fpfh(self):
         """download() of a cloud of pcl::FPFHSignature33 records (what FPFHEstimation.compute returns): an FPFHCloud."""
         n, stride, w, h, dense = self.info()
@@ -1381,19 +1448,47 @@ class RadiusOutlierRemoval:
         return _filter_io(self._in, self.ctx, run)
 
 
+def _compute_over_surface(est, run, download):
+    """compute() of an estimator with an input cloud (est._in) and an optional search surface (est._surface), each a host cloud or
+    a DeviceCloud: run(input on the device, surface on the device or None) gives the DeviceCloud of the rows; a DeviceCloud input
+    gets it as it is, a host input gets download(rows).  What was uploaded here is released here."""
+    ctx = next((c.ctx for c in (est._in, est._surface) if isinstance(c, DeviceCloud)), None) or est.ctx or default_context()
+    made = []
+
+    def on_device(cloud):
+        if cloud is None or isinstance(cloud, DeviceCloud):
+            return cloud
+        made.append(DeviceCloud(cloud, ctx=ctx))
+        return made[-1]
+
+    try:
+        dev_in, dev_surface = on_device(est._in), on_device(est._surface)
+        rows = run(dev_in, dev_surface) if dev_surface is not None else run(dev_in)
+        if isinstance(est._in, DeviceCloud):
+            return rows
+        out = download(rows)
+        rows.close()
+        return out
+    finally:
+        for d in made:
+            d.close()
+
+
 class NormalEstimation:
     """pcl::NormalEstimation<PointXYZRGB, Normal> on the GPU: with setKSearch over an exact k-nearest-neighbour search
     (csrc/normals_kernels.hpp, rsreg_cloud_normals), 3 <= k <= 64, or with setRadiusSearch over an exact radius search
     (csrc/radius_kernels.hpp, rsreg_cloud_normals_radius), any number of neighbours.  As in PCL exactly one of the two is set:
     compute() refuses both and neither; setKSearch(0) / setRadiusSearch(0) unset them.  The covariance is the one the formula
     defines, in double about the query point: PCL's float accumulation about the origin is not reproduced (include/rsreg.h).
-    compute() of a DeviceCloud gives a DeviceCloud of pcl::Normal records, of a host cloud a NormalCloud."""
+    setSearchSurface (with setRadiusSearch only): the neighbours come from another cloud (csrc/surface_kernels.hpp,
+    rsreg_cloud_normals_radius_surface).  compute() of a DeviceCloud gives a DeviceCloud of pcl::Normal records, of a host cloud a NormalCloud."""
 
     def __init__(self, ctx=None):
         self.k = 0                                   # PCL's default: no search set
         self.radius = 0.0
         self.viewpoint = (0.0, 0.0, 0.0)
         self._in = None
+        self._surface = None
         self.ctx = ctx
 
     def setInputCloud(self, cloud):
@@ -1417,7 +1512,14 @@ class NormalEstimation:
     def getViewPoint(self):
         return self.viewpoint
 
-    def _normals_cloud(self, dev):
+    def setSearchSurface(self, surface):
+        """The cloud the neighbours are taken from (a host cloud or a DeviceCloud; None: the input cloud itself, PCL's default).
+        With a surface only setRadiusSearch is built."""
+        self._surface = surface
+
+    def _normals_cloud(self, dev, surface=None):
+        if surface is not None:
+            return dev.normals_radius_surface_cloud(surface, self.radius, self.viewpoint)
         return dev.normals_radius_cloud(self.radius, self.viewpoint) if self.radius != 0.0 else dev.normals_cloud(self.k, self.viewpoint)
 
     def compute(self):
@@ -1427,24 +1529,17 @@ class NormalEstimation:
             raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "both setKSearch and setRadiusSearch are set: set one of them to 0")
         if self.k == 0 and self.radius == 0.0:
             raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "neither setKSearch nor setRadiusSearch is set")
-        if isinstance(self._in, DeviceCloud):
-            return self._normals_cloud(self._in)
-        tmp = DeviceCloud(self._in, ctx=self.ctx or default_context())
-        try:
-            dev = self._normals_cloud(tmp)
-            out = dev.download_normals()
-            dev.close()
-        finally:
-            tmp.close()
-        return out
+        if self._surface is not None and self.k != 0:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "NormalEstimation: setKSearch with setSearchSurface is not built; use setRadiusSearch")
+        return _compute_over_surface(self, self._normals_cloud, lambda dev: dev.download_normals())
 
 
 class FPFHEstimation:
     """pcl::FPFHEstimation<PointXYZRGB, Normal, FPFHSignature33> on the GPU with setKSearch, 2 <= k <= 64, over the exact
     k-nearest-neighbour search (csrc/fpfh_kernels.hpp, rsreg_cloud_fpfh; include/rsreg.h holds the contract).  PCL's two quirks are
     kept -- the weight is 1 / squared distance, the record's own SPFH does not enter -- and the pair features are computed in
-    double, not in float.  setRadiusSearch is refused here: FPFHEstimationOMP, below, takes either search.  setSearchSurface and
-    setIndices are not built.  compute() of a DeviceCloud gives a DeviceCloud of pcl::FPFHSignature33 records, of a host cloud an
+    double, not in float.  setRadiusSearch and setSearchSurface are refused here: FPFHEstimationOMP, below, takes either search
+    and, with a radius, a search surface.  setIndices is not built.  compute() of a DeviceCloud gives a DeviceCloud of pcl::FPFHSignature33 records, of a host cloud an
     FPFHCloud."""
 
     def __init__(self, ctx=None):
@@ -1468,6 +1563,10 @@ class FPFHEstimation:
     def setRadiusSearch(self, radius):
         if float(radius) != 0.0:
             raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "FPFHEstimation: setRadiusSearch is not built; use setKSearch")
+
+    def setSearchSurface(self, surface):
+        if surface is not None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "FPFHEstimation: setSearchSurface is not built; use FPFHEstimationOMP with setRadiusSearch")
 
     def compute(self):
         if self._in is None:
@@ -1493,7 +1592,9 @@ class FPFHEstimationOMP:
     FPFHEstimation (rsreg_cloud_fpfh); with setRadiusSearch over the exact radius search (csrc/fpfh_radius_kernels.hpp,
     rsreg_cloud_fpfh_radius; include/rsreg.h holds the contract), any number of neighbours, the histogram sums in double.  As in
     PCL exactly one of the two is set: compute() refuses both and neither before any device call; setKSearch(0) /
-    setRadiusSearch(0) unset them.  setNumberOfThreads is accepted and ignored.  compute() of a DeviceCloud gives a DeviceCloud of
+    setRadiusSearch(0) unset them.  setNumberOfThreads is accepted and ignored.  setSearchSurface (with setRadiusSearch only): the
+    descriptors of the input cloud's records over another cloud and that cloud's normals (csrc/surface_kernels.hpp,
+    rsreg_cloud_fpfh_radius_surface).  compute() of a DeviceCloud gives a DeviceCloud of
     pcl::FPFHSignature33 records, of a host cloud an FPFHCloud."""
 
     def __init__(self, ctx=None):
@@ -1501,6 +1602,7 @@ class FPFHEstimationOMP:
         self.radius = 0.0
         self.threads = 0
         self._in = None
+        self._surface = None
         self._normals = None
         self.ctx = ctx
 
@@ -1525,7 +1627,14 @@ class FPFHEstimationOMP:
     def setNumberOfThreads(self, threads=0):
         self.threads = int(threads)
 
-    def _fpfh_cloud(self, dev):
+    def setSearchSurface(self, surface):
+        """The cloud the neighbours are taken from (a host cloud or a DeviceCloud; None: the input cloud itself, PCL's default).
+        With a surface setInputNormals must hold the SURFACE's normals, as in PCL, and only setRadiusSearch is built."""
+        self._surface = surface
+
+    def _fpfh_cloud(self, dev, surface=None):
+        if surface is not None:
+            return dev.fpfh_radius_surface_cloud(surface, self._normals, self.radius)
         return dev.fpfh_radius_cloud(self._normals, self.radius) if self.radius != 0.0 else dev.fpfh_cloud(self._normals, self.k)
 
     def compute(self):
@@ -1537,16 +1646,9 @@ class FPFHEstimationOMP:
             raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "both setKSearch and setRadiusSearch are set: set one of them to 0")
         if self.k == 0 and self.radius == 0.0:
             raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "neither setKSearch nor setRadiusSearch is set")
-        if isinstance(self._in, DeviceCloud):
-            return self._fpfh_cloud(self._in)
-        tmp = DeviceCloud(self._in, ctx=self.ctx or default_context())
-        try:
-            dev = self._fpfh_cloud(tmp)
-            out = dev.download_fpfh()
-            dev.close()
-        finally:
-            tmp.close()
-        return out
+        if self._surface is not None and self.k != 0:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "FPFHEstimationOMP: setKSearch with setSearchSurface is not built; use setRadiusSearch")
+        return _compute_over_surface(self, self._fpfh_cloud, lambda dev: dev.download_fpfh())
 
 
 class CorrespondenceEstimation:

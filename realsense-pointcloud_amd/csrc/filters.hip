@@ -7,7 +7,8 @@
 // pcl::RadiusOutlierRemoval and NormalEstimation by radius: the exact radius search of radius_kernels.hpp over an index of its own
 // placement, then the same flag / scan / gather, or k_normals' tail.  pcl::FPFHEstimation (setKSearch): the k-NN search once, with
 // the pair features of fpfh_kernels.hpp behind it, then the weighting pass over the neighbour rows the search left.  pcl::FPFHEstimationOMP
-// (setRadiusSearch): fpfh_radius_kernels.hpp's two walks of the radius index, no neighbour list between them.
+// (setRadiusSearch): fpfh_radius_kernels.hpp's two walks of the radius index, no neighbour list between them.  setSearchSurface
+// (the *_surface calls): the same radius index over the surface, searched from the records of another cloud (surface_kernels.hpp).
 // Everything runs on the context's stream with the index rsreg_ctx::knn and the scratch rsreg_ctx::filt (the radius search:
 // rsreg_ctx::rad too): nothing here reads or writes a buffer of the alignment's index or of the fitness indices.
 #include <cmath>
@@ -18,6 +19,7 @@
 #include "radius_kernels.hpp"
 #include "fpfh_kernels.hpp"
 #include "fpfh_radius_kernels.hpp"
+#include "surface_kernels.hpp"
 #include "cloud_ops.hpp"
 
 using namespace rsreg;
@@ -266,9 +268,220 @@ template <typename Launch> int normals_into(rsreg_ctx *ctx, const CloudView &v, 
     return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kNormalBytes, v.width, v.height, (nfin < n || any_nan) ? 0 : v.is_dense);
 }
 
+// ---- a search surface (surface_kernels.hpp): the queries are one cloud, the index holds another
+constexpr size_t kFpfhBytes = kFpfhRow * 4;   // pcl::FPFHSignature33
+enum SurfacePass { kSurfaceOrder, kSurfaceCount, kSurfaceCountMark };   // how far surface_begin goes
+
+struct SurfaceCall {
+    CloudView qv, sv, nv;     // the queries, the surface, the surface's normals
+    RadiusQuery rq;
+    uint32_t nfin = 0;        // finite records of the surface: 0 = nothing is indexed and no query has a neighbour
+    SurfaceQueries sq;        // the queries in the order of the surface cells they fall in (nfin and qv.n above 0)
+    bool searched() const { return nfin && qv.n; }
+};
+
+// The way in of every call with a search surface, not waited for: the views (normals: null for a call without them), the refusals,
+// the index over the surface, the queries' order, and -- pass above kSurfaceOrder -- every query's count in rs.d_count (zero for a
+// non-finite one, and for all of them when the surface holds nothing finite); kSurfaceCountMark: rs.d_mark[j] = 1 for every
+// surface record j that is a neighbour of a query, 0 for the others.
+int surface_begin(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface, const rsreg_cloud *normals, const rsreg_cloud *out, double radius,
+                  SurfacePass pass, SurfaceCall &sc)
+{
+    int rc = cloud_view(ctx, queries, out, kXyzRule, sc.qv);
+    if (rc) return rc;
+    rc = cloud_view(ctx, surface, nullptr, kXyzRule, sc.sv);
+    if (rc) return rc;
+    if (normals) {
+        rc = cloud_view(ctx, normals, nullptr, kXyzRule, sc.nv);
+        if (rc) return rc;
+    }
+    if (!(radius > 0.0) || !std::isfinite(radius)) return fail(ctx, RSREG_ERR_INVALID_ARG, "the radius must be finite and above 0");
+    if (normals && sc.nv.n != sc.sv.n) return fail(ctx, RSREG_ERR_INVALID_ARG, "the normals must hold one record per record of the search surface");
+    if (sc.qv.n >= (1ull << 30)) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
+    RadiusScratch &rs = ctx->rad;
+    hipStream_t st = ctx->stream;
+    const uint32_t nq = (uint32_t)sc.qv.n;
+    if (pass != kSurfaceOrder) {
+        RSREG_HIP(ctx, rs.d_count.reserve(sc.qv.n * 4 + 16));
+        if (nq) RSREG_HIP(ctx, hipMemsetAsync(rs.d_count.ptr, 0, sc.qv.n * 4, st));
+    }
+    if (pass == kSurfaceCountMark) {
+        RSREG_HIP(ctx, rs.d_mark.reserve(sc.sv.n * 4 + 16));
+        if (sc.sv.n) RSREG_HIP(ctx, hipMemsetAsync(rs.d_mark.ptr, 0, sc.sv.n * 4, st));
+    }
+    if (!nq || !sc.sv.n) return RSREG_OK;
+    rc = radius_index_device(ctx, sc.sv, radius, nullptr, &sc.rq, &sc.nfin);
+    if (rc || !sc.nfin) return rc;
+    // the queries by the surface cell they fall in, clamped like any point; a non-finite one behind them all
+    const PointGridDev g = grid_dev(ctx->knn);
+    const size_t cells = (size_t)ctx->knn.dims[0] * (size_t)ctx->knn.dims[1] * (size_t)ctx->knn.dims[2];
+    unsigned bits = 1;
+    while ((cells >> bits) != 0) ++bits;
+    for (int k = 0; k < 2; ++k) {
+        RSREG_HIP(ctx, rs.d_qkeys[k].reserve(sc.qv.n * 4 + 16));
+        RSREG_HIP(ctx, rs.d_qvals[k].reserve(sc.qv.n * 4 + 16));
+    }
+    RSREG_HIP(ctx, rs.d_sort.reserve((size_t)osort_plan<uint32_t>(sc.qv.n, 0, bits).words * 4));
+    uint32_t *keys[2] = {rs.d_qkeys[0].as<uint32_t>(), rs.d_qkeys[1].as<uint32_t>()}, *vals[2] = {rs.d_qvals[0].as<uint32_t>(), rs.d_qvals[1].as<uint32_t>()};
+    k_radius_cell_keys<<<div_up(nq, kBlock), kBlock, 0, st>>>(RadiusRecords{sc.qv.rec, sc.qv.stride, nullptr}, nq, g, (uint32_t)cells, keys[0], vals[0]);
+    RSREG_HIP(ctx, hipGetLastError());
+    bool in_first = true;
+    RSREG_HIP(ctx, osort_pairs_cleared<uint32_t>(rs.d_sort.as<uint32_t>(), keys[0], keys[1], vals[0], vals[1], sc.qv.n, 0, bits, st, &in_first));
+    const int at = in_first ? 0 : 1;
+    sc.sq = SurfaceQueries{sc.qv.rec, sc.qv.stride, keys[at], vals[at], nq, (uint32_t)cells};
+    if (pass == kSurfaceOrder) return RSREG_OK;
+    k_surface_count_mark<<<std::min<uint32_t>(nq, 1u << 16), kKnnWave, 0, st>>>(g, sc.rq, sc.sq, rs.d_count.as<uint32_t>(),
+                                                                               pass == kSurfaceCountMark ? rs.d_mark.as<uint32_t>() : nullptr);
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
+// Behind surface_begin(kSurfaceCountMark), with queries that were searched: the list of the needed points of the index (rs.d_list;
+// waits for their number, *n_spfh_out) and their SPFH rows in fs.d_spfh, the other rows zero if `zero_rest` and unwritten otherwise.
+int surface_spfh_device(rsreg_ctx *ctx, const SurfaceCall &sc, bool zero_rest, uint32_t *n_spfh_out)
+{
+    FilterScratch &fs = ctx->filt;
+    RadiusScratch &rs = ctx->rad;
+    PointGrid &kx = ctx->knn;
+    hipStream_t st = ctx->stream;
+    const PointGridDev g = grid_dev(kx);
+    const uint32_t nfin = sc.nfin;
+    RSREG_HIP(ctx, rs.d_need.reserve((size_t)nfin * 4 + 16));
+    RSREG_HIP(ctx, rs.d_list.reserve((size_t)nfin * 4 + 16));
+    RSREG_HIP(ctx, kx.d_scan.reserve(oscan_scratch_bytes<uint32_t>(nfin)));
+    RSREG_HIP(ctx, fs.d_spfh.reserve(sc.sv.n * kFpfhRow * 4 + 16));
+    uint32_t *need = rs.d_need.as<uint32_t>(), *h_n = fs.host.as<uint32_t>() + kFiltWord;
+    k_surface_needed<<<div_up(nfin, kBlock), kBlock, 0, st>>>(g, rs.d_mark.as<uint32_t>(), need);
+    RSREG_HIP(ctx, hipGetLastError());
+    RSREG_HIP(ctx, (oscan<uint32_t, true>(need, need, nfin, 0u, kx.d_scan.ptr, st)));
+    RSREG_HIP(ctx, hipMemcpyAsync(h_n, need + (nfin - 1), 4, hipMemcpyDeviceToHost, st));
+    if (zero_rest) RSREG_HIP(ctx, hipMemsetAsync(fs.d_spfh.ptr, 0, sc.sv.n * kFpfhRow * 4, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    const uint32_t n_spfh = *h_n;
+    *n_spfh_out = n_spfh;
+    if (!n_spfh) return RSREG_OK;
+    k_surface_list<<<div_up(nfin, kBlock), kBlock, 0, st>>>(need, nfin, rs.d_list.as<uint32_t>());
+    RSREG_HIP(ctx, hipGetLastError());
+    k_surface_spfh<<<std::min<uint32_t>(n_spfh, 1u << 16), kKnnWave, 0, st>>>(g, sc.rq, sc.nv.rec, sc.nv.stride, rs.d_list.as<uint32_t>(), n_spfh,
+                                                                             fs.d_spfh.as<float>());
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
+// The tail of a call that leaves one row of `row_bytes` per query in fs.d_out (room for them has been reserved): the rows of
+// non-finite queries have been queued by the caller; with nothing to search every row is `nan_mask`'s, otherwise launch(d_any)
+// queues the kernel of the finite ones.  The rows go to `out` with the queries' shape; a NaN row makes it not dense.
+template <typename Launch> int surface_rows_into(rsreg_ctx *ctx, const SurfaceCall &sc, size_t row_bytes, unsigned long long nan_mask, rsreg_cloud *out, Launch launch)
+{
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    const CloudView &qv = sc.qv;
+    bool nan_rows = false;
+    if (qv.n && !sc.nfin) {
+        const size_t words = qv.n * (row_bytes / 4);
+        k_surface_no_neighbours<<<div_up64(words, kBlock), kBlock, 0, st>>>(fs.d_out.as<float>(), words, (uint32_t)(row_bytes / 4), nan_mask);
+        RSREG_HIP(ctx, hipGetLastError());
+        nan_rows = true;
+    } else if (qv.n) {
+        // whether a query was not finite: the last key of the sorted pairs; it comes home with the kernel's word
+        uint32_t *h_last = fs.host.as<uint32_t>() + kFiltWord + 1, any_nan = 0;
+        RSREG_HIP(ctx, hipMemcpyAsync(h_last, sc.sq.keys + (sc.sq.n - 1), 4, hipMemcpyDeviceToHost, st));
+        const int rc = word_home(ctx, true, launch, &any_nan);
+        if (rc) return rc;
+        nan_rows = any_nan || *h_last == sc.sq.no_cell;
+    }
+    return rsreg_cloud_adopt_(out, &fs.d_out, qv.n, row_bytes, qv.width, qv.height, nan_rows ? 0 : qv.is_dense);
+}
+
 }  // namespace
 
 extern "C" {
+
+int rsreg_cloud_radius_count_surface(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface, double radius, uint32_t *host_out)
+{
+    if (!host_out) return RSREG_ERR_INVALID_ARG;
+    SurfaceCall sc;
+    int rc = surface_begin(ctx, queries, surface, nullptr, nullptr, radius, kSurfaceCount, sc);
+    if (rc || !sc.qv.n) return rc;
+    RSREG_HIP(ctx, hipMemcpyAsync(host_out, ctx->rad.d_count.ptr, sc.qv.n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RSREG_OK;
+}
+
+int rsreg_cloud_normals_radius_surface(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface, double radius, const float viewpoint[3],
+                                       rsreg_cloud *out)
+{
+    if (!out || out == queries || out == surface) return RSREG_ERR_INVALID_ARG;
+    SurfaceCall sc;
+    int rc = surface_begin(ctx, queries, surface, nullptr, out, radius, kSurfaceOrder, sc);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    const uint32_t nq = (uint32_t)sc.qv.n;
+    RSREG_HIP(ctx, fs.d_out.reserve(sc.qv.n * kNormalBytes + 16));
+    if (sc.searched()) {
+        k_normals_not_finite<<<div_up(nq, kBlock), kBlock, 0, st>>>(sc.qv.rec, sc.qv.stride, nq, fs.d_out.as<float>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    const float vp[3] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f, viewpoint ? viewpoint[2] : 0.0f};
+    return surface_rows_into(ctx, sc, kNormalBytes, 0x17ull, out, [&](uint32_t *d_any) {
+        k_surface_normals<<<std::min<uint32_t>(nq, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), sc.rq, sc.sq, vp[0], vp[1], vp[2], fs.d_out.as<float>(), d_any);
+    });
+}
+
+int rsreg_cloud_spfh_radius_surface(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface, const rsreg_cloud *surface_normals, double radius,
+                                    float *host_out, uint32_t *needed_out, uint32_t *count_out)
+{
+    if (!host_out || !surface_normals) return RSREG_ERR_INVALID_ARG;
+    SurfaceCall sc;
+    int rc = surface_begin(ctx, queries, surface, surface_normals, nullptr, radius, kSurfaceCountMark, sc);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    if (!sc.searched()) {   // nothing is needed and nobody has a neighbour
+        std::memset(host_out, 0, sc.sv.n * kFpfhRow * 4);
+        if (needed_out) std::memset(needed_out, 0, sc.sv.n * 4);
+        if (count_out) std::memset(count_out, 0, sc.qv.n * 4);
+        return RSREG_OK;
+    }
+    uint32_t n_spfh = 0;
+    rc = surface_spfh_device(ctx, sc, true, &n_spfh);
+    if (rc) return rc;
+    RSREG_HIP(ctx, hipMemcpyAsync(host_out, ctx->filt.d_spfh.ptr, sc.sv.n * kFpfhRow * 4, hipMemcpyDeviceToHost, st));
+    if (needed_out) RSREG_HIP(ctx, hipMemcpyAsync(needed_out, ctx->rad.d_mark.ptr, sc.sv.n * 4, hipMemcpyDeviceToHost, st));
+    if (count_out) RSREG_HIP(ctx, hipMemcpyAsync(count_out, ctx->rad.d_count.ptr, sc.qv.n * 4, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    return RSREG_OK;
+}
+
+int rsreg_cloud_fpfh_radius_surface(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface, const rsreg_cloud *surface_normals, double radius,
+                                    rsreg_cloud *out, uint64_t *n_spfh_out)
+{
+    if (!out || !surface_normals || out == queries || out == surface || out == surface_normals) return RSREG_ERR_INVALID_ARG;
+    SurfaceCall sc;
+    int rc = surface_begin(ctx, queries, surface, surface_normals, out, radius, kSurfaceCountMark, sc);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    RadiusScratch &rs = ctx->rad;
+    hipStream_t st = ctx->stream;
+    const uint32_t nq = (uint32_t)sc.qv.n;
+    uint32_t n_spfh = 0;
+    if (sc.searched()) {
+        rc = surface_spfh_device(ctx, sc, false, &n_spfh);
+        if (rc) return rc;
+    }
+    RSREG_HIP(ctx, fs.d_out.reserve(sc.qv.n * kFpfhBytes + 16));
+    if (sc.searched()) {
+        k_fpfh_radius_not_finite<<<div_up64((unsigned long long)nq * kFpfhRow, kBlock), kBlock, 0, st>>>(sc.qv.rec, sc.qv.stride, nq, fs.d_out.as<float>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    rc = surface_rows_into(ctx, sc, kFpfhBytes, 0x1ffffffffull, out, [&](uint32_t *d_any) {
+        k_surface_fpfh_weight<<<std::min<uint32_t>(nq, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), sc.rq, sc.sq, rs.d_count.as<uint32_t>(), fs.d_spfh.as<float>(),
+                                                                                    fs.d_out.as<float>(), d_any);
+    });
+    if (rc) return rc;
+    if (n_spfh_out) *n_spfh_out = n_spfh;
+    return RSREG_OK;
+}
 
 int rsreg_cloud_passthrough(rsreg_ctx *ctx, const rsreg_cloud *in, int field, float lo, float hi, int negative, int keep_organized,
                             rsreg_cloud *out)

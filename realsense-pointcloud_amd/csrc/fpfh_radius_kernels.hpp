@@ -87,35 +87,40 @@ struct RadiusSpfhPairs {
     }
 };
 
-// One workgroup of ONE wave per finite record, queries in cell order (the grid-stride loop of k_normals_radius).  Row `record` of
-// spfh: the 33 floats; count[record] (nullable) = m, the neighbours within the radius, the record itself among them.  The rows and
-// counts of records not visited (non-finite ones) have been zeroed before the launch.
+// The SPFH row of the indexed point q (q.w: its record) by one wave: row `record` of spfh, the 33 floats; count[record] (nullable) = m,
+// the neighbours within the radius, the record itself among them.  queue, cnt: the workgroup's LDS (RadiusSpfhPairs); the barrier at
+// the end lets the next row clear the counts.
+__device__ __forceinline__ void radius_spfh_row(const PointGridDev &g, const RadiusQuery rq, const char *nrm, size_t nstride, const float4 q, float4 *queue,
+                                                uint32_t *cnt, int lane, float *spfh, uint32_t *count)
+{
+    const size_t record = (size_t)__float_as_uint(q.w);
+    const float *ni = rec_xyz(nrm, nstride, record);
+    RadiusSpfhPairs f{queue, cnt, nrm, nstride, q, ni[0], ni[1], ni[2], false, lane};
+    f.own = finite3(f.nix, f.niy, f.niz);
+    if (lane < kFpfhRow) cnt[lane] = 0u;
+    __syncthreads();
+    radius_walk_wave(g, q, rq, lane, f);
+    f.finish();
+    if (lane < kFpfhRow) {
+        // m == 1: no pair, no addition -- the infinite increment is never used
+        const float hist_incr = __fdiv_rn(100.0f, (float)(f.m - 1u));
+        const uint32_t c = cnt[lane];
+        float acc = 0.0f;
+        for (uint32_t u = 0; u < c; ++u) acc = __fadd_rn(acc, hist_incr);
+        spfh[record * kFpfhRow + (size_t)lane] = acc;
+    }
+    if (count && lane == 0) count[record] = f.m;
+    __syncthreads();   // (the counts have been read: the next row may clear them)
+}
+
+// One workgroup of ONE wave per finite record, queries in cell order (the grid-stride loop of k_normals_radius): radius_spfh_row of
+// every indexed point.  The rows and counts of records not visited (non-finite ones) have been zeroed before the launch.
 __global__ __launch_bounds__(kKnnWave) void k_fpfh_radius_spfh(PointGridDev g, RadiusQuery rq, const char *nrm, size_t nstride, float *spfh, uint32_t *count)
 {
     __shared__ float4 queue[2 * kKnnWave];
     __shared__ uint32_t cnt[kFpfhRow];
     const int lane = (int)threadIdx.x;
-    for (uint32_t j = blockIdx.x; j < g.n; j += gridDim.x) {
-        const float4 q = g.pts[j];
-        const size_t record = (size_t)__float_as_uint(q.w);
-        const float *ni = rec_xyz(nrm, nstride, record);
-        RadiusSpfhPairs f{queue, cnt, nrm, nstride, q, ni[0], ni[1], ni[2], false, lane};
-        f.own = finite3(f.nix, f.niy, f.niz);
-        if (lane < kFpfhRow) cnt[lane] = 0u;
-        __syncthreads();
-        radius_walk_wave(g, q, rq, lane, f);
-        f.finish();
-        if (lane < kFpfhRow) {
-            // m == 1: no pair, no addition -- the infinite increment is never used
-            const float hist_incr = __fdiv_rn(100.0f, (float)(f.m - 1u));
-            const uint32_t c = cnt[lane];
-            float acc = 0.0f;
-            for (uint32_t u = 0; u < c; ++u) acc = __fadd_rn(acc, hist_incr);
-            spfh[record * kFpfhRow + (size_t)lane] = acc;
-        }
-        if (count && lane == 0) count[record] = f.m;
-        __syncthreads();   // (the counts have been read: the next query may clear them)
-    }
+    for (uint32_t j = blockIdx.x; j < g.n; j += gridDim.x) radius_spfh_row(g, rq, nrm, nstride, g.pts[j], queue, cnt, lane, spfh, count);
 }
 
 // The consumer of the second pass: lane b < 33 owns bin b.

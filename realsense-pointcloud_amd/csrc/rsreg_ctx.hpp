@@ -206,7 +206,12 @@ struct FilterScratch {
 struct RadiusScratch {
     DevBuf d_keys[2], d_vals[2];   // uint32 per record, twice: (cell, record) pairs on their way through the stable sort that places the index
     DevBuf d_sort;                 // the sort's scratch block
-    DevBuf d_count;                // uint32 per record: its neighbours within the radius
+    DevBuf d_count;                // uint32 per record: its neighbours within the radius (a search surface: per query)
+    // a search surface (surface_kernels.hpp): the index holds the surface, the queries are another cloud
+    DevBuf d_qkeys[2], d_qvals[2]; // uint32 per query, twice: (surface cell, query record) pairs on their way through the sort that orders the queries
+    DevBuf d_mark;                 // uint32 per surface record: 1 if it is a neighbour of a query
+    DevBuf d_need;                 // uint32 per indexed point: the marks in the order of the index, then their inclusive prefix sum
+    DevBuf d_list;                 // uint32 per indexed point: the places in the index of the needed points
 };
 
 // Scratch of feature matching (features.hip, feature_kernels.hpp), per row of the two descriptor clouds of a call; not part of an index

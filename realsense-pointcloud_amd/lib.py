@@ -52,6 +52,7 @@ EXPORTS = [
     "rsreg_prerej_params_default", "rsreg_cloud_score_transforms", "rsreg_cloud_prerejective",
     "rsreg_cloud_radius_count", "rsreg_cloud_radius_outlier_removal", "rsreg_cloud_normals_radius",
     "rsreg_cloud_fpfh_radius", "rsreg_cloud_spfh_radius",
+    "rsreg_cloud_radius_count_surface", "rsreg_cloud_normals_radius_surface", "rsreg_cloud_fpfh_radius_surface", "rsreg_cloud_spfh_radius_surface",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
     "rsreg_iin_params_default", "rsreg_cloud_integral_normals",
@@ -354,6 +355,10 @@ def lib():
     L.rsreg_cloud_normals_radius.argtypes = [vp, vp, dbl, vp, vp]
     L.rsreg_cloud_fpfh_radius.argtypes = [vp, vp, vp, dbl, vp]
     L.rsreg_cloud_spfh_radius.argtypes = [vp, vp, vp, dbl, vp, vp]
+    L.rsreg_cloud_radius_count_surface.argtypes = [vp, vp, vp, dbl, vp]
+    L.rsreg_cloud_normals_radius_surface.argtypes = [vp, vp, vp, dbl, vp, vp]
+    L.rsreg_cloud_fpfh_radius_surface.argtypes = [vp, vp, vp, vp, dbl, vp, C.POINTER(C.c_uint64)]
+    L.rsreg_cloud_spfh_radius_surface.argtypes = [vp, vp, vp, vp, dbl, vp, vp, vp]
     L.rsreg_iin_params_default.argtypes = [C.POINTER(IinParams)]
     L.rsreg_iin_params_default.restype = None
     L.rsreg_cloud_integral_normals.argtypes = [vp, vp, C.POINTER(IinParams), vp, vp]
