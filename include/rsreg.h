@@ -905,6 +905,53 @@ int rsreg_cloud_radius_outlier_removal(rsreg_ctx *ctx, const rsreg_cloud *in, do
  * (computeMeanAndCovarianceMatrix); this is the covariance the formula defines, in double, about the record.  A PCL build
  * agrees with it to PCL's own rounding. */
 int rsreg_cloud_normals_radius(rsreg_ctx *ctx, const rsreg_cloud *in, double radius, const float viewpoint[3], rsreg_cloud *out);
+/* ---- pcl::ISSKeypoint3D (Intrinsic Shape Signatures) over the radius search above: the keypoint detector in front of the
+ * descriptors.  PCL 1.9.1 keypoints/impl/iss_3d.hpp (getScatterMatrix, detectKeypoints), recalled; PCL is not available to check
+ * against, so what follows IS the contract.
+ * Neighbourhood: both radii use the neighbourhood of rsreg_cloud_radius_count, unchanged -- record j is a neighbour of the finite
+ *   record i when j is finite and float32 d2(i, j) < (float)((double)r * (double)r), strictly; the record itself and exact copies
+ *   among them; no cap.  m_s(i), m_n(i): the counts at the salient and at the non-max radius.
+ * Scatter (PCL's getScatterMatrix, recalled): S = sum d d^T over the m_s neighbours, d = (double)neighbour - (double)record, in
+ *   double without contraction; not divided, not centred.  The sums run in the order of the index, a function of the cloud and
+ *   the SALIENT radius alone (inside a cell the points lie in ascending record index): what rsreg_cloud_normals_radius states.
+ *   m_s < min_neighbors: S stays zero.
+ * Eigenvalues: l1 >= l2 >= l3 of S by the f64 cyclic Jacobi of rsreg_cloud_normals; eig_out holds them ASCENDING, three per
+ *   record; a non-finite record, and one below min_neighbors, gets zeros.
+ *   DEVIATION FROM PCL 1.9.1, stated: PCL runs Eigen's SelfAdjointEigenSolver; a PCL build agrees to the rounding of the solve.
+ * Saliency (PCL's third_eigen_value_): 0 unless all three values are finite, l3 >= 0, l2 / l1 < gamma_21 and l3 / l2 < gamma_32
+ *   (IEEE double divisions; a NaN ratio fails its compare); otherwise l3.
+ * Non-maximum suppression: record i is a keypoint iff saliency[i] > 0, m_n(i) >= min_neighbors, and no neighbour j within the
+ *   non-max radius has saliency[i] < saliency[j].  The compare is strict: exact ties all remain.  rsreg_cloud_iss_non_max takes
+ *   the CALLER'S saliencies and compares them as written: a NaN is never above 0 and never exceeds anything, a negative value is
+ *   never a keypoint and never suppresses a positive one, +inf is allowed.
+ * Output: the keypoints in ascending record index.  out (may be NULL): their records with every byte kept, width = n_keypoints,
+ *   height = 1, is_dense = 1; out != in; `out` follows the versioning rules above.  index_out (may be NULL): the first `capacity`
+ *   of the same indices (PCL's getKeypointsIndices); *n_keypoints (may be NULL) is their full number and may exceed capacity.
+ * ONE INDEX: rsreg_cloud_iss_keypoints builds the index once, at the salient radius, and walks it a second time with the non-max
+ *   radius -- the reach of a walk is taken from the actual cell, so a radius above or below the cell stays exact (a non-max radius
+ *   far below the salient one reads more candidates than an index of its own would).  rsreg_cloud_iss_non_max indexes at its radius.
+ * Refused with RSREG_ERR_INVALID_ARG, nothing launched and `out` untouched: a radius that is not finite or <= 0 (rsreg_cloud_iss_saliency
+ *   does not read non_max_radius), min_neighbors < 0, a gamma that is not finite, out == in, a null `in`, params, saliency or
+ *   is_keypoint_out, a cloud of another context.  An empty cloud, or one without a finite record: zero keypoints, zero rows.
+ * Determinism: the same cloud and parameters give the same bytes from any context, whatever it has indexed before.
+ * Every call waits for the stream.
+ * Not built: border estimation (setBorderRadius / setNormalRadius / setAngleThreshold with BoundaryEstimation), setIndices,
+ *   setSearchSurface, the other keypoint detectors (Harris3D, SIFT, NARF, ...). */
+typedef struct rsreg_iss_params {
+    double salient_radius;    /* setSalientRadius: > 0, finite */
+    double non_max_radius;    /* setNonMaxRadius:  > 0, finite */
+    double gamma_21;          /* setThreshold21, PCL default 0.975 */
+    double gamma_32;          /* setThreshold32, PCL default 0.975 */
+    int32_t min_neighbors;    /* setMinNeighbors, PCL default 5; >= 0 */
+    int32_t reserved;         /* 0 */
+} rsreg_iss_params;
+void rsreg_iss_params_default(rsreg_iss_params *p);   /* gammas 0.975, min_neighbors 5, radii 0 (refused until set) */
+int rsreg_cloud_iss_saliency(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_iss_params *params, double *eig_out /* n*3, may be NULL */,
+                             double *saliency_out /* n, may be NULL */, uint32_t *count_out /* n, may be NULL */);
+int rsreg_cloud_iss_non_max(rsreg_ctx *ctx, const rsreg_cloud *in, const double *saliency /* n, host */, double non_max_radius,
+                            int min_neighbors, uint8_t *is_keypoint_out /* n */);
+int rsreg_cloud_iss_keypoints(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_iss_params *params, rsreg_cloud *out /* may be NULL */,
+                              int32_t *index_out /* capacity entries, may be NULL */, size_t capacity, uint64_t *n_keypoints /* may be NULL */);
 /* ---- pcl::FPFHEstimationOMP with setRadiusSearch(radius): SPFH and FPFH over the radius search above -- a support of fixed
  * metric size, any number of neighbours.  PCL 1.9.1 features/impl/fpfh.hpp (computePointSPFHSignature, weightPointSPFHSignature)
  * and pfh_tools.cpp (computePairFeatures), recalled; PCL is not available to check against, so what follows IS the contract.

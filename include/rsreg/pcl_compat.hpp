@@ -881,6 +881,66 @@ template <typename PointT> class RadiusOutlierRemoval {
     std::shared_ptr<Context> ctx_;
 };
 
+// ---- pcl::ISSKeypoint3D<PointInT, PointOutT> over the exact radius search on the GPU (csrc/iss_kernels.hpp,
+// rsreg_cloud_iss_keypoints; include/rsreg.h holds the contract and the one stated deviation, the eigen-solve): the records whose
+// scatter over the salient radius has eigenvalue ratios below the two thresholds and whose smallest eigenvalue no neighbour within
+// the non-max radius exceeds, in ascending record index, every byte of a record kept.  PCL's defaults: both radii 0 (compute()
+// refuses them), thresholds 0.975, min_neighbors 5.  Border estimation is not built: setBorderRadius / setNormalRadius above 0
+// make compute() throw RSREG_ERR_INVALID_ARG.  No setIndices, no setSearchSurface.
+template <typename PointInT, typename PointOutT = PointInT> class ISSKeypoint3D {
+    static_assert(sizeof(PointOutT) == sizeof(PointInT), "the keypoints are the input's records");
+  public:
+    ISSKeypoint3D() { rsreg_iss_params_default(&params_); }
+    explicit ISSKeypoint3D(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) { rsreg_iss_params_default(&params_); }
+    void setInputCloud(const typename PointCloud<PointInT>::Ptr &cloud) { input_ = cloud, dinput_ = nullptr; }
+    void setInputCloud(const DeviceCloud<PointInT> &cloud) { dinput_ = &cloud, input_.reset(); }   // (must outlive compute())
+    void setSalientRadius(double radius) { params_.salient_radius = radius; }
+    void setNonMaxRadius(double radius) { params_.non_max_radius = radius; }
+    void setThreshold21(double gamma_21) { params_.gamma_21 = gamma_21; }
+    void setThreshold32(double gamma_32) { params_.gamma_32 = gamma_32; }
+    void setMinNeighbors(int min_neighbors) { params_.min_neighbors = min_neighbors; }
+    void setBorderRadius(double radius) { border_radius_ = radius; }
+    void setNormalRadius(double radius) { normal_radius_ = radius; }
+    void compute(PointCloud<PointOutT> &output)
+    {
+        check_built();
+        if (dinput_) {
+            DeviceCloud<PointOutT> out(dinput_->context());
+            compute(*dinput_, out);
+            out.download(output);
+            return;
+        }
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        const std::shared_ptr<Context> ctx = ctx_ ? ctx_ : Context::Default();
+        DeviceCloud<PointInT> tmp(*input_, ctx);
+        DeviceCloud<PointOutT> out(ctx);
+        compute(tmp, out);
+        out.download(output);
+    }
+    void compute(const DeviceCloud<PointInT> &input, DeviceCloud<PointOutT> &output)
+    {
+        check_built();
+        rsreg_ctx *c = input.context()->get();
+        indices_.assign(input.size(), 0);
+        uint64_t found = 0;
+        check(rsreg_cloud_iss_keypoints(c, input.handle(), &params_, output.handle(), indices_.data(), indices_.size(), &found), c);
+        indices_.resize((size_t)found);
+    }
+    const std::vector<int> &getKeypointsIndices() const { return indices_; }   // (PCL hands out a PointIndices: these are its indices)
+  private:
+    void check_built() const
+    {
+        if (border_radius_ > 0.0 || normal_radius_ > 0.0)
+            throw Error(RSREG_ERR_INVALID_ARG, "rsreg: ISSKeypoint3D: border estimation (setBorderRadius / setNormalRadius) is not built");
+    }
+    rsreg_iss_params params_;
+    double border_radius_ = 0.0, normal_radius_ = 0.0;
+    std::vector<int> indices_;
+    typename PointCloud<PointInT>::Ptr input_;
+    const DeviceCloud<PointInT> *dinput_ = nullptr;
+    std::shared_ptr<Context> ctx_;
+};
+
 // ---- pcl::NormalEstimation<PointInT, PointOutT> on the GPU: with setKSearch (3 .. 64) over an exact k-nearest-neighbour search
 // (csrc/normals_kernels.hpp, rsreg_cloud_normals), or with setRadiusSearch over an exact radius search (csrc/radius_kernels.hpp,
 // rsreg_cloud_normals_radius; any number of neighbours, fewer than three give NaNs).  As in PCL exactly one of the two is set:

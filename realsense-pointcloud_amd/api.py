@@ -550,6 +550,42 @@ class DeviceCloud:
         out.close()
         return np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
 
+    def iss_saliency(self, **params):
+        """The first pass of pcl::ISSKeypoint3D (rsreg_cloud_iss_saliency; params: the fields of iss_params(), salient_radius
+        among them): (eig (n, 3) float64, the eigenvalues of every record's scatter over its neighbours within the salient radius,
+        ascending; saliency (n,) float64, the smallest one where both ratios are below their gammas, else 0; counts (n,) uint32,
+        what radius_count(salient_radius) gives).  Zeros for a non-finite record and for one below min_neighbors."""
+        p = iss_params(**params)
+        n = self.info()[0]
+        eig, sal, m = np.zeros((n, 3), np.float64), np.zeros(n, np.float64), np.zeros(n, np.uint32)
+        _l.check(_l.lib().rsreg_cloud_iss_saliency(self.ctx.h, self.h, C.byref(p), eig.ctypes.data, sal.ctypes.data, m.ctypes.data), self.ctx.h)
+        return eig, sal, m
+
+    def iss_non_max(self, saliency, radius, min_neighbors):
+        """The second pass of pcl::ISSKeypoint3D over the caller's saliencies (rsreg_cloud_iss_non_max): (n,) bool, True where
+        saliency[i] > 0, the record has min_neighbors or more neighbours within `radius`, and none of them has a larger saliency."""
+        n = self.info()[0]
+        sal = np.ascontiguousarray(saliency, np.float64).reshape(-1)
+        if len(sal) != n:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "one saliency per record")
+        out = np.zeros(n, np.uint8)
+        _l.check(_l.lib().rsreg_cloud_iss_non_max(self.ctx.h, self.h, sal.ctypes.data, float(radius), int(min_neighbors), out.ctypes.data), self.ctx.h)
+        return out.astype(bool)
+
+    def iss_keypoints(self, **params):
+        """pcl::ISSKeypoint3D (rsreg_cloud_iss_keypoints; params: the fields of iss_params()): (a DeviceCloud of the keypoints'
+        records in ascending record index, their indices as an int32 array -- PCL's getKeypointsIndices)."""
+        p = iss_params(**params)
+        n = self.info()[0]
+        idx = np.zeros(max(n, 1), np.int32)
+        out = DeviceCloud(ctx=self.ctx)
+        found = C.c_uint64(0)
+        rc = _l.lib().rsreg_cloud_iss_keypoints(self.ctx.h, self.h, C.byref(p), out.h, idx.ctypes.data, n, C.byref(found))
+        if rc:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out, idx[:int(found.value)].copy()
+
     def integral_normals_cloud(self, params=None, rect=False):
         """pcl::IntegralImageNormalEstimation of this organized cloud (rsreg_cloud_integral_normals; params: iin_params(),
         None = PCL's defaults): a DeviceCloud of 32-byte pcl::Normal records.  rect=True: (cloud, the window size of every
@@ -665,6 +701,17 @@ def iin_params(**kw):
     for k, v in kw.items():
         if k == "viewpoint":
             v = (C.c_float * 3)(*[float(x) for x in v])
+        setattr(p, k, v)
+    return p
+
+
+def iss_params(**kw):
+    """rsreg_iss_params with PCL's defaults: gamma_21 = gamma_32 = 0.975, min_neighbors 5; the two radii are 0 until set (refused)."""
+    p = _l.IssParams()
+    _l.lib().rsreg_iss_params_default(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "rsreg_iss_params has no field %r" % (k,))
         setattr(p, k, v)
     return p
 
@@ -1446,6 +1493,73 @@ class RadiusOutlierRemoval:
         def run(cin, cout):
             _, self.n_kept = cin.radius_outlier_removal(self.radius, self.min_neighbors, self.negative, self.keep_organized, out=cout)
         return _filter_io(self._in, self.ctx, run)
+
+
+class ISSKeypoint3D:
+    """pcl::ISSKeypoint3D<PointXYZRGB, PointXYZRGB> on the GPU over the exact radius search (csrc/iss_kernels.hpp,
+    rsreg_cloud_iss_keypoints; include/rsreg.h holds the contract): the records whose scatter over the salient radius has
+    eigenvalue ratios below gamma_21 and gamma_32 and whose smallest eigenvalue no neighbour within the non-max radius exceeds.
+    PCL's defaults: both radii 0 (compute() refuses them), thresholds 0.975, min_neighbors 5.  Border estimation (setBorderRadius,
+    setNormalRadius above 0) is not built and compute() says so; no setIndices, no setSearchSurface.  compute() of a DeviceCloud
+    gives a DeviceCloud of the keypoints, of a host cloud a PointCloud; getKeypointsIndices() their record indices."""
+
+    def __init__(self, ctx=None):
+        self.salient_radius = 0.0
+        self.non_max_radius = 0.0
+        self.gamma_21 = 0.975
+        self.gamma_32 = 0.975
+        self.min_neighbors = 5
+        self.border_radius = 0.0
+        self.normal_radius = 0.0
+        self._indices = np.zeros(0, np.int32)
+        self._in = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setSalientRadius(self, radius):
+        self.salient_radius = float(radius)
+
+    def setNonMaxRadius(self, radius):
+        self.non_max_radius = float(radius)
+
+    def setThreshold21(self, gamma):
+        self.gamma_21 = float(gamma)
+
+    def setThreshold32(self, gamma):
+        self.gamma_32 = float(gamma)
+
+    def setMinNeighbors(self, m):
+        self.min_neighbors = int(m)
+
+    def setBorderRadius(self, radius):
+        self.border_radius = float(radius)
+
+    def setNormalRadius(self, radius):
+        self.normal_radius = float(radius)
+
+    def getKeypointsIndices(self):
+        return self._indices
+
+    def compute(self):
+        if self.border_radius > 0.0 or self.normal_radius > 0.0:   # (before any device call)
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "ISSKeypoint3D: border estimation (setBorderRadius / setNormalRadius) is not built")
+        if self._in is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCloud not called")
+        on_device = isinstance(self._in, DeviceCloud)
+        dev = self._in if on_device else DeviceCloud(self._in, ctx=self.ctx or default_context())
+        try:
+            out, self._indices = dev.iss_keypoints(salient_radius=self.salient_radius, non_max_radius=self.non_max_radius, gamma_21=self.gamma_21,
+                                                   gamma_32=self.gamma_32, min_neighbors=self.min_neighbors)
+            if on_device:
+                return out
+            host = out.download()
+            out.close()
+            return host
+        finally:
+            if not on_device:
+                dev.close()
 
 
 def _compute_over_surface(est, run, download):

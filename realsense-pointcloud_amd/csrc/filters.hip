@@ -9,6 +9,7 @@
 // the pair features of fpfh_kernels.hpp behind it, then the weighting pass over the neighbour rows the search left.  pcl::FPFHEstimationOMP
 // (setRadiusSearch): fpfh_radius_kernels.hpp's two walks of the radius index, no neighbour list between them.  setSearchSurface
 // (the *_surface calls): the same radius index over the surface, searched from the records of another cloud (surface_kernels.hpp).
+// pcl::ISSKeypoint3D: iss_kernels.hpp's two walks over ONE radius index (the salient radius'), then the flag / scan / gather.
 // Everything runs on the context's stream with the index rsreg_ctx::knn and the scratch rsreg_ctx::filt (the radius search:
 // rsreg_ctx::rad too): nothing here reads or writes a buffer of the alignment's index or of the fitness indices.
 #include <cmath>
@@ -20,6 +21,7 @@
 #include "fpfh_kernels.hpp"
 #include "fpfh_radius_kernels.hpp"
 #include "surface_kernels.hpp"
+#include "iss_kernels.hpp"
 #include "cloud_ops.hpp"
 
 using namespace rsreg;
@@ -393,9 +395,176 @@ template <typename Launch> int surface_rows_into(rsreg_ctx *ctx, const SurfaceCa
     return rsreg_cloud_adopt_(out, &fs.d_out, qv.n, row_bytes, qv.width, qv.height, nan_rows ? 0 : qv.is_dense);
 }
 
+
+// ---- pcl::ISSKeypoint3D (iss_kernels.hpp)
+// what every ISS call refuses before anything is launched
+int iss_check(rsreg_ctx *ctx, const double *radii, int n_radii, int min_neighbors, const double *gammas, int n_gammas)
+{
+    for (int k = 0; k < n_radii; ++k)
+        if (!(radii[k] > 0.0) || !std::isfinite(radii[k])) return fail(ctx, RSREG_ERR_INVALID_ARG, "the salient and the non-max radius must be finite and above 0");
+    if (min_neighbors < 0) return fail(ctx, RSREG_ERR_INVALID_ARG, "min_neighbors must not be negative");
+    for (int k = 0; k < n_gammas; ++k)
+        if (!std::isfinite(gammas[k])) return fail(ctx, RSREG_ERR_INVALID_ARG, "gamma_21 and gamma_32 must be finite");
+    return RSREG_OK;
+}
+
+// The first pass, not waited for (v.n above 0): the index at the salient radius, then every record's eigenvalues (rs.d_iss_eig),
+// saliency (rs.d_iss_sal) and m_s (rs.d_count), zeros for a non-finite record.  *rq: the query of the salient radius.
+int iss_saliency_device(rsreg_ctx *ctx, const CloudView &v, const rsreg_iss_params &p, RadiusQuery *rq, uint32_t *nfin_out)
+{
+    RadiusScratch &rs = ctx->rad;
+    hipStream_t st = ctx->stream;
+    RSREG_HIP(ctx, rs.d_count.reserve(v.n * 4 + 16));
+    RSREG_HIP(ctx, rs.d_iss_eig.reserve(v.n * 24 + 16));
+    RSREG_HIP(ctx, rs.d_iss_sal.reserve(v.n * 8 + 16));
+    int rc = radius_index_device(ctx, v, p.salient_radius, rs.d_count.as<uint32_t>(), rq, nfin_out);
+    if (rc) return rc;
+    if (*nfin_out < v.n) {
+        RSREG_HIP(ctx, hipMemsetAsync(rs.d_iss_eig.ptr, 0, v.n * 24, st));
+        RSREG_HIP(ctx, hipMemsetAsync(rs.d_iss_sal.ptr, 0, v.n * 8, st));
+    }
+    if (!*nfin_out) {   // (the build stops at the box: nothing has written the counts)
+        RSREG_HIP(ctx, hipMemsetAsync(rs.d_count.ptr, 0, v.n * 4, st));
+        return RSREG_OK;
+    }
+    k_iss_saliency<<<std::min<uint32_t>(*nfin_out, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), *rq, (uint32_t)p.min_neighbors, p.gamma_21, p.gamma_32,
+                                                                                rs.d_iss_eig.as<double>(), rs.d_iss_sal.as<double>(), rs.d_count.as<uint32_t>());
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
+// The second pass, not waited for (v.n above 0), over whatever index the context holds (nfin points): fs.d_flags[i] = 1 for the
+// keypoints among the saliencies in rs.d_iss_sal
+int iss_non_max_device(rsreg_ctx *ctx, const CloudView &v, double non_max_radius, int min_neighbors, uint32_t nfin)
+{
+    FilterScratch &fs = ctx->filt;
+    RSREG_HIP(ctx, fs.d_flags.reserve(v.n * 4 + 16));
+    RSREG_HIP(ctx, hipMemsetAsync(fs.d_flags.ptr, 0, v.n * 4, ctx->stream));
+    if (!nfin) return RSREG_OK;
+    k_iss_non_max<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, ctx->stream>>>(grid_dev(ctx->knn), radius_query(non_max_radius, ctx->knn),
+                                                                                   ctx->rad.d_iss_sal.as<double>(), (uint32_t)min_neighbors, fs.d_flags.as<uint32_t>());
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void rsreg_iss_params_default(rsreg_iss_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->gamma_21 = 0.975;
+    p->gamma_32 = 0.975;
+    p->min_neighbors = 5;
+}
+
+int rsreg_cloud_iss_saliency(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_iss_params *params, double *eig_out, double *saliency_out,
+                             uint32_t *count_out)
+{
+    CloudView v;
+    if (!params) return RSREG_ERR_INVALID_ARG;
+    int rc = cloud_view(ctx, in, nullptr, kXyzRule, v);
+    if (rc) return rc;
+    const double gammas[2] = {params->gamma_21, params->gamma_32};
+    rc = iss_check(ctx, &params->salient_radius, 1, params->min_neighbors, gammas, 2);   // (the non-max radius is not used here)
+    if (rc || !v.n) return rc;
+    RadiusQuery rq;
+    uint32_t nfin = 0;
+    rc = iss_saliency_device(ctx, v, *params, &rq, &nfin);
+    if (rc) return rc;
+    RadiusScratch &rs = ctx->rad;
+    hipStream_t st = ctx->stream;
+    if (eig_out) RSREG_HIP(ctx, hipMemcpyAsync(eig_out, rs.d_iss_eig.ptr, v.n * 24, hipMemcpyDeviceToHost, st));
+    if (saliency_out) RSREG_HIP(ctx, hipMemcpyAsync(saliency_out, rs.d_iss_sal.ptr, v.n * 8, hipMemcpyDeviceToHost, st));
+    if (count_out) RSREG_HIP(ctx, hipMemcpyAsync(count_out, rs.d_count.ptr, v.n * 4, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    return RSREG_OK;
+}
+
+int rsreg_cloud_iss_non_max(rsreg_ctx *ctx, const rsreg_cloud *in, const double *saliency, double non_max_radius, int min_neighbors, uint8_t *is_keypoint_out)
+{
+    CloudView v;
+    if (!saliency || !is_keypoint_out) return RSREG_ERR_INVALID_ARG;
+    int rc = cloud_view(ctx, in, nullptr, kXyzRule, v);
+    if (rc) return rc;
+    rc = iss_check(ctx, &non_max_radius, 1, min_neighbors, nullptr, 0);
+    if (rc || !v.n) return rc;
+    RadiusScratch &rs = ctx->rad;
+    FilterScratch &fs = ctx->filt;
+    hipStream_t st = ctx->stream;
+    RSREG_HIP(ctx, rs.d_iss_sal.reserve(v.n * 8 + 16));
+    RadiusQuery rq;
+    uint32_t nfin = 0;
+    rc = radius_index_device(ctx, v, non_max_radius, nullptr, &rq, &nfin);
+    if (rc) return rc;
+    RSREG_HIP(ctx, hipMemcpyAsync(rs.d_iss_sal.ptr, saliency, v.n * 8, hipMemcpyHostToDevice, st));
+    rc = iss_non_max_device(ctx, v, non_max_radius, min_neighbors, nfin);
+    if (rc) return rc;
+    // the flags are words on the device and bytes at the caller's: they come home through the pinned scratch, a slice at a time
+    constexpr size_t kSlice = 1u << 16;
+    RSREG_HIP(ctx, fs.host.reserve(kSlice * 4));
+    for (size_t at = 0; at < v.n; at += kSlice) {
+        const size_t m = std::min(kSlice, v.n - at);
+        RSREG_HIP(ctx, hipMemcpyAsync(fs.host.ptr, fs.d_flags.as<uint32_t>() + at, m * 4, hipMemcpyDeviceToHost, st));
+        RSREG_HIP(ctx, hipStreamSynchronize(st));
+        for (size_t i = 0; i < m; ++i) is_keypoint_out[at + i] = (uint8_t)fs.host.as<uint32_t>()[i];
+    }
+    return RSREG_OK;
+}
+
+int rsreg_cloud_iss_keypoints(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_iss_params *params, rsreg_cloud *out, int32_t *index_out, size_t capacity,
+                              uint64_t *n_keypoints)
+{
+    CloudView v;
+    if (!params || (out && out == in)) return RSREG_ERR_INVALID_ARG;
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
+    if (rc) return rc;
+    const double radii[2] = {params->salient_radius, params->non_max_radius}, gammas[2] = {params->gamma_21, params->gamma_32};
+    rc = iss_check(ctx, radii, 2, params->min_neighbors, gammas, 2);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    RadiusScratch &rs = ctx->rad;
+    PointGrid &kx = ctx->knn;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)v.n;
+    uint32_t kept = 0;
+    if (n) {
+        RadiusQuery rq;
+        uint32_t nfin = 0;
+        rc = iss_saliency_device(ctx, v, *params, &rq, &nfin);
+        if (rc) return rc;
+        rc = iss_non_max_device(ctx, v, params->non_max_radius, params->min_neighbors, nfin);   // (over the same index)
+        if (rc) return rc;
+        // flags -> positions -> the keypoints' indices and, for `out`, their records (the path of RadiusOutlierRemoval); waits for their number
+        RSREG_HIP(ctx, fs.d_pos.reserve(v.n * 4 + 16));
+        RSREG_HIP(ctx, kx.d_scan.reserve(oscan_scratch_bytes<uint32_t>(v.n)));
+        RSREG_HIP(ctx, rs.d_iss_index.reserve(v.n * 4 + 16));
+        if (out) RSREG_HIP(ctx, fs.d_out.reserve(v.n * v.stride + 16));
+        RSREG_HIP(ctx, kx.d_box.reserve(64));
+        RSREG_HIP(ctx, fs.host.reserve(256));
+        RSREG_HIP(ctx, oscan<uint32_t>(fs.d_flags.as<uint32_t>(), fs.d_pos.as<uint32_t>(), v.n, 0u, kx.d_scan.ptr, st));
+        rc = word_home(ctx, false, [&](uint32_t *d_kept) {
+            k_iss_indices<<<div_up(n, kBlock), kBlock, 0, st>>>(fs.d_flags.as<uint32_t>(), fs.d_pos.as<uint32_t>(), n, rs.d_iss_index.as<int32_t>(), d_kept);
+            if (out)
+                k_filter_gather<<<div_up64((unsigned long long)n * (v.stride / 4), kBlock), kBlock, 0, st>>>(v.rec, v.stride, n, fs.d_flags.as<uint32_t>(),
+                                                                                                           fs.d_pos.as<uint32_t>(), fs.d_out.as<char>(), d_kept);
+        }, &kept);
+        if (rc) return rc;
+        const size_t home = std::min<size_t>(kept, capacity);
+        if (index_out && home) {
+            RSREG_HIP(ctx, hipMemcpyAsync(index_out, rs.d_iss_index.ptr, home * 4, hipMemcpyDeviceToHost, st));
+            RSREG_HIP(ctx, hipStreamSynchronize(st));
+        }
+    }
+    if (out) {
+        rc = rsreg_cloud_adopt_(out, &fs.d_out, kept, v.stride, kept, 1, 1);
+        if (rc) return rc;
+    }
+    if (n_keypoints) *n_keypoints = kept;
+    return RSREG_OK;
+}
 
 int rsreg_cloud_radius_count_surface(rsreg_ctx *ctx, const rsreg_cloud *queries, const rsreg_cloud *surface, double radius, uint32_t *host_out)
 {

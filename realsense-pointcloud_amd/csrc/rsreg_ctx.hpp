@@ -212,6 +212,9 @@ struct RadiusScratch {
     DevBuf d_mark;                 // uint32 per surface record: 1 if it is a neighbour of a query
     DevBuf d_need;                 // uint32 per indexed point: the marks in the order of the index, then their inclusive prefix sum
     DevBuf d_list;                 // uint32 per indexed point: the places in the index of the needed points
+    // ISSKeypoint3D (iss_kernels.hpp), per record of the cloud
+    DevBuf d_iss_eig, d_iss_sal;   // three f64 eigenvalues of the scatter, ascending; the f64 saliency (a caller's own: rsreg_cloud_iss_non_max)
+    DevBuf d_iss_index;            // int32 per record: the keypoints' record indices, ascending
 };
 
 // Scratch of feature matching (features.hip, feature_kernels.hpp), per row of the two descriptor clouds of a call; not part of an index

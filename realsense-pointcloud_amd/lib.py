@@ -52,6 +52,7 @@ EXPORTS = [
     "rsreg_prerej_params_default", "rsreg_cloud_score_transforms", "rsreg_cloud_prerejective",
     "rsreg_cloud_radius_count", "rsreg_cloud_radius_outlier_removal", "rsreg_cloud_normals_radius",
     "rsreg_cloud_fpfh_radius", "rsreg_cloud_spfh_radius",
+    "rsreg_iss_params_default", "rsreg_cloud_iss_saliency", "rsreg_cloud_iss_non_max", "rsreg_cloud_iss_keypoints",
     "rsreg_cloud_radius_count_surface", "rsreg_cloud_normals_radius_surface", "rsreg_cloud_fpfh_radius_surface", "rsreg_cloud_spfh_radius_surface",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
@@ -121,6 +122,11 @@ class PrerejParams(C.Structure):   # rsreg_prerej_params
 class PrerejResult(C.Structure):   # rsreg_prerej_result
     _fields_ = [("transform", C.c_float * 16), ("found", C.c_int32), ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 3),
                 ("match", C.c_int32 * 3), ("n_valid", C.c_uint64), ("n_inliers", C.c_uint64), ("fitness", C.c_double)]
+
+
+class IssParams(C.Structure):   # rsreg_iss_params
+    _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double),
+                ("min_neighbors", C.c_int32), ("reserved", C.c_int32)]
 
 
 class IinParams(C.Structure):   # rsreg_iin_params
@@ -353,6 +359,11 @@ def lib():
     L.rsreg_cloud_radius_count.argtypes = [vp, vp, dbl, vp]
     L.rsreg_cloud_radius_outlier_removal.argtypes = [vp, vp, dbl, i32, i32, i32, vp, C.POINTER(C.c_uint64)]
     L.rsreg_cloud_normals_radius.argtypes = [vp, vp, dbl, vp, vp]
+    L.rsreg_iss_params_default.argtypes = [C.POINTER(IssParams)]
+    L.rsreg_iss_params_default.restype = None
+    L.rsreg_cloud_iss_saliency.argtypes = [vp, vp, C.POINTER(IssParams), vp, vp, vp]
+    L.rsreg_cloud_iss_non_max.argtypes = [vp, vp, vp, dbl, i32, vp]
+    L.rsreg_cloud_iss_keypoints.argtypes = [vp, vp, C.POINTER(IssParams), vp, vp, sz, C.POINTER(C.c_uint64)]
     L.rsreg_cloud_fpfh_radius.argtypes = [vp, vp, vp, dbl, vp]
     L.rsreg_cloud_spfh_radius.argtypes = [vp, vp, vp, dbl, vp, vp]
     L.rsreg_cloud_radius_count_surface.argtypes = [vp, vp, vp, dbl, vp]
