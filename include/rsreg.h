@@ -746,8 +746,8 @@ int rsreg_cloud_feature_correspondences(rsreg_ctx *ctx, const rsreg_cloud *sourc
  *   the first `capacity` are written and the call still returns RSREG_OK (the convention of rsreg_cloud_feature_correspondences).
  *   Every output is a function of the two clouds, the list and the parameters alone: the counts are integers, the generator is a
  *   function of (seed, h, draw), every float sum has its order written above.
- * Not built: SampleConsensusInitialAlignment, the other CorrespondenceRejector*, refineModel.  (SampleConsensusPrerejective: the
- * section after this one.) */
+ * Not built: the other CorrespondenceRejector*, refineModel.  (SampleConsensusPrerejective and SampleConsensusInitialAlignment: the two
+ * sections after this one.) */
 typedef struct rsreg_sac_params {
     double inlier_threshold;      /* 0.05 */
     double probability;           /* 0.99 */
@@ -844,8 +844,8 @@ int rsreg_cloud_sac_correspondences(rsreg_ctx *ctx, const rsreg_cloud *source, c
  *   `capacity` are written and the call still returns RSREG_OK (the convention of rsreg_cloud_feature_correspondences).  inliers_out
  *   may be NULL when capacity is 0.
  *   Every output is a function of the two clouds, the table and the parameters alone.
- * Not built: SampleConsensusInitialAlignment, nr_samples other than 3, a device-resident neighbour table, a refit over the winner's
- * inliers. */
+ * Not built: a device-resident neighbour table, a refit over the winner's inliers.  (SampleConsensusInitialAlignment, which takes
+ * nr_samples up to 8: the section after this one; this estimator stays at 3.) */
 typedef struct rsreg_prerej_params {
     double max_correspondence_distance;   /* sqrt(DBL_MAX) */
     double inlier_fraction;               /* 0 */
@@ -871,6 +871,113 @@ int rsreg_cloud_score_transforms(rsreg_ctx *ctx, const rsreg_cloud *source, cons
 int rsreg_cloud_prerejective(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const int32_t *neighbor_index /* ns*k */, int k,
                              const rsreg_prerej_params *params /* may be NULL */, int32_t *inliers_out, size_t capacity, size_t *n_out,
                              rsreg_prerej_result *result /* may be NULL */);
+/* ---- pose from descriptor neighbours, scored by a robust error: pcl::SampleConsensusInitialAlignment (SAC-IA), the estimator FPFH was
+ * published with -- nr_samples source records that keep a minimum distance from one another, each paired with a random one of its k
+ * nearest descriptors; NO hypothesis is thrown away, every one is scored over EVERY source record by a bounded penalty of its
+ * nearest-point distance.  PCL 1.9.1 registration/impl/ia_ransac.hpp and ia_ransac.h, recalled; PCL is not available to check against,
+ * so what follows IS the contract, and where it leaves PCL it says DEVIATION.
+ * Inputs: those of rsreg_cloud_prerejective -- two device clouds of the context (records that start with x, y, z floats; source ==
+ *   target is allowed) and, where a call takes one, the HOST table neighbor_index of ns rows of k int32 that
+ *   rsreg_cloud_feature_knn(source_features, target_features, k) wrote, 1 <= k <= 16 (PCL's k_correspondences_, default 10), a row of -1
+ *   making its record INELIGIBLE.  The same checks, the same refusals (RSREG_ERR_INVALID_ARG before anything is launched).  Every call
+ *   that searches indexes the target once (the prerejective build) and every call waits for the stream.
+ * params NULL: rsreg_scia_params_default.
+ *   max_correspondence_distance (default sqrt(DBL_MAX)): thr = (float) of it.  PCL'S QUIRK, KEPT: thr is compared with the SQUARED
+ *     distance (the PCL tutorial passes 0.01f * 0.01f).  thr NaN or <= 0: RSREG_ERR_INVALID_ARG; +inf is allowed (the default is +inf
+ *     as a float).
+ *   min_sample_distance (default 0): negative or NaN: RSREG_ERR_INVALID_ARG.
+ *   nr_samples (default 3): outside 3 .. 8: RSREG_ERR_INVALID_ARG.
+ *   error_function: RSREG_SCIA_TRUNCATED (PCL's default) or RSREG_SCIA_HUBER; anything else: RSREG_ERR_INVALID_ARG.
+ *   max_iterations (default 10, pcl::Registration's own): negative: RSREG_ERR_INVALID_ARG.  seed (default 0).
+ *
+ * THE ERROR of a transform T over the source: for every source record whose x, y, z are finite, p' = the float32 transform of the
+ *   sections above (transformPointCloud's order, every operation rounded once, no contraction); e = the EXACT nearest float32
+ *   L2_Simple squared distance from p' to the finite target records (the search of rsreg_cloud_score_transforms); e = +inf when p'
+ *   is not finite, when the target has no finite record, or when the nearest distance overflowed.
+ *   The record's term, TruncatedError: (e < +inf && e <= thr) ? (double)(e / thr) : 1.0 -- one IEEE float32 division, nothing flushed
+ *     (a denormal thr divides as IEEE; thr = +inf gives +0 for every finite e).
+ *   HuberPenalty, in double without contraction, e and thr converted exactly: e <= thr ? (0.5 * e) * e : (0.5 * thr) * (2.0 * e - thr);
+ *     +inf for e = +inf.  (PCL's functors take the squared distance as written here: the quirk above.)
+ *   A source record that is not finite is a term of +0.0.
+ *   error = the sum of the terms in double, in exactly the tree of the section above: record i is term i % 64 of wave (i / 64) % 2 of
+ *   group i / 128, +0.0 behind record ns - 1; a wave's 64 terms meet pairwise across lane bit 5, 4, 3, 2, 1, 0; a group is wave 0 +
+ *   wave 1; the groups are added in ascending order starting from group 0's value.  The tree is a function of ns alone.
+ *   DEVIATION: PCL adds the terms in float in point order.
+ *   With the truncated term the search may stop at thr (nothing farther changes the term); with Huber it is unbounded.
+ *
+ * rsreg_cloud_error_transforms: the scoring stage on its own, the counterpart of rsreg_cloud_score_transforms.  errors_out[h] = the
+ *   error of transforms[16 * h .. 16 * h + 15] (column-major 4 x 4, host; the last row is not read), h < H.  Any floats are allowed in a
+ *   transform.  H == 0: nothing is written.  An empty source: zeros.  An empty or all-non-finite target: every finite source record
+ *   has e = +inf.  thr and error_function are checked as above.
+ *
+ * HYPOTHESIS h uses the generator of the sections above: index(h, draw, n) = ((z >> 32) * n) >> 32 over z = the splitmix64 finaliser
+ *   of seed + (64 * h + draw) * 0x9E3779B97F4A7C15.
+ *   THE SAMPLER: the candidate draws d = 0 .. 55 give c = index(h, d, ns), taken in order.  A candidate is ACCEPTED when its row is
+ *   eligible, its record is finite, it differs from every accepted sample, and for every accepted sample s
+ *   (double)d2(c, s) >= min_sample_distance * min_sample_distance (a double product), d2 the float32 L2_Simple of the two source
+ *   points: at min_sample_distance 0 coincident records pass and the solve decides.  DEVIATION: PCL compares a float sqrt.
+ *   The first nr_samples accepted candidates are s_0, s_1, ..; fewer after the 56 draws: the hypothesis is INVALID.
+ *   DEVIATION: PCL halves min_sample_distance_ after 3 * ns failures and KEEPS the halved value for the rest of the call; this is not
+ *   reproduced -- n_valid tells the caller how many hypotheses found a sample.  ns < nr_samples: nothing is valid.
+ *   Target records: t_j = neighbor_index[s_j * k + index(h, 56 + j, k)], j < nr_samples.
+ *   h is VALID when the sampler filled, every t_j is finite and rsreg_umeyama_from_sums succeeds on the pairs' sums (double, each
+ *   sum 0.0 + the term of pair 0 + that of pair 1 + .., as the sections above form them); T(h) is that solve's result.
+ *   A valid hypothesis is ALWAYS scored; an invalid one is never searched.  DEVIATION: rand() is not reproduced.
+ *
+ * rsreg_cloud_initial_alignment_hypotheses: the sampler and the fit alone, for hypotheses first .. first + count - 1 (params gives
+ *   seed, nr_samples and min_sample_distance; every field is checked as above).  Per hypothesis: transforms_out 16 floats (column-major,
+ *   last row 0 0 0 1; sixteen quiet NaNs when it is invalid), valid_out one int32 (1 / 0), samples_out 16 int32: s_0 .. in [0, 8),
+ *   t_0 .. in [8, 16), -1 behind nr_samples, -1 x 16 when the sampler did not fill.  Each output may be NULL.  The rows do not depend
+ *   on `first` and `count`: hypothesis h is a function of (seed, h).
+ *
+ * rsreg_cloud_initial_alignment: SELECTION is replayed on the host in hypothesis order, PCL's `i_iter == 0 || error < lowest_error`
+ *   in double.  guess (a column-major 4 x 4, may be NULL; the last row is not read): the guess is scored first, whatever
+ *   max_iterations is, and spends one iteration: the hypotheses are h = 0 .. H - 1 with H = max(max_iterations - 1, 0); without a guess
+ *   H = max_iterations.  DEVIATION: PCL's guess.isApprox(Identity, 0.01) test is replaced by NULL.
+ *   A guess whose error is not NaN holds lowest_error.  The valid hypotheses follow in order: while nothing holds lowest_error the
+ *   first whose error is not NaN takes it (+inf included); afterwards one takes it iff its error is strictly lower.  The winner is
+ *   thus the first valid h with the strictly lowest error; a NaN error never wins.
+ *   errors_out (may be NULL): max_iterations doubles; [h] = the error of hypothesis h, quiet NaN for an invalid one and for the
+ *   places h >= H.
+ *   result: found is PCL's converged_: 1 only when a hypothesis won (not the guess); then transform = T(winner), best_hypothesis = h,
+ *   sample / match = its s_j / t_j (-1 behind nr_samples), error = its error.  Otherwise best_hypothesis, sample and match are -1,
+ *   the transform is the guess if there is one and its error is finite (the guess's 16 floats as given), the identity if not, and
+ *   error = the guess's error, +inf when nothing was scored.  n_valid: the valid hypotheses, i.e. the ones that were scored.  An empty
+ *   source: nothing is scored.  No early stop: every h < H is generated.
+ * Determinism: every output is a function of the two clouds, the table and the parameters alone: the same bytes for any batch, slice,
+ *   launch order or context; no float atomics anywhere.
+ * Not built: PCL's persistent relaxation of min_sample_distance, setIndices, a device-resident neighbour table. */
+typedef enum rsreg_scia_error_function {
+    RSREG_SCIA_TRUNCATED = 0,             /* pcl::SampleConsensusInitialAlignment::TruncatedError, PCL's default */
+    RSREG_SCIA_HUBER = 1                  /* ... ::HuberPenalty */
+} rsreg_scia_error_function;
+typedef struct rsreg_scia_params {
+    double max_correspondence_distance;   /* sqrt(DBL_MAX); compared, as a float, with the SQUARED distance */
+    double min_sample_distance;           /* 0 */
+    int32_t nr_samples;                   /* 3; 3 .. 8 */
+    int32_t error_function;               /* RSREG_SCIA_TRUNCATED */
+    int32_t max_iterations;               /* 10 */
+    int32_t reserved0;
+    uint64_t seed;                        /* 0 */
+} rsreg_scia_params;
+typedef struct rsreg_scia_result {
+    float transform[16];                  /* column-major */
+    int32_t found;                        /* a hypothesis won */
+    int32_t best_hypothesis;
+    int32_t sample[8];                    /* the winner's source records, -1 behind nr_samples */
+    int32_t match[8];                     /* ... and their target records */
+    uint64_t n_valid;                     /* hypotheses that were scored */
+    double error;                         /* the winner's (or the guess's) error; +inf when nothing was scored */
+} rsreg_scia_result;
+void rsreg_scia_params_default(rsreg_scia_params *p);
+int rsreg_cloud_error_transforms(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const float *transforms /* H*16 */, size_t H,
+                                 int error_function, double max_correspondence_distance, double *errors_out /* H */);
+int rsreg_cloud_initial_alignment_hypotheses(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const int32_t *neighbor_index /* ns*k */,
+                                             int k, const rsreg_scia_params *params /* may be NULL */, uint64_t first, size_t count,
+                                             float *transforms_out /* count*16 */, int32_t *valid_out /* count */, int32_t *samples_out /* count*16 */);
+int rsreg_cloud_initial_alignment(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, const int32_t *neighbor_index /* ns*k */, int k,
+                                  const rsreg_scia_params *params /* may be NULL */, const float *guess /* 16, may be NULL */,
+                                  double *errors_out /* max_iterations, may be NULL */, rsreg_scia_result *result /* may be NULL */);
 /* ---- radius search: every record's neighbours within a radius in its own cloud, EXACT.  Record j is a neighbour of the finite
  * record i when j is finite and d2(i, j) < r2, with d2 the float32 L2_Simple squared distance of every search here and
  * r2 = (float)((double)radius * (double)radius): KdTreeFLANN::radiusSearch's cast and the STRICT compare of FLANN's

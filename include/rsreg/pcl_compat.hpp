@@ -1443,6 +1443,120 @@ template <typename PointSource, typename PointTarget = PointSource, typename Fea
     std::shared_ptr<Context> ctx_;
 };
 
+// ---- pcl::SampleConsensusInitialAlignment<PointSource, PointTarget, FeatureT> on the GPU: poses from nr_samples source records that
+// keep a minimum distance from one another and a random one of each one's k nearest descriptors; none is thrown away, every one is
+// scored over every source record by a bounded penalty of its exact nearest-point distance (csrc/scia_kernels.hpp,
+// rsreg_cloud_initial_alignment; include/rsreg.h holds the contract and the stated deviations from PCL: the sampler, the double sum,
+// no persistent relaxation of the minimum distance, a guess given as an argument and not told from the identity).  As in PCL,
+// setMaxCorrespondenceDistance is compared with the SQUARED distance.  align() makes two calls, rsreg_cloud_feature_knn and
+// rsreg_cloud_initial_alignment, and writes the source moved by the final transformation.
+// Engine extras: setSeed, getResult, the device overloads.
+template <typename PointSource, typename PointTarget = PointSource, typename FeatureT = FPFHSignature33> class SampleConsensusInitialAlignment {
+    static_assert(sizeof(PointSource) >= 12 && sizeof(PointSource) % 4 == 0 && sizeof(PointTarget) >= 12 && sizeof(PointTarget) % 4 == 0,
+                  "records start with x, y, z floats");
+    static_assert(sizeof(FeatureT) >= 132 && sizeof(FeatureT) % 4 == 0, "descriptor records start with 33 floats");
+  public:
+    enum ErrorFunction { TRUNCATED_ERROR = RSREG_SCIA_TRUNCATED, HUBER_PENALTY = RSREG_SCIA_HUBER };
+    SampleConsensusInitialAlignment() { rsreg_scia_params_default(&prm_); reset(); }
+    explicit SampleConsensusInitialAlignment(std::shared_ptr<Context> ctx) : SampleConsensusInitialAlignment() { ctx_ = std::move(ctx); }
+    void setInputSource(const typename PointCloud<PointSource>::Ptr &cloud) { source_ = cloud, dsource_ = nullptr; }
+    void setInputTarget(const typename PointCloud<PointTarget>::Ptr &cloud) { target_ = cloud, dtarget_ = nullptr; }
+    void setSourceFeatures(const typename PointCloud<FeatureT>::Ptr &features) { sfeat_ = features, dsfeat_ = nullptr; }
+    void setTargetFeatures(const typename PointCloud<FeatureT>::Ptr &features) { tfeat_ = features, dtfeat_ = nullptr; }
+    void setInputSource(const DeviceCloud<PointSource> &cloud) { dsource_ = &cloud, source_.reset(); }   // (the clouds must outlive the calls)
+    void setInputTarget(const DeviceCloud<PointTarget> &cloud) { dtarget_ = &cloud, target_.reset(); }
+    void setSourceFeatures(const DeviceCloud<FeatureT> &features) { dsfeat_ = &features, sfeat_.reset(); }
+    void setTargetFeatures(const DeviceCloud<FeatureT> &features) { dtfeat_ = &features, tfeat_.reset(); }
+    void setMaximumIterations(int n) { prm_.max_iterations = n; }
+    int getMaximumIterations() const { return prm_.max_iterations; }
+    void setMinSampleDistance(float d) { prm_.min_sample_distance = d; }
+    float getMinSampleDistance() const { return (float)prm_.min_sample_distance; }
+    void setNumberOfSamples(int n) { prm_.nr_samples = n; }
+    int getNumberOfSamples() const { return prm_.nr_samples; }
+    void setCorrespondenceRandomness(int k) { k_ = k; }
+    int getCorrespondenceRandomness() const { return k_; }
+    void setMaxCorrespondenceDistance(double d) { prm_.max_correspondence_distance = d; }
+    double getMaxCorrespondenceDistance() const { return prm_.max_correspondence_distance; }
+    void setErrorFunction(ErrorFunction f) { prm_.error_function = (int32_t)f; }
+    ErrorFunction getErrorFunction() const { return (ErrorFunction)prm_.error_function; }
+    void setSeed(uint64_t seed) { prm_.seed = seed; }
+    void align(PointCloud<PointSource> &output) { align_host(output, nullptr); }
+    void align(PointCloud<PointSource> &output, const Matrix4f &guess) { align_host(output, guess.data()); }
+    void align(DeviceCloud<PointSource> &output) { align_device(output, nullptr); }
+    void align(DeviceCloud<PointSource> &output, const Matrix4f &guess) { align_device(output, guess.data()); }
+    bool hasConverged() const { return res_.found != 0; }
+    Matrix4f getFinalTransformation() const
+    {
+        Matrix4f T;
+        std::memcpy(T.data(), res_.transform, sizeof res_.transform);
+        return T;
+    }
+    double getFitnessScore() const { return res_.error; }   // the winner's error (the guess's when nothing beat it)
+    const rsreg_scia_result &getResult() const { return res_; }
+  private:
+    void reset()
+    {
+        std::memset(&res_, 0, sizeof res_);
+        const Matrix4f eye = Matrix4f::Identity();
+        std::memcpy(res_.transform, eye.data(), sizeof res_.transform);
+        res_.best_hypothesis = -1;
+        for (int i = 0; i < 8; ++i) res_.sample[i] = res_.match[i] = -1;
+        res_.error = std::numeric_limits<double>::infinity();
+    }
+    std::shared_ptr<Context> context() const
+    {
+        return dsource_ ? dsource_->context() : dtarget_ ? dtarget_->context() : dsfeat_ ? dsfeat_->context() : dtfeat_ ? dtfeat_->context()
+             : ctx_ ? ctx_ : Context::Default();
+    }
+    void align_host(PointCloud<PointSource> &output, const float *guess)
+    {
+        const std::shared_ptr<Context> ctx = context();
+        run(ctx, guess);
+        if (source_) {
+            transformPointCloud(*source_, output, getFinalTransformation(), ctx);
+        } else {
+            DeviceCloud<PointSource> moved(ctx);
+            transformPointCloud(*dsource_, moved, getFinalTransformation());
+            moved.download(output);
+        }
+    }
+    void align_device(DeviceCloud<PointSource> &output, const float *guess)
+    {
+        if (!dsource_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputSource (device cloud) not called");
+        run(context(), guess);
+        transformPointCloud(*dsource_, output, getFinalTransformation());
+    }
+    void run(const std::shared_ptr<Context> &ctx, const float *guess)
+    {
+        if (!source_ && !dsource_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputSource not called");
+        if (!target_ && !dtarget_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputTarget not called");
+        if (!sfeat_ && !dsfeat_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setSourceFeatures not called");
+        if (!tfeat_ && !dtfeat_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setTargetFeatures not called");
+        reset();
+        const registration::DeviceInput<PointSource> s(source_, dsource_, ctx);
+        const registration::DeviceInput<PointTarget> t(target_, dtarget_, ctx);
+        const registration::DeviceInput<FeatureT> fs(sfeat_, dsfeat_, ctx), ft(tfeat_, dtfeat_, ctx);
+        size_t n = 0, nf = 0;
+        check(rsreg_cloud_info(s.handle(), &n, nullptr, nullptr, nullptr, nullptr), ctx->get());
+        check(rsreg_cloud_info(fs.handle(), &nf, nullptr, nullptr, nullptr, nullptr), ctx->get());
+        if (n != nf) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: the source and its features differ in size");
+        if (k_ < 1 || k_ > 16) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setCorrespondenceRandomness needs 1 .. 16");
+        std::vector<int32_t> nbr(n * (size_t)k_, -1);
+        check(rsreg_cloud_feature_knn(ctx->get(), fs.handle(), ft.handle(), k_, nbr.data(), nullptr), ctx->get());
+        check(rsreg_cloud_initial_alignment(ctx->get(), s.handle(), t.handle(), nbr.data(), k_, &prm_, guess, nullptr, &res_), ctx->get());
+    }
+    rsreg_scia_params prm_;
+    rsreg_scia_result res_;
+    int k_ = 10;                           // PCL's default
+    typename PointCloud<PointSource>::Ptr source_;
+    typename PointCloud<PointTarget>::Ptr target_;
+    typename PointCloud<FeatureT>::Ptr sfeat_, tfeat_;
+    const DeviceCloud<PointSource> *dsource_ = nullptr;
+    const DeviceCloud<PointTarget> *dtarget_ = nullptr;
+    const DeviceCloud<FeatureT> *dsfeat_ = nullptr, *dtfeat_ = nullptr;
+    std::shared_ptr<Context> ctx_;
+};
+
 // ---- extract_edge_features (src/edge_extractor.hpp:7-39): the RGB-Canny edge points of an organized cloud
 inline std::shared_ptr<PointCloud<PointXYZRGB>> extract_edge_features(const std::shared_ptr<PointCloud<PointXYZRGB>> &cloud,
                                                                       const std::shared_ptr<Context> &ctx = Context::Default())

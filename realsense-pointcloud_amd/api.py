@@ -508,6 +508,49 @@ class DeviceCloud:
                                                    C.byref(found), C.byref(res)), self.ctx.h)
         return out[:min(found.value, room)], PrerejResult(res, found.value)
 
+    def _scia_table(self, neighbor_index):
+        nbr = np.ascontiguousarray(neighbor_index, np.int32)
+        ns = self.info()[0]
+        if nbr.ndim != 2 or nbr.shape[0] != ns:
+            raise ValueError("neighbor_index must be (%d, k) int32" % ns)
+        return nbr
+
+    def error_transforms(self, target, transforms, error_function, max_correspondence_distance):
+        """float64 per transform: SampleConsensusInitialAlignment's error of this cloud moved by it against `target`
+        (rsreg_cloud_error_transforms; include/rsreg.h holds the terms and the order of the sum).  error_function: SCIA_TRUNCATED or
+        SCIA_HUBER; max_correspondence_distance is compared, as a float, with the SQUARED distance.  transforms: (H, 4, 4), or one 4 x 4."""
+        t = np.asarray(transforms, np.float32).reshape(-1, 4, 4)
+        packed = np.ascontiguousarray(t.transpose(0, 2, 1))   # column-major, one after the other
+        errors = np.zeros(len(t), np.float64)
+        _l.check(_l.lib().rsreg_cloud_error_transforms(self.ctx.h, self.h, target.h, packed.ctypes.data, len(t), int(error_function),
+                                                       float(max_correspondence_distance), errors.ctypes.data), self.ctx.h)
+        return errors
+
+    def initial_alignment_hypotheses(self, target, neighbor_index, first=0, count=1, **params):
+        """(transforms (count, 4, 4) float32, valid (count,) bool, samples (count, 16) int32) of the hypotheses first .. first + count - 1
+        of SampleConsensusInitialAlignment: the sampler and the fit alone (rsreg_cloud_initial_alignment_hypotheses).  An invalid
+        hypothesis's transform is NaN; samples: the source records in [:, :8], their target records in [:, 8:], -1 where there is none."""
+        nbr = self._scia_table(neighbor_index)
+        p = scia_params(**params)
+        t, valid, samples = np.zeros((count, 16), np.float32), np.zeros(count, np.int32), np.zeros((count, 16), np.int32)
+        _l.check(_l.lib().rsreg_cloud_initial_alignment_hypotheses(self.ctx.h, self.h, target.h, nbr.ctypes.data, nbr.shape[1], C.byref(p), int(first), count,
+                                                                   t.ctypes.data, valid.ctypes.data, samples.ctypes.data), self.ctx.h)
+        return np.ascontiguousarray(t.reshape(count, 4, 4).transpose(0, 2, 1)), valid != 0, samples
+
+    def initial_alignment(self, target, neighbor_index, guess=None, errors=False, **params):
+        """pcl::SampleConsensusInitialAlignment (rsreg_cloud_initial_alignment): a SciaResult, or (SciaResult, the error of every
+        hypothesis: max_iterations float64, NaN for an invalid or unused one) with errors=True.  neighbor_index: (ns, k) int32, what
+        source_features.feature_knn(target_features, k)[0] returned.  guess: a 4 x 4 that is scored first and spends an iteration.
+        params: max_correspondence_distance, min_sample_distance, nr_samples, error_function, max_iterations, seed (scia_params())."""
+        nbr = self._scia_table(neighbor_index)
+        p = scia_params(**params)
+        g = None if guess is None else _colmajor(guess)
+        errs = np.zeros(max(int(p.max_iterations), 0), np.float64) if errors else None
+        res = _l.SciaResult()
+        _l.check(_l.lib().rsreg_cloud_initial_alignment(self.ctx.h, self.h, target.h, nbr.ctypes.data, nbr.shape[1], C.byref(p), None if g is None else g.ctypes.data,
+                                                        None if errs is None else errs.ctypes.data, C.byref(res)), self.ctx.h)
+        return (SciaResult(res), errs) if errors else SciaResult(res)
+
     def radius_count(self, radius):
         """radiusSearch of every record in its own cloud, counted (rsreg_cloud_radius_count, exact): uint32 per record, its
         neighbours with float32 d2 < (float)(radius * radius) -- strictly, itself and exact copies among them; 0 for a non-finite
@@ -2023,6 +2066,125 @@ class SampleConsensusPrerejective:
     def getFitnessScore(self):
         """the winner's error, sum of its inliers' squared distances / their number (0.0 without a winner)"""
         return 0.0 if self._result is None else self._result.fitness
+
+    @property
+    def result(self):
+        return self._result
+
+
+SCIA_TRUNCATED, SCIA_HUBER = _l.SCIA_TRUNCATED, _l.SCIA_HUBER
+
+
+def scia_params(**kw):
+    """rsreg_scia_params: the defaults (rsreg_scia_params_default) with the given fields replaced."""
+    p = _l.SciaParams()
+    _l.lib().rsreg_scia_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(p._fields_):
+            raise TypeError("rsreg_scia_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+class SciaResult:
+    """rsreg_scia_result: transform (4 x 4), found (a hypothesis won, not the guess), best_hypothesis, sample (source records) and
+    match (target records), -1 behind nr_samples, n_valid, error."""
+
+    def __init__(self, r):
+        self.transform = _rowmajor(list(r.transform))
+        self.found, self.best_hypothesis = bool(r.found), int(r.best_hypothesis)
+        self.sample, self.match = tuple(r.sample), tuple(r.match)
+        self.n_valid, self.error = int(r.n_valid), float(r.error)
+
+
+class SampleConsensusInitialAlignment:
+    """pcl::SampleConsensusInitialAlignment on the GPU: poses from nr_samples source records that keep a minimum distance from one
+    another and a random one of each one's k nearest descriptors; none is thrown away, every one is scored over every source record
+    by a bounded penalty of its exact nearest-point distance (csrc/scia_kernels.hpp, rsreg_cloud_initial_alignment; include/rsreg.h
+    holds the contract and the stated deviations from PCL).  Clouds and features as SampleConsensusPrerejective takes them.  align()
+    makes two calls, rsreg_cloud_feature_knn and rsreg_cloud_initial_alignment, and returns the source moved by the final
+    transformation.  As in PCL, setMaxCorrespondenceDistance is compared with the SQUARED distance.  params.seed is this library's own."""
+
+    def __init__(self, ctx=None):
+        self._src = self._tgt = self._src_feat = self._tgt_feat = None
+        self.ctx = ctx
+        self.params = scia_params()
+        self.k = 10                                  # PCL's default k_correspondences_
+        self._result = None
+
+    def setInputSource(self, cloud):
+        self._src = cloud
+
+    def setInputTarget(self, cloud):
+        self._tgt = cloud
+
+    def setSourceFeatures(self, features):
+        self._src_feat = features
+
+    def setTargetFeatures(self, features):
+        self._tgt_feat = features
+
+    def setMaximumIterations(self, n):
+        self.params.max_iterations = int(n)
+
+    def setNumberOfSamples(self, n):
+        self.params.nr_samples = int(n)
+
+    def getNumberOfSamples(self):
+        return self.params.nr_samples
+
+    def setCorrespondenceRandomness(self, k):
+        self.k = int(k)
+
+    def getCorrespondenceRandomness(self):
+        return self.k
+
+    def setMinSampleDistance(self, d):
+        self.params.min_sample_distance = float(d)
+
+    def getMinSampleDistance(self):
+        return self.params.min_sample_distance
+
+    def setMaxCorrespondenceDistance(self, d):
+        self.params.max_correspondence_distance = float(d)
+
+    def setErrorFunction(self, f):
+        self.params.error_function = int(f)
+
+    def setSeed(self, seed):
+        self.params.seed = int(seed)
+
+    def align(self, guess=None):
+        for what, v in (("setInputSource", self._src), ("setInputTarget", self._tgt), ("setSourceFeatures", self._src_feat),
+                        ("setTargetFeatures", self._tgt_feat)):
+            if v is None:
+                raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, what + " not called")
+        ctx = next((c.ctx for c in (self._src, self._tgt, self._src_feat, self._tgt_feat) if isinstance(c, DeviceCloud)), None) or self.ctx or default_context()
+        src, tgt, made = _as_device_pair(self._src, self._tgt, ctx)
+        try:
+            fs, ft, more = _as_device_pair(self._src_feat, self._tgt_feat, ctx)
+            made += more
+            nbr, _ = fs.feature_knn(ft, self.k)
+            self._result = src.initial_alignment(tgt, nbr, guess=guess, **{k: getattr(self.params, k) for k, _ in self.params._fields_})
+            moved = transformPointCloud(src, self._result.transform)
+            if isinstance(self._src, DeviceCloud):
+                return moved
+            out = moved.download()
+            moved.close()
+            return out
+        finally:
+            for c in made:
+                c.close()
+
+    def hasConverged(self):
+        return self._result is not None and self._result.found
+
+    def getFinalTransformation(self):
+        return np.eye(4, dtype=np.float32) if self._result is None else self._result.transform
+
+    def getFitnessScore(self):
+        """the winner's error (+inf before align(), or when nothing was scored)"""
+        return float("inf") if self._result is None else self._result.error
 
     @property
     def result(self):

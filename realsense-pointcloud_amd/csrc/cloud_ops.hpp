@@ -75,4 +75,21 @@ constexpr CloudRule kXyzRule{12, true, "records need x, y, z floats and a stride
 // when the cloud holds records that cannot be reached (their upload failed).
 int cloud_view(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *out_or_null, const CloudRule &rule, CloudView &view);
 
+// ---- prerej.hip, for scia.hip: the two estimators that score poses against a whole target cloud share the context's PrerejScratch,
+// the target's index and the kernel that adds a launch's partial sums
+struct PrejClouds {
+    CloudView sv, tv;
+    uint32_t ns = 0, nt = 0;
+};
+// both clouds checked (kXyzRule); nothing is launched
+int prerej_views(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, PrejClouds &c);
+// the host table of descriptor neighbours: 1 <= k <= 16, a table where there are records, every entry -1 or a target record, no row -1 in part
+int prerej_table_check(rsreg_ctx *ctx, const int32_t *neighbor_index, int k, uint32_t ns, uint32_t nt);
+// the target's block-major point grid into ctx->prerej.grid, queued and (for its box) waited for
+int prerej_index(rsreg_ctx *ctx, const PrejClouds &c);
+// ctx->prerej's per-round buffers, for rounds of R hypotheses against ns source records
+int prerej_reserve(rsreg_ctx *ctx, uint32_t ns, uint32_t R);
+// k_prerej_final, queued: d_sums[h] = the partials a scoring launch left of its hypothesis h < B (d_valid null: of every one)
+int prerej_final(rsreg_ctx *ctx, const uint32_t *d_valid, uint32_t B, uint32_t tiles, double *d_sums);
+
 }  // namespace rsreg

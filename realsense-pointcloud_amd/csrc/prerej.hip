@@ -28,10 +28,10 @@ float prerej_thr_up(double t2)
     return f;
 }
 
-struct PrejClouds {
-    CloudView sv, tv;
-    uint32_t ns = 0, nt = 0;
-};
+}  // namespace
+
+// ---- what scia.hip calls as well (declared in cloud_ops.hpp)
+namespace rsreg {
 
 // both clouds checked; nothing is launched
 int prerej_views(rsreg_ctx *ctx, const rsreg_cloud *source, const rsreg_cloud *target, PrejClouds &c)
@@ -53,18 +53,27 @@ int prerej_index(rsreg_ctx *ctx, const PrejClouds &c)
     return grid_build<FitGridPolicy>(ctx, sc.grid, PrejRecords{c.tv.rec, c.tv.stride}, c.nt, 1, sc.host.as<uint32_t>());
 }
 
-// the rows [0, B) of sc.d_table + 12 * at scored into sc.d_counts + at and sc.d_sums + at (valid: sc.d_valid + at, or every row), queued
-int prerej_score(rsreg_ctx *ctx, const PrejClouds &c, uint32_t at, uint32_t B, bool use_valid, float limit2)
+// the caller's table of descriptor neighbours, checked on the host: k, every entry, the rows of -1
+int prerej_table_check(rsreg_ctx *ctx, const int32_t *neighbor_index, int k, uint32_t ns, uint32_t nt)
 {
-    PrerejScratch &sc = ctx->prerej;
-    hipStream_t st = ctx->stream;
-    const PrejPlan p = prerej_plan(c.ns, B);
-    const uint32_t *valid = use_valid ? sc.d_valid.as<uint32_t>() + at : nullptr;
-    RSREG_HIP(ctx, hipMemsetAsync(sc.d_counts.as<uint32_t>() + at, 0, (size_t)B * 4, st));
-    k_prerej_score<<<p.tiles * p.slices, kPrejBlock, 0, st>>>(c.sv.rec, c.sv.stride, c.ns, sc.d_table.as<float>() + (size_t)at * 12, valid, B, p.tiles, p.slice_chunks,
-                                                             grid_dev(sc.grid), limit2, sc.d_counts.as<uint32_t>() + at, sc.d_partials.as<double>());
-    RSREG_HIP(ctx, hipGetLastError());
-    k_prerej_final<<<div_up(B, (uint32_t)kPrejLanes), kPrejLanes, 0, st>>>(sc.d_partials.as<double>(), valid, B, p.tiles, sc.d_sums.as<double>() + at);
+    if (k < 1 || k > 16) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must lie in 1 .. 16");
+    if (ns && !neighbor_index) return fail(ctx, RSREG_ERR_INVALID_ARG, "a neighbour table is needed");
+    for (size_t i = 0; i < ns; ++i) {
+        const int32_t *row = neighbor_index + i * (size_t)k;
+        int minus = 0;
+        for (int j = 0; j < k; ++j) {
+            if (row[j] == -1) ++minus;
+            else if (row[j] < 0 || (uint32_t)row[j] >= nt) return fail(ctx, RSREG_ERR_INVALID_ARG, "the neighbour table names a record outside the target");
+        }
+        if (minus && minus != k) return fail(ctx, RSREG_ERR_INVALID_ARG, "a row of the neighbour table is -1 in part");
+    }
+    return RSREG_OK;
+}
+
+// d_sums[h] = the partials of hypothesis h < B of the launch before (d_valid: which rows have any; null: every row), queued
+int prerej_final(rsreg_ctx *ctx, const uint32_t *d_valid, uint32_t B, uint32_t tiles, double *d_sums)
+{
+    k_prerej_final<<<div_up(B, (uint32_t)kPrejLanes), kPrejLanes, 0, ctx->stream>>>(ctx->prerej.d_partials.as<double>(), d_valid, B, tiles, d_sums);
     RSREG_HIP(ctx, hipGetLastError());
     return RSREG_OK;
 }
@@ -82,6 +91,24 @@ int prerej_reserve(rsreg_ctx *ctx, uint32_t ns, uint32_t R)
     RSREG_HIP(ctx, sc.d_partials.reserve((size_t)prerej_batch_cap(ns) * groups * kPrejPartialStride + 16));
     RSREG_HIP(ctx, sc.host.reserve((size_t)R * 96 + 4096));
     return RSREG_OK;
+}
+
+}  // namespace rsreg
+
+namespace {
+
+// the rows [0, B) of sc.d_table + 12 * at scored into sc.d_counts + at and sc.d_sums + at (valid: sc.d_valid + at, or every row), queued
+int prerej_score(rsreg_ctx *ctx, const PrejClouds &c, uint32_t at, uint32_t B, bool use_valid, float limit2)
+{
+    PrerejScratch &sc = ctx->prerej;
+    hipStream_t st = ctx->stream;
+    const PrejPlan p = prerej_plan(c.ns, B);
+    const uint32_t *valid = use_valid ? sc.d_valid.as<uint32_t>() + at : nullptr;
+    RSREG_HIP(ctx, hipMemsetAsync(sc.d_counts.as<uint32_t>() + at, 0, (size_t)B * 4, st));
+    k_prerej_score<<<p.tiles * p.slices, kPrejBlock, 0, st>>>(c.sv.rec, c.sv.stride, c.ns, sc.d_table.as<float>() + (size_t)at * 12, valid, B, p.tiles, p.slice_chunks,
+                                                             grid_dev(sc.grid), limit2, sc.d_counts.as<uint32_t>() + at, sc.d_partials.as<double>());
+    RSREG_HIP(ctx, hipGetLastError());
+    return prerej_final(ctx, valid, B, p.tiles, sc.d_sums.as<double>() + at);
 }
 
 }  // namespace
@@ -148,23 +175,14 @@ int rsreg_cloud_prerejective(rsreg_ctx *ctx, const rsreg_cloud *source, const rs
     int rc = prerej_views(ctx, source, target, c);
     if (rc) return rc;
     if (!n_out || (capacity && !inliers_out)) return fail(ctx, RSREG_ERR_INVALID_ARG, "n_out, and inliers_out with a capacity, are needed");
-    if (k < 1 || k > 16) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must lie in 1 .. 16");
-    if (c.ns && !neighbor_index) return fail(ctx, RSREG_ERR_INVALID_ARG, "a neighbour table is needed");
     rsreg_prerej_params prm;
     if (params) prm = *params; else rsreg_prerej_params_default(&prm);
     if (prm.max_iterations < 0) return fail(ctx, RSREG_ERR_INVALID_ARG, "max_iterations must not be negative");
     if (!(prm.similarity_threshold >= 0.0f && prm.similarity_threshold < 1.0f)) return fail(ctx, RSREG_ERR_INVALID_ARG, "similarity_threshold must lie in [0, 1)");
     if (!(prm.max_correspondence_distance >= 0.0)) return fail(ctx, RSREG_ERR_INVALID_ARG, "max_correspondence_distance must not be negative or NaN");
     if (!(prm.inlier_fraction >= 0.0 && prm.inlier_fraction <= 1.0)) return fail(ctx, RSREG_ERR_INVALID_ARG, "inlier_fraction must lie in [0, 1]");
-    for (size_t i = 0; i < c.ns; ++i) {
-        const int32_t *row = neighbor_index + i * (size_t)k;
-        int minus = 0;
-        for (int j = 0; j < k; ++j) {
-            if (row[j] == -1) ++minus;
-            else if (row[j] < 0 || (uint32_t)row[j] >= c.nt) return fail(ctx, RSREG_ERR_INVALID_ARG, "the neighbour table names a record outside the target");
-        }
-        if (minus && minus != k) return fail(ctx, RSREG_ERR_INVALID_ARG, "a row of the neighbour table is -1 in part");
-    }
+    rc = prerej_table_check(ctx, neighbor_index, k, c.ns, c.nt);
+    if (rc) return rc;
 
     rsreg_prerej_result res;
     std::memset(&res, 0, sizeof res);

@@ -245,7 +245,8 @@ struct SacScratch {
     PinnedBuf host;                // counts, samples, rows, sums and words on their way home; a caller's transforms on their way out
 };
 
-// Index and scratch of SampleConsensusPrerejective (prerej.hip, prerej_kernels.hpp): the target's point grid, rebuilt by every call,
+// Index and scratch of SampleConsensusPrerejective (prerej.hip, prerej_kernels.hpp) and, a call at a time, of
+// SampleConsensusInitialAlignment (scia.hip: 16 sample words a hypothesis, errors in d_sums): the target's point grid, rebuilt by every call,
 // and what a round of hypotheses leaves; shares no buffer with another index or with the correspondence rejector
 struct PrerejScratch {
     PointGrid grid;                // the target of the call, block-major (FitGridPolicy)

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(_HERE)
 DIAG = os.environ.get("RSREG_DIAG", "") == "1"
 SO_PATH = (os.environ.get("RSREG_SO") if DIAG else None) or os.path.join(_HERE, "librsreg_diag.so" if DIAG else "librsreg.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip", "depthcloud.hip", "depth_host.cpp", "features.hip", "sac.hip", "prerej.hip"]
+SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip", "depthcloud.hip", "depth_host.cpp", "features.hip", "sac.hip", "prerej.hip", "scia.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) if os.path.isdir(CSRC) else []
 NUM_SUMS = 17
 NUM_PLANE_SUMS = 32                                      # include/rsreg.h: RSREG_NUM_PLANE_SUMS
@@ -26,6 +26,7 @@ IIN_BORDER_IGNORE, IIN_BORDER_MIRROR = 0, 1              # rsreg_iin_border_poli
 # rsreg_distortion (rs2_distortion)
 DISTORTION_NONE, DISTORTION_MODIFIED_BROWN_CONRADY, DISTORTION_INVERSE_BROWN_CONRADY, DISTORTION_FTHETA, DISTORTION_BROWN_CONRADY, DISTORTION_KANNALA_BRANDT4 = range(6)
 RSREG_ERR_INVALID_ARG, RSREG_ERR_STATE = -1, -9   # include/rsreg.h: rsreg_status
+SCIA_TRUNCATED, SCIA_HUBER = 0, 1                 # include/rsreg.h: rsreg_scia_error_function
 UNIQUE_ID_BYTES = 128
 
 # every symbol include/rsreg.h declares (checked by tests/test_abi.py)
@@ -50,6 +51,7 @@ EXPORTS = [
     "rsreg_cloud_fpfh", "rsreg_cloud_spfh", "rsreg_cloud_feature_knn", "rsreg_cloud_feature_correspondences",
     "rsreg_sac_params_default", "rsreg_cloud_count_inliers", "rsreg_cloud_estimate_rigid_svd", "rsreg_cloud_sac_correspondences",
     "rsreg_prerej_params_default", "rsreg_cloud_score_transforms", "rsreg_cloud_prerejective",
+    "rsreg_scia_params_default", "rsreg_cloud_error_transforms", "rsreg_cloud_initial_alignment_hypotheses", "rsreg_cloud_initial_alignment",
     "rsreg_cloud_radius_count", "rsreg_cloud_radius_outlier_removal", "rsreg_cloud_normals_radius",
     "rsreg_cloud_fpfh_radius", "rsreg_cloud_spfh_radius",
     "rsreg_iss_params_default", "rsreg_cloud_iss_saliency", "rsreg_cloud_iss_non_max", "rsreg_cloud_iss_keypoints",
@@ -122,6 +124,16 @@ class PrerejParams(C.Structure):   # rsreg_prerej_params
 class PrerejResult(C.Structure):   # rsreg_prerej_result
     _fields_ = [("transform", C.c_float * 16), ("found", C.c_int32), ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 3),
                 ("match", C.c_int32 * 3), ("n_valid", C.c_uint64), ("n_inliers", C.c_uint64), ("fitness", C.c_double)]
+
+
+class SciaParams(C.Structure):   # rsreg_scia_params
+    _fields_ = [("max_correspondence_distance", C.c_double), ("min_sample_distance", C.c_double), ("nr_samples", C.c_int32),
+                ("error_function", C.c_int32), ("max_iterations", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64)]
+
+
+class SciaResult(C.Structure):   # rsreg_scia_result
+    _fields_ = [("transform", C.c_float * 16), ("found", C.c_int32), ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 8),
+                ("match", C.c_int32 * 8), ("n_valid", C.c_uint64), ("error", C.c_double)]
 
 
 class IssParams(C.Structure):   # rsreg_iss_params
@@ -356,6 +368,11 @@ def lib():
     L.rsreg_prerej_params_default.restype = None
     L.rsreg_cloud_score_transforms.argtypes = [vp, vp, vp, vp, sz, dbl, vp, vp]
     L.rsreg_cloud_prerejective.argtypes = [vp, vp, vp, vp, i32, C.POINTER(PrerejParams), vp, sz, C.POINTER(sz), C.POINTER(PrerejResult)]
+    L.rsreg_scia_params_default.argtypes = [C.POINTER(SciaParams)]
+    L.rsreg_scia_params_default.restype = None
+    L.rsreg_cloud_error_transforms.argtypes = [vp, vp, vp, vp, sz, i32, dbl, vp]
+    L.rsreg_cloud_initial_alignment_hypotheses.argtypes = [vp, vp, vp, vp, i32, C.POINTER(SciaParams), C.c_uint64, sz, vp, vp, vp]
+    L.rsreg_cloud_initial_alignment.argtypes = [vp, vp, vp, vp, i32, C.POINTER(SciaParams), vp, vp, C.POINTER(SciaResult)]
     L.rsreg_cloud_radius_count.argtypes = [vp, vp, dbl, vp]
     L.rsreg_cloud_radius_outlier_removal.argtypes = [vp, vp, dbl, i32, i32, i32, vp, C.POINTER(C.c_uint64)]
     L.rsreg_cloud_normals_radius.argtypes = [vp, vp, dbl, vp, vp]
