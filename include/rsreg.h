@@ -357,6 +357,131 @@ int rsreg_icp_plane_sums_last(rsreg_ctx *ctx, double sums[RSREG_NUM_PLANE_SUMS])
 /* The solve alone (host only, no ctx): t_out = the increment, column-major; *rank_out (nullable) = eigen-directions used. */
 int rsreg_plane_solve_from_sums(const double sums[RSREG_NUM_PLANE_SUMS], float t_out[16], int *rank_out);
 
+/* ---- GICP: pcl::GeneralizedIterativeClosestPoint (plane-to-plane ICP, Segal et al.) ------------------------------------------
+ * A sibling of point-to-plane ICP with entry points of its own (rsreg_icp_params.estimation has no value for it): the context's
+ * ICP source, target, index and staged search are shared -- the clouds come in through rsreg_icp_set_source* / rsreg_icp_set_target*
+ * -- and every correspondence is weighted by the surface covariance of both clouds.  PCL 1.9.1 (registration/gicp.h, impl/gicp.hpp)
+ * is recalled, not read; what is kept from it: the objective, the correspondences, the Mahalanobis matrices, the defaults and the
+ * outer stopping rule.  DEVIATIONS, stated where they apply: (1) the covariance is rebuilt as I - (1 - epsilon) n n^T, not through
+ * an SVD; (2) every sum is f64 in a fixed order; (3) the inner minimiser is Gauss-Newton with step halving, not PCL's BFGS.
+ *
+ * COVARIANCES (rsreg_cloud_gicp_covariances; PCL: computeCovariances, k = setCorrespondenceRandomness, default 20, epsilon =
+ * gicp_epsilon_, default 0.001).  For every finite record q of `in`: its k nearest neighbours t_1 .. t_k as rsreg_cloud_knn returns
+ * them, the record itself and exact copies included, 4 <= k <= 64 (RSREG_ERR_INVALID_ARG otherwise, and when fewer than k records
+ * are finite); the moments of d_i = t_i - q in f64, c = (sum d d^T) / k - (sum d / k)(sum d / k)^T -- the sums, their order and the
+ * covariance are those of rsreg_cloud_normals; n = the unit eigenvector of c's smallest eigenvalue by the same Jacobi, (0, 0, 1) when
+ * trace(c) == 0 (all neighbours coincide); then, every operation rounded once, no contraction, s = 1 - epsilon:
+ *     C'_ab = delta_ab - s * (n_a * n_b)                 (a diagonal entry: 1 - s * (n_a * n_a); another: 0 - s * (n_a * n_b))
+ * PCL replaces the singular values of c by (1, 1, epsilon) and rebuilds U diag(1, 1, epsilon) U^T; with U orthonormal that is the
+ * matrix above.  DEVIATION (1): the rounding order differs from PCL's SVD rebuild (and PCL's moments are sums about the origin in
+ * its own neighbour order); where the two smallest eigenvalues of c coincide, n is any unit vector of their plane, here as there.
+ * out: one 48-byte record per input record, six doubles (xx, xy, xz, yy, yz, zz), width and height of the input; a non-finite input
+ * record gets six quiet NaNs and makes the cloud not dense, otherwise is_dense is the input's.  The result depends on the cloud
+ * alone, not on the launch or the context.
+ *
+ * PARAMETERS (rsreg_gicp_params_default = PCL 1.9.1 gicp.h, recalled: 200, 20, 5.0, 5e-4, 2e-3, 20, 1e-3).  k_correspondences and
+ * gicp_epsilon are what the C++ and Python classes hand to rsreg_cloud_gicp_covariances when the caller gave no covariances; the
+ * alignment itself reads the covariances that were set.
+ *
+ * SETTING THE COVARIANCES.  One 48-byte-or-wider record of six doubles per source (target) RECORD, in the caller's order, n = the
+ * record count of the cloud set by rsreg_icp_set_source* (rsreg_icp_set_target*): RSREG_ERR_INVALID_ARG otherwise, RSREG_ERR_NO_SOURCE
+ * / RSREG_ERR_NO_TARGET without the cloud; stride >= 48 (a device cloud: a multiple of 8).  The next rsreg_icp_set_source*
+ * (rsreg_icp_set_target*) drops them.  The host buffer has been read when the call returns; a device cloud is read on the context's
+ * stream.  Exact copies of a source point have the same neighbours and so the same covariance: the engine's merged copies use the
+ * first copy's record and the pair weight W below.
+ *
+ * ONE OUTER ITERATION (T = the current transform, float 4 x 4, the guess at first; R = its rotation block, float -> double):
+ * 1. Search: the source under T (from the records, not incrementally), rsreg_icp_search's exact nearest neighbour and gate
+ *    (a pair is rejected iff (double)d2 > max_correspondence_distance^2).  p = the moved source point (float), q = its target.
+ * 2. Per kept pair (source record i, target record j), in f64, every operation rounded once:
+ *      B = R C_s[i]:  B_rc = (R_r0 C_0c + R_r1 C_1c) + R_r2 C_2c        D = B R^T:  D_rc = (B_r0 R_c0 + B_r1 R_c1) + B_r2 R_c2   (c >= r)
+ *      A = C_t[j] + D      adjugate: a00 = A11 A22 - A12 A12   a01 = A02 A12 - A01 A22   a02 = A01 A12 - A02 A11
+ *                                    a11 = A00 A22 - A02 A02   a12 = A01 A02 - A00 A12   a22 = A00 A11 - A01 A01
+ *      det = (A00 a00 + A01 a01) + A02 a02      M_ab = a_ab * (1 / det)
+ *    once per outer iteration, as PCL computes mahalanobis_.  Both summands have eigenvalues >= epsilon, so finite covariances give
+ *    a finite M.  A pair with a non-finite entry in C_s[i] or C_t[j], or in M, is SKIPPED: it adds to sums [0] and [1] only (PCL's
+ *    rule, the one plane mode follows for NaN normals).
+ * 3. Inner minimisation of sum W e^T M e over an increment X (double 4 x 4, I at first) applied on the left of the moved points:
+ *      p' = X p:  p'_r = ((X_r0 p.x + X_r1 p.y) + X_r2 p.z) + X_r3      e = q - p'      J = [-[p']x | I3]  (small angles, as plane mode)
+ *      g = M e:  g_r = (M_r0 e_0 + M_r1 e_1) + M_r2 e_2      G = [p']x M:  G_0c = p'y M_2c - p'z M_1c   G_1c = p'z M_0c - p'x M_2c
+ *                                                                           G_2c = p'x M_1c - p'y M_0c
+ *    The 32 sums at X (RSREG_NUM_GICP_SUMS, all f64; W = how many source records the pair stands for):
+ *      [0] sum W over the gated pairs      [1] sum W * (double)d2 of the search -- bit-equal to rsreg_icp_sums [0] and [16]
+ *      [2] sum W over the pairs in the system      [3] sum W * ((e_0 g_0 + e_1 g_1) + e_2 g_2), the cost
+ *      [4..24] H = sum W J^T M J, upper triangle row-major (00 01 .. 05 11 .. 55):
+ *              rows 0-2 x cols 0-2: H_r0 = G_r2 p'y - G_r1 p'z   H_r1 = G_r0 p'z - G_r2 p'x   H_r2 = G_r1 p'x - G_r0 p'y
+ *              rows 0-2 x cols 3-5: G      rows 3-5 x cols 3-5: M
+ *      [25..30] b = sum W J^T M e = (p'y g_2 - p'z g_1,  p'z g_0 - p'x g_2,  p'x g_1 - p'y g_0,  g_0, g_1, g_2)      [31] 0
+ *    in the fixed addition order of the plane sums (per tile by halving over lanes, then the tiles): the same 32 doubles on any
+ *    context, at any launch.  x = pinv(H) b by rsreg_plane_solve_from_sums' rule (same eigenvalue cut over [2]) is the Gauss-Newton
+ *    step, and Delta(x) = PCL's constructTransformationMatrix(x), kept in double.
+ *    Step control, decided by the sums alone:  S = sums(I);  repeat { x = solve(S), stop if its rank is 0;  c = 1;
+ *      repeat { X' = Delta(c x) X  (entries ((a0 b0 + a1 b1) + a2 b2) + a3 b3);  S' = sums(X');  accept (X, S <- X', S') if S'[3] <= S[3],
+ *      else c <- c / 2 };  stop if every |c x_0..2| <= rotation_epsilon and every |c x_3..5| <= transformation_epsilon }.
+ *    Every evaluation after the first counts against max_inner_iterations; the loop ends where they are used up (a step not yet
+ *    accepted is dropped).
+ *    DEVIATION (3): PCL minimises the same objective over (t, Euler angles) with its own BFGS port and line search.
+ * 4. T_new = float(X T), entries ((X_r0 T_0c + X_r1 T_1c) + X_r2 T_2c) + X_r3 T_3c in double.  PCL's test, recalled: delta = the
+ *    largest |T(k,l) - T_new(k,l)| over the 3 x 4 block times 1 / rotation_epsilon (l < 3) or 1 / transformation_epsilon (l = 3)
+ *    (an entry that did not change counts 0 whatever the epsilon); the loop stops when delta < 1 (RSREG_CONV_TRANSFORM) or the
+ *    iteration count reaches max_iterations (RSREG_CONV_ITERATIONS); converged is 1 in both cases, as PCL sets it.  Fewer than 4
+ *    pairs in [0]: RSREG_CONV_NO_CORRESPONDENCES, converged 0, the transform as it was.
+ *
+ * CALLS.  rsreg_gicp_align[_cloud] runs the loop (aligned_out as rsreg_icp_align[_cloud]).  Step-wise, for tests and callers with a
+ * loop of their own:  begin -> { search -> sums(X) ... -> update(X) } -> end.  rsreg_gicp_search: step 1 and 2 (outputs as
+ * rsreg_icp_search); rsreg_gicp_sums: the 32 sums at X (column-major 4 x 4, NULL = I) of the last search; rsreg_gicp_step_from_sums
+ * (host only, no ctx): x_out = scale * pinv(H) b, delta_out = Delta(x_out) column-major (identity when the rank is 0);
+ * rsreg_gicp_update: step 4 with the caller's X and the sums at it (n_correspondences, mse = [1] / [0]; inner_evaluations adds to
+ * the result's count), *done = 1 when the loop must stop.  Alignments without both covariance sets: RSREG_ERR_STATE from
+ * rsreg_gicp_begin; a communicator of more than one rank: RSREG_ERR_INVALID_ARG (nothing is all-reduced).  rsreg_icp_fitness_score
+ * works after a GICP alignment as after any other. */
+#define RSREG_NUM_GICP_SUMS 32
+
+typedef struct rsreg_gicp_params {
+    int32_t max_iterations;             /* setMaximumIterations, 200                                  */
+    int32_t max_inner_iterations;       /* setMaximumOptimizerIterations, 20                          */
+    int32_t k_correspondences;          /* setCorrespondenceRandomness, 20                            */
+    int32_t reserved0;
+    double max_correspondence_distance; /* setMaxCorrespondenceDistance, 5.0                          */
+    double transformation_epsilon;      /* setTransformationEpsilon, 5e-4                             */
+    double rotation_epsilon;            /* setRotationEpsilon, 2e-3                                   */
+    double gicp_epsilon;                /* gicp_epsilon_, 1e-3                                        */
+} rsreg_gicp_params;
+
+typedef struct rsreg_gicp_result {
+    float transform[16];        /* final_transformation_, column-major                               */
+    int32_t converged;
+    int32_t state;              /* rsreg_convergence_state: ITERATIONS, TRANSFORM or NO_CORRESPONDENCES */
+    int32_t iterations;         /* outer iterations                                                  */
+    int32_t inner_evaluations;  /* evaluations of the 32 sums after the first of every outer iteration, all iterations */
+    uint64_t n_correspondences; /* [0] of the last iteration                                         */
+    double mse;                 /* [1] / [0] of the last iteration                                   */
+    double sums_last[RSREG_NUM_GICP_SUMS]; /* the 32 sums at the accepted X of the last iteration  */
+    double ms_total;            /* device-time breakdown as rsreg_icp_result (0 if profiling off)    */
+    double ms_nn;
+    double ms_reduce;           /* the Mahalanobis and sums kernels                                  */
+    double ms_transform;
+    int32_t n_nn_launches;
+    int32_t rank_last;          /* eigen-directions the last solve used                              */
+} rsreg_gicp_result;
+
+void rsreg_gicp_params_default(rsreg_gicp_params *p);
+int rsreg_cloud_gicp_covariances(rsreg_ctx *ctx, const rsreg_cloud *in, int k, double epsilon, rsreg_cloud *out);
+int rsreg_gicp_set_source_covariances(rsreg_ctx *ctx, const void *cov, size_t n, size_t stride);
+int rsreg_gicp_set_target_covariances(rsreg_ctx *ctx, const void *cov, size_t n, size_t stride);
+int rsreg_gicp_set_source_covariances_cloud(rsreg_ctx *ctx, const rsreg_cloud *cov);
+int rsreg_gicp_set_target_covariances_cloud(rsreg_ctx *ctx, const rsreg_cloud *cov);
+int rsreg_gicp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params);
+int rsreg_gicp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out);
+int rsreg_gicp_sums(rsreg_ctx *ctx, const double X[16], double sums[RSREG_NUM_GICP_SUMS]);
+int rsreg_gicp_step_from_sums(const double sums[RSREG_NUM_GICP_SUMS], double scale, double x_out[6], double delta_out[16], int *rank_out);
+int rsreg_gicp_update(rsreg_ctx *ctx, const double X[16], const double sums[RSREG_NUM_GICP_SUMS], int inner_evaluations, int *done);
+int rsreg_gicp_end(rsreg_ctx *ctx, rsreg_gicp_result *result, void *aligned_out, size_t out_stride);
+int rsreg_gicp_align(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, rsreg_gicp_result *result,
+                     void *aligned_out, size_t out_stride);
+int rsreg_gicp_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, rsreg_gicp_result *result,
+                           rsreg_cloud *aligned_out);
+
 /* ---- pcl::transformPointCloud(in, out, Matrix4f) ------------------------------------ */
 /* incremental_icp.hpp:63, icp_edge...hpp:116-117, ndt_edge...hpp:104-105.  in == out is
  * allowed.  Records are copied whole (stride bytes) and xyz rewritten; when !is_dense,

@@ -582,6 +582,110 @@ class IterativeClosestPointWithNormals : public IterativeClosestPoint<PointSourc
     std::pair<uint64_t, uint64_t> normals_stamp_{0, 0};
 };
 
+// ---- pcl::GeneralizedIterativeClosestPoint: plane-to-plane ICP (rsreg.h: the rsreg_gicp_* section holds the contract and the
+// stated deviations from PCL -- I - (1 - eps) n n^T in the place of the SVD rebuild, f64 fixed-order sums, Gauss-Newton with step
+// halving in the place of PCL's BFGS).  Covariances: six doubles a record (xx, xy, xz, yy, yz, zz) in the caller's order; a cloud
+// without them gets its own from rsreg_cloud_gicp_covariances on a device cloud, with setCorrespondenceRandomness' k, as PCL
+// computes them in computeTransformation when none are given.
+using GicpCovariances = std::vector<std::array<double, 6>>;
+template <typename PointSource, typename PointTarget> class GeneralizedIterativeClosestPoint {
+  public:
+    using SourcePtr = typename PointCloud<PointSource>::Ptr;
+    using TargetPtr = typename PointCloud<PointTarget>::Ptr;
+    using CovariancesPtr = std::shared_ptr<const GicpCovariances>;
+
+    explicit GeneralizedIterativeClosestPoint(std::shared_ptr<Context> ctx = Context::Default()) : ctx_(std::move(ctx))
+    {
+        rsreg_gicp_params_default(&prm_);
+        final_ = Matrix4f::Identity();
+    }
+    void setCorrespondenceRandomness(int k) { prm_.k_correspondences = k; source_cov_dirty_ = target_cov_dirty_ = true; }
+    int getCorrespondenceRandomness() const { return prm_.k_correspondences; }
+    void setRotationEpsilon(double e) { prm_.rotation_epsilon = e; }
+    void setTransformationEpsilon(double e) { prm_.transformation_epsilon = e; }
+    void setMaximumOptimizerIterations(int n) { prm_.max_inner_iterations = n; }
+    void setMaximumIterations(int n) { prm_.max_iterations = n; }
+    void setMaxCorrespondenceDistance(double d)
+    {
+        if (d != prm_.max_correspondence_distance) target_dirty_ = true;  // the index cell size derives from it
+        prm_.max_correspondence_distance = d;
+    }
+    void setInputSource(const SourcePtr &cloud) { source_ = cloud; source_cov_.reset(); source_dirty_ = true; }
+    void setInputTarget(const TargetPtr &cloud) { target_ = cloud; target_cov_.reset(); target_dirty_ = true; }
+    // one record per source / target point; call them after setInputSource / setInputTarget (a new cloud drops them, as in PCL)
+    void setSourceCovariances(const CovariancesPtr &cov) { source_cov_ = cov; source_cov_dirty_ = true; }
+    void setTargetCovariances(const CovariancesPtr &cov) { target_cov_ = cov; target_cov_dirty_ = true; }
+
+    void align(PointCloud<PointSource> &output) { align(output, Matrix4f::Identity()); }
+    void align(PointCloud<PointSource> &output, const Matrix4f &guess)
+    {
+        if (!source_ || !target_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputSource / setInputTarget not called");
+        rsreg_ctx *c = ctx_->get();
+        if (source_dirty_ || ctx_->icp_source_owner != this) {
+            check(rsreg_icp_set_source(c, source_->points.data(), source_->size(), sizeof(PointSource), source_->is_dense), c);
+            source_dirty_ = false;
+            source_cov_dirty_ = true;   // (a new source drops the covariances of the one before)
+            ctx_->icp_source_owner = this;
+        }
+        if (target_dirty_ || ctx_->icp_target_owner != this) {
+            check(rsreg_icp_set_target(c, target_->points.data(), target_->size(), sizeof(PointTarget), target_->is_dense,
+                                       prm_.max_correspondence_distance), c);
+            target_dirty_ = false;
+            target_cov_dirty_ = true;
+            ctx_->icp_target_owner = this;
+        }
+        if (source_cov_dirty_) {
+            if (source_cov_) check(rsreg_gicp_set_source_covariances(c, source_cov_->data(), source_cov_->size(), sizeof(std::array<double, 6>)), c);
+            else compute_covariances_(*source_, true);
+            source_cov_dirty_ = false;
+        }
+        if (target_cov_dirty_) {
+            if (target_cov_) check(rsreg_gicp_set_target_covariances(c, target_cov_->data(), target_cov_->size(), sizeof(std::array<double, 6>)), c);
+            else compute_covariances_(*target_, false);
+            target_cov_dirty_ = false;
+        }
+        PointCloud<PointSource> tmp;
+        detail::copy_aligned(*source_, tmp);   // `output = input`, then xyz <- final * xyz
+        check(rsreg_gicp_align(c, guess.data(), &prm_, &res_, tmp.size() ? tmp.points.data() : nullptr, sizeof(PointSource)), c);
+        std::memcpy(final_.m, res_.transform, sizeof(final_.m));
+        output = std::move(tmp);
+    }
+    bool hasConverged() const { return res_.converged != 0; }
+    Matrix4f getFinalTransformation() const { return final_; }
+    double getFitnessScore(double max_range = std::numeric_limits<double>::max())
+    {
+        rsreg_ctx *c = ctx_->get();
+        if (source_dirty_ || target_dirty_ || ctx_->icp_source_owner != this || ctx_->icp_target_owner != this)
+            throw Error(RSREG_ERR_STATE, "rsreg: getFitnessScore before align() of the current source and target");
+        double score = 0;
+        check(rsreg_icp_fitness_score(c, max_range, &score, nullptr), c);
+        return score;
+    }
+    const rsreg_gicp_result &result() const { return res_; }
+
+  private:
+    template <typename PointT> void compute_covariances_(const PointCloud<PointT> &cloud, bool source)
+    {
+        rsreg_ctx *c = ctx_->get();
+        DeviceCloud<PointT> dev(cloud, ctx_);
+        rsreg_cloud *cov = nullptr;
+        check(rsreg_cloud_create(c, &cov), c);
+        int rc = rsreg_cloud_gicp_covariances(c, dev.handle(), prm_.k_correspondences, prm_.gicp_epsilon, cov);
+        if (!rc) rc = source ? rsreg_gicp_set_source_covariances_cloud(c, cov) : rsreg_gicp_set_target_covariances_cloud(c, cov);
+        if (!rc) rc = rsreg_ctx_synchronize(c);   // (the copy reads `cov` on the context's stream: done before the handle goes)
+        rsreg_cloud_destroy(cov);
+        check(rc, c);
+    }
+    std::shared_ptr<Context> ctx_;
+    rsreg_gicp_params prm_;
+    rsreg_gicp_result res_{};
+    Matrix4f final_;
+    SourcePtr source_;
+    TargetPtr target_;
+    CovariancesPtr source_cov_, target_cov_;
+    bool source_dirty_ = true, target_dirty_ = true, source_cov_dirty_ = true, target_cov_dirty_ = true;
+};
+
 // ---- pcl::NormalDistributionsTransform
 template <typename PointSource, typename PointTarget> class NormalDistributionsTransform {
   public:

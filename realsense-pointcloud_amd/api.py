@@ -260,6 +260,27 @@ class DeviceCloud:
         out.close()
         return np.stack([rec["normal_x"], rec["normal_y"], rec["normal_z"], rec["curvature"]], axis=1)
 
+    def gicp_covariances_cloud(self, k=20, epsilon=1e-3):
+        """GeneralizedIterativeClosestPoint's computeCovariances (rsreg_cloud_gicp_covariances; include/rsreg.h holds the contract):
+        a DeviceCloud of 48-byte records, six doubles (xx, xy, xz, yy, yz, zz) of I - (1 - epsilon) n n^T per record."""
+        out = DeviceCloud(ctx=self.ctx)
+        rc = _l.lib().rsreg_cloud_gicp_covariances(self.ctx.h, self.h, int(k), float(epsilon), out.h)
+        if rc:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out
+
+    def gicp_covariances(self, k=20, epsilon=1e-3):
+        """(covariances (n, 6) float64 -- NaN rows for non-finite records --, is_dense of the result)."""
+        out = self.gicp_covariances_cloud(k, epsilon)
+        n, stride, _, _, dense = out.info()
+        if n and stride != 48:
+            raise ValueError("the device cloud does not hold 48-byte covariance records")
+        cov = np.zeros((n, 6), np.float64)
+        _l.check(_l.lib().rsreg_cloud_download(out.h, cov.ctypes.data, n), self.ctx.h)
+        out.close()
+        return cov, dense
+
     def _normals_on_device(self, normals):
         """(a DeviceCloud of this context that holds the normals, whether it was made here): a DeviceCloud as it is, a NormalCloud,
         a structured array that starts with normal_x, normal_y, normal_z, or an (n, >= 3) float32 array uploaded."""
@@ -1155,6 +1176,171 @@ class IterativeClosestPointWithNormals(IterativeClosestPoint):
         s = np.zeros(_l.NUM_PLANE_SUMS, np.float64)
         _l.check(_l.lib().rsreg_icp_plane_sums_last(self.ctx.h, s.ctypes.data), self.ctx.h)
         return s
+
+
+def gicp_params(**kw):
+    p = _l.GicpParams()
+    _l.lib().rsreg_gicp_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _colmajor64(X):
+    return None if X is None else np.ascontiguousarray(np.asarray(X, np.float64).reshape(4, 4).T).copy()
+
+
+def gicp_step_from_sums(sums, scale=1.0):
+    """(x (6,), Delta(x) 4x4 float64, rank): x = scale * pinv(H) b of the 32 GICP sums (rsreg_gicp_step_from_sums, host only)."""
+    sums = np.ascontiguousarray(sums, np.float64)
+    if sums.size != _l.NUM_GICP_SUMS:
+        raise ValueError("gicp_step_from_sums takes the 32 GICP sums")
+    x, d, rank = np.zeros(6), np.zeros(16), C.c_int(0)
+    _l.check(_l.lib().rsreg_gicp_step_from_sums(sums.ctypes.data, float(scale), x.ctypes.data, d.ctypes.data, C.byref(rank)))
+    return x, d.reshape(4, 4).T.copy(), rank.value
+
+
+class GeneralizedIterativeClosestPoint(IterativeClosestPoint):
+    """pcl::GeneralizedIterativeClosestPoint on the MI355X (plane-to-plane ICP; include/rsreg.h: the rsreg_gicp_* section holds the
+    contract and the stated deviations from PCL).  Covariances: setSourceCovariances / setTargetCovariances take an (n, 6) float64
+    array (xx, xy, xz, yy, yz, zz per record) or a DeviceCloud of such records (DeviceCloud.gicp_covariances_cloud); a cloud without
+    them gets its own from rsreg_cloud_gicp_covariances with setCorrespondenceRandomness' k, as PCL computes them."""
+
+    def __init__(self, ctx=None):
+        super().__init__(ctx)
+        self.gparams = gicp_params()
+        self.params.max_correspondence_distance = self.gparams.max_correspondence_distance   # (the target index's gate)
+        self._cov = {"source": None, "target": None}
+        self._cov_dirty = {"source": True, "target": True}
+
+    def setCorrespondenceRandomness(self, k):
+        self.gparams.k_correspondences = int(k)
+        self._cov_dirty = {"source": True, "target": True}
+
+    def setRotationEpsilon(self, e):
+        self.gparams.rotation_epsilon = float(e)
+
+    def setTransformationEpsilon(self, e):
+        self.gparams.transformation_epsilon = float(e)
+
+    def setMaximumOptimizerIterations(self, n):
+        self.gparams.max_inner_iterations = int(n)
+
+    def setMaximumIterations(self, n):
+        self.gparams.max_iterations = int(n)
+
+    def setMaxCorrespondenceDistance(self, d):
+        super().setMaxCorrespondenceDistance(d)
+        self.gparams.max_correspondence_distance = float(d)
+
+    def setInputSource(self, cloud):
+        super().setInputSource(cloud)
+        self._cov["source"], self._cov_dirty["source"] = None, True
+
+    def setInputTarget(self, cloud):
+        super().setInputTarget(cloud)
+        self._cov["target"], self._cov_dirty["target"] = None, True
+
+    def setSourceCovariances(self, cov):
+        self._cov["source"], self._cov_dirty["source"] = cov, True
+
+    def setTargetCovariances(self, cov):
+        self._cov["target"], self._cov_dirty["target"] = cov, True
+
+    def _set_covariances(self, which, cloud):
+        L, h = _l.lib(), self.ctx.h
+        cov = self._cov[which]
+        set_host = getattr(L, "rsreg_gicp_set_%s_covariances" % which)
+        set_cloud = getattr(L, "rsreg_gicp_set_%s_covariances_cloud" % which)
+        if cov is None:   # PCL: computeCovariances of the cloud itself
+            dev, made = (cloud, False) if isinstance(cloud, DeviceCloud) else (DeviceCloud(cloud, ctx=self.ctx), True)
+            out = dev.gicp_covariances_cloud(self.gparams.k_correspondences, self.gparams.gicp_epsilon)
+            rc = set_cloud(h, out.h)
+            out.close()
+            if made:
+                dev.close()
+            _l.check(rc, h)
+        elif isinstance(cov, DeviceCloud):
+            _l.check(set_cloud(h, cov.h), h)
+        else:
+            a = np.ascontiguousarray(cov, np.float64)
+            if a.ndim != 2 or a.shape[1] < 6:
+                raise ValueError("covariances must be a DeviceCloud or an (n, >= 6) float64 array")
+            _l.check(set_host(h, a.ctypes.data, a.shape[0], a.shape[1] * 8), h)
+        self._cov_dirty[which] = False
+
+    def _sync_inputs(self):
+        self.params.max_correspondence_distance = self.gparams.max_correspondence_distance
+        src_new = self._src_dirty or self.ctx.icp_source_owner is not self
+        tgt_new = self._tgt_dirty or self.ctx.icp_target_owner is not self or getattr(self, "_tgt_gate", None) != self.params.max_correspondence_distance
+        if isinstance(self._src, DeviceCloud) and getattr(self, "_src_stamp", None) != self._src.stamp:
+            src_new = True
+        if isinstance(self._tgt, DeviceCloud) and getattr(self, "_tgt_stamp", None) != self._tgt.stamp:
+            tgt_new = True
+        super()._sync_inputs()
+        # (a new source or target drops the covariances of the one before)
+        if src_new or self._cov_dirty["source"]:
+            self._set_covariances("source", self._src)
+        if tgt_new or self._cov_dirty["target"]:
+            self._set_covariances("target", self._tgt)
+
+    def align(self, guess=None):
+        """gicp.align(out[, guess]): the aligned cloud, as IterativeClosestPoint.align returns it."""
+        self._sync_inputs()
+        g = _colmajor(guess)
+        gp = g.ctypes.data if g is not None else None
+        res = _l.GicpResult()
+        if isinstance(self._src, DeviceCloud):
+            out = DeviceCloud(ctx=self.ctx)
+            _l.check(_l.lib().rsreg_gicp_align_cloud(self.ctx.h, gp, C.byref(self.gparams), C.byref(res), out.h), self.ctx.h)
+            self.result = res
+            return out
+        out = self._src.points.copy() if isinstance(self._src, PointCloud) else np.zeros(self._n_src, POINT_DTYPE)
+        _l.check(_l.lib().rsreg_gicp_align(self.ctx.h, gp, C.byref(self.gparams), C.byref(res), out.ctypes.data if len(out) else None,
+                                           out.dtype.itemsize), self.ctx.h)
+        self.result = res
+        src = self._src if isinstance(self._src, PointCloud) else None
+        return PointCloud(out, width=src.width if src else len(out), height=src.height if src else 1, is_dense=src.is_dense if src else False)
+
+    # ---- step-wise form: begin -> { search -> gicp_sums(X) ... -> update(X, sums, evaluations) } -> end
+    def begin(self, guess=None):
+        self._sync_inputs()
+        g = _colmajor(guess)
+        _l.check(_l.lib().rsreg_gicp_begin(self.ctx.h, g.ctypes.data if g is not None else None, C.byref(self.gparams)), self.ctx.h)
+
+    def search(self, want_output=True):
+        idx = np.empty(self._n_src, np.int32) if want_output else None
+        d2 = np.empty(self._n_src, np.float32) if want_output else None
+        _l.check(_l.lib().rsreg_gicp_search(self.ctx.h, idx.ctypes.data if want_output else None, d2.ctypes.data if want_output else None), self.ctx.h)
+        return (idx, d2) if want_output else None
+
+    def gicp_sums(self, X=None):
+        """The 32 sums (RSREG_NUM_GICP_SUMS) of the last search at the increment X (4x4 float64, None: the identity)."""
+        s = np.zeros(_l.NUM_GICP_SUMS, np.float64)
+        Xc = _colmajor64(X)
+        _l.check(_l.lib().rsreg_gicp_sums(self.ctx.h, Xc.ctypes.data if Xc is not None else None, s.ctypes.data), self.ctx.h)
+        return s
+
+    def sums(self):
+        raise _l.RsregError(_l.RSREG_ERR_STATE, "GICP alignment: gicp_sums(X)")
+
+    def update(self, X, sums, inner_evaluations=0):
+        """Compose T = float(X T) and test PCL's criterion: True when the loop must stop."""
+        sums = np.ascontiguousarray(sums, np.float64)
+        if sums.size != _l.NUM_GICP_SUMS:
+            raise ValueError("update takes the 32 GICP sums")
+        Xc = _colmajor64(X)
+        done = C.c_int(0)
+        _l.check(_l.lib().rsreg_gicp_update(self.ctx.h, Xc.ctypes.data if Xc is not None else None, sums.ctypes.data, int(inner_evaluations),
+                                            C.byref(done)), self.ctx.h)
+        return bool(done.value)
+
+    def end(self, want_aligned=False):
+        res = _l.GicpResult()
+        out = np.zeros((self._n_src, 4), np.float32) if want_aligned else None
+        _l.check(_l.lib().rsreg_gicp_end(self.ctx.h, C.byref(res), out.ctypes.data if want_aligned else None, 16), self.ctx.h)
+        self.result = res
+        return (res, out) if want_aligned else res
 
 
 class NormalDistributionsTransform:

@@ -923,33 +923,72 @@ int rsreg_icp_set_source_cloud(rsreg_ctx *ctx, const rsreg_cloud *c)
     return RSREG_OK;
 }
 
-// icp.align(out[, guess]) with the aligned cloud left in HBM (nullable; may be the source cloud itself)
-int rsreg_icp_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, rsreg_icp_result *result,
-                          rsreg_cloud *aligned_out)
+// The two ends of an alignment that leaves its aligned cloud in HBM (ICP, GICP): before the loop the handle is checked ...
+static int aligned_cloud_begin(rsreg_ctx *ctx, rsreg_cloud *aligned_out)
 {
-    if (!ctx || !params || !result) return RSREG_ERR_INVALID_ARG;
     if (aligned_out && (aligned_out->ctx != ctx || !ctx->src_cloud)) return fail(ctx, RSREG_ERR_STATE, "rsreg_icp_set_source_cloud not called");
     // the aligned cloud is the SOURCE CLOUD's records under the final transform: the handle must still be the cloud that was loaded
     if (aligned_out && (ctx->src_cloud->id != ctx->src_cloud_id || ctx->src_cloud->version != ctx->src_cloud_version))
         return fail(ctx, RSREG_ERR_STATE, "the source cloud was rewritten after rsreg_icp_set_source_cloud");
     RSREG_HIP(ctx, settle(aligned_out));
-    int rc = rsreg_icp_align(ctx, guess, params, result, nullptr, 0);
-    if (!rc) harvest_source_box(ctx);   // (the alignment has been waited for: a small source's box is there; the aligned cloud below starts from it)
-    if (rc || !aligned_out) return rc;
+    return RSREG_OK;
+}
+
+// ... and after it the source cloud's records go into it under the final transform (column-major 4 x 4)
+static int aligned_cloud_end(rsreg_ctx *ctx, const float *transform, rsreg_cloud *aligned_out)
+{
     const rsreg_cloud *src = ctx->src_cloud;
     if (aligned_out != src) RSREG_HIP(ctx, cloud_reserve(ctx, aligned_out->buf, src->n * src->stride + 16));
     Mat4f T;
-    std::memcpy(T.m, result->transform, 64);
+    std::memcpy(T.m, transform, 64);
     if (src->n) {
         RSREG_HIP(ctx, launch_records_transform(ctx->stream, src->buf.as<char>(), aligned_out->buf.as<char>(), (uint32_t)src->n, src->stride, to_mat34(T), 1));
     }
-    const rsreg::CloudBox moved_box = (src->box.valid && src->box_version == src->version) ? rsreg::transformed_box(src->box, result->transform) : rsreg::CloudBox{};
+    const rsreg::CloudBox moved_box = (src->box.valid && src->box_version == src->version) ? rsreg::transformed_box(src->box, transform) : rsreg::CloudBox{};
     cloud_rewritten(aligned_out, src->n, src->stride, src->width, src->height, src->is_dense);
     if (moved_box.valid && rsreg::tunables().box_cache) {
         aligned_out->box = moved_box;
         aligned_out->box_version = aligned_out->version;
     }
     return RSREG_OK;
+}
+
+// icp.align(out[, guess]) with the aligned cloud left in HBM (nullable; may be the source cloud itself)
+int rsreg_icp_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, rsreg_icp_result *result,
+                          rsreg_cloud *aligned_out)
+{
+    if (!ctx || !params || !result) return RSREG_ERR_INVALID_ARG;
+    if (int rcb = aligned_cloud_begin(ctx, aligned_out)) return rcb;
+    int rc = rsreg_icp_align(ctx, guess, params, result, nullptr, 0);
+    if (!rc) harvest_source_box(ctx);   // (the alignment has been waited for: a small source's box is there; the aligned cloud below starts from it)
+    if (rc || !aligned_out) return rc;
+    return aligned_cloud_end(ctx, result->transform, aligned_out);
+}
+
+// ---- GICP on cloud handles: the covariances rsreg_cloud_gicp_covariances wrote (48-byte records), and the aligned cloud in HBM
+int rsreg_gicp_set_source_covariances_cloud(rsreg_ctx *ctx, const rsreg_cloud *c)
+{
+    if (!ctx || !c || c->ctx != ctx) return RSREG_ERR_INVALID_ARG;
+    RSREG_HIP(ctx, settle(c));
+    return rsreg_gicp_set_covariances_device_(ctx, 1, c->n ? c->buf.ptr : nullptr, c->n, c->stride);
+}
+
+int rsreg_gicp_set_target_covariances_cloud(rsreg_ctx *ctx, const rsreg_cloud *c)
+{
+    if (!ctx || !c || c->ctx != ctx) return RSREG_ERR_INVALID_ARG;
+    RSREG_HIP(ctx, settle(c));
+    return rsreg_gicp_set_covariances_device_(ctx, 0, c->n ? c->buf.ptr : nullptr, c->n, c->stride);
+}
+
+// rsreg_icp_align_cloud with the GICP loop in the place of the ICP loop
+int rsreg_gicp_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, rsreg_gicp_result *result, rsreg_cloud *aligned_out)
+{
+    if (!ctx || !params || !result) return RSREG_ERR_INVALID_ARG;
+    if (int rcb = aligned_cloud_begin(ctx, aligned_out)) return rcb;
+    int rc = rsreg_gicp_align(ctx, guess, params, result, nullptr, 0);
+    if (!rc) harvest_source_box(ctx);
+    if (rc || !aligned_out) return rc;
+    return aligned_cloud_end(ctx, result->transform, aligned_out);
 }
 
 // ---- NDT on cloud handles

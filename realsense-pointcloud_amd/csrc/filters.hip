@@ -17,6 +17,7 @@
 
 #include "knn_kernels.hpp"
 #include "normals_kernels.hpp"
+#include "gicp_cov_kernels.hpp"
 #include "radius_kernels.hpp"
 #include "fpfh_kernels.hpp"
 #include "fpfh_radius_kernels.hpp"
@@ -778,6 +779,33 @@ int rsreg_cloud_normals(rsreg_ctx *ctx, const rsreg_cloud *in, int k, const floa
         RSREG_HIP(ctx, hipGetLastError());
         return (int)RSREG_OK;
     });
+}
+
+// GeneralizedIterativeClosestPoint::computeCovariances (include/rsreg.h: the contract): the index and the walk of rsreg_cloud_normals,
+// k_gicp_cov in the place of k_normals, 48-byte records of six doubles
+int rsreg_cloud_gicp_covariances(rsreg_ctx *ctx, const rsreg_cloud *in, int k, double epsilon, rsreg_cloud *out)
+{
+    CloudView v;
+    if (!out || out == in) return RSREG_ERR_INVALID_ARG;
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
+    if (rc) return rc;
+    if (k < 4 || k > kKnnMaxK) return fail(ctx, RSREG_ERR_INVALID_ARG, "k must be between 4 and 64");
+    if (!std::isfinite(epsilon)) return fail(ctx, RSREG_ERR_INVALID_ARG, "epsilon must be finite");
+    uint32_t nfin = 0;
+    rc = knn_index_device(ctx, v, k, "the cloud has fewer than k finite records", &nfin);
+    if (rc) return rc;
+    FilterScratch &fs = ctx->filt;
+    const uint32_t n = (uint32_t)v.n;
+    RSREG_HIP(ctx, fs.d_out.reserve(v.n * kGicpCovBytes + 16));
+    if (nfin < n) {
+        k_gicp_cov_not_finite<<<div_up(n, kBlock), kBlock, 0, ctx->stream>>>(v.rec, v.stride, n, fs.d_out.as<double>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    if (nfin) {
+        k_gicp_cov<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, ctx->stream>>>(grid_dev(ctx->knn), k, v.rec, v.stride, epsilon, fs.d_out.as<double>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    return rsreg_cloud_adopt_(out, &fs.d_out, v.n, kGicpCovBytes, v.width, v.height, nfin < n ? 0 : v.is_dense);
 }
 
 int rsreg_cloud_spfh(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *normals, int k, float *host_out)

@@ -464,11 +464,12 @@ template <int N> inline void eig_sym(const double *Ain, double *evals, double *e
 // eigen-directions of AtA that carry data, T = PCL's constructTransformationMatrix(x) (Rz Ry Rx, full sines and cosines in
 // double) rounded to float.  Nothing in the system, or nothing above the cut: the identity.  *rank_out (nullable): the
 // number of directions used.
-inline void plane_solve_from_sums(const double *sums, Mat4f &T, int *rank_out = nullptr)
+// (in two pieces, so that the GICP inner loop can take the unknowns in double, scale them and build its own increment:
+// plane_unknowns_from_sums is the pseudo-inverse, plane_matrix_from_unknowns the construction, both exactly as they were)
+inline int plane_unknowns_from_sums(const double *sums, double (&x)[6])
 {
-    T = Mat4f::identity();
     int rank = 0;
-    double x[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 6; ++i) x[i] = 0;
     if (sums[2] > 0) {
         double A[36], evals[6], evecs[36], trace = 0;
         int k = 4;
@@ -490,21 +491,37 @@ inline void plane_solve_from_sums(const double *sums, Mat4f &T, int *rank_out = 
         if (rank == 0)
             for (int i = 0; i < 6; ++i) x[i] = 0;
     }
+    return rank;
+}
+
+// PCL's constructTransformationMatrix in double: D = the 3 x 4 part, row-major (D[r * 4 + c]), of Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)
+inline void plane_matrix_from_unknowns(const double (&x)[6], double (&D)[12])
+{
+    const double sa = std::sin(x[0]), ca = std::cos(x[0]), sb = std::sin(x[1]), cb = std::cos(x[1]), sg = std::sin(x[2]), cg = std::cos(x[2]);
+    D[0] = cg * cb;
+    D[1] = -sg * ca + cg * sb * sa;
+    D[2] = sg * sa + cg * sb * ca;
+    D[4] = sg * cb;
+    D[5] = cg * ca + sg * sb * sa;
+    D[6] = -cg * sa + sg * sb * ca;
+    D[8] = -sb;
+    D[9] = cb * sa;
+    D[10] = cb * ca;
+    D[3] = x[3];
+    D[7] = x[4];
+    D[11] = x[5];
+}
+
+inline void plane_solve_from_sums(const double *sums, Mat4f &T, int *rank_out = nullptr)
+{
+    T = Mat4f::identity();
+    double x[6], D[12];
+    const int rank = plane_unknowns_from_sums(sums, x);
     if (rank_out) *rank_out = rank;
     if (rank == 0) return;
-    const double sa = std::sin(x[0]), ca = std::cos(x[0]), sb = std::sin(x[1]), cb = std::cos(x[1]), sg = std::sin(x[2]), cg = std::cos(x[2]);
-    T(0, 0) = float(cg * cb);
-    T(0, 1) = float(-sg * ca + cg * sb * sa);
-    T(0, 2) = float(sg * sa + cg * sb * ca);
-    T(1, 0) = float(sg * cb);
-    T(1, 1) = float(cg * ca + sg * sb * sa);
-    T(1, 2) = float(-cg * sa + sg * sb * ca);
-    T(2, 0) = float(-sb);
-    T(2, 1) = float(cb * sa);
-    T(2, 2) = float(cb * ca);
-    T(0, 3) = float(x[3]);
-    T(1, 3) = float(x[4]);
-    T(2, 3) = float(x[5]);
+    plane_matrix_from_unknowns(x, D);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) T(r, c) = float(D[r * 4 + c]);
 }
 
 inline bool inv3(const double *M, double *Inv)

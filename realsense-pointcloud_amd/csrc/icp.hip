@@ -22,6 +22,7 @@
 #include "oscan.hpp"
 #include "fitness_kernels.hpp"
 #include "plane_kernels.hpp"
+#include "gicp_kernels.hpp"
 #include "cloud_ops.hpp"
 #include "icp_grid_plan.hpp"
 
@@ -868,6 +869,8 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
     RSREG_HIP(ctx, ctx->d_smisc.reserve(kSmiscWords * sizeof(uint32_t)));
     RSREG_HIP(ctx, ctx->h_smisc.reserve(kHsWords * sizeof(uint32_t)));
     ctx->icp_fit_ok = false;   // (a new source: no fitness score until it is aligned)
+    ctx->have_gicp_cs = false;   // (the covariances of the source before this one)
+    ctx->gicp.active = 0;
     ctx->n_source = n;
     ctx->n_work = 0;
     ctx->src_cloud = nullptr;
@@ -1747,6 +1750,7 @@ int rsreg_icp_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
     (void)is_dense;
     if (!ctx || (n && !d_points) || stride < 12 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
     ctx->have_normals = false;   // (of the target before this one)
+    ctx->have_gicp_ct = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     return build_grid(ctx, static_cast<const char *>(d_points), n, stride, max_correspondence_distance);
 }
@@ -1755,6 +1759,7 @@ int rsreg_icp_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
 int rsreg_icp_set_target_scan_(rsreg_ctx *ctx, const void *d_points, size_t n, size_t stride, double max_correspondence_distance)
 {
     ctx->have_normals = false;
+    ctx->have_gicp_ct = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     return scan_target(ctx, static_cast<const char *>(d_points), n, stride, max_correspondence_distance);
 }
@@ -1765,6 +1770,7 @@ int rsreg_icp_set_target(rsreg_ctx *ctx, const void *points, size_t n, size_t st
     (void)is_dense;
     if (!ctx || (n && !points) || stride < 12) return RSREG_ERR_INVALID_ARG;
     ctx->have_normals = false;   // (of the target before this one)
+    ctx->have_gicp_ct = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     rsreg_host_timing &ht = ctx->host_timing;
     // a counting build that was queued and not waited for (build_dense) still reads d_tgt_raw on the main stream, and the
@@ -1804,7 +1810,8 @@ int rsreg_icp_set_source(rsreg_ctx *ctx, const void *points, size_t n, size_t st
     return load_source(ctx, ctx->d_src_raw.as<char>(), n, 12);
 }
 
-int rsreg_icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params)
+// rsreg_icp_begin; need_index: the alignment runs the staged kernels over the index whatever the source's size (plane mode, GICP)
+static int icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, bool need_index)
 {
     if (!ctx || !params) return RSREG_ERR_INVALID_ARG;
     if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
@@ -1829,7 +1836,7 @@ int rsreg_icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *
         int rcj = join_source(ctx);
         if (rcj) return rcj;
     }
-    if (ctx->grid.dense == 2 && (ctx->n_work > kScanMaxSource || filters_on(*params) || plane_on(*params))) {
+    if (ctx->grid.dense == 2 && (ctx->n_work > kScanMaxSource || filters_on(*params) || need_index)) {
         // the target was set for a handful of queries (scan_target); this alignment needs the index after all
         if (!ctx->scan_raw) return fail(ctx, RSREG_ERR_NO_TARGET, "the target cloud was released before its index was built");
         int rcb = build_grid(ctx, ctx->scan_raw, ctx->n_target_raw, ctx->scan_stride, ctx->gate_built_for);
@@ -1850,7 +1857,13 @@ int rsreg_icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *
     ctx->ev_transform.clear();
     ctx->ev_allreduce.clear();
     s.restart_pending = true;   // input_transformed = guess * input (App. A.2 prologue): ensure_restarted / launch_fused
+    ctx->gicp.active = 0;
     return RSREG_OK;
+}
+
+int rsreg_icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params)
+{
+    return icp_begin(ctx, guess, params, params && plane_on(*params));
 }
 
 int rsreg_icp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out)
@@ -2191,6 +2204,324 @@ int icp_align(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params
     return icp_end(ctx, result, aligned_out, out_stride, source_records);
 }
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------- GICP
+// pcl::GeneralizedIterativeClosestPoint on the staged pipeline (include/rsreg.h holds the contract): the ICP state carries the
+// transform, the search and the counters; an outer iteration is restart (cur = T * source) -> search -> k_gicp_mahalanobis ->
+// { k_gicp_reduce at X -> host solve } -> T = float(X T).  One rank only: nothing is all-reduced.
+static_assert(RSREG_NUM_GICP_SUMS == RSREG_NUM_PLANE_SUMS, "k_gicp_reduce goes through plane_tile_reduce_store and k_final_reduce as the plane sums do");
+
+void rsreg_gicp_params_default(rsreg_gicp_params *p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->max_iterations = 200;
+    p->max_inner_iterations = 20;
+    p->k_correspondences = 20;
+    p->max_correspondence_distance = 5.0;
+    p->transformation_epsilon = 5e-4;
+    p->rotation_epsilon = 2e-3;
+    p->gicp_epsilon = 1e-3;
+}
+
+// one covariance record per record of the source (the target): from the host (waited for: the buffer has been read) or from HBM
+static int gicp_set_covariances(rsreg_ctx *ctx, bool source, const void *host, const void *dev, size_t n, size_t stride)
+{
+    if (!ctx || (n && !host && !dev) || stride < 48 || (dev && (stride & 7))) return RSREG_ERR_INVALID_ARG;
+    if (source) {
+        if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
+        if (n != ctx->n_source) return fail(ctx, RSREG_ERR_INVALID_ARG, "one covariance per source record: the counts differ");
+    } else {
+        if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
+        if (n != ctx->n_target_raw) return fail(ctx, RSREG_ERR_INVALID_ARG, "one covariance per target record: the counts differ");
+    }
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    DevBuf &d = source ? ctx->d_gicp_cs : ctx->d_gicp_ct;
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (an alignment before this one may still read the buffer)
+    RSREG_HIP(ctx, d.reserve((n + 1) * 48));
+    if (n && host) {
+        RSREG_HIP(ctx, hipMemcpy2DAsync(d.ptr, 48, host, stride, 48, n, hipMemcpyHostToDevice, ctx->stream));
+        RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    } else if (n) {
+        k_gicp_pack_cov<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const char *>(dev), stride, (uint32_t)n, d.as<double>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    (source ? ctx->have_gicp_cs : ctx->have_gicp_ct) = true;
+    return RSREG_OK;
+}
+
+int rsreg_gicp_set_source_covariances(rsreg_ctx *ctx, const void *cov, size_t n, size_t stride)
+{
+    return gicp_set_covariances(ctx, true, cov, nullptr, n, stride);
+}
+
+int rsreg_gicp_set_target_covariances(rsreg_ctx *ctx, const void *cov, size_t n, size_t stride)
+{
+    return gicp_set_covariances(ctx, false, cov, nullptr, n, stride);
+}
+
+int rsreg_gicp_set_covariances_device_(rsreg_ctx *ctx, int source, const void *d_cov, size_t n, size_t stride)
+{
+    return gicp_set_covariances(ctx, source != 0, nullptr, d_cov, n, stride);
+}
+
+int rsreg_gicp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params)
+{
+    if (!ctx || !params) return RSREG_ERR_INVALID_ARG;
+    if (params->max_iterations < 0 || params->max_inner_iterations < 0 || !(params->max_correspondence_distance >= 0) ||
+        !(params->transformation_epsilon >= 0) || !(params->rotation_epsilon >= 0))
+        return fail(ctx, RSREG_ERR_INVALID_ARG, "bad GICP parameters");
+    if (ctx->nranks > 1) return fail(ctx, RSREG_ERR_INVALID_ARG, "GICP: not with more than one rank");
+    if (ctx->have_target && ctx->have_source && !(ctx->have_gicp_cs && ctx->have_gicp_ct))
+        return fail(ctx, RSREG_ERR_STATE, "GICP needs rsreg_gicp_set_source_covariances and rsreg_gicp_set_target_covariances after the clouds are set");
+    rsreg_icp_params ip;
+    rsreg_icp_params_default(&ip);
+    ip.max_iterations = params->max_iterations;
+    ip.criteria_mode = RSREG_CRITERIA_FIXED;
+    ip.pipeline_mode = RSREG_PIPELINE_STAGED;
+    ip.max_correspondence_distance = params->max_correspondence_distance;
+    int rc = icp_begin(ctx, guess, &ip, true);
+    if (rc) return rc;
+    ctx->gicp = GicpState();
+    ctx->gicp.prm = *params;
+    ctx->gicp.active = 1;
+    return RSREG_OK;
+}
+
+int rsreg_gicp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out)
+{
+    if (!ctx) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->gicp.active || !ctx->icp.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_gicp_begin not called");
+    if (!ctx->have_gicp_cs || !ctx->have_gicp_ct || !ctx->have_target) return fail(ctx, RSREG_ERR_STATE, "a cloud was set after rsreg_gicp_begin: its covariances are gone");
+    IcpState &s = ctx->icp;
+    s.restart_pending = true;   // the source under the whole current transform, from the records
+    s.pending_transform = false;
+    int rc = rsreg_icp_search(ctx, index_out, sqr_dist_out);
+    if (rc) return rc;
+    const uint32_t n = (uint32_t)ctx->n_work;
+    if (n) {
+        RSREG_HIP(ctx, ctx->d_gicp_m.reserve((size_t)n * 48 + 16));
+        Mat34d R{};
+        for (int c = 0; c < 3; ++c) {
+            R.r0[c] = (double)s.final_t(0, c);
+            R.r1[c] = (double)s.final_t(1, c);
+            R.r2[c] = (double)s.final_t(2, c);
+        }
+        ScopedEvents ev(ctx, &ctx->ev_reduce);
+        k_gicp_mahalanobis<<<div_up(n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_corr_pos.as<int>(), ctx->d_tgt_sorted.as<float4>(), ctx->d_perm.as<uint32_t>(),
+                                                                         ctx->d_first.as<uint32_t>(), ctx->d_gicp_cs.as<double>(), ctx->d_gicp_ct.as<double>(), R, n,
+                                                                         ctx->d_gicp_m.as<double>());
+        RSREG_HIP(ctx, hipGetLastError());
+        s.idle_after_sums = false;
+    }
+    ctx->gicp.have_search = true;
+    return RSREG_OK;
+}
+
+// the 32 sums at X (column-major double 4 x 4) over the pairs of the last search: launch_plane_sums with k_gicp_reduce
+static int gicp_launch_sums(rsreg_ctx *ctx, const double *X, double *sums)
+{
+    ctx->icp.idle_after_sums = false;
+    const uint32_t n = (uint32_t)ctx->n_work;
+    const uint32_t nb = reduce_blocks(n);
+    RSREG_HIP(ctx, ctx->d_plane_partials.reserve((size_t)nb * RSREG_NUM_GICP_SUMS * 8));
+    Mat34d Xr;
+    for (int c = 0; c < 4; ++c) {
+        Xr.r0[c] = X[c * 4 + 0];
+        Xr.r1[c] = X[c * 4 + 1];
+        Xr.r2[c] = X[c * 4 + 2];
+    }
+    {
+        ScopedEvents ev(ctx, &ctx->ev_reduce);
+        k_gicp_reduce<<<nb, kTile, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), ctx->d_tgt_sorted.as<float4>(),
+                                                     ctx->d_gicp_m.as<double>(), Xr, n, ctx->d_plane_partials.as<double>());
+        RSREG_HIP(ctx, hipGetLastError());
+        k_final_reduce<<<RSREG_NUM_GICP_SUMS, kReduceBlock, 0, ctx->stream>>>(ctx->d_plane_partials.as<double>(), nb, host_sums_target(ctx));
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    double *h = ctx->h_sums.as<double>();
+    if (ctx->comm) RSREG_HIP(ctx, hipMemcpyAsync(h, ctx->d_sums.ptr, RSREG_NUM_GICP_SUMS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->icp.idle_after_sums = true;
+    (void)target_counts(ctx, false);
+    std::memcpy(sums, h, RSREG_NUM_GICP_SUMS * 8);
+    return RSREG_OK;
+}
+
+static void gicp_identity(double *X)
+{
+    for (int k = 0; k < 16; ++k) X[k] = (k % 5 == 0) ? 1.0 : 0.0;
+}
+
+// C = A B, column-major double 4 x 4, entries ((a0 b0 + a1 b1) + a2 b2) + a3 b3
+static void gicp_mul(const double *A, const double *B, double *C)
+{
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            C[c * 4 + r] = ((A[0 * 4 + r] * B[c * 4 + 0] + A[1 * 4 + r] * B[c * 4 + 1]) + A[2 * 4 + r] * B[c * 4 + 2]) + A[3 * 4 + r] * B[c * 4 + 3];
+}
+
+// x = scale * pinv(H) b and D = Delta(x), column-major; the rank of the solve (0: x = 0, D = I)
+static int gicp_step(const double *sums, double scale, double (&x)[6], double *D)
+{
+    const int rank = plane_unknowns_from_sums(sums, x);
+    gicp_identity(D);
+    if (rank == 0) return 0;
+    for (int i = 0; i < 6; ++i) x[i] *= scale;
+    double d12[12];
+    plane_matrix_from_unknowns(x, d12);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) D[c * 4 + r] = d12[r * 4 + c];
+    return rank;
+}
+
+int rsreg_gicp_sums(rsreg_ctx *ctx, const double X[16], double sums[RSREG_NUM_GICP_SUMS])
+{
+    if (!ctx || !sums) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->gicp.active || !ctx->icp.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_gicp_begin not called");
+    if (!ctx->gicp.have_search) return fail(ctx, RSREG_ERR_STATE, "rsreg_gicp_search not called for this iteration");
+    double I[16];
+    gicp_identity(I);
+    return gicp_launch_sums(ctx, X ? X : I, sums);
+}
+
+int rsreg_gicp_step_from_sums(const double sums[RSREG_NUM_GICP_SUMS], double scale, double x_out[6], double delta_out[16], int *rank_out)
+{
+    if (!sums || !delta_out) return RSREG_ERR_INVALID_ARG;
+    double x[6];
+    const int rank = gicp_step(sums, scale, x, delta_out);
+    if (x_out) std::memcpy(x_out, x, sizeof(x));
+    if (rank_out) *rank_out = rank;
+    return RSREG_OK;
+}
+
+int rsreg_gicp_update(rsreg_ctx *ctx, const double X[16], const double sums[RSREG_NUM_GICP_SUMS], int inner_evaluations, int *done)
+{
+    if (!ctx || !sums || !done) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->gicp.active || !ctx->icp.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_gicp_begin not called");
+    IcpState &s = ctx->icp;
+    GicpState &g = ctx->gicp;
+    std::memcpy(g.sums_last, sums, sizeof(g.sums_last));
+    std::memset(s.sums_last, 0, sizeof(s.sums_last));
+    s.sums_last[0] = sums[0];
+    s.sums_last[16] = sums[1];
+    s.ncorr = (uint64_t)(sums[0] + 0.5);
+    g.inner_evaluations += inner_evaluations;
+    g.have_search = false;
+    s.have_search = false;
+    if (s.ncorr < 4) {
+        s.state = RSREG_CONV_NO_CORRESPONDENCES;
+        s.converged = 0;
+        *done = 1;
+        return RSREG_OK;
+    }
+    {
+        double xs[6];
+        g.rank_last = plane_unknowns_from_sums(sums, xs);
+    }
+    s.cur_mse = sums[1] / sums[0];
+    double I[16], Td[16], Tn[16];
+    gicp_identity(I);
+    for (int k = 0; k < 16; ++k) Td[k] = (double)s.final_t.m[k];
+    gicp_mul(X ? X : I, Td, Tn);
+    Mat4f T_new = s.final_t;
+    double delta = 0.0;
+    const double rot_ratio = 1.0 / g.prm.rotation_epsilon, trans_ratio = 1.0 / g.prm.transformation_epsilon;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) {
+            T_new(r, c) = (float)Tn[c * 4 + r];
+            const double diff = std::fabs((double)s.final_t(r, c) - (double)T_new(r, c));
+            const double cd = diff == 0.0 ? 0.0 : diff * (c < 3 ? rot_ratio : trans_ratio);
+            if (!(cd <= delta)) delta = cd;
+        }
+    s.final_t = T_new;
+    s.iterations++;
+    if (delta < 1.0) {
+        s.state = RSREG_CONV_TRANSFORM;
+        s.converged = 1;
+    } else if (s.iterations >= g.prm.max_iterations) {
+        s.state = RSREG_CONV_ITERATIONS;
+        s.converged = 1;
+    } else {
+        s.state = RSREG_CONV_NOT_CONVERGED;
+        s.converged = 0;
+    }
+    *done = s.converged;
+    return RSREG_OK;
+}
+
+int rsreg_gicp_end(rsreg_ctx *ctx, rsreg_gicp_result *result, void *aligned_out, size_t out_stride)
+{
+    if (!ctx) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->gicp.active || !ctx->icp.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_gicp_begin not called");
+    rsreg_icp_result ir;
+    int rc = icp_end(ctx, &ir, aligned_out, out_stride, nullptr);
+    if (rc) return rc;
+    const GicpState &g = ctx->gicp;
+    if (result) {
+        std::memset(result, 0, sizeof(*result));
+        std::memcpy(result->transform, ir.transform, 64);
+        result->converged = ir.converged;
+        result->state = ir.state;
+        result->iterations = ir.iterations;
+        result->inner_evaluations = g.inner_evaluations;
+        result->n_correspondences = ir.n_correspondences;
+        result->mse = ir.mse;
+        std::memcpy(result->sums_last, g.sums_last, sizeof(g.sums_last));
+        result->ms_total = ir.ms_total;
+        result->ms_nn = ir.ms_nn;
+        result->ms_reduce = ir.ms_reduce;
+        result->ms_transform = ir.ms_transform;
+        result->n_nn_launches = ir.n_nn_launches;
+        result->rank_last = g.rank_last;
+    }
+    ctx->gicp.active = 0;
+    return RSREG_OK;
+}
+
+int rsreg_gicp_align(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, rsreg_gicp_result *result, void *aligned_out, size_t out_stride)
+{
+    int rc = rsreg_gicp_begin(ctx, guess, params);
+    if (rc) return rc;
+    const rsreg_gicp_params prm = *params;
+    int done = 0;
+    while (!done) {
+        rc = rsreg_gicp_search(ctx, nullptr, nullptr);
+        if (rc) return rc;
+        double X[16], S[RSREG_NUM_GICP_SUMS], Xc[16], Sc[RSREG_NUM_GICP_SUMS], D[16], x[6];
+        gicp_identity(X);
+        rc = gicp_launch_sums(ctx, X, S);
+        if (rc) return rc;
+        int evals = 0;
+        // the step control of include/rsreg.h, decided by the sums alone
+        while ((uint64_t)(S[0] + 0.5) >= 4 && evals < prm.max_inner_iterations) {
+            double scale = 1.0;
+            bool accepted = false;
+            if (gicp_step(S, scale, x, D) == 0) break;
+            while (evals < prm.max_inner_iterations) {
+                gicp_mul(D, X, Xc);
+                rc = gicp_launch_sums(ctx, Xc, Sc);
+                if (rc) return rc;
+                ++evals;
+                if (Sc[3] <= S[3]) {
+                    std::memcpy(X, Xc, sizeof(X));
+                    std::memcpy(S, Sc, sizeof(S));
+                    accepted = true;
+                    break;
+                }
+                scale *= 0.5;
+                (void)gicp_step(S, scale, x, D);
+            }
+            if (!accepted) break;
+            bool small = true;
+            for (int i = 0; i < 6; ++i) small = small && std::fabs(x[i]) <= (i < 3 ? prm.rotation_epsilon : prm.transformation_epsilon);
+            if (small) break;
+        }
+        rc = rsreg_gicp_update(ctx, X, S, evals, &done);
+        if (rc) return rc;
+    }
+    return rsreg_gicp_end(ctx, result, aligned_out, out_stride);
+}
 
 int rsreg_icp_grid_info(rsreg_ctx *ctx, rsreg_grid_info *info)
 {

@@ -127,6 +127,46 @@ __global__ __launch_bounds__(kBlock) void k_normals_not_finite(const char *rec, 
     o[1] = make_float4(qnan, 0.0f, 0.0f, 0.0f);
 }
 
+// The covariance {xx, xy, xz, yy, yz, zz} of kk neighbours about the query from their nine moment sums: S / kk - m m^T.  One place
+// for the normals (k neighbours, a radius) and the GICP covariances (gicp_cov_kernels.hpp): the same operations in the same order.
+__device__ __forceinline__ void cov_about_query(double kk, double sx, double sy, double sz, double sxx, double sxy, double sxz, double syy, double syz,
+                                                double szz, double (&c)[6])
+{
+#pragma clang fp contract(off)
+    const double mx = sx / kk, my = sy / kk, mz = sz / kk;
+    c[0] = sxx / kk - mx * mx;
+    c[1] = sxy / kk - mx * my;
+    c[2] = sxz / kk - mx * mz;
+    c[3] = syy / kk - my * my;
+    c[4] = syz / kk - my * mz;
+    c[5] = szz / kk - mz * mz;
+}
+
+// The nine moment sums {x, y, z, xx, xy, xz, yy, yz, zz} of (neighbour - query) in f64 over the k neighbours whose keys knn_walk left
+// in buf, the same bits in every lane.  A barrier stands between the lanes' reads of the keys and the return: the caller may search
+// the next query at once.
+__device__ __forceinline__ void knn_moment_sums(const unsigned long long *buf, int k, const char *rec, size_t stride, const float4 &q, int lane, double (&s)[9])
+{
+#pragma clang fp contract(off)
+    double dx = 0.0, dy = 0.0, dz = 0.0;
+    if (lane < k) {
+        const float *t = rec_xyz(rec, stride, (size_t)(uint32_t)buf[lane]);
+        dx = (double)t[0] - (double)q.x;
+        dy = (double)t[1] - (double)q.y;
+        dz = (double)t[2] - (double)q.z;
+    }
+    __syncthreads();   // (the keys have been read: the next query may append)
+    s[0] = wave_sum_fixed(dx);
+    s[1] = wave_sum_fixed(dy);
+    s[2] = wave_sum_fixed(dz);
+    s[3] = wave_sum_fixed(dx * dx);
+    s[4] = wave_sum_fixed(dx * dy);
+    s[5] = wave_sum_fixed(dx * dz);
+    s[6] = wave_sum_fixed(dy * dy);
+    s[7] = wave_sum_fixed(dy * dz);
+    s[8] = wave_sum_fixed(dz * dz);
+}
+
 // The tail of both estimators (k neighbours here, the neighbours within a radius in radius_kernels.hpp), by every lane of the wave that
 // holds the sums over the kk neighbours of the query q (the same bits in every lane): the covariance, its smallest eigenpair, the
 // curvature, the flip towards the viewpoint; lanes 0 .. 7 write the record `q.w` of out.
@@ -134,8 +174,8 @@ __device__ __forceinline__ void normal_from_sums(const float4 &q, double kk, dou
                                                  double syz, double szz, float vpx, float vpy, float vpz, int lane, float *out)
 {
 #pragma clang fp contract(off)
-    const double mx = sx / kk, my = sy / kk, mz = sz / kk;
-    const double c[6] = {sxx / kk - mx * mx, sxy / kk - mx * my, sxz / kk - mx * mz, syy / kk - my * my, syz / kk - my * mz, szz / kk - mz * mz};
+    double c[6];
+    cov_about_query(kk, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz, c);
     const double trace = (c[0] + c[3]) + c[5];
     float nx = 0.0f, ny = 0.0f, nz = 1.0f, curv = 0.0f;
     if (trace != 0.0) {
@@ -170,18 +210,9 @@ __global__ __launch_bounds__(kKnnWave) void k_normals(PointGridDev g, int k, con
     for (uint32_t j = blockIdx.x; j < g.n; j += gridDim.x) {
         const float4 q = g.pts[j];
         knn_walk<KnnKeys>(g, q, k, buf, lane);
-        double dx = 0.0, dy = 0.0, dz = 0.0;
-        if (lane < k) {
-            const float *t = rec_xyz(rec, stride, (size_t)(uint32_t)buf[lane]);
-            dx = (double)t[0] - (double)q.x;
-            dy = (double)t[1] - (double)q.y;
-            dz = (double)t[2] - (double)q.z;
-        }
-        __syncthreads();   // (the keys have been read: the next query may append)
-        const double sx = wave_sum_fixed(dx), sy = wave_sum_fixed(dy), sz = wave_sum_fixed(dz);
-        const double sxx = wave_sum_fixed(dx * dx), sxy = wave_sum_fixed(dx * dy), sxz = wave_sum_fixed(dx * dz);
-        const double syy = wave_sum_fixed(dy * dy), syz = wave_sum_fixed(dy * dz), szz = wave_sum_fixed(dz * dz);
-        normal_from_sums(q, (double)k, sx, sy, sz, sxx, sxy, sxz, syy, syz, szz, vpx, vpy, vpz, lane, out);
+        double s[9];
+        knn_moment_sums(buf, k, rec, stride, q, lane, s);
+        normal_from_sums(q, (double)k, s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], vpx, vpy, vpz, lane, out);
     }
 }
 

@@ -298,6 +298,16 @@ struct IcpState {
     bool idle_after_sums = false;  // the caller's thread has waited for the main stream (the sums) and queued nothing since: rsreg_icp_end need not wait again
 };
 
+// A GICP alignment (rsreg_gicp_begin .. rsreg_gicp_end) on top of the ICP state above, which holds the transform, the search and
+// the counters of the staged pipeline it runs on
+struct GicpState {
+    rsreg_gicp_params prm;
+    int active = 0;
+    bool have_search = false;      // d_gicp_m holds the Mahalanobis matrices of the current search
+    int inner_evaluations = 0, rank_last = 0;
+    double sums_last[RSREG_NUM_GICP_SUMS] = {0};
+};
+
 }  // namespace rsreg
 
 // Every buffer, event and stream below releases itself (owned.hpp), and rsreg_ctx_destroy deletes the context only after
@@ -350,7 +360,12 @@ struct rsreg_ctx {
     rsreg::DevBuf d_nrm_raw;      // packed normals of a host buffer as they came over the link (n x float3) ...
     rsreg::PinnedBuf h_nrm;       // ... their staging buffer (rsreg_icp_set_target_normals, on the upload stream like the target's) ...
     rsreg::Event ev_nrm, ev_nrm_packed;   // ... the event behind its last copy, and: the main stream has read d_nrm_raw (made at first use)
-    rsreg::DevBuf d_plane_partials;   // double[32][blocks] of k_plane_reduce
+    rsreg::DevBuf d_plane_partials;   // double[32][blocks] of k_plane_reduce (and of k_gicp_reduce)
+    // GICP (rsreg_gicp_*): six doubles per source / target RECORD in the caller's order, dropped by the next rsreg_icp_set_source* /
+    // rsreg_icp_set_target*; the Mahalanobis matrices of the last search, six doubles per distinct source point
+    bool have_gicp_cs = false, have_gicp_ct = false;
+    rsreg::DevBuf d_gicp_cs, d_gicp_ct, d_gicp_m;
+    rsreg::GicpState gicp;
 
     // ---- ICP source
     bool have_source = false;

@@ -20,6 +20,7 @@ SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) if os.path.isdir(CSRC) else []
 NUM_SUMS = 17
 NUM_PLANE_SUMS = 32                                      # include/rsreg.h: RSREG_NUM_PLANE_SUMS
+NUM_GICP_SUMS = 32                                       # include/rsreg.h: RSREG_NUM_GICP_SUMS
 ESTIMATION_SVD, ESTIMATION_POINT_TO_PLANE_LLS = 0, 1     # include/rsreg.h: rsreg_estimation
 IIN_COVARIANCE_MATRIX, IIN_AVERAGE_3D_GRADIENT, IIN_AVERAGE_DEPTH_CHANGE, IIN_SIMPLE_3D_GRADIENT = 0, 1, 2, 3   # rsreg_iin_method
 IIN_BORDER_IGNORE, IIN_BORDER_MIRROR = 0, 1              # rsreg_iin_border_policy
@@ -58,6 +59,9 @@ EXPORTS = [
     "rsreg_cloud_radius_count_surface", "rsreg_cloud_normals_radius_surface", "rsreg_cloud_fpfh_radius_surface", "rsreg_cloud_spfh_radius_surface",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
+    "rsreg_gicp_params_default", "rsreg_cloud_gicp_covariances", "rsreg_gicp_set_source_covariances", "rsreg_gicp_set_target_covariances",
+    "rsreg_gicp_set_source_covariances_cloud", "rsreg_gicp_set_target_covariances_cloud", "rsreg_gicp_begin", "rsreg_gicp_search",
+    "rsreg_gicp_sums", "rsreg_gicp_step_from_sums", "rsreg_gicp_update", "rsreg_gicp_end", "rsreg_gicp_align", "rsreg_gicp_align_cloud",
     "rsreg_iin_params_default", "rsreg_cloud_integral_normals",
     "rsreg_voxel_grid_params_default", "rsreg_voxel_grid", "rsreg_voxel_grid_gpu", "rsreg_cloud_voxel_grid",
     "rsreg_depth_params_default", "rsreg_depth_params_reference", "rsreg_depth_to_cloud", "rsreg_cloud_from_depth", "rsreg_cloud_from_depth_device",
@@ -95,6 +99,19 @@ class IcpResult(C.Structure):
         ("ms_nn", C.c_double), ("ms_reduce", C.c_double), ("ms_transform", C.c_double),
         ("n_nn_launches", C.c_int32), ("n_scheduled_launches", C.c_int32), ("ms_allreduce", C.c_double),
     ]
+
+
+class GicpParams(C.Structure):   # rsreg_gicp_params
+    _fields_ = [("max_iterations", C.c_int32), ("max_inner_iterations", C.c_int32), ("k_correspondences", C.c_int32), ("reserved0", C.c_int32),
+                ("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
+                ("gicp_epsilon", C.c_double)]
+
+
+class GicpResult(C.Structure):   # rsreg_gicp_result
+    _fields_ = [("transform", C.c_float * 16), ("converged", C.c_int32), ("state", C.c_int32), ("iterations", C.c_int32),
+                ("inner_evaluations", C.c_int32), ("n_correspondences", C.c_uint64), ("mse", C.c_double),
+                ("sums_last", C.c_double * NUM_GICP_SUMS), ("ms_total", C.c_double), ("ms_nn", C.c_double), ("ms_reduce", C.c_double),
+                ("ms_transform", C.c_double), ("n_nn_launches", C.c_int32), ("rank_last", C.c_int32)]
 
 
 class SorStats(C.Structure):   # rsreg_sor_stats
@@ -315,6 +332,20 @@ def lib():
     L.rsreg_icp_update_plane.argtypes = [vp, vp, vp, C.POINTER(i32)]
     L.rsreg_icp_plane_sums_last.argtypes = [vp, vp]
     L.rsreg_plane_solve_from_sums.argtypes = [vp, vp, C.POINTER(i32)]
+    L.rsreg_gicp_params_default.argtypes = [C.POINTER(GicpParams)]
+    L.rsreg_gicp_params_default.restype = None
+    L.rsreg_cloud_gicp_covariances.argtypes = [vp, vp, i32, dbl, vp]
+    for f in ("rsreg_gicp_set_source_covariances", "rsreg_gicp_set_target_covariances"):
+        getattr(L, f).argtypes = [vp, vp, sz, sz]
+        getattr(L, f + "_cloud").argtypes = [vp, vp]
+    L.rsreg_gicp_begin.argtypes = [vp, vp, C.POINTER(GicpParams)]
+    L.rsreg_gicp_search.argtypes = [vp, vp, vp]
+    L.rsreg_gicp_sums.argtypes = [vp, vp, vp]
+    L.rsreg_gicp_step_from_sums.argtypes = [vp, dbl, vp, vp, C.POINTER(i32)]
+    L.rsreg_gicp_update.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
+    L.rsreg_gicp_end.argtypes = [vp, C.POINTER(GicpResult), vp, sz]
+    L.rsreg_gicp_align.argtypes = [vp, vp, C.POINTER(GicpParams), C.POINTER(GicpResult), vp, sz]
+    L.rsreg_gicp_align_cloud.argtypes = [vp, vp, C.POINTER(GicpParams), C.POINTER(GicpResult), vp]
     L.rsreg_transform_cloud.argtypes = [vp, vp, vp, sz, sz, i32, vp]
     L.rsreg_approx_voxel_grid.argtypes = [vp, sz, sz, vp, vp, C.POINTER(sz)]
     L.rsreg_approx_voxel_grid_gpu.argtypes = [vp, vp, sz, sz, vp, vp, C.POINTER(sz)]
