@@ -357,6 +357,78 @@ int rsreg_icp_plane_sums_last(rsreg_ctx *ctx, double sums[RSREG_NUM_PLANE_SUMS])
 /* The solve alone (host only, no ctx): t_out = the increment, column-major; *rank_out (nullable) = eigen-directions used. */
 int rsreg_plane_solve_from_sums(const double sums[RSREG_NUM_PLANE_SUMS], float t_out[16], int *rank_out);
 
+/* ---- correspondence rejectors: pcl::Registration::addCorrespondenceRejector ------------------------------------------------
+ * An ordered chain of rejectors on the context, applied in every ICP iteration between determineCorrespondences and the
+ * transformation estimate, for point-to-point and point-to-plane estimation alike.  The rules are RECALLED FROM PCL 1.9.1
+ * (registration/correspondence_rejection_*.{h,cpp}, icp.hpp) and CANNOT BE PINNED WITHOUT PCL; the deviations are stated.
+ *
+ * WHERE THE CHAIN SITS.  A pair is IN PLAY when its source record is finite, has a target within the gate, has passed the
+ * reciprocal test if rsreg_icp_params.use_reciprocal_correspondences is on and the trim if trim_overlap_ratio is set: those two
+ * run first, as without a chain.  The chain then runs in the order given, each rejector over what the one before left, as PCL's
+ * loop feeds each rejector the previous one's getCorrespondences.  It works on ORIGINAL source records in the caller's order on
+ * both source paths (up to 65 536 records searched as they come; larger sources, or RSREG_SORT_SMALL=1, merged into weighted
+ * distinct points): copies of a point are separate pairs, every tie goes to the lowest source index, and a rejector may keep any
+ * subset of a point's copies (exact copies may carry different normals).  A non-empty chain makes the iteration run as
+ * RSREG_PIPELINE_STAGED whatever pipeline_mode asks for, like the two filters, and makes a target that was set without an index
+ * build it.  A context whose communicator has more than one rank refuses a non-empty chain (RSREG_ERR_INVALID_ARG from
+ * rsreg_icp_begin).  The chain stays on the context until replaced; an alignment uses the chain rsreg_icp_begin found.
+ * rsreg_icp_fitness_score and the rsreg_gicp_* entry points ignore it (PCL's fitness score and PCL's GICP loop consult no
+ * rejector).  Behind the chain, fewer than 3 pairs ([0] of the 17 or 32 sums) end the alignment with
+ * RSREG_CONV_NO_CORRESPONDENCES, as without one.  An empty chain -- the default -- changes nothing at all.
+ * The whole chain is queued on the context's stream and adds no host wait to an iteration; it uses integer atomics only, so
+ * the same chain on the same inputs keeps the same pairs and gives the same sums on any context, at any launch.
+ *
+ * RSREG_REJECTOR_MEDIAN_DISTANCE (CorrespondenceRejectorMedianDistance, value = setMedianFactor, PCL default 1.0).  m = the pairs
+ * in play; m == 0: nothing happens.  The median is the float d2 at 0-based rank floor(m / 2) of the in-play d2 in ascending
+ * order: the upper median, PCL's nth_element(begin + size / 2).  A pair stays iff (double)d2 <= (double)median * factor,
+ * evaluated as written in IEEE double: a pair at the bound stays, a NaN product (0 * inf) drops every pair.  factor must not be
+ * NaN or negative.  The d2 is the one the search returned.  DEVIATION: PCL's ICP hands the rejector a data container through
+ * which it recomputes the distance from the clouds -- the same quantity in another rounding.
+ * RSREG_REJECTOR_ONE_TO_ONE (CorrespondenceRejectorOneToOne).  Of the pairs in play that share a target record the one with the
+ * smallest (d2, source index) stays.  DEVIATION: PCL's std::sort leaves the order of equal distances open; the lowest source
+ * index is this library's rule.
+ * RSREG_REJECTOR_SURFACE_NORMAL (CorrespondenceRejectorSurfaceNormal, DataContainer::getCorrespondenceScoreFromNormals, value =
+ * setThreshold, a cosine, PCL default 1.0).  A pair stays iff (double)((sx*tx + sy*ty) + sz*tz) > threshold: float arithmetic,
+ * every operation rounded once, no contraction; the comparison is strict; a NaN score drops the pair.  t = the matched target
+ * RECORD's normal (rsreg_icp_set_target_normals*).  s = the source record's CURRENT normal: the one handed in
+ * (rsreg_icp_set_source_normals*), turned at rsreg_icp_begin by the guess's 3 x 3 block -- (r0*x + r1*y) + r2*z per row, the
+ * arithmetic of rsreg_transform_cloud without the translation; an identity guess copies it -- and after every update turned in
+ * place by the increment's 3 x 3 block, as the points are moved (PCL transforms its working cloud's normals with each increment
+ * too).  A chain with this kind and either set of normals missing: RSREG_ERR_STATE from rsreg_icp_begin.  A new rsreg_icp_begin
+ * on the same source starts again from the normals as handed in.
+ * RSREG_REJECTOR_TRIMMED (CorrespondenceRejectorTrimmed, value = setOverlapRatio, 0 < r < 1, anything else:
+ * RSREG_ERR_INVALID_ARG).  The rule of trim_overlap_ratio at that place of the chain, over the pairs in play there: the same
+ * kernels, the first floor((float)r * (float)count) pairs in (d2, source index) order stay.  rsreg_icp_params.trim_overlap_ratio
+ * keeps its place in front of the chain.
+ *
+ * rsreg_icp_set_rejectors: n = 0 clears the chain; at most 8 entries; an unknown kind, a bad value or n > 8:
+ * RSREG_ERR_INVALID_ARG, and the chain set before stays.
+ * rsreg_icp_rejector_stats: valid after a rsreg_icp_search (or an alignment) with a chain, until the next search;
+ * RSREG_ERR_STATE otherwise.  One record per chain entry, as many as `capacity` holds; n_in / n_out = the pairs in front of and
+ * behind the entry, counted in original records; median_distance = the median d2 of a MEDIAN_DISTANCE entry
+ * (getMedianDistance()), 0 when m == 0 and for the other kinds.  *n_out (nullable) = the chain's length, which may exceed
+ * `capacity`.  This call waits for the stream; nothing else of the chain does.
+ * rsreg_icp_search's index_out / sqr_dist_out report -1 for every record the chain dropped, as for the two filters.
+ * rsreg_icp_set_source_normals*: one normal per source RECORD in the caller's order, layout and lifetime as
+ * rsreg_icp_set_target_normals*.  Call it after rsreg_icp_set_source*; n must be that source's record count
+ * (RSREG_ERR_INVALID_ARG otherwise, RSREG_ERR_NO_SOURCE without a source); any later rsreg_icp_set_source* drops them.
+ * NOT BUILT: CorrespondenceRejectorVarTrimmed, ...Distance (max_correspondence_distance is it), ...Features, ...Poly inside ICP,
+ * rejectors over a stand-alone correspondence list, and the chain across ranks. */
+typedef enum rsreg_rejector_kind {
+    RSREG_REJECTOR_MEDIAN_DISTANCE = 1,   /* value = factor,    PCL default 1.0 */
+    RSREG_REJECTOR_ONE_TO_ONE      = 2,   /* value unused                        */
+    RSREG_REJECTOR_SURFACE_NORMAL  = 3,   /* value = threshold (a cosine), PCL default 1.0 */
+    RSREG_REJECTOR_TRIMMED         = 4    /* value = overlap ratio, 0 < r < 1    */
+} rsreg_rejector_kind;
+typedef struct rsreg_rejector { int32_t kind; int32_t reserved0; double value; } rsreg_rejector;
+typedef struct rsreg_rejector_stat { uint64_t n_in, n_out; double median_distance; double reserved0; } rsreg_rejector_stat;
+#define RSREG_MAX_REJECTORS 8
+
+int rsreg_icp_set_rejectors(rsreg_ctx *ctx, const rsreg_rejector *chain, int32_t n);      /* n = 0 clears; at most 8 */
+int rsreg_icp_rejector_stats(rsreg_ctx *ctx, rsreg_rejector_stat *stats, int32_t capacity, int32_t *n_out);
+int rsreg_icp_set_source_normals(rsreg_ctx *ctx, const void *normals, size_t n, size_t stride);
+int rsreg_icp_set_source_normals_cloud(rsreg_ctx *ctx, const rsreg_cloud *normals);
+
 /* ---- GICP: pcl::GeneralizedIterativeClosestPoint (plane-to-plane ICP, Segal et al.) ------------------------------------------
  * A sibling of point-to-plane ICP with entry points of its own (rsreg_icp_params.estimation has no value for it): the context's
  * ICP source, target, index and staged search are shared -- the clouds come in through rsreg_icp_set_source* / rsreg_icp_set_target*

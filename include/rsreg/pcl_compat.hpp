@@ -378,6 +378,65 @@ template <typename PointT> void copy_aligned(const PointCloud<PointT> &src, Poin
 }
 }  // namespace detail
 
+namespace detail {
+template <typename PointT, typename = void> struct has_normal : std::false_type {};
+template <typename PointT> struct has_normal<PointT, decltype((void)std::declval<PointT &>().normal_x)> : std::true_type {};
+}  // namespace detail
+
+// ---- pcl::registration::CorrespondenceRejector and the four rejectors an ICP object's chain takes (rsreg.h:
+// rsreg_icp_set_rejectors holds the contract and the stated deviations).  The objects carry a kind and a value; the rejection
+// itself runs inside the alignment, on the GPU, in the order the rejectors were added.
+namespace registration {
+class CorrespondenceRejector {
+  public:
+    using Ptr = std::shared_ptr<CorrespondenceRejector>;
+    using ConstPtr = std::shared_ptr<const CorrespondenceRejector>;
+    virtual ~CorrespondenceRejector() = default;
+    int kind() const { return kind_; }
+    double value() const { return value_; }
+    // engine extra: the pairs in front of and behind this rejector in the last iteration of the last align()
+    const rsreg_rejector_stat &stat() const { return stat_; }
+    void set_stat_(const rsreg_rejector_stat &s) { stat_ = s; }
+
+  protected:
+    CorrespondenceRejector(int kind, double value) : kind_(kind), value_(value) {}
+    int kind_;
+    double value_;
+    rsreg_rejector_stat stat_{};
+};
+
+class CorrespondenceRejectorMedianDistance : public CorrespondenceRejector {
+  public:
+    using Ptr = std::shared_ptr<CorrespondenceRejectorMedianDistance>;
+    CorrespondenceRejectorMedianDistance() : CorrespondenceRejector(RSREG_REJECTOR_MEDIAN_DISTANCE, 1.0) {}
+    void setMedianFactor(double factor) { value_ = factor; }
+    double getMedianFactor() const { return value_; }
+    double getMedianDistance() const { return stat_.median_distance; }   // of the last iteration of the last align(): a SQUARED distance, as in PCL
+};
+
+class CorrespondenceRejectorOneToOne : public CorrespondenceRejector {
+  public:
+    using Ptr = std::shared_ptr<CorrespondenceRejectorOneToOne>;
+    CorrespondenceRejectorOneToOne() : CorrespondenceRejector(RSREG_REJECTOR_ONE_TO_ONE, 0.0) {}
+};
+
+class CorrespondenceRejectorSurfaceNormal : public CorrespondenceRejector {
+  public:
+    using Ptr = std::shared_ptr<CorrespondenceRejectorSurfaceNormal>;
+    CorrespondenceRejectorSurfaceNormal() : CorrespondenceRejector(RSREG_REJECTOR_SURFACE_NORMAL, 1.0) {}
+    void setThreshold(double threshold) { value_ = threshold; }
+    double getThreshold() const { return value_; }
+};
+
+class CorrespondenceRejectorTrimmed : public CorrespondenceRejector {
+  public:
+    using Ptr = std::shared_ptr<CorrespondenceRejectorTrimmed>;
+    CorrespondenceRejectorTrimmed() : CorrespondenceRejector(RSREG_REJECTOR_TRIMMED, 0.5) {}
+    void setOverlapRatio(double ratio) { value_ = ratio; }
+    double getOverlapRatio() const { return value_; }
+};
+}  // namespace registration
+
 // ---- pcl::IterativeClosestPoint
 template <typename PointSource, typename PointTarget> class IterativeClosestPoint {
   public:
@@ -404,6 +463,26 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
     void setUseReciprocalCorrespondences(bool on) { prm_.use_reciprocal_correspondences = on ? 1 : 0; }
     // addCorrespondenceRejector (CorrespondenceRejectorTrimmed with setOverlapRatio (ratio)); <= 0 or >= 1: none
     void setTrimmedRejectorOverlapRatio(double ratio) { prm_.trim_overlap_ratio = ratio; }
+    // Registration::addCorrespondenceRejector and its companions: the chain runs in this order in every iteration, behind the two
+    // filters above.  A CorrespondenceRejectorSurfaceNormal reads the normals of both clouds: inside the records (PointXYZRGBNormal)
+    // or beside them (setInputSourceNormals; setInputTargetNormals of IterativeClosestPointWithNormals)
+    using CorrespondenceRejectorPtr = registration::CorrespondenceRejector::Ptr;
+    void addCorrespondenceRejector(const CorrespondenceRejectorPtr &rejector)
+    {
+        if (!rejector) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: addCorrespondenceRejector(null)");
+        if (rejectors_.size() >= RSREG_MAX_REJECTORS) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: a rejector chain has at most 8 entries");
+        rejectors_.push_back(rejector);
+    }
+    std::vector<CorrespondenceRejectorPtr> getCorrespondenceRejectors() const { return rejectors_; }
+    bool removeCorrespondenceRejector(unsigned int i)
+    {
+        if (i >= rejectors_.size()) return false;
+        rejectors_.erase(rejectors_.begin() + i);
+        return true;
+    }
+    void clearCorrespondenceRejectors() { rejectors_.clear(); }
+    // one normal per source record; the cloud must stay alive and unchanged until align has returned
+    void setInputSourceNormals(const PointCloud<Normal> &normals) { src_normals_ = &normals; src_normals_dirty_ = true; }
     // engine knobs without a PCL counterpart
     void setFixedIterationCount(bool on) { prm_.criteria_mode = on ? RSREG_CRITERIA_FIXED : RSREG_CRITERIA_PCL; }
     void setPipelineMode(int mode) { prm_.pipeline_mode = mode; }
@@ -419,18 +498,21 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
             check(rsreg_icp_set_source(c, source_->points.data(), source_->size(), sizeof(PointSource), source_->is_dense), c);
             source_dirty_ = false;
             ctx_->icp_source_owner = this;
+            src_normals_dirty_ = true;   // (a new source drops the normals of the one before)
         }
         if (target_dirty_ || ctx_->icp_target_owner != this) {
             check(rsreg_icp_set_target(c, target_->points.data(), target_->size(), sizeof(PointTarget), target_->is_dense,
                                        prm_.max_correspondence_distance), c);
             target_dirty_ = false;
             ctx_->icp_target_owner = this;
+            target_normals_set_ = false;
             target_set_(c, true);
         } else {
             target_set_(c, false);
         }
         // `output = input` (PCL copies the input cloud first, then rewrites xyz) is made inside the call, by the host threads that
         // write the aligned positions anyway (rsreg_icp_align_records): the records are never constructed or copied here
+        set_rejectors_(c);
         PointCloud<PointSource> tmp;
         tmp.points = uninitialized_points<PointSource>(source_->size());
         tmp.width = source_->width;
@@ -441,6 +523,7 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
         else
             check(rsreg_icp_align(c, guess.data(), &prm_, &res_, nullptr, 0), c);
         std::memcpy(final_.m, res_.transform, sizeof(final_.m));
+        fetch_rejector_stats_(c);
         output = std::move(tmp);
     }
     // the same calls on clouds resident in HBM: nothing is uploaded or downloaded (the handles must
@@ -466,6 +549,7 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
             source_stamp_ = cloud_stamp(dsource_->handle());
             source_dirty_ = false;
             ctx_->icp_source_owner = this;
+            src_normals_dirty_ = true;
         }
         t1_ = std::chrono::steady_clock::now();
         if (target_dirty_ || ctx_->icp_target_owner != this) {
@@ -474,13 +558,16 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
             target_stamp_ = cloud_stamp(dtarget_->handle());
             target_dirty_ = false;
             ctx_->icp_target_owner = this;
+            target_normals_set_ = false;
             target_set_(c, true);
         } else {
             target_set_(c, false);
         }
+        set_rejectors_(c);
         const auto t2 = std::chrono::steady_clock::now();
         check(rsreg_icp_align_cloud(c, guess.data(), &prm_, &res_, output.handle()), c);
         std::memcpy(final_.m, res_.transform, sizeof(final_.m));
+        fetch_rejector_stats_(c);
         const auto t3 = std::chrono::steady_clock::now();
         call_ms[0] += std::chrono::duration<double, std::milli>(t1_ - t0).count();
         call_ms[1] += std::chrono::duration<double, std::milli>(t2 - t1_).count();
@@ -510,7 +597,59 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
   protected:
     // the context holds this object's target (`fresh`: it has just been set): what a derived class hands over with it
     // (IterativeClosestPointWithNormals: the target's normals, which a new target drops)
-    virtual void target_set_(rsreg_ctx *, bool /*fresh*/) {}
+    // (here: a target whose records carry normals hands them over when the chain's normal test will read them)
+    virtual void target_set_(rsreg_ctx *c, bool fresh)
+    {
+        if (!has_normal_rejector_() || !target_) return;
+        if (fresh || !target_normals_set_) set_target_record_normals_(c, detail::has_normal<PointTarget>());
+    }
+    bool has_normal_rejector_() const
+    {
+        for (const auto &r : rejectors_)
+            if (r->kind() == RSREG_REJECTOR_SURFACE_NORMAL) return true;
+        return false;
+    }
+    // this object's chain onto the context (another object's may be there), and the source's normals if the chain reads them
+    void set_rejectors_(rsreg_ctx *c)
+    {
+        rsreg_rejector chain[RSREG_MAX_REJECTORS];
+        for (size_t i = 0; i < rejectors_.size(); ++i) chain[i] = rsreg_rejector{rejectors_[i]->kind(), 0, rejectors_[i]->value()};
+        check(rsreg_icp_set_rejectors(c, rejectors_.empty() ? nullptr : chain, (int32_t)rejectors_.size()), c);
+        if (!has_normal_rejector_() || !src_normals_dirty_) return;
+        if (src_normals_)
+            check(rsreg_icp_set_source_normals(c, src_normals_->points.data(), src_normals_->size(), sizeof(Normal)), c);
+        else
+            set_source_record_normals_(c, detail::has_normal<PointSource>());
+        src_normals_dirty_ = false;
+    }
+    void fetch_rejector_stats_(rsreg_ctx *c)
+    {
+        if (rejectors_.empty()) return;
+        rsreg_rejector_stat st[RSREG_MAX_REJECTORS];
+        int32_t n = 0;
+        if (rsreg_icp_rejector_stats(c, st, RSREG_MAX_REJECTORS, &n) != RSREG_OK) return;   // (an alignment that never searched)
+        for (size_t i = 0; i < rejectors_.size() && i < (size_t)n; ++i) rejectors_[i]->set_stat_(st[i]);
+    }
+    void set_source_record_normals_(rsreg_ctx *c, std::true_type)
+    {
+        if (!source_) throw Error(RSREG_ERR_STATE, "rsreg: a device-cloud source needs setInputSourceNormals");
+        const char *rec = reinterpret_cast<const char *>(source_->points.data());
+        check(rsreg_icp_set_source_normals(c, source_->size() ? rec + offsetof(PointSource, data_n) : nullptr, source_->size(), sizeof(PointSource)), c);
+    }
+    void set_source_record_normals_(rsreg_ctx *, std::false_type)
+    {
+        throw Error(RSREG_ERR_STATE, "rsreg: the source's points carry no normals: setInputSourceNormals");
+    }
+    void set_target_record_normals_(rsreg_ctx *c, std::true_type)
+    {
+        const char *rec = reinterpret_cast<const char *>(target_->points.data());
+        check(rsreg_icp_set_target_normals(c, target_->size() ? rec + offsetof(PointTarget, data_n) : nullptr, target_->size(), sizeof(PointTarget)), c);
+        target_normals_set_ = true;
+    }
+    void set_target_record_normals_(rsreg_ctx *, std::false_type) {}   // (rsreg_icp_begin refuses the chain: RSREG_ERR_STATE)
+    std::vector<CorrespondenceRejectorPtr> rejectors_;
+    const PointCloud<Normal> *src_normals_ = nullptr;
+    bool src_normals_dirty_ = true, target_normals_set_ = false;
     std::shared_ptr<Context> ctx_;
     rsreg_icp_params prm_;
     rsreg_icp_result res_{};
@@ -523,11 +662,6 @@ template <typename PointSource, typename PointTarget> class IterativeClosestPoin
     std::pair<uint64_t, uint64_t> source_stamp_{0, 0}, target_stamp_{0, 0};   // (id, version) of the device clouds as loaded
     std::chrono::steady_clock::time_point t1_;
 };
-
-namespace detail {
-template <typename PointT, typename = void> struct has_normal : std::false_type {};
-template <typename PointT> struct has_normal<PointT, decltype((void)std::declval<PointT &>().normal_x)> : std::true_type {};
-}  // namespace detail
 
 // ---- pcl::IterativeClosestPointWithNormals: point-to-plane ICP with PCL's default estimator,
 // TransformationEstimationPointToPlaneLLS (rsreg.h: rsreg_estimation, RSREG_NUM_PLANE_SUMS; the two stated deviations from

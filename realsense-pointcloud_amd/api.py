@@ -889,6 +889,63 @@ def _own_alignment(reg, owns):
         raise _l.RsregError(_l.RSREG_ERR_STATE, "getFitnessScore before this object's align()")
 
 
+class CorrespondenceRejector:
+    """pcl::registration::CorrespondenceRejector as an entry of an ICP object's chain (include/rsreg.h: rsreg_icp_set_rejectors):
+    a kind and a value.  The rejectors run inside the alignment, on the GPU; the objects only carry their settings."""
+    kind = 0
+
+    def __init__(self, value=0.0):
+        self.value = float(value)
+        self._stat = None   # (n_in, n_out, median d2) of the last search of the ICP object that holds it: rejector_stats()
+
+
+class CorrespondenceRejectorMedianDistance(CorrespondenceRejector):
+    kind = _l.REJECTOR_MEDIAN_DISTANCE
+
+    def __init__(self, factor=1.0):
+        super().__init__(factor)
+
+    def setMedianFactor(self, factor):
+        self.value = float(factor)
+
+    def getMedianFactor(self):
+        return self.value
+
+    def getMedianDistance(self):
+        """The median squared distance of the last search (after IterativeClosestPoint.rejector_stats())."""
+        return self._stat[2] if self._stat else 0.0
+
+
+class CorrespondenceRejectorOneToOne(CorrespondenceRejector):
+    kind = _l.REJECTOR_ONE_TO_ONE
+
+
+class CorrespondenceRejectorSurfaceNormal(CorrespondenceRejector):
+    kind = _l.REJECTOR_SURFACE_NORMAL
+
+    def __init__(self, threshold=1.0):
+        super().__init__(threshold)
+
+    def setThreshold(self, threshold):
+        self.value = float(threshold)
+
+    def getThreshold(self):
+        return self.value
+
+
+class CorrespondenceRejectorTrimmed(CorrespondenceRejector):
+    kind = _l.REJECTOR_TRIMMED
+
+    def __init__(self, overlap_ratio=0.5):
+        super().__init__(overlap_ratio)
+
+    def setOverlapRatio(self, ratio):
+        self.value = float(ratio)
+
+    def getOverlapRatio(self):
+        return self.value
+
+
 class IterativeClosestPoint:
     """pcl::IterativeClosestPoint<PointXYZRGB, PointXYZRGB> on the MI355X."""
 
@@ -901,6 +958,117 @@ class IterativeClosestPoint:
         self._src_dirty = True
         self._quiet_search = False   # run_sharded_icp: skip the per-iteration D2H of the correspondences
         self.result = None
+        self._rejectors = []         # Registration::correspondence_rejectors_
+        self._src_normals = None     # setInputSourceNormals: what a CorrespondenceRejectorSurfaceNormal compares
+        self._src_normals_dirty = True
+        self._normals = None         # setInputTargetNormals: the other side of that comparison (and point-to-plane ICP's planes)
+        self._normals_dirty = True
+
+    # Registration::addCorrespondenceRejector and its companions: the chain runs in this order in every iteration, behind
+    # setUseReciprocalCorrespondences / setTrimmedRejectorOverlapRatio (include/rsreg.h: rsreg_icp_set_rejectors)
+    def addCorrespondenceRejector(self, rejector):
+        if not isinstance(rejector, CorrespondenceRejector) or rejector.kind == 0:
+            raise ValueError("addCorrespondenceRejector takes a CorrespondenceRejectorMedianDistance, ...OneToOne, ...SurfaceNormal or ...Trimmed")
+        if len(self._rejectors) >= _l.MAX_REJECTORS:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "a rejector chain has at most %d entries" % _l.MAX_REJECTORS)
+        self._rejectors.append(rejector)
+
+    def getCorrespondenceRejectors(self):
+        return list(self._rejectors)
+
+    def removeCorrespondenceRejector(self, i):
+        if not 0 <= i < len(self._rejectors):
+            return False
+        del self._rejectors[i]
+        return True
+
+    def clearCorrespondenceRejectors(self):
+        self._rejectors = []
+
+    def setInputSourceNormals(self, normals):
+        """The source's normals, one per record (a NormalCloud / NORMAL_DTYPE array, an (n, >= 3) float32 array or a DeviceCloud
+        of pcl::Normal records); a POINT_NORMAL_DTYPE source carries its own.  Read by CorrespondenceRejectorSurfaceNormal."""
+        self._src_normals = normals
+        self._src_normals_dirty = True
+
+    def setInputTargetNormals(self, normals):
+        """The target's normals, one per record, in the forms setInputSourceNormals takes; a POINT_NORMAL_DTYPE target carries its own."""
+        self._normals = normals
+        self._normals_dirty = True
+
+    def _needs_target_normals(self):
+        return any(r.kind == _l.REJECTOR_SURFACE_NORMAL for r in self._rejectors)
+
+    def _sync_target_normals(self, rebuilt):
+        if not (rebuilt or self._normals_dirty):   # (a new target index drops the normals of the one before)
+            return
+        L, h = _l.lib(), self.ctx.h
+        nrm = self._normals
+        if nrm is None:
+            pts = getattr(self._tgt, "points", self._tgt)
+            if not (isinstance(pts, np.ndarray) and pts.dtype.names and "normal_x" in pts.dtype.names):
+                raise _l.RsregError(_l.RSREG_ERR_STATE, "%s: the target has no normals (setInputTargetNormals)" % type(self).__name__)
+            pts = np.ascontiguousarray(pts)
+            _l.check(L.rsreg_icp_set_target_normals(h, pts.ctypes.data + pts.dtype.fields["normal_x"][1], len(pts), pts.dtype.itemsize), h)
+        elif isinstance(nrm, DeviceCloud):
+            _l.check(L.rsreg_icp_set_target_normals_cloud(h, nrm.h), h)
+            self._nrm_stamp = nrm.stamp
+        else:
+            rec = np.ascontiguousarray(getattr(nrm, "points", nrm))
+            if rec.dtype.names:
+                off = rec.dtype.fields["normal_x"][1]
+                _l.check(L.rsreg_icp_set_target_normals(h, rec.ctypes.data + off, len(rec), rec.dtype.itemsize), h)
+            else:
+                if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] < 3:
+                    raise ValueError("normals must be a NormalCloud, a structured array with normal_x or an (n, >=3) float32 array")
+                _l.check(L.rsreg_icp_set_target_normals(h, rec.ctypes.data, rec.shape[0], rec.shape[1] * 4), h)
+        self._normals_dirty = False
+
+    def _sync_rejectors(self, source_loaded):
+        """The object's chain onto the context (another object's may be there), and the source's normals if the chain reads them."""
+        L, h = _l.lib(), self.ctx.h
+        n = len(self._rejectors)
+        arr = (_l.Rejector * max(n, 1))()
+        for k, r in enumerate(self._rejectors):
+            arr[k].kind, arr[k].value = r.kind, r.value
+        _l.check(L.rsreg_icp_set_rejectors(h, C.cast(arr, C.c_void_p) if n else None, n), h)
+        if not any(r.kind == _l.REJECTOR_SURFACE_NORMAL for r in self._rejectors):
+            return
+        nrm = self._src_normals
+        if isinstance(nrm, DeviceCloud) and getattr(self, "_src_nrm_stamp", None) != nrm.stamp:
+            self._src_normals_dirty = True
+        if not (source_loaded or self._src_normals_dirty):
+            return
+        if nrm is None:
+            pts = getattr(self._src, "points", self._src)
+            if not (isinstance(pts, np.ndarray) and pts.dtype.names and "normal_x" in pts.dtype.names):
+                raise _l.RsregError(_l.RSREG_ERR_STATE, "CorrespondenceRejectorSurfaceNormal: the source has no normals (setInputSourceNormals)")
+            pts = np.ascontiguousarray(pts)
+            _l.check(L.rsreg_icp_set_source_normals(h, pts.ctypes.data + pts.dtype.fields["normal_x"][1], len(pts), pts.dtype.itemsize), h)
+        elif isinstance(nrm, DeviceCloud):
+            _l.check(L.rsreg_icp_set_source_normals_cloud(h, nrm.h), h)
+            self._src_nrm_stamp = nrm.stamp
+        else:
+            rec = np.ascontiguousarray(getattr(nrm, "points", nrm))
+            if rec.dtype.names:
+                _l.check(L.rsreg_icp_set_source_normals(h, rec.ctypes.data + rec.dtype.fields["normal_x"][1], len(rec), rec.dtype.itemsize), h)
+            else:
+                if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] < 3:
+                    raise ValueError("normals must be a NormalCloud, a structured array with normal_x or an (n, >=3) float32 array")
+                _l.check(L.rsreg_icp_set_source_normals(h, rec.ctypes.data, rec.shape[0], rec.shape[1] * 4), h)
+        self._src_normals_dirty = False
+
+    def rejector_stats(self):
+        """[(n_in, n_out, median d2)] per rejector of the chain for the last search (rsreg_icp_rejector_stats); also left on the
+        rejector objects (getMedianDistance)."""
+        n = len(self._rejectors)
+        st = (_l.RejectorStat * max(n, 1))()
+        got = C.c_int32(0)
+        _l.check(_l.lib().rsreg_icp_rejector_stats(self.ctx.h, C.cast(st, C.c_void_p), n, C.byref(got)), self.ctx.h)
+        out = [(int(st[k].n_in), int(st[k].n_out), float(st[k].median_distance)) for k in range(min(n, got.value))]
+        for r, s in zip(self._rejectors, out):
+            r._stat = s
+        return out
 
     # setters the reference calls (incremental_icp.hpp:46-49)
     def setMaximumIterations(self, n):
@@ -956,6 +1124,11 @@ class IterativeClosestPoint:
         L, h = _l.lib(), self.ctx.h
         if self._tgt is None or self._src is None:
             raise ValueError("setInputSource / setInputTarget not called")
+        rebuilt = self._tgt_dirty or self.ctx.icp_target_owner is not self or getattr(self, "_tgt_gate", None) != self.params.max_correspondence_distance
+        if isinstance(self._tgt, DeviceCloud) and getattr(self, "_tgt_stamp", None) != self._tgt.stamp:
+            rebuilt = True
+        if isinstance(self._normals, DeviceCloud) and getattr(self, "_nrm_stamp", None) != self._normals.stamp:
+            self._normals_dirty = True
         # the source first, as the reference does (incremental_icp.hpp:57-58): the library loads it on a stream of its own,
         # beside the target's index build
         # a device cloud rewritten in place since it was loaded (filter(x, x), +=, a transform or an alignment into it) is
@@ -979,6 +1152,7 @@ class IterativeClosestPoint:
             self._n_src = n
             self._src_dirty = False
             self.ctx.icp_source_owner = self
+            self._src_loaded = True   # (the library dropped the source normals of the load before: _sync_rejectors)
         # the index's cell size derives from the gate: a gate that has changed since the build -- through the setter or by assigning
         # `params` -- means a new index (PCL lets the caller change it between two aligns of the same target)
         if getattr(self, "_tgt_gate", None) != self.params.max_correspondence_distance:
@@ -999,6 +1173,10 @@ class IterativeClosestPoint:
                 _l.check(L.rsreg_icp_set_target(h, p, n, s, dense, self.params.max_correspondence_distance), h)
             self._tgt_dirty = False
             self.ctx.icp_target_owner = self
+        if self._needs_target_normals():
+            self._sync_target_normals(rebuilt)
+        loaded, self._src_loaded = getattr(self, "_src_loaded", False), False
+        self._sync_rejectors(loaded)
 
     def align(self, guess=None):
         """icp.align(out[, guess]): returns the aligned cloud (source colours, xyz <- final * xyz)."""
@@ -1114,48 +1292,14 @@ class IterativeClosestPointWithNormals(IterativeClosestPoint):
     def __init__(self, ctx=None):
         super().__init__(ctx)
         self.params.estimation = _l.ESTIMATION_POINT_TO_PLANE_LLS
-        self._normals = None
-        self._normals_dirty = True
 
     def setInputTarget(self, cloud, normals=None):
         super().setInputTarget(cloud)
         self._normals = normals
         self._normals_dirty = True
 
-    def setInputTargetNormals(self, normals):
-        self._normals = normals
-        self._normals_dirty = True
-
-    def _sync_inputs(self):
-        rebuilt = self._tgt_dirty or self.ctx.icp_target_owner is not self or getattr(self, "_tgt_gate", None) != self.params.max_correspondence_distance
-        if isinstance(self._tgt, DeviceCloud) and getattr(self, "_tgt_stamp", None) != self._tgt.stamp:
-            rebuilt = True
-        if isinstance(self._normals, DeviceCloud) and getattr(self, "_nrm_stamp", None) != self._normals.stamp:
-            self._normals_dirty = True
-        super()._sync_inputs()
-        if not (rebuilt or self._normals_dirty):   # (a new target index drops the normals of the one before)
-            return
-        L, h = _l.lib(), self.ctx.h
-        nrm = self._normals
-        if nrm is None:
-            pts = getattr(self._tgt, "points", self._tgt)
-            if not (isinstance(pts, np.ndarray) and pts.dtype.names and "normal_x" in pts.dtype.names):
-                raise _l.RsregError(_l.RSREG_ERR_STATE, "IterativeClosestPointWithNormals: the target has no normals (setInputTargetNormals)")
-            pts = np.ascontiguousarray(pts)
-            _l.check(L.rsreg_icp_set_target_normals(h, pts.ctypes.data + pts.dtype.fields["normal_x"][1], len(pts), pts.dtype.itemsize), h)
-        elif isinstance(nrm, DeviceCloud):
-            _l.check(L.rsreg_icp_set_target_normals_cloud(h, nrm.h), h)
-            self._nrm_stamp = nrm.stamp
-        else:
-            rec = np.ascontiguousarray(getattr(nrm, "points", nrm))
-            if rec.dtype.names:
-                off = rec.dtype.fields["normal_x"][1]
-                _l.check(L.rsreg_icp_set_target_normals(h, rec.ctypes.data + off, len(rec), rec.dtype.itemsize), h)
-            else:
-                if rec.dtype != np.float32 or rec.ndim != 2 or rec.shape[1] < 3:
-                    raise ValueError("normals must be a NormalCloud, a structured array with normal_x or an (n, >=3) float32 array")
-                _l.check(L.rsreg_icp_set_target_normals(h, rec.ctypes.data, rec.shape[0], rec.shape[1] * 4), h)
-        self._normals_dirty = False
+    def _needs_target_normals(self):
+        return True
 
     # ---- step-wise form: begin -> { search -> plane_sums -> update_plane } -> end
     def plane_sums(self):

@@ -896,6 +896,14 @@ int rsreg_icp_set_target_normals_cloud(rsreg_ctx *ctx, const rsreg_cloud *c)
     return rsreg_icp_set_target_normals_device_(ctx, c->n ? c->buf.ptr : nullptr, c->n, c->stride);
 }
 
+// the same for the ICP source's normals (the surface normal rejector): one per source record
+int rsreg_icp_set_source_normals_cloud(rsreg_ctx *ctx, const rsreg_cloud *c)
+{
+    if (!ctx || !c || c->ctx != ctx) return RSREG_ERR_INVALID_ARG;
+    RSREG_HIP(ctx, settle(c));
+    return rsreg_icp_set_source_normals_device_(ctx, c->n ? c->buf.ptr : nullptr, c->n, c->stride);
+}
+
 // 1 when the context's ICP target index was built from this cloud, as it is now, for this gate: the ICP edge scheme
 // hands the same grown feature cloud to its coarse and to its refining ICP, one after the other
 // (icp_edge_based_registration.hpp:94-95,108-109), and the second of them may keep the index instead of building it again

@@ -27,6 +27,7 @@ int rsreg_icp_set_target_scan_(rsreg_ctx *ctx, const void *d_points, size_t n, s
 // icp.hip: the ICP target's normals from records in HBM whose first 12 bytes are the normal, one per target record, copied on
 // the context's stream
 int rsreg_icp_set_target_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride);
+int rsreg_icp_set_source_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride);
 // icp.hip: the GICP covariances of the ICP source (source != 0) or target from records in HBM whose first 48 bytes are six doubles
 // (stride: a multiple of 8), one per record of that cloud, copied on the context's stream
 int rsreg_gicp_set_covariances_device_(rsreg_ctx *ctx, int source, const void *d_cov, size_t n, size_t stride);

@@ -22,6 +22,7 @@
 #include "oscan.hpp"
 #include "fitness_kernels.hpp"
 #include "plane_kernels.hpp"
+#include "rejector_kernels.hpp"
 #include "gicp_kernels.hpp"
 #include "cloud_ops.hpp"
 #include "icp_grid_plan.hpp"
@@ -870,6 +871,7 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
     RSREG_HIP(ctx, ctx->h_smisc.reserve(kHsWords * sizeof(uint32_t)));
     ctx->icp_fit_ok = false;   // (a new source: no fitness score until it is aligned)
     ctx->have_gicp_cs = false;   // (the covariances of the source before this one)
+    ctx->have_src_normals = false;   // (and its normals)
     ctx->gicp.active = 0;
     ctx->n_source = n;
     ctx->n_work = 0;
@@ -969,6 +971,9 @@ bool filters_on(const rsreg_icp_params &p)
     return p.use_reciprocal_correspondences != 0 || (p.trim_overlap_ratio > 0.0 && p.trim_overlap_ratio < 1.0);
 }
 
+// the pairs carry explicit weights (d_corr_w): one of the two filters, or a rejector chain, ran behind the search
+bool weights_on(const rsreg_ctx *ctx) { return filters_on(ctx->icp.prm) || ctx->icp.chain.n > 0; }
+
 // point-to-plane ICP (rsreg_estimation): the 32 sums and the 6-unknown solve take the place of the 17 sums and Umeyama
 bool plane_on(const rsreg_icp_params &p) { return p.estimation == RSREG_ESTIMATION_POINT_TO_PLANE_LLS; }
 
@@ -992,6 +997,7 @@ __global__ __launch_bounds__(kBlock) void k_recip_filter(const float4 *tgt, int 
 }
 
 int refuse_unserved(rsreg_ctx *ctx, const rsreg_ctx *grid_of);   // (below, with launch_search)
+int launch_trim(rsreg_ctx *ctx, float ratio, uint32_t *flags, const uint32_t *count_in, uint32_t *count_out);   // (below)
 
 // the optional filters PCL's ICP applies between determineCorrespondences and the transformation estimate:
 // reciprocal correspondences (CorrespondenceEstimation::determineReciprocalCorrespondences) and the trimmed rejector
@@ -1037,43 +1043,141 @@ int apply_filters(rsreg_ctx *ctx)
             RSREG_HIP(ctx, hipGetLastError());
         }
     }
-    if (s.prm.trim_overlap_ratio > 0.0 && s.prm.trim_overlap_ratio < 1.0) {
-        // one key per ORIGINAL record, (d2, caller's index): ties at the cut go to the lowest index, also among the copies of
-        // a distinct point on the merged (Morton-ordered) path -- the library's own 64-bit sort over the bits the keys use
-        uint32_t idx_bits = 1;
-        while (idx_bits < 32 && (ns - 1u) >> idx_bits) ++idx_bits;
-        const unsigned sort_bits = 31u + idx_bits;
-        RSREG_HIP(ctx, ctx->d_keys.reserve((size_t)ns * 8));
-        RSREG_HIP(ctx, ctx->d_keys_alt.reserve((size_t)ns * 8));
-        RSREG_HIP(ctx, ctx->d_vals.reserve((size_t)ns * 4));
-        RSREG_HIP(ctx, ctx->d_vals_alt.reserve((size_t)ns * 4));
-        auto *keys = ctx->d_keys.as<unsigned long long>(), *keys2 = ctx->d_keys_alt.as<unsigned long long>();
-        uint32_t *vals = ctx->d_vals.as<uint32_t>(), *vals2 = ctx->d_vals_alt.as<uint32_t>();
-        const Radix32Plan plan = radix32_plan<unsigned long long>(ns, 0, sort_bits);
-        const size_t off_total = ((size_t)plan.words * 4 + 255) & ~(size_t)255;
-        RSREG_HIP(ctx, ctx->d_tmp.reserve(off_total + 256));
-        uint32_t *total = reinterpret_cast<uint32_t *>(ctx->d_tmp.as<char>() + off_total);
-        RSREG_HIP(ctx, hipMemsetAsync(total, 0, 4, st));
-        // (the keys are written into the pair the sort ends in, so that the result lies in (keys2, vals2); its state is
-        // cleared by the keys kernel on its way)
-        const bool start_in_out = plan.ends_in_first;
-        unsigned long long *k_a = start_in_out ? keys2 : keys, *k_b = start_in_out ? keys : keys2;
-        uint32_t *v_a = start_in_out ? vals2 : vals, *v_b = start_in_out ? vals : vals2;
-        const uint32_t nbs = div_up(ns, kBlock);
-        k_trim_keys<<<nbs, kBlock, 0, st>>>(corr_pos, cw, ctx->d_corr_d2.as<float>(), ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(),
-                                            ctx->d_first.as<uint32_t>(), ns, idx_bits, k_a, v_a, ctx->d_tmp.as<uint32_t>(), plan.words);
-        RSREG_HIP(ctx, hipGetLastError());
-        {
-            bool in_first = false;
-            RSREG_HIP(ctx, radix32_sort_pairs<unsigned long long>(plan, ctx->d_tmp.as<uint32_t>(), k_a, k_b, v_a, v_b, ns, 0, sort_bits, st, &in_first));
-            if ((in_first ? v_a : v_b) != vals2) return fail(ctx, RSREG_ERR_STATE, "osort: the sorted pairs are not where they belong");
-        }
+    if (s.prm.trim_overlap_ratio > 0.0 && s.prm.trim_overlap_ratio < 1.0) return launch_trim(ctx, (float)s.prm.trim_overlap_ratio, nullptr, nullptr, nullptr);
+    return RSREG_OK;
+}
+
+// CorrespondenceRejectorTrimmed over the records in play.  flags == nullptr: rsreg_icp_params.trim_overlap_ratio, the records
+// in play are the first cw[u] copies of every matched point and the cut lowers cw / corr_pos.  flags: the trim as an entry of
+// the rejector chain -- one flag per record, *count_in of them set (known on the device: no counting pass), *count_out = how many the cut leaves.
+int launch_trim(rsreg_ctx *ctx, float ratio, uint32_t *flags, const uint32_t *count_in, uint32_t *count_out)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t ns = (uint32_t)ctx->n_source;
+    uint32_t *cw = ctx->d_corr_w.as<uint32_t>();
+    int *corr_pos = ctx->d_corr_pos.as<int>();
+    // one key per ORIGINAL record, (d2, caller's index): ties at the cut go to the lowest index, also among the copies of
+    // a distinct point on the merged (Morton-ordered) path -- the library's own 64-bit sort over the bits the keys use
+    uint32_t idx_bits = 1;
+    while (idx_bits < 32 && (ns - 1u) >> idx_bits) ++idx_bits;
+    const unsigned sort_bits = 31u + idx_bits;
+    RSREG_HIP(ctx, ctx->d_keys.reserve((size_t)ns * 8));
+    RSREG_HIP(ctx, ctx->d_keys_alt.reserve((size_t)ns * 8));
+    RSREG_HIP(ctx, ctx->d_vals.reserve((size_t)ns * 4));
+    RSREG_HIP(ctx, ctx->d_vals_alt.reserve((size_t)ns * 4));
+    auto *keys = ctx->d_keys.as<unsigned long long>(), *keys2 = ctx->d_keys_alt.as<unsigned long long>();
+    uint32_t *vals = ctx->d_vals.as<uint32_t>(), *vals2 = ctx->d_vals_alt.as<uint32_t>();
+    const Radix32Plan plan = radix32_plan<unsigned long long>(ns, 0, sort_bits);
+    const size_t off_total = ((size_t)plan.words * 4 + 255) & ~(size_t)255;
+    RSREG_HIP(ctx, ctx->d_tmp.reserve(off_total + 256));
+    uint32_t *total = reinterpret_cast<uint32_t *>(ctx->d_tmp.as<char>() + off_total);
+    if (!flags) RSREG_HIP(ctx, hipMemsetAsync(total, 0, 4, st));
+    // (the keys are written into the pair the sort ends in, so that the result lies in (keys2, vals2); its state is
+    // cleared by the keys kernel on its way)
+    const bool start_in_out = plan.ends_in_first;
+    unsigned long long *k_a = start_in_out ? keys2 : keys, *k_b = start_in_out ? keys : keys2;
+    uint32_t *v_a = start_in_out ? vals2 : vals, *v_b = start_in_out ? vals : vals2;
+    const uint32_t nbs = div_up(ns, kBlock);
+    (flags ? k_trim_keys<true> : k_trim_keys<false>)<<<nbs, kBlock, 0, st>>>(corr_pos, flags ? flags : cw, ctx->d_corr_d2.as<float>(), ctx->d_perm.as<uint32_t>(),
+                                                                             ctx->d_uniq_of.as<uint32_t>(), ctx->d_first.as<uint32_t>(), ns, idx_bits, k_a, v_a,
+                                                                             ctx->d_tmp.as<uint32_t>(), plan.words);
+    RSREG_HIP(ctx, hipGetLastError());
+    {
+        bool in_first = false;
+        RSREG_HIP(ctx, radix32_sort_pairs<unsigned long long>(plan, ctx->d_tmp.as<uint32_t>(), k_a, k_b, v_a, v_b, ns, 0, sort_bits, st, &in_first));
+        if ((in_first ? v_a : v_b) != vals2) return fail(ctx, RSREG_ERR_STATE, "osort: the sorted pairs are not where they belong");
+    }
+    if (flags) {
+        k_trim_apply<true><<<nbs, kBlock, 0, st>>>(vals2, count_in, ns, ratio, ctx->d_uniq_of.as<uint32_t>(), ctx->d_first.as<uint32_t>(), flags, corr_pos, count_out);
+    } else {
         k_trim_count<<<nbs, kBlock, 0, st>>>(keys2, ns, idx_bits, total);
         RSREG_HIP(ctx, hipGetLastError());
-        k_trim_apply<<<nbs, kBlock, 0, st>>>(vals2, total, ns, (float)s.prm.trim_overlap_ratio, ctx->d_uniq_of.as<uint32_t>(), ctx->d_first.as<uint32_t>(),
-                                             cw, corr_pos);
+        k_trim_apply<false><<<nbs, kBlock, 0, st>>>(vals2, total, ns, ratio, ctx->d_uniq_of.as<uint32_t>(), ctx->d_first.as<uint32_t>(), cw, corr_pos, nullptr);
+    }
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
+// d_src_nrm_cur = the guess's 3 x 3 block * the source's normals as handed in: what rsreg_icp_begin leaves pending for a chain
+// with the normal test, done by whoever touches the current normals first
+int ensure_normals_restarted(rsreg_ctx *ctx)
+{
+    IcpState &s = ctx->icp;
+    if (!s.normals_restart_pending) return RSREG_OK;
+    s.normals_restart_pending = false;
+    const uint32_t ns = (uint32_t)ctx->n_source;
+    if (!ns) return RSREG_OK;
+    RSREG_HIP(ctx, ctx->d_src_nrm_cur.reserve(((size_t)ns + 1) * sizeof(float4)));
+    k_restart_normals<<<div_up(ns, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_src_nrm.as<float4>(), ns, to_mat34(s.final_t), s.final_t.is_identity() ? 0 : 1,
+                                                                     ctx->d_src_nrm_cur.as<float4>());
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
+// The rejector chain (include/rsreg.h: rsreg_icp_set_rejectors) behind apply_filters, all of it queued on the context's stream:
+// flags per original record <- (corr_pos, cw); every entry rewrites them and leaves its count; the flags are counted back
+// into cw / corr_pos.  Nothing is read back here: the counts and medians wait in d_rej_words for rsreg_icp_rejector_stats.
+int apply_chain(rsreg_ctx *ctx)
+{
+    IcpState &s = ctx->icp;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)ctx->n_work, ns = (uint32_t)ctx->n_source;
+    RSREG_HIP(ctx, ctx->d_rej_words.reserve(kRejWords * 4));
+    uint32_t *words = ctx->d_rej_words.as<uint32_t>();
+    RSREG_HIP(ctx, hipMemsetAsync(words, 0, kRejWords * 4, st));
+    s.chain_stats = true;
+    if (!n || !ns) return RSREG_OK;
+    RSREG_HIP(ctx, ctx->d_rej_flags.reserve((size_t)ns * 4 + 16));
+    uint32_t *flags = ctx->d_rej_flags.as<uint32_t>();
+    uint32_t *cw = ctx->d_corr_w.as<uint32_t>();
+    int *corr_pos = ctx->d_corr_pos.as<int>();
+    const float *d2 = ctx->d_corr_d2.as<float>();
+    const uint32_t *perm = ctx->d_perm.as<uint32_t>(), *uniq_of = ctx->d_uniq_of.as<uint32_t>(), *first = ctx->d_first.as<uint32_t>();
+    const uint32_t nbs = div_up(ns, kBlock);
+    const uint32_t nbg = rej_grid(ns);   // (the kernels that count, and the median's, which re-derive the select's state per workgroup: a bounded grid)
+    uint32_t *cnt = words + kRejCnt;
+    k_rej_flags_init<<<nbg, kBlock, 0, st>>>(corr_pos, cw, uniq_of, first, ns, flags, &cnt[0]);
+    RSREG_HIP(ctx, hipGetLastError());
+    for (int e = 0; e < s.chain.n; ++e) {
+        const rsreg_rejector &r = s.chain.e[e];
+        switch (r.kind) {
+        case RSREG_REJECTOR_MEDIAN_DISTANCE: {
+            uint32_t *hist = words + kRejHist + (uint32_t)e * kRejHistWords;
+            for (uint32_t digit = 0; digit < kRejDigits; ++digit)
+                k_rej_median_hist<<<nbg, kBlock, 0, st>>>(flags, d2, uniq_of, ns, digit, &cnt[e], hist);
+            k_rej_median_apply<<<nbg, kBlock, 0, st>>>(flags, d2, uniq_of, ns, &cnt[e], hist, r.value, words + kRejMed + e, &cnt[e + 1]);
+            break;
+        }
+        case RSREG_REJECTOR_ONE_TO_ONE: {
+            const size_t nt = ctx->grid.n_points;   // (positions of the sorted target: the count, or its bound while a build's counts are pending)
+            RSREG_HIP(ctx, ctx->d_rej_table.reserve((nt + 1) * 8));
+            RSREG_HIP(ctx, hipMemsetAsync(ctx->d_rej_table.ptr, 0xff, (nt + 1) * 8, st));
+            k_rej_o2o_min<<<nbg, kBlock, 0, st>>>(flags, corr_pos, d2, perm, uniq_of, ns, ctx->d_rej_table.as<unsigned long long>());
+            k_rej_o2o_keep<<<nbg, kBlock, 0, st>>>(flags, corr_pos, d2, perm, uniq_of, ns, ctx->d_rej_table.as<unsigned long long>(), &cnt[e + 1]);
+            break;
+        }
+        case RSREG_REJECTOR_SURFACE_NORMAL: {
+            int rcn = ensure_normals_restarted(ctx);
+            if (rcn) return rcn;
+            k_rej_normal<<<nbg, kBlock, 0, st>>>(flags, corr_pos, perm, uniq_of, ns, ctx->d_tgt_sorted.as<float4>(), ctx->d_normals.as<float4>(),
+                                                 ctx->d_src_nrm_cur.as<float4>(), r.value, &cnt[e + 1]);
+            break;
+        }
+        case RSREG_REJECTOR_TRIMMED: {
+            int rct = launch_trim(ctx, (float)r.value, flags, &cnt[e], &cnt[e + 1]);
+            if (rct) return rct;
+            break;
+        }
+        default:
+            return fail(ctx, RSREG_ERR_STATE, "rejector chain: unknown kind");
+        }
         RSREG_HIP(ctx, hipGetLastError());
     }
+    RSREG_HIP(ctx, hipMemsetAsync(cw, 0, (size_t)n * 4, st));
+    k_rej_fold<<<nbs, kBlock, 0, st>>>(flags, uniq_of, ns, cw);
+    RSREG_HIP(ctx, hipGetLastError());
+    k_rej_fold_pos<<<div_up(n, kBlock), kBlock, 0, st>>>(cw, n, corr_pos);
+    RSREG_HIP(ctx, hipGetLastError());
     return RSREG_OK;
 }
 
@@ -1122,8 +1226,9 @@ int launch_search(rsreg_ctx *ctx)
         RSREG_HIP(ctx, hipGetLastError());
         s.n_nn_launches++;
     }
-    if (filters_on(s.prm)) {
+    if (weights_on(ctx)) {
         int rc = apply_filters(ctx);
+        if (!rc && s.chain.n > 0) rc = apply_chain(ctx);
         if (rc) return rc;
     }
     s.have_search = true;
@@ -1160,7 +1265,7 @@ int launch_sums(rsreg_ctx *ctx, double *sums, bool global)
     const uint32_t n = (uint32_t)ctx->n_work;
     {
         ScopedEvents ev(ctx, &ctx->ev_reduce);
-        if (filters_on(ctx->icp.prm))
+        if (weights_on(ctx))
             k_cov_reduce_w<<<reduce_blocks(n), kTile, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_corr_pos.as<int>(),
                                                                       ctx->d_corr_d2.as<float>(), ctx->d_corr_w.as<uint32_t>(),
                                                                       ctx->d_tgt_sorted.as<float4>(), n, ctx->d_partials.as<double>());
@@ -1190,7 +1295,7 @@ int launch_plane_sums(rsreg_ctx *ctx, double *sums)
     {
         ScopedEvents ev(ctx, &ctx->ev_reduce);
         k_plane_reduce<<<nb, kTile, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(),
-                                                      filters_on(ctx->icp.prm) ? ctx->d_corr_w.as<uint32_t>() : nullptr,
+                                                      weights_on(ctx) ? ctx->d_corr_w.as<uint32_t>() : nullptr,
                                                       ctx->d_tgt_sorted.as<float4>(), ctx->d_normals.as<float4>(), n,
                                                       ctx->d_plane_partials.as<double>());
         RSREG_HIP(ctx, hipGetLastError());
@@ -1502,6 +1607,12 @@ int apply_pending_transform(rsreg_ctx *ctx)
         k_transform<<<div_up(n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), n, to_mat34(s.t_inc));
         RSREG_HIP(ctx, hipGetLastError());
     }
+    if (s.chain.has(RSREG_REJECTOR_SURFACE_NORMAL) && ctx->n_source) {   // the source's normals turn with it
+        int rcn = ensure_normals_restarted(ctx);
+        if (rcn) return rcn;
+        k_rotate_normals<<<div_up((uint32_t)ctx->n_source, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_src_nrm_cur.as<float4>(), (uint32_t)ctx->n_source, to_mat34(s.t_inc));
+        RSREG_HIP(ctx, hipGetLastError());
+    }
     s.pending_transform = false;
     return RSREG_OK;
 }
@@ -1811,7 +1922,7 @@ int rsreg_icp_set_source(rsreg_ctx *ctx, const void *points, size_t n, size_t st
 }
 
 // rsreg_icp_begin; need_index: the alignment runs the staged kernels over the index whatever the source's size (plane mode, GICP)
-static int icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, bool need_index)
+static int icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, bool need_index, bool use_chain)
 {
     if (!ctx || !params) return RSREG_ERR_INVALID_ARG;
     if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
@@ -1824,6 +1935,11 @@ static int icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params 
     // the reciprocal search, a different answer from one GPU's (a global trim across ranks is not implemented)
     if (ctx->nranks > 1 && filters_on(*params))
         return fail(ctx, RSREG_ERR_INVALID_ARG, "reciprocal correspondences and the trimmed rejector need the whole source: not with more than one rank");
+    const RejectorChain chain = use_chain ? ctx->rejectors : RejectorChain();
+    if (ctx->nranks > 1 && chain.n > 0)
+        return fail(ctx, RSREG_ERR_INVALID_ARG, "a rejector chain needs the whole source: not with more than one rank");
+    if (chain.has(RSREG_REJECTOR_SURFACE_NORMAL) && !(ctx->have_normals && ctx->have_src_normals))
+        return fail(ctx, RSREG_ERR_STATE, "the surface normal rejector needs rsreg_icp_set_source_normals and rsreg_icp_set_target_normals after the clouds are set");
     if (params->estimation != RSREG_ESTIMATION_SVD && params->estimation != RSREG_ESTIMATION_POINT_TO_PLANE_LLS)
         return fail(ctx, RSREG_ERR_INVALID_ARG, "unknown transformation estimation");
     if (plane_on(*params)) {
@@ -1836,7 +1952,7 @@ static int icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params 
         int rcj = join_source(ctx);
         if (rcj) return rcj;
     }
-    if (ctx->grid.dense == 2 && (ctx->n_work > kScanMaxSource || filters_on(*params) || need_index)) {
+    if (ctx->grid.dense == 2 && (ctx->n_work > kScanMaxSource || filters_on(*params) || chain.n > 0 || need_index)) {
         // the target was set for a handful of queries (scan_target); this alignment needs the index after all
         if (!ctx->scan_raw) return fail(ctx, RSREG_ERR_NO_TARGET, "the target cloud was released before its index was built");
         int rcb = build_grid(ctx, ctx->scan_raw, ctx->n_target_raw, ctx->scan_stride, ctx->gate_built_for);
@@ -1845,6 +1961,8 @@ static int icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params 
     IcpState &s = ctx->icp;
     s = IcpState();
     s.prm = *params;
+    s.chain = chain;
+    s.normals_restart_pending = chain.has(RSREG_REJECTOR_SURFACE_NORMAL);
     // the rings must cover THIS call's gate (it may be smaller than the one built for)
     s.final_t = Mat4f::identity();
     if (guess) std::memcpy(s.final_t.m, guess, sizeof(s.final_t.m));
@@ -1863,7 +1981,7 @@ static int icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params 
 
 int rsreg_icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params)
 {
-    return icp_begin(ctx, guess, params, params && plane_on(*params));
+    return icp_begin(ctx, guess, params, params && plane_on(*params), true);
 }
 
 int rsreg_icp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out)
@@ -1879,7 +1997,11 @@ int rsreg_icp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out)
         RSREG_HIP(ctx, ctx->d_tmp.reserve(n * 8 + 32));
         int *d_idx = ctx->d_tmp.as<int>();
         float *d_d2 = reinterpret_cast<float *>(d_idx + n);
-        if (filters_on(ctx->icp.prm))
+        if (ctx->icp.chain.n > 0)
+            k_export_corr_flags<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(
+                ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), ctx->d_rej_flags.as<uint32_t>(), ctx->d_tgt_sorted.as<float4>(),
+                ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(), (uint32_t)n, d_idx, d_d2);
+        else if (filters_on(ctx->icp.prm))
             k_export_corr_w<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(
                 ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), ctx->d_corr_w.as<uint32_t>(), ctx->d_tgt_sorted.as<float4>(),
                 ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(), ctx->d_first.as<uint32_t>(), (uint32_t)n, d_idx, d_d2);
@@ -1949,6 +2071,97 @@ int rsreg_icp_set_target_normals_device_(rsreg_ctx *ctx, const void *d_normals, 
     if (!ctx || (n && !d_normals) || stride < 12 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     return set_normals_device(ctx, static_cast<const char *>(d_normals), n, stride);
+}
+
+// ---- the rejector chain (include/rsreg.h holds the contract; apply_chain above runs it)
+int rsreg_icp_set_rejectors(rsreg_ctx *ctx, const rsreg_rejector *chain, int32_t n)
+{
+    if (!ctx || n < 0 || (n && !chain)) return RSREG_ERR_INVALID_ARG;
+    if (n > kRejMax) return fail(ctx, RSREG_ERR_INVALID_ARG, "a rejector chain has at most 8 entries");
+    RejectorChain c;
+    for (int i = 0; i < n; ++i) {
+        const double v = chain[i].value;
+        switch (chain[i].kind) {
+        case RSREG_REJECTOR_MEDIAN_DISTANCE:
+            if (!(v >= 0.0)) return fail(ctx, RSREG_ERR_INVALID_ARG, "median distance rejector: the factor must not be NaN or negative");
+            break;
+        case RSREG_REJECTOR_ONE_TO_ONE:
+            break;
+        case RSREG_REJECTOR_SURFACE_NORMAL:
+            break;
+        case RSREG_REJECTOR_TRIMMED:
+            if (!(v > 0.0 && v < 1.0)) return fail(ctx, RSREG_ERR_INVALID_ARG, "trimmed rejector: the overlap ratio must lie inside (0, 1)");
+            break;
+        default:
+            return fail(ctx, RSREG_ERR_INVALID_ARG, "unknown rejector kind");
+        }
+        c.e[i] = chain[i];
+    }
+    c.n = n;
+    ctx->rejectors = c;
+    return RSREG_OK;
+}
+
+int rsreg_icp_rejector_stats(rsreg_ctx *ctx, rsreg_rejector_stat *stats, int32_t capacity, int32_t *n_out)
+{
+    if (!ctx || capacity < 0 || (capacity && !stats)) return RSREG_ERR_INVALID_ARG;
+    const IcpState &s = ctx->icp;
+    if (!s.chain_stats) return fail(ctx, RSREG_ERR_STATE, "no search with a rejector chain yet");
+    if (n_out) *n_out = s.chain.n;
+    uint32_t w[kRejHist];
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    RSREG_HIP(ctx, hipMemcpyAsync(w, ctx->d_rej_words.ptr, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int e = 0; e < s.chain.n && e < capacity; ++e) {
+        float med;
+        std::memcpy(&med, &w[kRejMed + e], 4);
+        stats[e].n_in = w[kRejCnt + e];
+        stats[e].n_out = w[kRejCnt + e + 1];
+        stats[e].median_distance = s.chain.e[e].kind == RSREG_REJECTOR_MEDIAN_DISTANCE ? (double)med : 0.0;
+        stats[e].reserved0 = 0.0;
+    }
+    return RSREG_OK;
+}
+
+// the source's normals from records already in HBM (three floats at d_rec + i * stride), on the context's stream
+static int set_source_normals_device(rsreg_ctx *ctx, const char *d_rec, size_t n, size_t stride)
+{
+    if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
+    if (n != ctx->n_source) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per source record: the counts differ");
+    RSREG_HIP(ctx, ctx->d_src_nrm.reserve((n + 1) * sizeof(float4)));
+    if (n) {
+        k_pack_normals<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(d_rec, stride, (uint32_t)n, ctx->d_src_nrm.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    ctx->have_src_normals = true;
+    return RSREG_OK;
+}
+
+int rsreg_icp_set_source_normals(rsreg_ctx *ctx, const void *normals, size_t n, size_t stride)
+{
+    if (!ctx || (n && !normals) || stride < 12) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
+    if (n != ctx->n_source) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per source record: the counts differ");
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    // staged like the target's normals: packed into pinned memory of its own, over the link on the upload stream, the main stream behind it
+    RSREG_HIP(ctx, ctx->h2d.ensure());
+    RSREG_HIP(ctx, ctx->ev_src_nrm.ensure());
+    RSREG_HIP(ctx, ctx->ev_src_nrm_packed.ensure());
+    RSREG_HIP(ctx, hipStreamWaitEvent(ctx->h2d.stream, ctx->ev_src_nrm_packed, 0));   // (normals set before may still be read from d_src_nrm_raw)
+    int rc = upload_packed(ctx, ctx->h_src_nrm, ctx->ev_src_nrm, ctx->d_src_nrm_raw, normals, n, stride, ctx->stream, nullptr, nullptr);
+    if (rc) return rc;
+    rc = set_source_normals_device(ctx, ctx->d_src_nrm_raw.as<char>(), n, 12);
+    if (rc) return rc;
+    RSREG_HIP(ctx, hipEventRecord(ctx->ev_src_nrm_packed, ctx->stream));
+    return RSREG_OK;
+}
+
+// (internal, cloud.hip: rsreg_icp_set_source_normals_cloud) normals already in HBM
+int rsreg_icp_set_source_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride)
+{
+    if (!ctx || (n && !d_normals) || stride < 12 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    return set_source_normals_device(ctx, static_cast<const char *>(d_normals), n, stride);
 }
 
 int rsreg_icp_plane_sums(rsreg_ctx *ctx, double sums[RSREG_NUM_PLANE_SUMS])
@@ -2181,7 +2394,7 @@ int icp_align(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params
     int done = 0;
     double sums[RSREG_NUM_PLANE_SUMS];   // (the 17 of a point-to-point iteration, or the 32 of a point-to-plane one)
     const bool plane = plane_on(*params);     // point-to-plane: staged, with its own sums and solve
-    const bool filtered = filters_on(*params) || plane;   // the optional correspondence filters run between the staged kernels
+    const bool filtered = weights_on(ctx) || plane;   // the optional correspondence filters and the rejector chain run between the staged kernels
     const bool scan = ctx->grid.dense == 2;   // no index: the staged kernels (search over the whole target, sums)
     const bool fused = !filtered && !scan && (params->pipeline_mode == RSREG_PIPELINE_FUSED || params->pipeline_mode == RSREG_PIPELINE_DEVICE_LOOP);
     if (!filtered && !scan && params->pipeline_mode == RSREG_PIPELINE_DEVICE_LOOP && params->criteria_mode == RSREG_CRITERIA_FIXED) {
@@ -2280,7 +2493,7 @@ int rsreg_gicp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params
     ip.criteria_mode = RSREG_CRITERIA_FIXED;
     ip.pipeline_mode = RSREG_PIPELINE_STAGED;
     ip.max_correspondence_distance = params->max_correspondence_distance;
-    int rc = icp_begin(ctx, guess, &ip, true);
+    int rc = icp_begin(ctx, guess, &ip, true, false);   // (PCL's GICP loop consults no rejector)
     if (rc) return rc;
     ctx->gicp = GicpState();
     ctx->gicp.prm = *params;

@@ -1367,7 +1367,10 @@ __global__ __launch_bounds__(kBlock) void k_recip_points(const float4 *cur, cons
 // 0x7fffffff, above every distance.  The copies of u are ordered by caller's index and share d2, so those the cut keeps
 // are the first of u's copies in play: what k_export_corr_w expects of cw[u].
 // (sort_scratch: the state of the sort that follows, cleared on the way -- osort.hpp)
+// kFlags (the trim as an entry of the rejector chain, rejector_kernels.hpp): cw holds one in-play flag per RECORD j instead,
+// and the cut clears the flags of the records it drops.
 constexpr uint32_t kTrimOut = 0x7fffffffu;
+template <bool kFlags>
 __global__ __launch_bounds__(kBlock) void k_trim_keys(const int *corr_pos, const uint32_t *cw, const float *corr_d2, const uint32_t *perm,
                                                       const uint32_t *uniq_of, const uint32_t *first, uint32_t n_source, uint32_t idx_bits,
                                                       unsigned long long *keys, uint32_t *vals, uint32_t *sort_scratch, uint32_t sort_scratch_words)
@@ -1376,7 +1379,7 @@ __global__ __launch_bounds__(kBlock) void k_trim_keys(const int *corr_pos, const
     if (sort_scratch) radix32_clear(sort_scratch, sort_scratch_words, j, gridDim.x * blockDim.x);
     if (j >= n_source) return;
     const uint32_t u = uniq_of[j];
-    const bool in_play = corr_pos[u] >= 0 && j - first[u] < cw[u];
+    const bool in_play = kFlags ? cw[j] != 0u : (corr_pos[u] >= 0 && j - first[u] < cw[u]);
     const uint32_t hi = in_play ? __float_as_uint(corr_d2[u]) : kTrimOut;   // (squared distances are >= 0: their bits order like the values)
     keys[j] = ((unsigned long long)hi << idx_bits) | perm[j];
     vals[j] = j;
@@ -1394,16 +1397,22 @@ __global__ __launch_bounds__(kBlock) void k_trim_count(const unsigned long long 
 
 // of the records in order (d2, caller's index) the first floor(ratio * total) keep their match: every record the cut drops
 // lowers its distinct point's cw to its copy number (the dropped copies of u are the last of those in play), and the point
-// loses its match when its first copy is dropped
+// loses its match when its first copy is dropped.  kFlags: the record's flag is cleared instead, and *kept_out = how many stay.
+template <bool kFlags>
 __global__ __launch_bounds__(kBlock) void k_trim_apply(const uint32_t *order, const uint32_t *total_p, uint32_t n_source, float ratio,
-                                                       const uint32_t *uniq_of, const uint32_t *first, uint32_t *cw, int *corr_pos)
+                                                       const uint32_t *uniq_of, const uint32_t *first, uint32_t *cw, int *corr_pos, uint32_t *kept_out)
 {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_source) return;
     const uint32_t total = *total_p;
     const uint32_t k = (uint32_t)floorf(ratio * (float)total);   // (int)(floor(overlap_ratio_ * float(size))), in float like PCL
+    if (kFlags && r == 0) *kept_out = k >= total ? total : k;
     if (k >= total || r < k || r >= total) return;                // ("number_valid >= size": nothing to trim)
     const uint32_t j = order[r];
+    if (kFlags) {
+        cw[j] = 0u;
+        return;
+    }
     const uint32_t u = uniq_of[j];
     const uint32_t copy = j - first[u];
     atomicMin(&cw[u], copy);

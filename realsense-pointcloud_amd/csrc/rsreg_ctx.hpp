@@ -279,8 +279,23 @@ struct DepthScratch {
     Event ev_up;         // behind the copy: the staging buffer is free again
 };
 
+// An ordered chain of correspondence rejectors (include/rsreg.h: rsreg_icp_set_rejectors); n == 0: none
+struct RejectorChain {
+    int n = 0;
+    rsreg_rejector e[8];
+    bool has(int kind) const
+    {
+        for (int i = 0; i < n; ++i)
+            if (e[i].kind == kind) return true;
+        return false;
+    }
+};
+
 struct IcpState {
     rsreg_icp_params prm;
+    RejectorChain chain;             // the context's chain as rsreg_icp_begin found it (GICP: none)
+    bool chain_stats = false;        // d_rej_words holds the counts of this alignment's last search
+    bool normals_restart_pending = false;   // d_src_nrm_cur = guess * d_src_nrm not done yet (a chain with the normal test)
     Mat4f final_t, t_inc;
     int iterations = 0, state = 0, converged = 0, similar = 0, active = 0;
     double prev_mse = 0, cur_mse = 0;
@@ -409,6 +424,19 @@ struct rsreg_ctx {
     rsreg::DevBuf d_corr_w;       // uint32 per distinct source point: how many of its copies keep their match
     rsreg::DevBuf d_recip_pts;    // float4 per ORIGINAL source point: the current source in the caller's order
     rsreg_ctx *recip = nullptr;   // child context holding the index over the current source (reciprocal search)
+    // the rejector chain (rsreg_icp_set_rejectors, rejector_kernels.hpp): it stays until replaced; an alignment works on the
+    // copy rsreg_icp_begin took (icp.chain)
+    rsreg::RejectorChain rejectors;
+    rsreg::DevBuf d_rej_flags;    // uint32 per ORIGINAL source record (sorted position): in play behind the chain so far
+    rsreg::DevBuf d_rej_words;    // kRejWords uint32: the counts in front of and behind every entry, the medians, the select's digit counts
+    rsreg::DevBuf d_rej_table;    // one-to-one: one (d2, caller's index) key per position of the sorted target
+    // the source's normals, float4 {nx, ny, nz, 0} per source RECORD in the caller's order: as handed in, and as they stand
+    // now (turned by the guess and every increment); dropped by every rsreg_icp_set_source*
+    bool have_src_normals = false;
+    rsreg::DevBuf d_src_nrm, d_src_nrm_cur;
+    rsreg::DevBuf d_src_nrm_raw;          // packed normals of a host buffer as they came over the link (n x float3) ...
+    rsreg::PinnedBuf h_src_nrm;           // ... their staging buffer, on the upload stream like the target's normals ...
+    rsreg::Event ev_src_nrm, ev_src_nrm_packed;   // ... the event behind its last copy, and: the main stream has read d_src_nrm_raw
     rsreg::PinnedBuf h_sums;      // pinned double[64]
     // next_*: the box of the cloud about to be set, when its handle knows it (consumed by build_grid / load_source_queue);
     // last_*: what the last index build / source load started from (valid: computed or taken over)

@@ -28,6 +28,8 @@ IIN_BORDER_IGNORE, IIN_BORDER_MIRROR = 0, 1              # rsreg_iin_border_poli
 DISTORTION_NONE, DISTORTION_MODIFIED_BROWN_CONRADY, DISTORTION_INVERSE_BROWN_CONRADY, DISTORTION_FTHETA, DISTORTION_BROWN_CONRADY, DISTORTION_KANNALA_BRANDT4 = range(6)
 RSREG_ERR_INVALID_ARG, RSREG_ERR_STATE = -1, -9   # include/rsreg.h: rsreg_status
 SCIA_TRUNCATED, SCIA_HUBER = 0, 1                 # include/rsreg.h: rsreg_scia_error_function
+REJECTOR_MEDIAN_DISTANCE, REJECTOR_ONE_TO_ONE, REJECTOR_SURFACE_NORMAL, REJECTOR_TRIMMED = 1, 2, 3, 4   # include/rsreg.h: rsreg_rejector_kind
+MAX_REJECTORS = 8                                 # include/rsreg.h: RSREG_MAX_REJECTORS
 UNIQUE_ID_BYTES = 128
 
 # every symbol include/rsreg.h declares (checked by tests/test_abi.py)
@@ -59,6 +61,7 @@ EXPORTS = [
     "rsreg_cloud_radius_count_surface", "rsreg_cloud_normals_radius_surface", "rsreg_cloud_fpfh_radius_surface", "rsreg_cloud_spfh_radius_surface",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
+    "rsreg_icp_set_rejectors", "rsreg_icp_rejector_stats", "rsreg_icp_set_source_normals", "rsreg_icp_set_source_normals_cloud",
     "rsreg_gicp_params_default", "rsreg_cloud_gicp_covariances", "rsreg_gicp_set_source_covariances", "rsreg_gicp_set_target_covariances",
     "rsreg_gicp_set_source_covariances_cloud", "rsreg_gicp_set_target_covariances_cloud", "rsreg_gicp_begin", "rsreg_gicp_search",
     "rsreg_gicp_sums", "rsreg_gicp_step_from_sums", "rsreg_gicp_update", "rsreg_gicp_end", "rsreg_gicp_align", "rsreg_gicp_align_cloud",
@@ -99,6 +102,14 @@ class IcpResult(C.Structure):
         ("ms_nn", C.c_double), ("ms_reduce", C.c_double), ("ms_transform", C.c_double),
         ("n_nn_launches", C.c_int32), ("n_scheduled_launches", C.c_int32), ("ms_allreduce", C.c_double),
     ]
+
+
+class Rejector(C.Structure):   # rsreg_rejector
+    _fields_ = [("kind", C.c_int32), ("reserved0", C.c_int32), ("value", C.c_double)]
+
+
+class RejectorStat(C.Structure):   # rsreg_rejector_stat
+    _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("median_distance", C.c_double), ("reserved0", C.c_double)]
 
 
 class GicpParams(C.Structure):   # rsreg_gicp_params
@@ -332,6 +343,10 @@ def lib():
     L.rsreg_icp_update_plane.argtypes = [vp, vp, vp, C.POINTER(i32)]
     L.rsreg_icp_plane_sums_last.argtypes = [vp, vp]
     L.rsreg_plane_solve_from_sums.argtypes = [vp, vp, C.POINTER(i32)]
+    L.rsreg_icp_set_rejectors.argtypes = [vp, vp, C.c_int32]
+    L.rsreg_icp_rejector_stats.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32)]
+    L.rsreg_icp_set_source_normals.argtypes = [vp, vp, sz, sz]
+    L.rsreg_icp_set_source_normals_cloud.argtypes = [vp, vp]
     L.rsreg_gicp_params_default.argtypes = [C.POINTER(GicpParams)]
     L.rsreg_gicp_params_default.restype = None
     L.rsreg_cloud_gicp_covariances.argtypes = [vp, vp, i32, dbl, vp]
