@@ -865,13 +865,13 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
             sched_regrown(ctx->sched, sched_capacity(ctx->d_sched.cap));
         }
     }
-    RSREG_HIP(ctx, ctx->d_sums.reserve(64 * 8));
+    RSREG_HIP(ctx, ctx->d_sums.reserve(kSumsBytes));
     RSREG_HIP(ctx, ctx->h_sums.reserve(kSumsBytes));
     RSREG_HIP(ctx, ctx->d_smisc.reserve(kSmiscWords * sizeof(uint32_t)));
     RSREG_HIP(ctx, ctx->h_smisc.reserve(kHsWords * sizeof(uint32_t)));
     ctx->icp_fit_ok = false;   // (a new source: no fitness score until it is aligned)
     ctx->have_gicp_cs = false;   // (the covariances of the source before this one)
-    ctx->have_src_normals = false;   // (and its normals)
+    ctx->src_nrm.have = false;   // (and its normals)
     ctx->gicp.active = 0;
     ctx->n_source = n;
     ctx->n_work = 0;
@@ -996,55 +996,12 @@ __global__ __launch_bounds__(kBlock) void k_recip_filter(const float4 *tgt, int 
     if (!ok) corr_pos[u] = -1;
 }
 
-int refuse_unserved(rsreg_ctx *ctx, const rsreg_ctx *grid_of);   // (below, with launch_search)
-int launch_trim(rsreg_ctx *ctx, float ratio, uint32_t *flags, const uint32_t *count_in, uint32_t *count_out);   // (below)
-
-// the optional filters PCL's ICP applies between determineCorrespondences and the transformation estimate:
-// reciprocal correspondences (CorrespondenceEstimation::determineReciprocalCorrespondences) and the trimmed rejector
-int apply_filters(rsreg_ctx *ctx)
+// Every correspondence search starts with this: a target whose grid is outside the served range (build_grid: unserved) is refused
+// here, before a launch, not answered wrongly.  (One host comparison per launch; the kernels are the ones of every other grid.)
+int refuse_unserved(rsreg_ctx *ctx, const rsreg_ctx *grid_of)
 {
-    IcpState &s = ctx->icp;
-    hipStream_t st = ctx->stream;
-    const uint32_t n = (uint32_t)ctx->n_work, ns = (uint32_t)ctx->n_source;
-    if (!n) return RSREG_OK;
-    RSREG_HIP(ctx, ctx->d_corr_w.reserve((size_t)n * 4 + 16));
-    uint32_t *cw = ctx->d_corr_w.as<uint32_t>();
-    int *corr_pos = ctx->d_corr_pos.as<int>();
-    const uint32_t nb = div_up(n, kBlock);
-    k_corr_weights<<<nb, kBlock, 0, st>>>(corr_pos, ctx->d_cur.as<float4>(), n, cw);
-    RSREG_HIP(ctx, hipGetLastError());
-    if (s.prm.use_reciprocal_correspondences) {
-        // index the CURRENT source (it moves every iteration; PCL rebuilds its reciprocal kd-tree too), in the caller's order
-        if (!ctx->recip) {
-            int rc = rsreg_ctx_create(ctx->device, ctx->stream, &ctx->recip);
-            if (rc) return fail(ctx, rc, "context of the reciprocal index");
-        }
-        RSREG_HIP(ctx, ctx->d_recip_pts.reserve(((size_t)ns + 1) * sizeof(float4)));
-        k_recip_points<<<div_up(ns, kBlock), kBlock, 0, st>>>(ctx->d_cur.as<float4>(), ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(), ns,
-                                                           ctx->d_recip_pts.as<float4>());
-        RSREG_HIP(ctx, hipGetLastError());
-        rsreg_ctx *c = ctx->recip;
-        int rc = build_grid(c, ctx->d_recip_pts.as<char>(), ns, sizeof(float4), s.prm.max_correspondence_distance, 1.0);
-        if (rc) {
-            std::string why;
-            {
-                std::lock_guard<std::mutex> lk(c->error_mutex);
-                why = c->last_error;
-            }
-            return fail(ctx, rc, why.c_str());
-        }
-        if (int rcu = refuse_unserved(ctx, c)) return rcu;   // (the index over the source: the same range)
-        if (c->grid.n_points) {   // (a bound while the child's counting build has not been waited for: never 0 for a cloud with a finite point)
-            const DenseDev gd = c->grid.dense ? dense_dev(c, s.prm.max_correspondence_distance) : DenseDev{};
-            const GridDev gh = grid_dev(c, s.prm.max_correspondence_distance);
-            auto kern = c->grid.dense ? k_recip_filter<true> : k_recip_filter<false>;
-            kern<<<nb, kBlock, 0, st>>>(ctx->d_tgt_sorted.as<float4>(), corr_pos, cw, n, gd, gh, c->d_tgt_sorted.as<float4>(),
-                                        ctx->d_perm.as<uint32_t>(), ctx->d_first.as<uint32_t>());
-            RSREG_HIP(ctx, hipGetLastError());
-        }
-    }
-    if (s.prm.trim_overlap_ratio > 0.0 && s.prm.trim_overlap_ratio < 1.0) return launch_trim(ctx, (float)s.prm.trim_overlap_ratio, nullptr, nullptr, nullptr);
-    return RSREG_OK;
+    if (!grid_of->grid.unserved) return RSREG_OK;
+    return fail(ctx, RSREG_ERR_INVALID_ARG, "target outside the range the ICP search serves: cell above 2^60 m or box wider than a float (rsreg.h: rsreg_icp_set_target)");
 }
 
 // CorrespondenceRejectorTrimmed over the records in play.  flags == nullptr: rsreg_icp_params.trim_overlap_ratio, the records
@@ -1098,6 +1055,54 @@ int launch_trim(rsreg_ctx *ctx, float ratio, uint32_t *flags, const uint32_t *co
     return RSREG_OK;
 }
 
+// the optional filters PCL's ICP applies between determineCorrespondences and the transformation estimate:
+// reciprocal correspondences (CorrespondenceEstimation::determineReciprocalCorrespondences) and the trimmed rejector
+int apply_filters(rsreg_ctx *ctx)
+{
+    IcpState &s = ctx->icp;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)ctx->n_work, ns = (uint32_t)ctx->n_source;
+    if (!n) return RSREG_OK;
+    RSREG_HIP(ctx, ctx->d_corr_w.reserve((size_t)n * 4 + 16));
+    uint32_t *cw = ctx->d_corr_w.as<uint32_t>();
+    int *corr_pos = ctx->d_corr_pos.as<int>();
+    const uint32_t nb = div_up(n, kBlock);
+    k_corr_weights<<<nb, kBlock, 0, st>>>(corr_pos, ctx->d_cur.as<float4>(), n, cw);
+    RSREG_HIP(ctx, hipGetLastError());
+    if (s.prm.use_reciprocal_correspondences) {
+        // index the CURRENT source (it moves every iteration; PCL rebuilds its reciprocal kd-tree too), in the caller's order
+        if (!ctx->recip) {
+            int rc = rsreg_ctx_create(ctx->device, ctx->stream, &ctx->recip);
+            if (rc) return fail(ctx, rc, "context of the reciprocal index");
+        }
+        RSREG_HIP(ctx, ctx->d_recip_pts.reserve(((size_t)ns + 1) * sizeof(float4)));
+        k_recip_points<<<div_up(ns, kBlock), kBlock, 0, st>>>(ctx->d_cur.as<float4>(), ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(), ns,
+                                                           ctx->d_recip_pts.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+        rsreg_ctx *c = ctx->recip;
+        int rc = build_grid(c, ctx->d_recip_pts.as<char>(), ns, sizeof(float4), s.prm.max_correspondence_distance, 1.0);
+        if (rc) {
+            std::string why;
+            {
+                std::lock_guard<std::mutex> lk(c->error_mutex);
+                why = c->last_error;
+            }
+            return fail(ctx, rc, why.c_str());
+        }
+        if (int rcu = refuse_unserved(ctx, c)) return rcu;   // (the index over the source: the same range)
+        if (c->grid.n_points) {   // (a bound while the child's counting build has not been waited for: never 0 for a cloud with a finite point)
+            const DenseDev gd = c->grid.dense ? dense_dev(c, s.prm.max_correspondence_distance) : DenseDev{};
+            const GridDev gh = grid_dev(c, s.prm.max_correspondence_distance);
+            auto kern = c->grid.dense ? k_recip_filter<true> : k_recip_filter<false>;
+            kern<<<nb, kBlock, 0, st>>>(ctx->d_tgt_sorted.as<float4>(), corr_pos, cw, n, gd, gh, c->d_tgt_sorted.as<float4>(),
+                                        ctx->d_perm.as<uint32_t>(), ctx->d_first.as<uint32_t>());
+            RSREG_HIP(ctx, hipGetLastError());
+        }
+    }
+    if (s.prm.trim_overlap_ratio > 0.0 && s.prm.trim_overlap_ratio < 1.0) return launch_trim(ctx, (float)s.prm.trim_overlap_ratio, nullptr, nullptr, nullptr);
+    return RSREG_OK;
+}
+
 // d_src_nrm_cur = the guess's 3 x 3 block * the source's normals as handed in: what rsreg_icp_begin leaves pending for a chain
 // with the normal test, done by whoever touches the current normals first
 int ensure_normals_restarted(rsreg_ctx *ctx)
@@ -1108,7 +1113,7 @@ int ensure_normals_restarted(rsreg_ctx *ctx)
     const uint32_t ns = (uint32_t)ctx->n_source;
     if (!ns) return RSREG_OK;
     RSREG_HIP(ctx, ctx->d_src_nrm_cur.reserve(((size_t)ns + 1) * sizeof(float4)));
-    k_restart_normals<<<div_up(ns, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_src_nrm.as<float4>(), ns, to_mat34(s.final_t), s.final_t.is_identity() ? 0 : 1,
+    k_restart_normals<<<div_up(ns, kBlock), kBlock, 0, ctx->stream>>>(ctx->src_nrm.d.as<float4>(), ns, to_mat34(s.final_t), s.final_t.is_identity() ? 0 : 1,
                                                                      ctx->d_src_nrm_cur.as<float4>());
     RSREG_HIP(ctx, hipGetLastError());
     return RSREG_OK;
@@ -1159,7 +1164,7 @@ int apply_chain(rsreg_ctx *ctx)
         case RSREG_REJECTOR_SURFACE_NORMAL: {
             int rcn = ensure_normals_restarted(ctx);
             if (rcn) return rcn;
-            k_rej_normal<<<nbg, kBlock, 0, st>>>(flags, corr_pos, perm, uniq_of, ns, ctx->d_tgt_sorted.as<float4>(), ctx->d_normals.as<float4>(),
+            k_rej_normal<<<nbg, kBlock, 0, st>>>(flags, corr_pos, perm, uniq_of, ns, ctx->d_tgt_sorted.as<float4>(), ctx->tgt_nrm.d.as<float4>(),
                                                  ctx->d_src_nrm_cur.as<float4>(), r.value, &cnt[e + 1]);
             break;
         }
@@ -1179,14 +1184,6 @@ int apply_chain(rsreg_ctx *ctx)
     k_rej_fold_pos<<<div_up(n, kBlock), kBlock, 0, st>>>(cw, n, corr_pos);
     RSREG_HIP(ctx, hipGetLastError());
     return RSREG_OK;
-}
-
-// Every correspondence search starts with this: a target whose grid is outside the served range (build_grid: unserved) is refused
-// here, before a launch, not answered wrongly.  (One host comparison per launch; the kernels are the ones of every other grid.)
-int refuse_unserved(rsreg_ctx *ctx, const rsreg_ctx *grid_of)
-{
-    if (!grid_of->grid.unserved) return RSREG_OK;
-    return fail(ctx, RSREG_ERR_INVALID_ARG, "target outside the range the ICP search serves: cell above 2^60 m or box wider than a float (rsreg.h: rsreg_icp_set_target)");
 }
 
 int launch_search(rsreg_ctx *ctx)
@@ -1235,11 +1232,24 @@ int launch_search(rsreg_ctx *ctx)
     return RSREG_OK;
 }
 
-// where k_final_reduce leaves the 17 sums the host is about to read: without a communicator straight in the pinned
+// ---- the tail that brings an iteration's sums to the host, in two halves (the staged callers close their ev_reduce bracket
+// between them): queue_final_reduce, then fetch_sums.  `count`: the 17 sums of a point-to-point iteration, the 32 of a
+// point-to-plane or of a GICP one.
+// where k_final_reduce leaves the sums the host is about to read: without a communicator straight in the pinned
 // host buffer (no copy to queue behind the kernel), otherwise in HBM (the all-reduce works there)
 double *host_sums_target(rsreg_ctx *ctx) { return ctx->comm ? ctx->d_sums.as<double>() : ctx->h_sums.as<double>(); }
 
-int fetch_sums(rsreg_ctx *ctx, double *sums, bool global)
+// one workgroup per sum over the `nb` workgroups' partials
+int queue_final_reduce(rsreg_ctx *ctx, const double *partials, uint32_t nb, int count)
+{
+    k_final_reduce<<<count, kReduceBlock, 0, ctx->stream>>>(partials, nb, host_sums_target(ctx));
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
+// (all-reduce,) copy where a communicator exists, wait, sums[0 .. count).  global: the sums of all ranks -- the 17 only: the
+// alignments with 32 sums refuse more than one rank (icp_begin, rsreg_gicp_begin) and never ask
+int fetch_sums(rsreg_ctx *ctx, double *sums, int count, bool global)
 {
     if (global && ctx->comm) {   // also on a one-rank communicator: same calls, same stream order
         ScopedEvents ev(ctx, &ctx->ev_allreduce);
@@ -1247,11 +1257,11 @@ int fetch_sums(rsreg_ctx *ctx, double *sums, bool global)
         if (rc) return rc;
     }
     double *h = ctx->h_sums.as<double>();
-    if (ctx->comm) RSREG_HIP(ctx, hipMemcpyAsync(h, ctx->d_sums.ptr, RSREG_NUM_SUMS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->comm) RSREG_HIP(ctx, hipMemcpyAsync(h, ctx->d_sums.ptr, (size_t)count * 8, hipMemcpyDeviceToHost, ctx->stream));
     RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->icp.idle_after_sums = true;
     (void)target_counts(ctx, false);
-    std::memcpy(sums, h, RSREG_NUM_SUMS * 8);
+    std::memcpy(sums, h, (size_t)count * 8);
     return RSREG_OK;
 }
 
@@ -1274,10 +1284,10 @@ int launch_sums(rsreg_ctx *ctx, double *sums, bool global)
                                                                     ctx->d_corr_d2.as<float>(), ctx->d_tgt_sorted.as<float4>(), n,
                                                                     ctx->d_partials.as<double>());
         RSREG_HIP(ctx, hipGetLastError());
-        k_final_reduce<<<RSREG_NUM_SUMS, kReduceBlock, 0, ctx->stream>>>(ctx->d_partials.as<double>(), reduce_blocks(n), host_sums_target(ctx));
-        RSREG_HIP(ctx, hipGetLastError());
+        int rc = queue_final_reduce(ctx, ctx->d_partials.as<double>(), reduce_blocks(n), RSREG_NUM_SUMS);
+        if (rc) return rc;
     }
-    return fetch_sums(ctx, sums, global);
+    return fetch_sums(ctx, sums, RSREG_NUM_SUMS, global);
 }
 
 // The 32 sums of a point-to-plane iteration (include/rsreg.h: RSREG_NUM_PLANE_SUMS) over the search's pairs: k_plane_reduce in
@@ -1296,19 +1306,13 @@ int launch_plane_sums(rsreg_ctx *ctx, double *sums)
         ScopedEvents ev(ctx, &ctx->ev_reduce);
         k_plane_reduce<<<nb, kTile, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(),
                                                       weights_on(ctx) ? ctx->d_corr_w.as<uint32_t>() : nullptr,
-                                                      ctx->d_tgt_sorted.as<float4>(), ctx->d_normals.as<float4>(), n,
+                                                      ctx->d_tgt_sorted.as<float4>(), ctx->tgt_nrm.d.as<float4>(), n,
                                                       ctx->d_plane_partials.as<double>());
         RSREG_HIP(ctx, hipGetLastError());
-        k_final_reduce<<<RSREG_NUM_PLANE_SUMS, kReduceBlock, 0, ctx->stream>>>(ctx->d_plane_partials.as<double>(), nb, host_sums_target(ctx));
-        RSREG_HIP(ctx, hipGetLastError());
+        int rc = queue_final_reduce(ctx, ctx->d_plane_partials.as<double>(), nb, RSREG_NUM_PLANE_SUMS);
+        if (rc) return rc;
     }
-    double *h = ctx->h_sums.as<double>();
-    if (ctx->comm) RSREG_HIP(ctx, hipMemcpyAsync(h, ctx->d_sums.ptr, RSREG_NUM_PLANE_SUMS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->icp.idle_after_sums = true;
-    (void)target_counts(ctx, false);
-    std::memcpy(sums, h, RSREG_NUM_PLANE_SUMS * 8);
-    return RSREG_OK;
+    return fetch_sums(ctx, sums, RSREG_NUM_PLANE_SUMS, false);
 }
 
 // ---- tile schedule of the fused dense kernel (tile_sched.hpp: what it is for, its layout, state and launch rule) ----------
@@ -1526,27 +1530,29 @@ int launch_fused(rsreg_ctx *ctx, double *sums, bool want_corr, bool device_loop 
     // (no events of their own for what follows: in the fused pipelines ms_reduce is the time
     // between consecutive search kernels, read off the search kernels' events)
     s.have_search = want_corr;
-    if (device_loop && !ctx->comm) {   // final reduce + solve in one launch
+    if (!device_loop) {   // the host loop: the sums come home
+        int rc = queue_final_reduce(ctx, ctx->d_partials.as<double>(), reduce_blocks(n), RSREG_NUM_SUMS);
+        if (rc) return rc;
+        return fetch_sums(ctx, sums, RSREG_NUM_SUMS, true);
+    }
+    // the device loop: the sums stay on the device
+    if (!ctx->comm) {   // final reduce + solve in one launch
         auto *st = ctx->d_icp_state.as<IcpDevState>();
         k_final_reduce_solve<<<RSREG_NUM_SUMS, kReduceBlock, 0, ctx->stream>>>(ctx->d_partials.as<double>(), reduce_blocks(n), ctx->d_sums.as<double>(),
                                                                           st, reinterpret_cast<unsigned int *>(st + 1));
         RSREG_HIP(ctx, hipGetLastError());
         return RSREG_OK;
     }
-    k_final_reduce<<<RSREG_NUM_SUMS, kReduceBlock, 0, ctx->stream>>>(ctx->d_partials.as<double>(), reduce_blocks(n),
-                                                               device_loop ? ctx->d_sums.as<double>() : host_sums_target(ctx));
+    k_final_reduce<<<RSREG_NUM_SUMS, kReduceBlock, 0, ctx->stream>>>(ctx->d_partials.as<double>(), reduce_blocks(n), ctx->d_sums.as<double>());
     RSREG_HIP(ctx, hipGetLastError());
-    if (device_loop) {   // the sums stay on the device: (all-reduce,) solve, next pass
-        if (ctx->comm) {
-            ScopedEvents ev(ctx, &ctx->ev_allreduce);
-            int rc = rsreg_comm_allreduce_device_(ctx, ctx->d_sums.as<double>(), RSREG_NUM_SUMS);
-            if (rc) return rc;
-        }
-        k_icp_solve<<<1, 64, 0, ctx->stream>>>(ctx->d_sums.as<double>(), ctx->d_icp_state.as<IcpDevState>());
-        RSREG_HIP(ctx, hipGetLastError());
-        return RSREG_OK;
+    {   // all-reduce, solve, next pass
+        ScopedEvents ev(ctx, &ctx->ev_allreduce);
+        int rc = rsreg_comm_allreduce_device_(ctx, ctx->d_sums.as<double>(), RSREG_NUM_SUMS);
+        if (rc) return rc;
     }
-    return fetch_sums(ctx, sums, true);
+    k_icp_solve<<<1, 64, 0, ctx->stream>>>(ctx->d_sums.as<double>(), ctx->d_icp_state.as<IcpDevState>());
+    RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
 }
 
 // RSREG_PIPELINE_DEVICE_LOOP with fixed-count criteria: every iteration is queued up front, the
@@ -1617,69 +1623,58 @@ int apply_pending_transform(rsreg_ctx *ctx)
     return RSREG_OK;
 }
 
-// Umeyama + compose + criteria for one iteration's (global) sums; the transform of the
-// source cloud itself is left pending so that the fused kernel can fold it into its pass.
+// result->sums_last of an iteration whose sums are not the 17 (point-to-plane, GICP): the layout stays, [0] the pairs and [16]
+// their squared error are filled
+void fill_sums_last(IcpState &s, double n, double err)
+{
+    std::memset(s.sums_last, 0, sizeof(s.sums_last));
+    s.sums_last[0] = n;
+    s.sums_last[16] = err;
+}
+
+// counts an iteration's pairs; true: fewer than the estimator's minimum, the alignment ends here without a transform
+bool too_few_pairs(IcpState &s, double n, uint64_t min_pairs, int *done)
+{
+    s.ncorr = (uint64_t)(n + 0.5);
+    if (s.ncorr >= min_pairs) return false;
+    s.state = RSREG_CONV_NO_CORRESPONDENCES;
+    s.converged = 0;
+    *done = 1;
+    return true;
+}
+
+// One iteration's update from its (global) sums, of which `n` is the number of pairs and `err` their squared error:
+// solve(s) leaves the increment in s.t_inc, then compose + criteria; the transform of the source cloud itself is left
+// pending so that the fused kernel can fold it into its pass.  (The caller has recorded the sums.)
+template <typename Solve>
+int update_with(rsreg_ctx *ctx, double n, double err, int *done, Solve solve)
+{
+    IcpState &s = ctx->icp;
+    if (too_few_pairs(s, n, 3, done)) return RSREG_OK;   // min_number_correspondences_
+    solve(s);
+    s.pending_transform = true;
+    s.final_t = mul(s.t_inc, s.final_t);
+    s.iterations++;
+    s.cur_mse = err / n;
+    s.converged = criteria_has_converged(s) ? 1 : 0;
+    s.have_search = false;
+    *done = s.converged;
+    return RSREG_OK;
+}
+
+// the 17 sums: Umeyama
 int update_from_sums(rsreg_ctx *ctx, const double *sums, int *done)
 {
-    IcpState &s = ctx->icp;
-    std::memcpy(s.sums_last, sums, sizeof(s.sums_last));
-    s.ncorr = (uint64_t)(sums[0] + 0.5);
-    if (s.ncorr < 3) {  // min_number_correspondences_
-        s.state = RSREG_CONV_NO_CORRESPONDENCES;
-        s.converged = 0;
-        *done = 1;
-        return RSREG_OK;
-    }
-    umeyama_from_sums(sums, s.t_inc, s.svd_v);
-    s.pending_transform = true;
-    s.final_t = mul(s.t_inc, s.final_t);
-    s.iterations++;
-    s.cur_mse = sums[16] / sums[0];
-    s.converged = criteria_has_converged(s) ? 1 : 0;
-    s.have_search = false;
-    *done = s.converged;
-    return RSREG_OK;
+    std::memcpy(ctx->icp.sums_last, sums, sizeof(ctx->icp.sums_last));
+    return update_with(ctx, sums[0], sums[16], done, [sums](IcpState &s) { umeyama_from_sums(sums, s.t_inc, s.svd_v); });
 }
 
-// The same for one point-to-plane iteration's 32 sums: TransformationEstimationPointToPlaneLLS (host_linalg.hpp:
-// plane_solve_from_sums) in the place of Umeyama.  result->sums_last keeps its layout: [0] and [16] are filled.
+// one point-to-plane iteration's 32 sums: TransformationEstimationPointToPlaneLLS (host_linalg.hpp: plane_solve_from_sums)
 int update_from_plane_sums(rsreg_ctx *ctx, const double *sums, int *done)
 {
-    IcpState &s = ctx->icp;
-    std::memcpy(s.plane_sums_last, sums, sizeof(s.plane_sums_last));
-    std::memset(s.sums_last, 0, sizeof(s.sums_last));
-    s.sums_last[0] = sums[0];
-    s.sums_last[16] = sums[1];
-    s.ncorr = (uint64_t)(sums[0] + 0.5);
-    if (s.ncorr < 3) {  // min_number_correspondences_
-        s.state = RSREG_CONV_NO_CORRESPONDENCES;
-        s.converged = 0;
-        *done = 1;
-        return RSREG_OK;
-    }
-    plane_solve_from_sums(sums, s.t_inc);
-    s.pending_transform = true;
-    s.final_t = mul(s.t_inc, s.final_t);
-    s.iterations++;
-    s.cur_mse = sums[1] / sums[0];
-    s.converged = criteria_has_converged(s) ? 1 : 0;
-    s.have_search = false;
-    *done = s.converged;
-    return RSREG_OK;
-}
-
-// the target's normals from records already in HBM (three floats at d_rec + i * stride), on the context's stream
-int set_normals_device(rsreg_ctx *ctx, const char *d_rec, size_t n, size_t stride)
-{
-    if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
-    if (n != ctx->n_target_raw) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per target record: the counts differ");
-    RSREG_HIP(ctx, ctx->d_normals.reserve((n + 1) * sizeof(float4)));
-    if (n) {
-        k_pack_normals<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(d_rec, stride, (uint32_t)n, ctx->d_normals.as<float4>());
-        RSREG_HIP(ctx, hipGetLastError());
-    }
-    ctx->have_normals = true;
-    return RSREG_OK;
+    std::memcpy(ctx->icp.plane_sums_last, sums, sizeof(ctx->icp.plane_sums_last));
+    fill_sums_last(ctx->icp, sums[0], sums[1]);
+    return update_with(ctx, sums[0], sums[1], done, [sums](IcpState &s) { plane_solve_from_sums(sums, s.t_inc); });
 }
 
 // A host cloud on its way into HBM, packed xyz (PCL's ICP reads nothing else of a point): the caller's records are
@@ -1719,7 +1714,426 @@ int upload_packed(rsreg_ctx *ctx, PinnedBuf &stage, const Event &ev, DevBuf &d_r
     return RSREG_OK;
 }
 
+// One normal per record of the source (the target), three floats at normals + i * stride.  on_host: a host buffer, staged like
+// the cloud itself -- packed into pinned memory of its own, over the link on the upload stream, the main stream behind it;
+// otherwise records already in HBM, read on the context's stream.
+int set_record_normals(rsreg_ctx *ctx, bool source, bool on_host, const void *normals, size_t n, size_t stride)
+{
+    if (!ctx || (n && !normals) || stride < 12 || (!on_host && (stride & 3))) return RSREG_ERR_INVALID_ARG;
+    if (source) {
+        if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
+        if (n != ctx->n_source) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per source record: the counts differ");
+    } else {
+        if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
+        if (n != ctx->n_target_raw) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per target record: the counts differ");
+    }
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    RecordNormals &r = source ? ctx->src_nrm : ctx->tgt_nrm;
+    const char *d_rec = static_cast<const char *>(normals);
+    if (on_host) {
+        RSREG_HIP(ctx, ctx->h2d.ensure());
+        RSREG_HIP(ctx, r.ev.ensure());
+        RSREG_HIP(ctx, r.ev_packed.ensure());
+        RSREG_HIP(ctx, hipStreamWaitEvent(ctx->h2d.stream, r.ev_packed, 0));   // (normals set before may still be read from d_raw)
+        int rc = upload_packed(ctx, r.h, r.ev, r.d_raw, normals, n, stride, ctx->stream, nullptr, nullptr);
+        if (rc) return rc;
+        d_rec = r.d_raw.as<char>();
+        stride = 12;
+    }
+    RSREG_HIP(ctx, r.d.reserve((n + 1) * sizeof(float4)));
+    if (n) {
+        k_pack_normals<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(d_rec, stride, (uint32_t)n, r.d.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    r.have = true;
+    if (on_host) RSREG_HIP(ctx, hipEventRecord(r.ev_packed, ctx->stream));
+    return RSREG_OK;
+}
+
+// rsreg_icp_begin; need_index: the alignment runs the staged kernels over the index whatever the source's size (plane mode, GICP)
+int icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, bool need_index, bool use_chain)
+{
+    if (!ctx || !params) return RSREG_ERR_INVALID_ARG;
+    if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
+    if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
+    if (params->max_iterations < 0 || !(params->max_correspondence_distance >= 0))
+        return fail(ctx, RSREG_ERR_INVALID_ARG, "bad ICP parameters");
+    if (params->max_correspondence_distance > ctx->gate_built_for)
+        return fail(ctx, RSREG_ERR_INVALID_ARG, "max_correspondence_distance exceeds the one the target index was built for");
+    // the filters need the whole source: each rank would trim its own block with its own cut and index only its own block for
+    // the reciprocal search, a different answer from one GPU's (a global trim across ranks is not implemented)
+    if (ctx->nranks > 1 && filters_on(*params))
+        return fail(ctx, RSREG_ERR_INVALID_ARG, "reciprocal correspondences and the trimmed rejector need the whole source: not with more than one rank");
+    const RejectorChain chain = use_chain ? ctx->rejectors : RejectorChain();
+    if (ctx->nranks > 1 && chain.n > 0)
+        return fail(ctx, RSREG_ERR_INVALID_ARG, "a rejector chain needs the whole source: not with more than one rank");
+    if (chain.has(RSREG_REJECTOR_SURFACE_NORMAL) && !(ctx->tgt_nrm.have && ctx->src_nrm.have))
+        return fail(ctx, RSREG_ERR_STATE, "the surface normal rejector needs rsreg_icp_set_source_normals and rsreg_icp_set_target_normals after the clouds are set");
+    if (params->estimation != RSREG_ESTIMATION_SVD && params->estimation != RSREG_ESTIMATION_POINT_TO_PLANE_LLS)
+        return fail(ctx, RSREG_ERR_INVALID_ARG, "unknown transformation estimation");
+    if (plane_on(*params)) {
+        // (the all-reduce of the 32 sums is not implemented, as a global trim is not)
+        if (ctx->nranks > 1) return fail(ctx, RSREG_ERR_INVALID_ARG, "point-to-plane ICP: not with more than one rank");
+        if (!ctx->tgt_nrm.have) return fail(ctx, RSREG_ERR_STATE, "point-to-plane ICP needs rsreg_icp_set_target_normals after rsreg_icp_set_target");
+    }
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    {
+        int rcj = join_source(ctx);
+        if (rcj) return rcj;
+    }
+    if (ctx->grid.dense == 2 && (ctx->n_work > kScanMaxSource || filters_on(*params) || chain.n > 0 || need_index)) {
+        // the target was set for a handful of queries (scan_target); this alignment needs the index after all
+        if (!ctx->scan_raw) return fail(ctx, RSREG_ERR_NO_TARGET, "the target cloud was released before its index was built");
+        int rcb = build_grid(ctx, ctx->scan_raw, ctx->n_target_raw, ctx->scan_stride, ctx->gate_built_for);
+        if (rcb) return rcb;
+    }
+    IcpState &s = ctx->icp;
+    s = IcpState();
+    s.prm = *params;
+    s.chain = chain;
+    s.normals_restart_pending = chain.has(RSREG_REJECTOR_SURFACE_NORMAL);
+    // the rings must cover THIS call's gate (it may be smaller than the one built for)
+    s.final_t = Mat4f::identity();
+    if (guess) std::memcpy(s.final_t.m, guess, sizeof(s.final_t.m));
+    s.t_inc = Mat4f::identity();
+    s.prev_mse = DBL_MAX;
+    s.active = 1;
+    ctx->ev_used = 0;
+    ctx->ev_nn.clear();
+    ctx->ev_reduce.clear();
+    ctx->ev_transform.clear();
+    ctx->ev_allreduce.clear();
+    s.restart_pending = true;   // input_transformed = guess * input (App. A.2 prologue): ensure_restarted / launch_fused
+    ctx->gicp.active = 0;
+    return RSREG_OK;
+}
+
+// rsreg_icp_end.  source_records (nullable): the caller's source records, out_stride bytes each -- every record of aligned_out is
+// then the WHOLE source record with xyz rewritten (what PCL's align(output) leaves: output = input, then xyz <- final * xyz),
+// copied by the host threads that write the aligned positions anyway
+int icp_end(rsreg_ctx *ctx, rsreg_icp_result *result, void *aligned_out, size_t out_stride, const void *source_records)
+{
+    if (!ctx) return RSREG_ERR_INVALID_ARG;
+    IcpState &s = ctx->icp;
+    if (!s.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_icp_begin not called");
+    const size_t n = ctx->n_source;
+    if (aligned_out && n) {
+        if (out_stride < 12) return RSREG_ERR_INVALID_ARG;
+        RSREG_HIP(ctx, ctx->d_tmp.reserve(n * 12 + 16));
+        RSREG_HIP(ctx, ctx->h_stage.reserve(n * 12 + 16));
+        k_apply_final<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_src_all.as<float4>(), (uint32_t)n, to_mat34(s.final_t),
+                                                                                ctx->d_perm.as<uint32_t>(), ctx->d_tmp.as<float>());
+        RSREG_HIP(ctx, hipGetLastError());
+        // home in pieces: while piece k + 1 is on the link, piece k is written into the caller's records by the host's threads
+        const auto t0 = std::chrono::steady_clock::now();
+        const size_t piece = (size_t)1 << 18;
+        const size_t pieces = (n + piece - 1) / piece;
+        while (ctx->ev_home.size() < pieces) {
+            Event e;
+            RSREG_HIP(ctx, e.ensure());
+            ctx->ev_home.push_back(std::move(e));
+        }
+        for (size_t k = 0; k < pieces; ++k) {
+            const size_t lo = k * piece, hi = std::min(n, lo + piece);
+            RSREG_HIP(ctx, hipMemcpyAsync(ctx->h_stage.as<char>() + lo * 12, ctx->d_tmp.as<char>() + lo * 12, (hi - lo) * 12, hipMemcpyDeviceToHost, ctx->stream));
+            RSREG_HIP(ctx, hipEventRecord(ctx->ev_home[k], ctx->stream));
+        }
+        const float *src = ctx->h_stage.as<float>();
+        char *dst = static_cast<char *>(aligned_out);
+        const char *rec = static_cast<const char *>(source_records);
+        // (the caller's records first, all of them, while the positions are still on the link: the positions then land in lines
+        // the cores already own)
+        // (icp_align has started that copy on a thread of its own, beside the iterations: it ends here)
+        if (ctx->records_copy.joinable()) ctx->records_copy.join();
+        else if (rec && rec != dst)
+            host_parallel_for(n, [=](size_t a, size_t b) { std::memcpy(dst + a * out_stride, rec + a * out_stride, (b - a) * out_stride); });
+        for (size_t k = 0; k < pieces; ++k) {
+            const size_t lo = k * piece, hi = std::min(n, lo + piece);
+            RSREG_HIP(ctx, hipEventSynchronize(ctx->ev_home[k]));
+            host_parallel_for(hi - lo, [=](size_t a, size_t b) {
+                const float one = 1.0f;
+                for (size_t i = lo + a; i < lo + b; ++i) {
+                    std::memcpy(dst + i * out_stride, src + 3 * i, 12);
+                    if (out_stride >= 16) std::memcpy(dst + i * out_stride + 12, &one, 4);
+                }
+            });
+        }
+        ctx->host_timing.aligned_copy = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    // (the usual end of an alignment: the last thing this thread did was wait for the sums, and nothing has been queued since)
+    if (!(s.idle_after_sums && !(aligned_out && n))) RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    (void)target_counts(ctx, false);
+#ifdef RSREG_DIAG
+    if (const char *sd_path = tunables().dump_seed) {   // dev: the position every query matched last, and the queries
+        const size_t nq = ctx->n_work;
+        std::vector<int> h(nq);
+        std::vector<float> hq(nq * 4);
+        (void)hipMemcpy(h.data(), ctx->d_seed.ptr, nq * 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(hq.data(), ctx->d_cur.ptr, nq * 16, hipMemcpyDeviceToHost);
+        if (FILE *f = std::fopen(sd_path, "wb")) {
+            std::fwrite(h.data(), 4, nq, f);
+            std::fwrite(hq.data(), 4, nq * 4, f);
+            const size_t np_ = ctx->grid.n_points;
+            std::vector<float> hp(np_ * 4);
+            (void)hipMemcpy(hp.data(), ctx->d_tgt_sorted.ptr, np_ * 16, hipMemcpyDeviceToHost);
+            std::fwrite(hp.data(), 4, np_ * 4, f);
+            std::fclose(f);
+        }
+    }
+    if (const char *wt_path = tunables().wave_times) {
+        if (ctx->grid.dense == 1 && ctx->n_work) {
+            const bool light = tunables().wave_times_light;
+            const size_t nw = light ? (size_t)(ctx->icp.sched.ready ? ctx->icp.sched.items : reduce_blocks(ctx->n_work)) * kTileWaves
+                                    : (ctx->n_work + 63) / 64;
+            std::vector<unsigned long long> h(16 * nw + (light ? 0 : (ctx->n_work + 1) / 2));   // wave records, then a uint32 of step counts per lane
+            (void)hipMemcpy(h.data(), ctx->d_brick.ptr, h.size() * 8, hipMemcpyDeviceToHost);
+            if (FILE *f = std::fopen(wt_path, "wb")) {
+                std::fwrite(h.data(), 8, h.size(), f);
+                std::fclose(f);
+            }
+        }
+    }
+#endif
+    if (result) {
+        std::memset(result, 0, sizeof(*result));
+        std::memcpy(result->transform, s.final_t.m, 64);
+        result->converged = s.converged;
+        result->state = s.state;
+        result->iterations = s.iterations;
+        result->n_correspondences = s.ncorr;
+        result->mse = s.cur_mse;
+        std::memcpy(result->sums_last, s.sums_last, sizeof(s.sums_last));
+        result->n_nn_launches = s.n_nn_launches;
+        result->n_scheduled_launches = s.n_sched_launches;
+        if (ctx->profiling) {
+            result->ms_nn = sum_events(ctx, ctx->ev_nn);
+#ifdef RSREG_DIAG
+            if (tunables().dump_nn_ms) {   // diagnostic builds: duration of every search launch of this call
+                std::fprintf(stderr, "[rsreg] search launches (us):");
+                for (auto &p : ctx->ev_nn) {
+                    float t = 0;
+                    (void)hipEventElapsedTime(&t, ctx->ev_pool[p.first], ctx->ev_pool[p.second]);
+                    std::fprintf(stderr, " %.1f", t * 1e3);
+                }
+                std::fprintf(stderr, "\n");
+            }
+#endif
+            result->ms_reduce = sum_events(ctx, ctx->ev_reduce);
+            if (ctx->ev_reduce.empty())   // fused pipelines: everything between two consecutive search kernels
+                for (size_t k = 0; k + 1 < ctx->ev_nn.size(); ++k) {
+                    float t = 0;
+                    if (hipEventElapsedTime(&t, ctx->ev_pool[ctx->ev_nn[k].second], ctx->ev_pool[ctx->ev_nn[k + 1].first]) == hipSuccess)
+                        result->ms_reduce += t;
+                }
+            result->ms_transform = sum_events(ctx, ctx->ev_transform);
+            result->ms_allreduce = sum_events(ctx, ctx->ev_allreduce);   // (already inside ms_reduce in the fused pipelines)
+            result->ms_total = result->ms_nn + result->ms_reduce + result->ms_transform;
+        }
+    }
+    s.active = 0;
+    ctx->icp_fit_ok = true;   // getFitnessScore: this alignment's source, final transform and target
+    ctx->icp_fit_t = s.final_t;
+    return RSREG_OK;
+}
+
+// rsreg_icp_align / rsreg_icp_align_records: begin, the iterations of the pipeline the parameters choose, end
+int icp_align(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, rsreg_icp_result *result, void *aligned_out, size_t out_stride,
+              const void *source_records)
+{
+    const auto t_align0 = std::chrono::steady_clock::now();
+    struct AlignClock {   // (whatever way the call ends: begin .. the last iteration + the aligned cloud's way home)
+        rsreg_ctx *c;
+        std::chrono::steady_clock::time_point t0;
+        ~AlignClock() { if (c) c->host_timing.align = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - c->host_timing.aligned_copy; }
+    } align_clock{ctx, t_align0};
+    if (ctx) ctx->host_timing.aligned_copy = 0;
+    // `output = input`: the caller's records go into the output on a thread of their own (the pool's threads under it) while this
+    // thread queues and waits for the iterations; icp_end joins it before the aligned positions are written over the records
+    struct CopyGuard {   // (an error on the way: the copy still owns aligned_out)
+        rsreg_ctx *c;
+        ~CopyGuard() { if (c && c->records_copy.joinable()) c->records_copy.join(); }
+    } copy_guard{ctx};
+    if (ctx && source_records && aligned_out && source_records != aligned_out && ctx->n_source && out_stride >= 12) {
+        const size_t n_rec = ctx->n_source;
+        const char *rec = static_cast<const char *>(source_records);
+        char *dst = static_cast<char *>(aligned_out);
+        ctx->records_copy = std::thread([=] {
+            host_parallel_for(n_rec, [=](size_t a, size_t b) { std::memcpy(dst + a * out_stride, rec + a * out_stride, (b - a) * out_stride); });
+        });
+    }
+    int rc = rsreg_icp_begin(ctx, guess, params);
+    if (rc) return rc;
+    int done = 0;
+    double sums[RSREG_NUM_PLANE_SUMS];   // (the 17 of a point-to-point iteration, or the 32 of a point-to-plane one)
+    const bool plane = plane_on(*params);     // point-to-plane: staged, with its own sums and solve
+    const bool filtered = weights_on(ctx) || plane;   // the optional correspondence filters and the rejector chain run between the staged kernels
+    const bool scan = ctx->grid.dense == 2;   // no index: the staged kernels (search over the whole target, sums)
+    const bool fused = !filtered && !scan && (params->pipeline_mode == RSREG_PIPELINE_FUSED || params->pipeline_mode == RSREG_PIPELINE_DEVICE_LOOP);
+    if (!filtered && !scan && params->pipeline_mode == RSREG_PIPELINE_DEVICE_LOOP && params->criteria_mode == RSREG_CRITERIA_FIXED) {
+        rc = run_device_loop(ctx);
+        if (rc) return rc;
+        done = 1;
+    }
+    while (!done) {
+        if (fused) {
+            rc = launch_fused(ctx, sums, false);
+        } else {
+            rc = apply_pending_transform(ctx);
+            if (!rc) rc = launch_search(ctx);
+            if (!rc) rc = plane ? launch_plane_sums(ctx, sums) : launch_sums(ctx, sums, true);
+        }
+        if (rc) return rc;
+        rc = plane ? update_from_plane_sums(ctx, sums, &done) : update_from_sums(ctx, sums, &done);
+        if (rc) return rc;
+    }
+    return icp_end(ctx, result, aligned_out, out_stride, source_records);
+}
+
+// ---- GICP's helpers (the ABI's GICP section below says what an outer iteration is)
+static_assert(RSREG_NUM_GICP_SUMS == RSREG_NUM_PLANE_SUMS, "k_gicp_reduce goes through plane_tile_reduce_store and k_final_reduce as the plane sums do");
+
+// one covariance record per record of the source (the target): from the host (waited for: the buffer has been read) or from HBM
+int gicp_set_covariances(rsreg_ctx *ctx, bool source, const void *host, const void *dev, size_t n, size_t stride)
+{
+    if (!ctx || (n && !host && !dev) || stride < 48 || (dev && (stride & 7))) return RSREG_ERR_INVALID_ARG;
+    if (source) {
+        if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
+        if (n != ctx->n_source) return fail(ctx, RSREG_ERR_INVALID_ARG, "one covariance per source record: the counts differ");
+    } else {
+        if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
+        if (n != ctx->n_target_raw) return fail(ctx, RSREG_ERR_INVALID_ARG, "one covariance per target record: the counts differ");
+    }
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    DevBuf &d = source ? ctx->d_gicp_cs : ctx->d_gicp_ct;
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (an alignment before this one may still read the buffer)
+    RSREG_HIP(ctx, d.reserve((n + 1) * 48));
+    if (n && host) {
+        RSREG_HIP(ctx, hipMemcpy2DAsync(d.ptr, 48, host, stride, 48, n, hipMemcpyHostToDevice, ctx->stream));
+        RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    } else if (n) {
+        k_gicp_pack_cov<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const char *>(dev), stride, (uint32_t)n, d.as<double>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    (source ? ctx->have_gicp_cs : ctx->have_gicp_ct) = true;
+    return RSREG_OK;
+}
+
+// the 32 sums at X (column-major double 4 x 4) over the pairs of the last search: launch_plane_sums with k_gicp_reduce
+int gicp_launch_sums(rsreg_ctx *ctx, const double *X, double *sums)
+{
+    ctx->icp.idle_after_sums = false;
+    const uint32_t n = (uint32_t)ctx->n_work;
+    const uint32_t nb = reduce_blocks(n);
+    RSREG_HIP(ctx, ctx->d_plane_partials.reserve((size_t)nb * RSREG_NUM_GICP_SUMS * 8));
+    Mat34d Xr;
+    for (int c = 0; c < 4; ++c) {
+        Xr.r0[c] = X[c * 4 + 0];
+        Xr.r1[c] = X[c * 4 + 1];
+        Xr.r2[c] = X[c * 4 + 2];
+    }
+    {
+        ScopedEvents ev(ctx, &ctx->ev_reduce);
+        k_gicp_reduce<<<nb, kTile, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), ctx->d_tgt_sorted.as<float4>(),
+                                                     ctx->d_gicp_m.as<double>(), Xr, n, ctx->d_plane_partials.as<double>());
+        RSREG_HIP(ctx, hipGetLastError());
+        int rc = queue_final_reduce(ctx, ctx->d_plane_partials.as<double>(), nb, RSREG_NUM_GICP_SUMS);
+        if (rc) return rc;
+    }
+    return fetch_sums(ctx, sums, RSREG_NUM_GICP_SUMS, false);
+}
+
+void gicp_identity(double *X)
+{
+    for (int k = 0; k < 16; ++k) X[k] = (k % 5 == 0) ? 1.0 : 0.0;
+}
+
+// C = A B, column-major double 4 x 4, entries ((a0 b0 + a1 b1) + a2 b2) + a3 b3
+void gicp_mul(const double *A, const double *B, double *C)
+{
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            C[c * 4 + r] = ((A[0 * 4 + r] * B[c * 4 + 0] + A[1 * 4 + r] * B[c * 4 + 1]) + A[2 * 4 + r] * B[c * 4 + 2]) + A[3 * 4 + r] * B[c * 4 + 3];
+}
+
+// x = scale * pinv(H) b and D = Delta(x), column-major; the rank of the solve (0: x = 0, D = I)
+int gicp_step(const double *sums, double scale, double (&x)[6], double *D)
+{
+    const int rank = plane_unknowns_from_sums(sums, x);
+    gicp_identity(D);
+    if (rank == 0) return 0;
+    for (int i = 0; i < 6; ++i) x[i] *= scale;
+    double d12[12];
+    plane_matrix_from_unknowns(x, d12);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) D[c * 4 + r] = d12[r * 4 + c];
+    return rank;
+}
+
+// ---- getFitnessScore's helpers
+// the float bound the search prunes with: never below max_range, so that no d2 with (double)d2 <= max_range is dropped
+float fit_limit2(double max_range)
+{
+    if (!(max_range >= 0)) return -1.0f;   // (negative or NaN: nothing is in range)
+    if (max_range >= (double)FLT_MAX) return __builtin_huge_valf();
+    float f = (float)max_range;
+    if ((double)f < max_range) f = std::nextafter(f, FLT_MAX);
+    return f;
+}
+
+// this rank's (count, sum of d2) of the last ICP alignment (rsreg_icp_fitness_sums / _score)
+int icp_fitness_block(rsreg_ctx *ctx, double max_range, double sums[2])
+{
+    if (!ctx->icp_fit_ok) return fail(ctx, RSREG_ERR_STATE, "no ICP alignment of the current source and target");
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = join_source(ctx);   // (nothing pending after an alignment; kept for the contract: the source's buffers are final)
+    if (rc) return rc;
+    rc = target_counts(ctx, true);   // (grid.n_points of a counting build nobody has waited for is only a bound)
+    if (rc) return rc;
+    const size_t n_tgt = ctx->grid.dense == 2 ? ctx->n_target_raw : ctx->grid.n_points;
+    return fitness_sums(ctx, ctx->fit_icp, ctx->d_tgt_sorted.as<float4>(), n_tgt, ctx->d_src_all.as<float4>(), ctx->d_perm.as<uint32_t>(),
+                        ctx->n_source, ctx->icp_fit_t, max_range, sums);
+}
+
+void fitness_result(const double sums[2], double *score, uint64_t *n_within)
+{
+    if (score) *score = sums[0] > 0 ? sums[1] / sums[0] : DBL_MAX;
+    if (n_within) *n_within = (uint64_t)sums[0];
+}
+
 }  // namespace
+
+// getFitnessScore's two sums (rsreg_ctx.hpp holds the contract; ndt.hip's score goes through here too)
+int rsreg::fitness_sums(rsreg_ctx *ctx, PointGrid &fx, const float4 *tgt, size_t n_tgt, const float4 *src, const uint32_t *perm, size_t n,
+                        const Mat4f &T, double max_range, double sums[2])
+{
+    hipStream_t st = ctx->stream;
+    if (n_tgt > 0xfffffff0ull || n > 0xfffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
+    if (!fx.built) {   // box (one round trip), counts and occupancy words, prefix sum, scatter: into fx's own buffers
+        RSREG_HIP(ctx, ctx->h_fit.reserve(64));
+        int rc = grid_build<FitGridPolicy>(ctx, fx, TargetRecords{tgt}, (uint32_t)n_tgt, 1, ctx->h_fit.as<uint32_t>());
+        if (rc) return rc;
+    }
+    sums[0] = sums[1] = 0;
+    if (n == 0) return RSREG_OK;
+    const uint32_t nb = div_up((uint32_t)n, kBlock);
+    RSREG_HIP(ctx, ctx->d_fit_d2.reserve(n * 4 + 16));
+    RSREG_HIP(ctx, ctx->d_fit_partials.reserve((size_t)nb * 2 * 8));
+    RSREG_HIP(ctx, ctx->d_fit_sums.reserve(64));
+    RSREG_HIP(ctx, ctx->h_fit.reserve(64));
+    k_fit_search<<<nb, kBlock, 0, st>>>(src, (uint32_t)n, to_mat34(T), perm, grid_dev(fx), fit_limit2(max_range), max_range,
+                                        ctx->d_fit_d2.as<float>());
+    RSREG_HIP(ctx, hipGetLastError());
+    k_fit_tiles<<<nb, kBlock, 0, st>>>(ctx->d_fit_d2.as<float>(), (uint32_t)n, ctx->d_fit_partials.as<double>());
+    RSREG_HIP(ctx, hipGetLastError());
+    k_final_reduce<<<2, kReduceBlock, 0, st>>>(ctx->d_fit_partials.as<double>(), nb, ctx->d_fit_sums.as<double>());
+    RSREG_HIP(ctx, hipGetLastError());
+    double *h = ctx->h_fit.as<double>();
+    RSREG_HIP(ctx, hipMemcpyAsync(h, ctx->d_fit_sums.ptr, 16, hipMemcpyDeviceToHost, st));
+    RSREG_HIP(ctx, hipStreamSynchronize(st));
+    sums[0] = h[0];
+    sums[1] = h[1];
+    return RSREG_OK;
+}
 
 // =============================================================================== C ABI
 extern "C" {
@@ -1860,7 +2274,7 @@ int rsreg_icp_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
 {
     (void)is_dense;
     if (!ctx || (n && !d_points) || stride < 12 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
-    ctx->have_normals = false;   // (of the target before this one)
+    ctx->tgt_nrm.have = false;   // (of the target before this one)
     ctx->have_gicp_ct = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     return build_grid(ctx, static_cast<const char *>(d_points), n, stride, max_correspondence_distance);
@@ -1869,7 +2283,7 @@ int rsreg_icp_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
 // (internal, cloud.hip) a target for the handful of source points already loaded: no index, see scan_target
 int rsreg_icp_set_target_scan_(rsreg_ctx *ctx, const void *d_points, size_t n, size_t stride, double max_correspondence_distance)
 {
-    ctx->have_normals = false;
+    ctx->tgt_nrm.have = false;
     ctx->have_gicp_ct = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     return scan_target(ctx, static_cast<const char *>(d_points), n, stride, max_correspondence_distance);
@@ -1880,7 +2294,7 @@ int rsreg_icp_set_target(rsreg_ctx *ctx, const void *points, size_t n, size_t st
 {
     (void)is_dense;
     if (!ctx || (n && !points) || stride < 12) return RSREG_ERR_INVALID_ARG;
-    ctx->have_normals = false;   // (of the target before this one)
+    ctx->tgt_nrm.have = false;   // (of the target before this one)
     ctx->have_gicp_ct = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     rsreg_host_timing &ht = ctx->host_timing;
@@ -1921,64 +2335,6 @@ int rsreg_icp_set_source(rsreg_ctx *ctx, const void *points, size_t n, size_t st
     return load_source(ctx, ctx->d_src_raw.as<char>(), n, 12);
 }
 
-// rsreg_icp_begin; need_index: the alignment runs the staged kernels over the index whatever the source's size (plane mode, GICP)
-static int icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, bool need_index, bool use_chain)
-{
-    if (!ctx || !params) return RSREG_ERR_INVALID_ARG;
-    if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
-    if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
-    if (params->max_iterations < 0 || !(params->max_correspondence_distance >= 0))
-        return fail(ctx, RSREG_ERR_INVALID_ARG, "bad ICP parameters");
-    if (params->max_correspondence_distance > ctx->gate_built_for)
-        return fail(ctx, RSREG_ERR_INVALID_ARG, "max_correspondence_distance exceeds the one the target index was built for");
-    // the filters need the whole source: each rank would trim its own block with its own cut and index only its own block for
-    // the reciprocal search, a different answer from one GPU's (a global trim across ranks is not implemented)
-    if (ctx->nranks > 1 && filters_on(*params))
-        return fail(ctx, RSREG_ERR_INVALID_ARG, "reciprocal correspondences and the trimmed rejector need the whole source: not with more than one rank");
-    const RejectorChain chain = use_chain ? ctx->rejectors : RejectorChain();
-    if (ctx->nranks > 1 && chain.n > 0)
-        return fail(ctx, RSREG_ERR_INVALID_ARG, "a rejector chain needs the whole source: not with more than one rank");
-    if (chain.has(RSREG_REJECTOR_SURFACE_NORMAL) && !(ctx->have_normals && ctx->have_src_normals))
-        return fail(ctx, RSREG_ERR_STATE, "the surface normal rejector needs rsreg_icp_set_source_normals and rsreg_icp_set_target_normals after the clouds are set");
-    if (params->estimation != RSREG_ESTIMATION_SVD && params->estimation != RSREG_ESTIMATION_POINT_TO_PLANE_LLS)
-        return fail(ctx, RSREG_ERR_INVALID_ARG, "unknown transformation estimation");
-    if (plane_on(*params)) {
-        // (the all-reduce of the 32 sums is not implemented, as a global trim is not)
-        if (ctx->nranks > 1) return fail(ctx, RSREG_ERR_INVALID_ARG, "point-to-plane ICP: not with more than one rank");
-        if (!ctx->have_normals) return fail(ctx, RSREG_ERR_STATE, "point-to-plane ICP needs rsreg_icp_set_target_normals after rsreg_icp_set_target");
-    }
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    {
-        int rcj = join_source(ctx);
-        if (rcj) return rcj;
-    }
-    if (ctx->grid.dense == 2 && (ctx->n_work > kScanMaxSource || filters_on(*params) || chain.n > 0 || need_index)) {
-        // the target was set for a handful of queries (scan_target); this alignment needs the index after all
-        if (!ctx->scan_raw) return fail(ctx, RSREG_ERR_NO_TARGET, "the target cloud was released before its index was built");
-        int rcb = build_grid(ctx, ctx->scan_raw, ctx->n_target_raw, ctx->scan_stride, ctx->gate_built_for);
-        if (rcb) return rcb;
-    }
-    IcpState &s = ctx->icp;
-    s = IcpState();
-    s.prm = *params;
-    s.chain = chain;
-    s.normals_restart_pending = chain.has(RSREG_REJECTOR_SURFACE_NORMAL);
-    // the rings must cover THIS call's gate (it may be smaller than the one built for)
-    s.final_t = Mat4f::identity();
-    if (guess) std::memcpy(s.final_t.m, guess, sizeof(s.final_t.m));
-    s.t_inc = Mat4f::identity();
-    s.prev_mse = DBL_MAX;
-    s.active = 1;
-    ctx->ev_used = 0;
-    ctx->ev_nn.clear();
-    ctx->ev_reduce.clear();
-    ctx->ev_transform.clear();
-    ctx->ev_allreduce.clear();
-    s.restart_pending = true;   // input_transformed = guess * input (App. A.2 prologue): ensure_restarted / launch_fused
-    ctx->gicp.active = 0;
-    return RSREG_OK;
-}
-
 int rsreg_icp_begin(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params)
 {
     return icp_begin(ctx, guess, params, params && plane_on(*params), true);
@@ -1997,18 +2353,13 @@ int rsreg_icp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out)
         RSREG_HIP(ctx, ctx->d_tmp.reserve(n * 8 + 32));
         int *d_idx = ctx->d_tmp.as<int>();
         float *d_d2 = reinterpret_cast<float *>(d_idx + n);
-        if (ctx->icp.chain.n > 0)
-            k_export_corr_flags<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(
-                ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), ctx->d_rej_flags.as<uint32_t>(), ctx->d_tgt_sorted.as<float4>(),
-                ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(), (uint32_t)n, d_idx, d_d2);
-        else if (filters_on(ctx->icp.prm))
-            k_export_corr_w<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(
-                ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), ctx->d_corr_w.as<uint32_t>(), ctx->d_tgt_sorted.as<float4>(),
-                ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(), ctx->d_first.as<uint32_t>(), (uint32_t)n, d_idx, d_d2);
-        else
-            k_export_corr<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(
-                ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), ctx->d_tgt_sorted.as<float4>(), ctx->d_perm.as<uint32_t>(),
-                ctx->d_uniq_of.as<uint32_t>(), (uint32_t)n, d_idx, d_d2);
+        // who keeps the match: the records the chain's flags leave, the first cw[u] copies the two filters leave, or every matched point
+        const bool by_flags = ctx->icp.chain.n > 0, by_copies = !by_flags && filters_on(ctx->icp.prm);
+        auto kern = by_flags ? k_export_corr<CorrKeep::flags> : by_copies ? k_export_corr<CorrKeep::copies> : k_export_corr<CorrKeep::matched>;
+        const uint32_t *keep = by_flags ? ctx->d_rej_flags.as<uint32_t>() : by_copies ? ctx->d_corr_w.as<uint32_t>() : nullptr;
+        kern<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), keep, ctx->d_tgt_sorted.as<float4>(),
+                                                                      ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(), ctx->d_first.as<uint32_t>(), (uint32_t)n,
+                                                                      d_idx, d_d2);
         RSREG_HIP(ctx, hipGetLastError());
         if (index_out) RSREG_HIP(ctx, hipMemcpyAsync(index_out, d_idx, n * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (sqr_dist_out) RSREG_HIP(ctx, hipMemcpyAsync(sqr_dist_out, d_d2, n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2046,32 +2397,11 @@ int rsreg_icp_update(rsreg_ctx *ctx, const double sums[RSREG_NUM_SUMS], float *t
     return RSREG_OK;
 }
 
-int rsreg_icp_set_target_normals(rsreg_ctx *ctx, const void *normals, size_t n, size_t stride)
-{
-    if (!ctx || (n && !normals) || stride < 12) return RSREG_ERR_INVALID_ARG;
-    if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
-    if (n != ctx->n_target_raw) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per target record: the counts differ");
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    // staged like the target: packed into pinned memory of its own, over the link on the upload stream, the main stream behind it
-    RSREG_HIP(ctx, ctx->h2d.ensure());
-    RSREG_HIP(ctx, ctx->ev_nrm.ensure());
-    RSREG_HIP(ctx, ctx->ev_nrm_packed.ensure());
-    RSREG_HIP(ctx, hipStreamWaitEvent(ctx->h2d.stream, ctx->ev_nrm_packed, 0));   // (normals set before may still be read from d_nrm_raw)
-    int rc = upload_packed(ctx, ctx->h_nrm, ctx->ev_nrm, ctx->d_nrm_raw, normals, n, stride, ctx->stream, nullptr, nullptr);
-    if (rc) return rc;
-    rc = set_normals_device(ctx, ctx->d_nrm_raw.as<char>(), n, 12);
-    if (rc) return rc;
-    RSREG_HIP(ctx, hipEventRecord(ctx->ev_nrm_packed, ctx->stream));
-    return RSREG_OK;
-}
-
-// (internal, cloud.hip: rsreg_icp_set_target_normals_cloud) normals already in HBM
-int rsreg_icp_set_target_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride)
-{
-    if (!ctx || (n && !d_normals) || stride < 12 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    return set_normals_device(ctx, static_cast<const char *>(d_normals), n, stride);
-}
+// ---- the records' normals (set_record_normals); the _device_ entries are internal (cloud.hip: rsreg_icp_set_*_normals_cloud)
+int rsreg_icp_set_target_normals(rsreg_ctx *ctx, const void *normals, size_t n, size_t stride) { return set_record_normals(ctx, false, true, normals, n, stride); }
+int rsreg_icp_set_target_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride) { return set_record_normals(ctx, false, false, d_normals, n, stride); }
+int rsreg_icp_set_source_normals(rsreg_ctx *ctx, const void *normals, size_t n, size_t stride) { return set_record_normals(ctx, true, true, normals, n, stride); }
+int rsreg_icp_set_source_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride) { return set_record_normals(ctx, true, false, d_normals, n, stride); }
 
 // ---- the rejector chain (include/rsreg.h holds the contract; apply_chain above runs it)
 int rsreg_icp_set_rejectors(rsreg_ctx *ctx, const rsreg_rejector *chain, int32_t n)
@@ -2123,47 +2453,6 @@ int rsreg_icp_rejector_stats(rsreg_ctx *ctx, rsreg_rejector_stat *stats, int32_t
     return RSREG_OK;
 }
 
-// the source's normals from records already in HBM (three floats at d_rec + i * stride), on the context's stream
-static int set_source_normals_device(rsreg_ctx *ctx, const char *d_rec, size_t n, size_t stride)
-{
-    if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
-    if (n != ctx->n_source) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per source record: the counts differ");
-    RSREG_HIP(ctx, ctx->d_src_nrm.reserve((n + 1) * sizeof(float4)));
-    if (n) {
-        k_pack_normals<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(d_rec, stride, (uint32_t)n, ctx->d_src_nrm.as<float4>());
-        RSREG_HIP(ctx, hipGetLastError());
-    }
-    ctx->have_src_normals = true;
-    return RSREG_OK;
-}
-
-int rsreg_icp_set_source_normals(rsreg_ctx *ctx, const void *normals, size_t n, size_t stride)
-{
-    if (!ctx || (n && !normals) || stride < 12) return RSREG_ERR_INVALID_ARG;
-    if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
-    if (n != ctx->n_source) return fail(ctx, RSREG_ERR_INVALID_ARG, "one normal per source record: the counts differ");
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    // staged like the target's normals: packed into pinned memory of its own, over the link on the upload stream, the main stream behind it
-    RSREG_HIP(ctx, ctx->h2d.ensure());
-    RSREG_HIP(ctx, ctx->ev_src_nrm.ensure());
-    RSREG_HIP(ctx, ctx->ev_src_nrm_packed.ensure());
-    RSREG_HIP(ctx, hipStreamWaitEvent(ctx->h2d.stream, ctx->ev_src_nrm_packed, 0));   // (normals set before may still be read from d_src_nrm_raw)
-    int rc = upload_packed(ctx, ctx->h_src_nrm, ctx->ev_src_nrm, ctx->d_src_nrm_raw, normals, n, stride, ctx->stream, nullptr, nullptr);
-    if (rc) return rc;
-    rc = set_source_normals_device(ctx, ctx->d_src_nrm_raw.as<char>(), n, 12);
-    if (rc) return rc;
-    RSREG_HIP(ctx, hipEventRecord(ctx->ev_src_nrm_packed, ctx->stream));
-    return RSREG_OK;
-}
-
-// (internal, cloud.hip: rsreg_icp_set_source_normals_cloud) normals already in HBM
-int rsreg_icp_set_source_normals_device_(rsreg_ctx *ctx, const void *d_normals, size_t n, size_t stride)
-{
-    if (!ctx || (n && !d_normals) || stride < 12 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    return set_source_normals_device(ctx, static_cast<const char *>(d_normals), n, stride);
-}
-
 int rsreg_icp_plane_sums(rsreg_ctx *ctx, double sums[RSREG_NUM_PLANE_SUMS])
 {
     if (!ctx || !sums) return RSREG_ERR_INVALID_ARG;
@@ -2200,155 +2489,16 @@ int rsreg_plane_solve_from_sums(const double sums[RSREG_NUM_PLANE_SUMS], float t
     return RSREG_OK;
 }
 
-namespace {
-int icp_end(rsreg_ctx *ctx, rsreg_icp_result *result, void *aligned_out, size_t out_stride, const void *source_records);
-}
-
 int rsreg_icp_end(rsreg_ctx *ctx, rsreg_icp_result *result, void *aligned_out, size_t out_stride)
 {
     return icp_end(ctx, result, aligned_out, out_stride, nullptr);
 }
-
-namespace {
-// source_records (nullable): the caller's source records, out_stride bytes each -- every record of aligned_out is then the
-// WHOLE source record with xyz rewritten (what PCL's align(output) leaves: output = input, then xyz <- final * xyz), copied by
-// the host threads that write the aligned positions anyway
-int icp_end(rsreg_ctx *ctx, rsreg_icp_result *result, void *aligned_out, size_t out_stride, const void *source_records)
-{
-    if (!ctx) return RSREG_ERR_INVALID_ARG;
-    IcpState &s = ctx->icp;
-    if (!s.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_icp_begin not called");
-    const size_t n = ctx->n_source;
-    if (aligned_out && n) {
-        if (out_stride < 12) return RSREG_ERR_INVALID_ARG;
-        RSREG_HIP(ctx, ctx->d_tmp.reserve(n * 12 + 16));
-        RSREG_HIP(ctx, ctx->h_stage.reserve(n * 12 + 16));
-        k_apply_final<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_src_all.as<float4>(), (uint32_t)n, to_mat34(s.final_t),
-                                                                                ctx->d_perm.as<uint32_t>(), ctx->d_tmp.as<float>());
-        RSREG_HIP(ctx, hipGetLastError());
-        // home in pieces: while piece k + 1 is on the link, piece k is written into the caller's records by the host's threads
-        const auto t0 = std::chrono::steady_clock::now();
-        const size_t piece = (size_t)1 << 18;
-        const size_t pieces = (n + piece - 1) / piece;
-        while (ctx->ev_home.size() < pieces) {
-            Event e;
-            RSREG_HIP(ctx, e.ensure());
-            ctx->ev_home.push_back(std::move(e));
-        }
-        for (size_t k = 0; k < pieces; ++k) {
-            const size_t lo = k * piece, hi = std::min(n, lo + piece);
-            RSREG_HIP(ctx, hipMemcpyAsync(ctx->h_stage.as<char>() + lo * 12, ctx->d_tmp.as<char>() + lo * 12, (hi - lo) * 12, hipMemcpyDeviceToHost, ctx->stream));
-            RSREG_HIP(ctx, hipEventRecord(ctx->ev_home[k], ctx->stream));
-        }
-        const float *src = ctx->h_stage.as<float>();
-        char *dst = static_cast<char *>(aligned_out);
-        const char *rec = static_cast<const char *>(source_records);
-        // (the caller's records first, all of them, while the positions are still on the link: the positions then land in lines
-        // the cores already own)
-        // (icp_align has started that copy on a thread of its own, beside the iterations: it ends here)
-        if (ctx->records_copy.joinable()) ctx->records_copy.join();
-        else if (rec && rec != dst)
-            host_parallel_for(n, [=](size_t a, size_t b) { std::memcpy(dst + a * out_stride, rec + a * out_stride, (b - a) * out_stride); });
-        for (size_t k = 0; k < pieces; ++k) {
-            const size_t lo = k * piece, hi = std::min(n, lo + piece);
-            RSREG_HIP(ctx, hipEventSynchronize(ctx->ev_home[k]));
-            host_parallel_for(hi - lo, [=](size_t a, size_t b) {
-                const float one = 1.0f;
-                for (size_t i = lo + a; i < lo + b; ++i) {
-                    std::memcpy(dst + i * out_stride, src + 3 * i, 12);
-                    if (out_stride >= 16) std::memcpy(dst + i * out_stride + 12, &one, 4);
-                }
-            });
-        }
-        ctx->host_timing.aligned_copy = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    // (the usual end of an alignment: the last thing this thread did was wait for the sums, and nothing has been queued since)
-    if (!(s.idle_after_sums && !(aligned_out && n))) RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)target_counts(ctx, false);
-#ifdef RSREG_DIAG
-    if (const char *sd_path = tunables().dump_seed) {   // dev: the position every query matched last, and the queries
-        const size_t nq = ctx->n_work;
-        std::vector<int> h(nq);
-        std::vector<float> hq(nq * 4);
-        (void)hipMemcpy(h.data(), ctx->d_seed.ptr, nq * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(hq.data(), ctx->d_cur.ptr, nq * 16, hipMemcpyDeviceToHost);
-        if (FILE *f = std::fopen(sd_path, "wb")) {
-            std::fwrite(h.data(), 4, nq, f);
-            std::fwrite(hq.data(), 4, nq * 4, f);
-            const size_t np_ = ctx->grid.n_points;
-            std::vector<float> hp(np_ * 4);
-            (void)hipMemcpy(hp.data(), ctx->d_tgt_sorted.ptr, np_ * 16, hipMemcpyDeviceToHost);
-            std::fwrite(hp.data(), 4, np_ * 4, f);
-            std::fclose(f);
-        }
-    }
-    if (const char *wt_path = tunables().wave_times) {
-        if (ctx->grid.dense == 1 && ctx->n_work) {
-            const bool light = tunables().wave_times_light;
-            const size_t nw = light ? (size_t)(ctx->icp.sched.ready ? ctx->icp.sched.items : reduce_blocks(ctx->n_work)) * kTileWaves
-                                    : (ctx->n_work + 63) / 64;
-            std::vector<unsigned long long> h(16 * nw + (light ? 0 : (ctx->n_work + 1) / 2));   // wave records, then a uint32 of step counts per lane
-            (void)hipMemcpy(h.data(), ctx->d_brick.ptr, h.size() * 8, hipMemcpyDeviceToHost);
-            if (FILE *f = std::fopen(wt_path, "wb")) {
-                std::fwrite(h.data(), 8, h.size(), f);
-                std::fclose(f);
-            }
-        }
-    }
-#endif
-    if (result) {
-        std::memset(result, 0, sizeof(*result));
-        std::memcpy(result->transform, s.final_t.m, 64);
-        result->converged = s.converged;
-        result->state = s.state;
-        result->iterations = s.iterations;
-        result->n_correspondences = s.ncorr;
-        result->mse = s.cur_mse;
-        std::memcpy(result->sums_last, s.sums_last, sizeof(s.sums_last));
-        result->n_nn_launches = s.n_nn_launches;
-        result->n_scheduled_launches = s.n_sched_launches;
-        if (ctx->profiling) {
-            result->ms_nn = sum_events(ctx, ctx->ev_nn);
-#ifdef RSREG_DIAG
-            if (tunables().dump_nn_ms) {   // diagnostic builds: duration of every search launch of this call
-                std::fprintf(stderr, "[rsreg] search launches (us):");
-                for (auto &p : ctx->ev_nn) {
-                    float t = 0;
-                    (void)hipEventElapsedTime(&t, ctx->ev_pool[p.first], ctx->ev_pool[p.second]);
-                    std::fprintf(stderr, " %.1f", t * 1e3);
-                }
-                std::fprintf(stderr, "\n");
-            }
-#endif
-            result->ms_reduce = sum_events(ctx, ctx->ev_reduce);
-            if (ctx->ev_reduce.empty())   // fused pipelines: everything between two consecutive search kernels
-                for (size_t k = 0; k + 1 < ctx->ev_nn.size(); ++k) {
-                    float t = 0;
-                    if (hipEventElapsedTime(&t, ctx->ev_pool[ctx->ev_nn[k].second], ctx->ev_pool[ctx->ev_nn[k + 1].first]) == hipSuccess)
-                        result->ms_reduce += t;
-                }
-            result->ms_transform = sum_events(ctx, ctx->ev_transform);
-            result->ms_allreduce = sum_events(ctx, ctx->ev_allreduce);   // (already inside ms_reduce in the fused pipelines)
-            result->ms_total = result->ms_nn + result->ms_reduce + result->ms_transform;
-        }
-    }
-    s.active = 0;
-    ctx->icp_fit_ok = true;   // getFitnessScore: this alignment's source, final transform and target
-    ctx->icp_fit_t = s.final_t;
-    return RSREG_OK;
-}
-}  // namespace
 
 int rsreg_ctx_host_timing(rsreg_ctx *ctx, rsreg_host_timing *out)
 {
     if (!ctx || !out) return RSREG_ERR_INVALID_ARG;
     *out = ctx->host_timing;
     return RSREG_OK;
-}
-
-namespace {
-int icp_align(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, rsreg_icp_result *result, void *aligned_out, size_t out_stride,
-              const void *source_records);
 }
 
 int rsreg_icp_align(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, rsreg_icp_result *result,
@@ -2364,66 +2514,10 @@ int rsreg_icp_align_records(rsreg_ctx *ctx, const float *guess, const rsreg_icp_
     return icp_align(ctx, guess, params, result, aligned_out, stride, source_records);
 }
 
-namespace {
-int icp_align(rsreg_ctx *ctx, const float *guess, const rsreg_icp_params *params, rsreg_icp_result *result, void *aligned_out, size_t out_stride,
-              const void *source_records)
-{
-    const auto t_align0 = std::chrono::steady_clock::now();
-    struct AlignClock {   // (whatever way the call ends: begin .. the last iteration + the aligned cloud's way home)
-        rsreg_ctx *c;
-        std::chrono::steady_clock::time_point t0;
-        ~AlignClock() { if (c) c->host_timing.align = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - c->host_timing.aligned_copy; }
-    } align_clock{ctx, t_align0};
-    if (ctx) ctx->host_timing.aligned_copy = 0;
-    // `output = input`: the caller's records go into the output on a thread of their own (the pool's threads under it) while this
-    // thread queues and waits for the iterations; icp_end joins it before the aligned positions are written over the records
-    struct CopyGuard {   // (an error on the way: the copy still owns aligned_out)
-        rsreg_ctx *c;
-        ~CopyGuard() { if (c && c->records_copy.joinable()) c->records_copy.join(); }
-    } copy_guard{ctx};
-    if (ctx && source_records && aligned_out && source_records != aligned_out && ctx->n_source && out_stride >= 12) {
-        const size_t n_rec = ctx->n_source;
-        const char *rec = static_cast<const char *>(source_records);
-        char *dst = static_cast<char *>(aligned_out);
-        ctx->records_copy = std::thread([=] {
-            host_parallel_for(n_rec, [=](size_t a, size_t b) { std::memcpy(dst + a * out_stride, rec + a * out_stride, (b - a) * out_stride); });
-        });
-    }
-    int rc = rsreg_icp_begin(ctx, guess, params);
-    if (rc) return rc;
-    int done = 0;
-    double sums[RSREG_NUM_PLANE_SUMS];   // (the 17 of a point-to-point iteration, or the 32 of a point-to-plane one)
-    const bool plane = plane_on(*params);     // point-to-plane: staged, with its own sums and solve
-    const bool filtered = weights_on(ctx) || plane;   // the optional correspondence filters and the rejector chain run between the staged kernels
-    const bool scan = ctx->grid.dense == 2;   // no index: the staged kernels (search over the whole target, sums)
-    const bool fused = !filtered && !scan && (params->pipeline_mode == RSREG_PIPELINE_FUSED || params->pipeline_mode == RSREG_PIPELINE_DEVICE_LOOP);
-    if (!filtered && !scan && params->pipeline_mode == RSREG_PIPELINE_DEVICE_LOOP && params->criteria_mode == RSREG_CRITERIA_FIXED) {
-        rc = run_device_loop(ctx);
-        if (rc) return rc;
-        done = 1;
-    }
-    while (!done) {
-        if (fused) {
-            rc = launch_fused(ctx, sums, false);
-        } else {
-            rc = apply_pending_transform(ctx);
-            if (!rc) rc = launch_search(ctx);
-            if (!rc) rc = plane ? launch_plane_sums(ctx, sums) : launch_sums(ctx, sums, true);
-        }
-        if (rc) return rc;
-        rc = plane ? update_from_plane_sums(ctx, sums, &done) : update_from_sums(ctx, sums, &done);
-        if (rc) return rc;
-    }
-    return icp_end(ctx, result, aligned_out, out_stride, source_records);
-}
-}  // namespace
-
 // ---------------------------------------------------------------------------------------------------------------------- GICP
 // pcl::GeneralizedIterativeClosestPoint on the staged pipeline (include/rsreg.h holds the contract): the ICP state carries the
 // transform, the search and the counters; an outer iteration is restart (cur = T * source) -> search -> k_gicp_mahalanobis ->
-// { k_gicp_reduce at X -> host solve } -> T = float(X T).  One rank only: nothing is all-reduced.
-static_assert(RSREG_NUM_GICP_SUMS == RSREG_NUM_PLANE_SUMS, "k_gicp_reduce goes through plane_tile_reduce_store and k_final_reduce as the plane sums do");
-
+// { k_gicp_reduce at X -> host solve } -> T = float(X T).  One rank only: nothing is all-reduced.  (Its helpers: gicp_* above.)
 void rsreg_gicp_params_default(rsreg_gicp_params *p)
 {
     if (!p) return;
@@ -2435,32 +2529,6 @@ void rsreg_gicp_params_default(rsreg_gicp_params *p)
     p->transformation_epsilon = 5e-4;
     p->rotation_epsilon = 2e-3;
     p->gicp_epsilon = 1e-3;
-}
-
-// one covariance record per record of the source (the target): from the host (waited for: the buffer has been read) or from HBM
-static int gicp_set_covariances(rsreg_ctx *ctx, bool source, const void *host, const void *dev, size_t n, size_t stride)
-{
-    if (!ctx || (n && !host && !dev) || stride < 48 || (dev && (stride & 7))) return RSREG_ERR_INVALID_ARG;
-    if (source) {
-        if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
-        if (n != ctx->n_source) return fail(ctx, RSREG_ERR_INVALID_ARG, "one covariance per source record: the counts differ");
-    } else {
-        if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
-        if (n != ctx->n_target_raw) return fail(ctx, RSREG_ERR_INVALID_ARG, "one covariance per target record: the counts differ");
-    }
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf &d = source ? ctx->d_gicp_cs : ctx->d_gicp_ct;
-    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (an alignment before this one may still read the buffer)
-    RSREG_HIP(ctx, d.reserve((n + 1) * 48));
-    if (n && host) {
-        RSREG_HIP(ctx, hipMemcpy2DAsync(d.ptr, 48, host, stride, 48, n, hipMemcpyHostToDevice, ctx->stream));
-        RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    } else if (n) {
-        k_gicp_pack_cov<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(static_cast<const char *>(dev), stride, (uint32_t)n, d.as<double>());
-        RSREG_HIP(ctx, hipGetLastError());
-    }
-    (source ? ctx->have_gicp_cs : ctx->have_gicp_ct) = true;
-    return RSREG_OK;
 }
 
 int rsreg_gicp_set_source_covariances(rsreg_ctx *ctx, const void *cov, size_t n, size_t stride)
@@ -2531,63 +2599,6 @@ int rsreg_gicp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out)
     return RSREG_OK;
 }
 
-// the 32 sums at X (column-major double 4 x 4) over the pairs of the last search: launch_plane_sums with k_gicp_reduce
-static int gicp_launch_sums(rsreg_ctx *ctx, const double *X, double *sums)
-{
-    ctx->icp.idle_after_sums = false;
-    const uint32_t n = (uint32_t)ctx->n_work;
-    const uint32_t nb = reduce_blocks(n);
-    RSREG_HIP(ctx, ctx->d_plane_partials.reserve((size_t)nb * RSREG_NUM_GICP_SUMS * 8));
-    Mat34d Xr;
-    for (int c = 0; c < 4; ++c) {
-        Xr.r0[c] = X[c * 4 + 0];
-        Xr.r1[c] = X[c * 4 + 1];
-        Xr.r2[c] = X[c * 4 + 2];
-    }
-    {
-        ScopedEvents ev(ctx, &ctx->ev_reduce);
-        k_gicp_reduce<<<nb, kTile, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), ctx->d_tgt_sorted.as<float4>(),
-                                                     ctx->d_gicp_m.as<double>(), Xr, n, ctx->d_plane_partials.as<double>());
-        RSREG_HIP(ctx, hipGetLastError());
-        k_final_reduce<<<RSREG_NUM_GICP_SUMS, kReduceBlock, 0, ctx->stream>>>(ctx->d_plane_partials.as<double>(), nb, host_sums_target(ctx));
-        RSREG_HIP(ctx, hipGetLastError());
-    }
-    double *h = ctx->h_sums.as<double>();
-    if (ctx->comm) RSREG_HIP(ctx, hipMemcpyAsync(h, ctx->d_sums.ptr, RSREG_NUM_GICP_SUMS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->icp.idle_after_sums = true;
-    (void)target_counts(ctx, false);
-    std::memcpy(sums, h, RSREG_NUM_GICP_SUMS * 8);
-    return RSREG_OK;
-}
-
-static void gicp_identity(double *X)
-{
-    for (int k = 0; k < 16; ++k) X[k] = (k % 5 == 0) ? 1.0 : 0.0;
-}
-
-// C = A B, column-major double 4 x 4, entries ((a0 b0 + a1 b1) + a2 b2) + a3 b3
-static void gicp_mul(const double *A, const double *B, double *C)
-{
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c)
-            C[c * 4 + r] = ((A[0 * 4 + r] * B[c * 4 + 0] + A[1 * 4 + r] * B[c * 4 + 1]) + A[2 * 4 + r] * B[c * 4 + 2]) + A[3 * 4 + r] * B[c * 4 + 3];
-}
-
-// x = scale * pinv(H) b and D = Delta(x), column-major; the rank of the solve (0: x = 0, D = I)
-static int gicp_step(const double *sums, double scale, double (&x)[6], double *D)
-{
-    const int rank = plane_unknowns_from_sums(sums, x);
-    gicp_identity(D);
-    if (rank == 0) return 0;
-    for (int i = 0; i < 6; ++i) x[i] *= scale;
-    double d12[12];
-    plane_matrix_from_unknowns(x, d12);
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 4; ++c) D[c * 4 + r] = d12[r * 4 + c];
-    return rank;
-}
-
 int rsreg_gicp_sums(rsreg_ctx *ctx, const double X[16], double sums[RSREG_NUM_GICP_SUMS])
 {
     if (!ctx || !sums) return RSREG_ERR_INVALID_ARG;
@@ -2615,19 +2626,11 @@ int rsreg_gicp_update(rsreg_ctx *ctx, const double X[16], const double sums[RSRE
     IcpState &s = ctx->icp;
     GicpState &g = ctx->gicp;
     std::memcpy(g.sums_last, sums, sizeof(g.sums_last));
-    std::memset(s.sums_last, 0, sizeof(s.sums_last));
-    s.sums_last[0] = sums[0];
-    s.sums_last[16] = sums[1];
-    s.ncorr = (uint64_t)(sums[0] + 0.5);
+    fill_sums_last(s, sums[0], sums[1]);
     g.inner_evaluations += inner_evaluations;
     g.have_search = false;
     s.have_search = false;
-    if (s.ncorr < 4) {
-        s.state = RSREG_CONV_NO_CORRESPONDENCES;
-        s.converged = 0;
-        *done = 1;
-        return RSREG_OK;
-    }
+    if (too_few_pairs(s, sums[0], 4, done)) return RSREG_OK;
     {
         double xs[6];
         g.rank_last = plane_unknowns_from_sums(sums, xs);
@@ -2808,84 +2811,7 @@ int rsreg_transform_cloud(rsreg_ctx *ctx, const void *in, void *out, size_t n, s
     return RSREG_OK;
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------- getFitnessScore
-namespace rsreg {
-namespace {
-
-// the float bound the search prunes with: never below max_range, so that no d2 with (double)d2 <= max_range is dropped
-float fit_limit2(double max_range)
-{
-    if (!(max_range >= 0)) return -1.0f;   // (negative or NaN: nothing is in range)
-    if (max_range >= (double)FLT_MAX) return __builtin_huge_valf();
-    float f = (float)max_range;
-    if ((double)f < max_range) f = std::nextafter(f, FLT_MAX);
-    return f;
-}
-
-}  // namespace
-
-int fitness_sums(rsreg_ctx *ctx, PointGrid &fx, const float4 *tgt, size_t n_tgt, const float4 *src, const uint32_t *perm, size_t n,
-                 const Mat4f &T, double max_range, double sums[2])
-{
-    hipStream_t st = ctx->stream;
-    if (n_tgt > 0xfffffff0ull || n > 0xfffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "cloud too large");
-    if (!fx.built) {   // box (one round trip), counts and occupancy words, prefix sum, scatter: into fx's own buffers
-        RSREG_HIP(ctx, ctx->h_fit.reserve(64));
-        int rc = grid_build<FitGridPolicy>(ctx, fx, TargetRecords{tgt}, (uint32_t)n_tgt, 1, ctx->h_fit.as<uint32_t>());
-        if (rc) return rc;
-    }
-    sums[0] = sums[1] = 0;
-    if (n == 0) return RSREG_OK;
-    const uint32_t nb = div_up((uint32_t)n, kBlock);
-    RSREG_HIP(ctx, ctx->d_fit_d2.reserve(n * 4 + 16));
-    RSREG_HIP(ctx, ctx->d_fit_partials.reserve((size_t)nb * 2 * 8));
-    RSREG_HIP(ctx, ctx->d_fit_sums.reserve(64));
-    RSREG_HIP(ctx, ctx->h_fit.reserve(64));
-    k_fit_search<<<nb, kBlock, 0, st>>>(src, (uint32_t)n, to_mat34(T), perm, grid_dev(fx), fit_limit2(max_range), max_range,
-                                        ctx->d_fit_d2.as<float>());
-    RSREG_HIP(ctx, hipGetLastError());
-    k_fit_tiles<<<nb, kBlock, 0, st>>>(ctx->d_fit_d2.as<float>(), (uint32_t)n, ctx->d_fit_partials.as<double>());
-    RSREG_HIP(ctx, hipGetLastError());
-    k_final_reduce<<<2, kReduceBlock, 0, st>>>(ctx->d_fit_partials.as<double>(), nb, ctx->d_fit_sums.as<double>());
-    RSREG_HIP(ctx, hipGetLastError());
-    double *h = ctx->h_fit.as<double>();
-    RSREG_HIP(ctx, hipMemcpyAsync(h, ctx->d_fit_sums.ptr, 16, hipMemcpyDeviceToHost, st));
-    RSREG_HIP(ctx, hipStreamSynchronize(st));
-    sums[0] = h[0];
-    sums[1] = h[1];
-    return RSREG_OK;
-}
-
-}  // namespace rsreg
-
-namespace {
-
-// this rank's (count, sum of d2) of the last ICP alignment (rsreg_icp_fitness_sums / _score)
-int icp_fitness_block(rsreg_ctx *ctx, double max_range, double sums[2])
-{
-    if (!ctx->icp_fit_ok) return fail(ctx, RSREG_ERR_STATE, "no ICP alignment of the current source and target");
-    RSREG_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = join_source(ctx);   // (nothing pending after an alignment; kept for the contract: the source's buffers are final)
-    if (rc) return rc;
-    rc = target_counts(ctx, true);   // (grid.n_points of a counting build nobody has waited for is only a bound)
-    if (rc) return rc;
-    const size_t n_tgt = ctx->grid.dense == 2 ? ctx->n_target_raw : ctx->grid.n_points;
-    return fitness_sums(ctx, ctx->fit_icp, ctx->d_tgt_sorted.as<float4>(), n_tgt, ctx->d_src_all.as<float4>(), ctx->d_perm.as<uint32_t>(),
-                        ctx->n_source, ctx->icp_fit_t, max_range, sums);
-}
-
-void fitness_result(const double sums[2], double *score, uint64_t *n_within)
-{
-    if (score) *score = sums[0] > 0 ? sums[1] / sums[0] : DBL_MAX;
-    if (n_within) *n_within = (uint64_t)sums[0];
-}
-
-}  // namespace
-
-extern "C" {
-
+// ---- getFitnessScore (fitness_sums and its helpers above)
 int rsreg_icp_fitness_sums(rsreg_ctx *ctx, double max_range, double sums[2])
 {
     if (!ctx || !sums) return RSREG_ERR_INVALID_ARG;

@@ -1328,20 +1328,6 @@ __global__ void k_scan_finish(const unsigned long long *keys, const float4 *cur,
     corr_d2[s] = hit ? __uint_as_float((uint32_t)(k >> 32)) : 0.0f;
 }
 
-// corr (sorted source order, position in the sorted target) -> caller's order and indices
-__global__ __launch_bounds__(kBlock) void k_export_corr(const int *corr_pos, const float *corr_d2, const float4 *tgt,
-                                                        const uint32_t *perm, const uint32_t *uniq_of, uint32_t n,
-                                                        int *index_out, float *d2_out)
-{
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;   // sorted position of an ORIGINAL source point
-    if (j >= n) return;
-    const uint32_t u = uniq_of[j];
-    const int pos = corr_pos[u];
-    const uint32_t o = perm ? perm[j] : j;
-    index_out[o] = pos >= 0 ? (int)tgt_idx(tgt[pos]) : -1;
-    d2_out[o] = corr_d2[u];
-}
-
 // ------------------------------------------------------------------------ optional correspondence filters
 // (rsreg_icp_params.use_reciprocal_correspondences / trim_overlap_ratio; staged pipeline only)
 
@@ -1365,7 +1351,7 @@ __global__ __launch_bounds__(kBlock) void k_recip_points(const float4 *cur, cons
 // at indices 5 and 900 of A, one of B at 300: keep 5 and 300, drop 900).  Every record j (sorted position) gets the key
 // (d2 bits << idx_bits) | caller's index; records whose copy is not in play (no match, or beyond cw[u]) get d2 bits
 // 0x7fffffff, above every distance.  The copies of u are ordered by caller's index and share d2, so those the cut keeps
-// are the first of u's copies in play: what k_export_corr_w expects of cw[u].
+// are the first of u's copies in play: what k_export_corr<CorrKeep::copies> expects of cw[u].
 // (sort_scratch: the state of the sort that follows, cleared on the way -- osort.hpp)
 // kFlags (the trim as an entry of the rejector chain, rejector_kernels.hpp): cw holds one in-play flag per RECORD j instead,
 // and the cut clears the flags of the records it drops.
@@ -1438,18 +1424,24 @@ __global__ __launch_bounds__(kTile) void k_cov_reduce_w(const float4 *cur, const
     tile_reduce_store(a, partials, gridDim.x);
 }
 
-// determineCorrespondences' list with the filters applied: of the copies of a distinct point the first cw[u] (lowest indices) keep their match
-// (the reciprocal filter keeps the first copy alone, the trim a prefix of the copies in play: k_trim_keys)
-__global__ __launch_bounds__(kBlock) void k_export_corr_w(const int *corr_pos, const float *corr_d2, const uint32_t *cw, const float4 *tgt,
-                                                          const uint32_t *perm, const uint32_t *uniq_of, const uint32_t *first, uint32_t n,
-                                                          int *index_out, float *d2_out)
+// corr (sorted source order, position in the sorted target) -> caller's order and indices: determineCorrespondences' list.
+// Record j (sorted position of an ORIGINAL source point) of distinct point u keeps u's match when
+//   matched: u has one (no filter ran: `keep` and `first` are not read);
+//   copies:  ... and j is among the first keep[u] = cw[u] copies of u, the lowest indices (the two filters: the reciprocal one
+//            keeps the first copy alone, the trim a prefix of the copies in play, k_trim_keys);
+//   flags:   ... and keep[j], the record's flag behind the rejector chain (rejector_kernels.hpp), is set.
+enum class CorrKeep { matched, copies, flags };
+template <CorrKeep kKeep>
+__global__ __launch_bounds__(kBlock) void k_export_corr(const int *corr_pos, const float *corr_d2, const uint32_t *keep, const float4 *tgt,
+                                                        const uint32_t *perm, const uint32_t *uniq_of, const uint32_t *first, uint32_t n,
+                                                        int *index_out, float *d2_out)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const uint32_t u = uniq_of[j];
     const int pos = corr_pos[u];
     const uint32_t o = perm ? perm[j] : j;
-    const bool kept = pos >= 0 && (j - first[u]) < cw[u];
+    const bool kept = pos >= 0 && (kKeep == CorrKeep::matched || (kKeep == CorrKeep::copies ? (j - first[u]) < keep[u] : keep[j] != 0u));
     index_out[o] = kept ? (int)tgt_idx(tgt[pos]) : -1;
     d2_out[o] = corr_d2[u];
 }

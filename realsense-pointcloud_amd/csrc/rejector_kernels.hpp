@@ -42,7 +42,7 @@ __device__ __forceinline__ void rej_block_count(uint32_t kept, uint32_t *dst)
 }
 
 // flags[j] = record j is in play behind the search, the reciprocal test and trim_overlap_ratio: its point has a match and it
-// is among the first cw[u] copies (k_export_corr_w's rule)
+// is among the first cw[u] copies (the rule of k_export_corr<CorrKeep::copies>)
 __global__ __launch_bounds__(kBlock) void k_rej_flags_init(const int *corr_pos, const uint32_t *cw, const uint32_t *uniq_of, const uint32_t *first,
                                                            uint32_t n_source, uint32_t *flags, uint32_t *cnt_out)
 {
@@ -223,19 +223,7 @@ __global__ __launch_bounds__(kBlock) void k_rej_fold_pos(const uint32_t *cw, uin
     if (u < n && cw[u] == 0u) corr_pos[u] = -1;
 }
 
-// determineCorrespondences' list behind the chain: the records whose flag is set keep their match
-__global__ __launch_bounds__(kBlock) void k_export_corr_flags(const int *corr_pos, const float *corr_d2, const uint32_t *flags, const float4 *tgt,
-                                                              const uint32_t *perm, const uint32_t *uniq_of, uint32_t n, int *index_out, float *d2_out)
-{
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t u = uniq_of[j];
-    const int pos = corr_pos[u];
-    const uint32_t o = perm ? perm[j] : j;
-    const bool kept = pos >= 0 && flags[j] != 0u;
-    index_out[o] = kept ? (int)tgt_idx(tgt[pos]) : -1;
-    d2_out[o] = corr_d2[u];
-}
+// (determineCorrespondences' list behind the chain, the records whose flag is set: icp_kernels.hpp, k_export_corr<CorrKeep::flags>)
 
 // ---- the source's normals, one float4 {nx, ny, nz, 0} per source RECORD in the caller's order.  They turn with the source:
 // by the guess when an alignment begins, by every increment after it -- xform's arithmetic without the translation,

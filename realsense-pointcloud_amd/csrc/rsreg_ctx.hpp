@@ -61,9 +61,14 @@ constexpr uint32_t kHsWords = 64;
 // knn.d_box and filt.host (pinned), the cloud filters' (filters.hip): the word behind the box is where one launch leaves a
 // flag or a count and where it lands at home
 constexpr uint32_t kFiltWord = kBoxWords;
-// the target's box borrows its scratch: the head of h_sums (pinned double[64]) is where the box, or the head of d_misc, lands;
+// d_sums and h_sums (pinned) hold so many doubles: room for an iteration's sums of every kind (k_final_reduce leaves them in one
+// or the other: icp.hip, host_sums_target).
+// the target's box borrows its scratch: the head of h_sums is where the box, or the head of d_misc, lands;
 // d_comm holds the partials behind the 64 doubles of an allreduce
-constexpr size_t kSumsBytes = 64 * sizeof(double);
+constexpr size_t kSumsDoubles = 64;
+constexpr size_t kSumsBytes = kSumsDoubles * sizeof(double);
+static_assert(RSREG_NUM_SUMS <= kSumsDoubles && RSREG_NUM_PLANE_SUMS <= kSumsDoubles && RSREG_NUM_GICP_SUMS <= kSumsDoubles,
+              "d_sums / h_sums hold the sums of an ICP, a point-to-plane and a GICP iteration");
 constexpr size_t kCommBytes = 64 * sizeof(double);
 constexpr size_t kCommPartialsAt = kCommBytes;      // (bytes)
 static_assert(kMiscBoxMax < kMiscStats && kMiscStats + 4 <= kCounterWords && kCounterWords <= kMiscMaxCount && kMiscMaxCount < kMiscWords, "d_misc");
@@ -279,6 +284,15 @@ struct DepthScratch {
     Event ev_up;         // behind the copy: the staging buffer is free again
 };
 
+// One normal per RECORD of the ICP target or source, in the caller's order (icp.hip: set_record_normals)
+struct RecordNormals {
+    bool have = false;
+    DevBuf d;                  // float4 {nx, ny, nz, 0} per record
+    DevBuf d_raw;              // packed normals of a host buffer as they came over the link (n x float3) ...
+    PinnedBuf h;               // ... their staging buffer, on the upload stream like the clouds' own ...
+    Event ev, ev_packed;       // ... the event behind its last copy, and: the main stream has read d_raw (made at first use)
+};
+
 // An ordered chain of correspondence rejectors (include/rsreg.h: rsreg_icp_set_rejectors); n == 0: none
 struct RejectorChain {
     int n = 0;
@@ -295,7 +309,7 @@ struct IcpState {
     rsreg_icp_params prm;
     RejectorChain chain;             // the context's chain as rsreg_icp_begin found it (GICP: none)
     bool chain_stats = false;        // d_rej_words holds the counts of this alignment's last search
-    bool normals_restart_pending = false;   // d_src_nrm_cur = guess * d_src_nrm not done yet (a chain with the normal test)
+    bool normals_restart_pending = false;   // d_src_nrm_cur = guess * src_nrm.d not done yet (a chain with the normal test)
     Mat4f final_t, t_inc;
     int iterations = 0, state = 0, converged = 0, similar = 0, active = 0;
     double prev_mse = 0, cur_mse = 0;
@@ -368,13 +382,9 @@ struct rsreg_ctx {
     const char *scan_raw = nullptr;      // ... and the records the index is built from if an alignment needs it after all
     size_t scan_stride = 0;
     uint64_t tgt_cloud_id = 0, tgt_cloud_version = 0;   // the device cloud the ICP target index was built from (0: none)
-    // point-to-plane ICP: the target's normals, float4 {nx, ny, nz, 0} per target RECORD in the caller's order (the sorted
-    // target records carry that index); dropped by every rsreg_icp_set_target*
-    bool have_normals = false;
-    rsreg::DevBuf d_normals;
-    rsreg::DevBuf d_nrm_raw;      // packed normals of a host buffer as they came over the link (n x float3) ...
-    rsreg::PinnedBuf h_nrm;       // ... their staging buffer (rsreg_icp_set_target_normals, on the upload stream like the target's) ...
-    rsreg::Event ev_nrm, ev_nrm_packed;   // ... the event behind its last copy, and: the main stream has read d_nrm_raw (made at first use)
+    // point-to-plane ICP and the surface normal rejector: the target's normals per target RECORD in the caller's order (the
+    // sorted target records carry that index); dropped by every rsreg_icp_set_target*
+    rsreg::RecordNormals tgt_nrm;
     rsreg::DevBuf d_plane_partials;   // double[32][blocks] of k_plane_reduce (and of k_gicp_reduce)
     // GICP (rsreg_gicp_*): six doubles per source / target RECORD in the caller's order, dropped by the next rsreg_icp_set_source* /
     // rsreg_icp_set_target*; the Mahalanobis matrices of the last search, six doubles per distinct source point
@@ -418,7 +428,7 @@ struct rsreg_ctx {
     rsreg::DevBuf d_corr_d2;      // float
     rsreg::DevBuf d_seed;         // int32: nearest target found in the previous iteration (-1 none)
     rsreg::DevBuf d_partials;     // double[blocks][17]
-    rsreg::DevBuf d_sums;         // double[17]
+    rsreg::DevBuf d_sums;         // double[kSumsDoubles]: an iteration's 17, 32 plane or 32 GICP sums where a communicator exists (icp.hip: host_sums_target)
     rsreg::DevBuf d_icp_state;    // IcpDevState of the device-resident loop
     // optional correspondence filters (reciprocal correspondences, trimmed rejector)
     rsreg::DevBuf d_corr_w;       // uint32 per distinct source point: how many of its copies keep their match
@@ -430,14 +440,11 @@ struct rsreg_ctx {
     rsreg::DevBuf d_rej_flags;    // uint32 per ORIGINAL source record (sorted position): in play behind the chain so far
     rsreg::DevBuf d_rej_words;    // kRejWords uint32: the counts in front of and behind every entry, the medians, the select's digit counts
     rsreg::DevBuf d_rej_table;    // one-to-one: one (d2, caller's index) key per position of the sorted target
-    // the source's normals, float4 {nx, ny, nz, 0} per source RECORD in the caller's order: as handed in, and as they stand
-    // now (turned by the guess and every increment); dropped by every rsreg_icp_set_source*
-    bool have_src_normals = false;
-    rsreg::DevBuf d_src_nrm, d_src_nrm_cur;
-    rsreg::DevBuf d_src_nrm_raw;          // packed normals of a host buffer as they came over the link (n x float3) ...
-    rsreg::PinnedBuf h_src_nrm;           // ... their staging buffer, on the upload stream like the target's normals ...
-    rsreg::Event ev_src_nrm, ev_src_nrm_packed;   // ... the event behind its last copy, and: the main stream has read d_src_nrm_raw
-    rsreg::PinnedBuf h_sums;      // pinned double[64]
+    // the source's normals per source RECORD in the caller's order: as handed in, and as they stand now (turned by the guess
+    // and every increment); dropped by every rsreg_icp_set_source*
+    rsreg::RecordNormals src_nrm;
+    rsreg::DevBuf d_src_nrm_cur;
+    rsreg::PinnedBuf h_sums;      // pinned double[kSumsDoubles]
     // next_*: the box of the cloud about to be set, when its handle knows it (consumed by build_grid / load_source_queue);
     // last_*: what the last index build / source load started from (valid: computed or taken over)
     rsreg::CloudBox next_tgt_box, last_tgt_box, next_src_box, last_src_box;
