@@ -554,6 +554,74 @@ int rsreg_gicp_align(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params
 int rsreg_gicp_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, rsreg_gicp_result *result,
                            rsreg_cloud *aligned_out);
 
+/* ---- GICP6D: pcl::GeneralizedIterativeClosestPoint6D (registration/gicp6d.h) -------------------------------------------------
+ * GICP whose correspondences are nearest neighbours in (x, y, z, w L', w a', w b'): the colour of a PointXYZRGB record decides
+ * between candidates that geometry cannot tell apart (a wall, a floor, a table top leave the in-plane part of a pose free under
+ * plane-to-plane ICP).  The covariances, the Mahalanobis pass, the 32 sums, the step control and the stopping rule are GICP's,
+ * above, untouched.  RECALLED from PCL 1.9.1 (gicp6d.h / gicp6d.cpp; no test here holds them against PCL): the two-table shape of RGB2Lab and
+ * its coefficients, the normalisation L / 100, a / 120, b / 120, the default weight 0.032, the rescaling of the colour
+ * coordinates before the tree sees the vector, FLANN's L2_Simple over the six coordinates.  THIS LIBRARY'S: everything marked
+ * "deviation" below, the clamps, the gate and tie rules, what a non-finite coordinate does, and the index.
+ *
+ * COLOUR (rsreg_lab_tables, rsreg_rgb_to_lab, rsreg_cloud_lab).  Every operation is a float operation rounded once, nothing fused:
+ *    r, g, b = bits 16-23, 8-15, 0-7 of the uint32 at byte 16 of the record (as rsreg_extract_edge_features reads it); a cloud of
+ *      stride < 20: RSREG_ERR_INVALID_ARG.
+ *    S[i], i = 0 .. 255:  f = i / 255.0;   f > 0.04045 ? pow((f + 0.055) / 1.055, 2.4) : f / 12.92     in double, rounded to float
+ *    F[i], i = 0 .. 3999: f = i / 4000.0;  f > 0.008856 ? cbrt(f) : 7.787 * f + 16.0 / 116.0           in double, rounded to float
+ *      (deviation: PCL fills both tables with powf in float)
+ *    x = (S[r] * 0.412453f + S[g] * 0.357580f) + S[b] * 0.180423f
+ *    y = (S[r] * 0.212671f + S[g] * 0.715160f) + S[b] * 0.072169f
+ *    z = (S[r] * 0.019334f + S[g] * 0.119193f) + S[b] * 0.950227f
+ *    vx = x / 0.95047f, vy = y, vz = z / 1.08883f;  table index (int)(v * 4000.0f) clamped to 0 .. 3999
+ *      (deviation: PCL does not clamp, and white indexes one past its table)
+ *    L = 116.0f * F[vy] - 16.0f, capped at 100;  a = 500.0f * (F[vx] - F[vy]),  b = 200.0f * (F[vy] - F[vz]), both clamped to +-120
+ *    out = L / 100.0f, a / 120.0f, b / 120.0f  (normalised as PCL's 6-D point is).  The colour does not depend on x, y, z: a record
+ *      with non-finite coordinates still gets its colour.
+ * rsreg_lab_tables (host only, no context) returns S and F as the library uses them; rsreg_rgb_to_lab (host only) is the formula
+ * over n packed words, lab_out n x 3 floats; rsreg_cloud_lab writes 16-byte records {L', a', b', 0.0f} with the width, height and
+ * is_dense of `in` (out != in) -- the bytes of rsreg_rgb_to_lab.
+ *
+ * COLOURS OF AN ALIGNMENT (rsreg_gicp_set_source_lab / _target_lab and their _cloud forms): one record per cloud RECORD in the
+ * caller's order whose first 12 bytes are L', a', b' (stride >= 12; a device cloud: a multiple of 4 -- what rsreg_cloud_lab wrote
+ * fits), n = the cloud's record count (else RSREG_ERR_INVALID_ARG).  Lifetime and error codes as the covariance setters': set
+ * after the cloud (RSREG_ERR_NO_SOURCE / _NO_TARGET before), dropped by the next rsreg_icp_set_source* / rsreg_icp_set_target*.
+ *    The target's setter reads the target's RECORDS once more (their x, y, z): the alignment's index keeps one point per distinct
+ *    position, and records that are copies in space but differ in colour are different candidates here.  A target from a host
+ *    buffer has them in the context; a target set from device memory or a cloud handle must still lie there unchanged
+ *    (RSREG_ERR_STATE if the handle's buffer has changed hands since).
+ *    The source's setter takes a source that was merged into weighted distinct points (more than 65 536 records) apart again:
+ *    EVERY SOURCE RECORD IS ITS OWN PAIR WITH ITS OWN COLOUR, W = 1 in the sums, and rsreg_icp_grid_info's n_source_distinct is the
+ *    record count from then on, for every alignment of that source (same pairs per record; the sums add the same terms one by one).
+ *
+ * SEARCH (after rsreg_gicp6d_begin, rsreg_gicp_search runs it).  c = w * lab', w = (float)lab_weight, one float multiply per
+ * coordinate, once per begin.  For a working point p (the source record under the current transform) and a target record t:
+ *    d6 = ((((dx^2 + dy^2) + dz^2) + dL^2) + da^2) + db^2     differences, squares and sums each rounded once; the 3-D part is d2 of
+ *      rsreg_icp_search, so w = 0 with finite colours gives that search's pairs
+ *    the pair of p is the target record of smallest (d6, record index) among ALL finite target records -- exact, ties to the lowest
+ *      index; a candidate whose d6 is NaN is skipped; a source record whose position or scaled colour is not finite gets no pair
+ *    rejected (index -1) iff (double)d6 > max_correspondence_distance^2: rsreg_gicp_search's rule on the 6-D value.
+ * index_out / sqr_dist_out, sums [1], mse and n_correspondences report d6.  The index is a grid over x, y, z of its own (every
+ * finite record but those whose six coordinates equal, bit for bit, a record's of lower index: they can never win), built by the
+ * first rsreg_gicp6d_begin after the target's colours were set; a bound on the 3-D
+ * part bounds d6 (adding non-negative terms with round-to-nearest is monotone), so the walk is exact at any gate and for queries
+ * anywhere.  rsreg_icp_fitness_score stays 3-D (PCL's getFitnessScore uses the plain tree).
+ *
+ * rsreg_gicp6d_begin = rsreg_gicp_begin + the colour checks: colours missing on either side RSREG_ERR_STATE; lab_weight NaN,
+ * infinite or negative RSREG_ERR_INVALID_ARG.  rsreg_gicp_sums, _update and _end are unchanged; a later rsreg_gicp_begin searches in
+ * three dimensions again.  rsreg_gicp6d_align[_cloud] runs rsreg_gicp_align's loop; PCL's default weight is 0.032. */
+int rsreg_lab_tables(float srgb_out[256], float f_out[4000]);
+int rsreg_rgb_to_lab(const uint32_t *rgba, size_t n, float *lab_out);
+int rsreg_cloud_lab(rsreg_ctx *ctx, const rsreg_cloud *in, rsreg_cloud *out);
+int rsreg_gicp_set_source_lab(rsreg_ctx *ctx, const void *lab, size_t n, size_t stride);
+int rsreg_gicp_set_target_lab(rsreg_ctx *ctx, const void *lab, size_t n, size_t stride);
+int rsreg_gicp_set_source_lab_cloud(rsreg_ctx *ctx, const rsreg_cloud *lab);
+int rsreg_gicp_set_target_lab_cloud(rsreg_ctx *ctx, const rsreg_cloud *lab);
+int rsreg_gicp6d_begin(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, double lab_weight);
+int rsreg_gicp6d_align(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, double lab_weight,
+                       rsreg_gicp_result *result, void *aligned_out, size_t out_stride);
+int rsreg_gicp6d_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, double lab_weight,
+                             rsreg_gicp_result *result, rsreg_cloud *aligned_out);
+
 /* ---- pcl::transformPointCloud(in, out, Matrix4f) ------------------------------------ */
 /* incremental_icp.hpp:63, icp_edge...hpp:116-117, ndt_edge...hpp:104-105.  in == out is
  * allowed.  Records are copied whole (stride bytes) and xyz rewritten; when !is_dense,

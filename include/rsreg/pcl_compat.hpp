@@ -733,6 +733,7 @@ template <typename PointSource, typename PointTarget> class GeneralizedIterative
         rsreg_gicp_params_default(&prm_);
         final_ = Matrix4f::Identity();
     }
+    virtual ~GeneralizedIterativeClosestPoint() = default;
     void setCorrespondenceRandomness(int k) { prm_.k_correspondences = k; source_cov_dirty_ = target_cov_dirty_ = true; }
     int getCorrespondenceRandomness() const { return prm_.k_correspondences; }
     void setRotationEpsilon(double e) { prm_.rotation_epsilon = e; }
@@ -755,10 +756,12 @@ template <typename PointSource, typename PointTarget> class GeneralizedIterative
     {
         if (!source_ || !target_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputSource / setInputTarget not called");
         rsreg_ctx *c = ctx_->get();
+        bool source_new = false, target_new = false;
         if (source_dirty_ || ctx_->icp_source_owner != this) {
             check(rsreg_icp_set_source(c, source_->points.data(), source_->size(), sizeof(PointSource), source_->is_dense), c);
             source_dirty_ = false;
             source_cov_dirty_ = true;   // (a new source drops the covariances of the one before)
+            source_new = true;
             ctx_->icp_source_owner = this;
         }
         if (target_dirty_ || ctx_->icp_target_owner != this) {
@@ -766,6 +769,7 @@ template <typename PointSource, typename PointTarget> class GeneralizedIterative
                                        prm_.max_correspondence_distance), c);
             target_dirty_ = false;
             target_cov_dirty_ = true;
+            target_new = true;
             ctx_->icp_target_owner = this;
         }
         if (source_cov_dirty_) {
@@ -778,9 +782,10 @@ template <typename PointSource, typename PointTarget> class GeneralizedIterative
             else compute_covariances_(*target_, false);
             target_cov_dirty_ = false;
         }
+        sync_more_(c, source_new, target_new);
         PointCloud<PointSource> tmp;
         detail::copy_aligned(*source_, tmp);   // `output = input`, then xyz <- final * xyz
-        check(rsreg_gicp_align(c, guess.data(), &prm_, &res_, tmp.size() ? tmp.points.data() : nullptr, sizeof(PointSource)), c);
+        check(run_(c, guess.data(), tmp.size() ? tmp.points.data() : nullptr, sizeof(PointSource)), c);
         std::memcpy(final_.m, res_.transform, sizeof(final_.m));
         output = std::move(tmp);
     }
@@ -797,7 +802,10 @@ template <typename PointSource, typename PointTarget> class GeneralizedIterative
     }
     const rsreg_gicp_result &result() const { return res_; }
 
-  private:
+  protected:
+    // what a derived alignment (GeneralizedIterativeClosestPoint6D) hands the context besides clouds and covariances, and its loop
+    virtual void sync_more_(rsreg_ctx *, bool /*source_new*/, bool /*target_new*/) {}
+    virtual int run_(rsreg_ctx *c, const float *guess, void *aligned_out, size_t stride) { return rsreg_gicp_align(c, guess, &prm_, &res_, aligned_out, stride); }
     template <typename PointT> void compute_covariances_(const PointCloud<PointT> &cloud, bool source)
     {
         rsreg_ctx *c = ctx_->get();
@@ -818,6 +826,65 @@ template <typename PointSource, typename PointTarget> class GeneralizedIterative
     TargetPtr target_;
     CovariancesPtr source_cov_, target_cov_;
     bool source_dirty_ = true, target_dirty_ = true, source_cov_dirty_ = true, target_cov_dirty_ = true;
+};
+
+// ---- pcl::GeneralizedIterativeClosestPoint6D: GICP whose correspondences are nearest neighbours in (x, y, z, w L', w a', w b')
+// (rsreg.h: the GICP6D section).  Otherwise GICP's surface.  The colours come from the clouds' own rgb words (rsreg_cloud_lab on a
+// device cloud) unless setSourceLab / setTargetLab hand them in: three floats L', a', b' a record, in the caller's order.
+using LabColours = std::vector<std::array<float, 3>>;
+template <typename PointSource, typename PointTarget>
+class GeneralizedIterativeClosestPoint6D : public GeneralizedIterativeClosestPoint<PointSource, PointTarget> {
+    using Base = GeneralizedIterativeClosestPoint<PointSource, PointTarget>;
+
+  public:
+    using LabPtr = std::shared_ptr<const LabColours>;
+    explicit GeneralizedIterativeClosestPoint6D(float lab_weight = 0.032f, std::shared_ptr<Context> ctx = Context::Default())
+        : Base(std::move(ctx)), lab_weight_(lab_weight)
+    {
+    }
+    void setLabWeight(float w) { lab_weight_ = w; }
+    float getLabWeight() const { return lab_weight_; }
+    void setInputSource(const typename Base::SourcePtr &cloud) { Base::setInputSource(cloud); source_lab_.reset(); source_lab_dirty_ = true; }
+    void setInputTarget(const typename Base::TargetPtr &cloud) { Base::setInputTarget(cloud); target_lab_.reset(); target_lab_dirty_ = true; }
+    // one record per source / target point; call them after setInputSource / setInputTarget (a new cloud drops them)
+    void setSourceLab(const LabPtr &lab) { source_lab_ = lab; source_lab_dirty_ = true; }
+    void setTargetLab(const LabPtr &lab) { target_lab_ = lab; target_lab_dirty_ = true; }
+
+  protected:
+    void sync_more_(rsreg_ctx *c, bool source_new, bool target_new) override
+    {
+        if (source_new || source_lab_dirty_) {
+            if (source_lab_) check(rsreg_gicp_set_source_lab(c, source_lab_->data(), source_lab_->size(), sizeof(std::array<float, 3>)), c);
+            else compute_lab_(*this->source_, true);
+            source_lab_dirty_ = false;
+        }
+        if (target_new || target_lab_dirty_) {
+            if (target_lab_) check(rsreg_gicp_set_target_lab(c, target_lab_->data(), target_lab_->size(), sizeof(std::array<float, 3>)), c);
+            else compute_lab_(*this->target_, false);
+            target_lab_dirty_ = false;
+        }
+    }
+    int run_(rsreg_ctx *c, const float *guess, void *aligned_out, size_t stride) override
+    {
+        return rsreg_gicp6d_align(c, guess, &this->prm_, (double)lab_weight_, &this->res_, aligned_out, stride);
+    }
+
+  private:
+    template <typename PointT> void compute_lab_(const PointCloud<PointT> &cloud, bool source)
+    {
+        rsreg_ctx *c = this->ctx_->get();
+        DeviceCloud<PointT> dev(cloud, this->ctx_);
+        rsreg_cloud *lab = nullptr;
+        check(rsreg_cloud_create(c, &lab), c);
+        int rc = rsreg_cloud_lab(c, dev.handle(), lab);
+        if (!rc) rc = source ? rsreg_gicp_set_source_lab_cloud(c, lab) : rsreg_gicp_set_target_lab_cloud(c, lab);
+        if (!rc) rc = rsreg_ctx_synchronize(c);   // (the copy reads `lab` on the context's stream: done before the handle goes)
+        rsreg_cloud_destroy(lab);
+        check(rc, c);
+    }
+    float lab_weight_;
+    LabPtr source_lab_, target_lab_;
+    bool source_lab_dirty_ = true, target_lab_dirty_ = true;
 };
 
 // ---- pcl::NormalDistributionsTransform

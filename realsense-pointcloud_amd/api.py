@@ -281,6 +281,27 @@ class DeviceCloud:
         out.close()
         return cov, dense
 
+    def lab_cloud(self):
+        """RGB -> normalised CIE L*a*b* of every record (rsreg_cloud_lab; include/rsreg.h holds the formula): a DeviceCloud of
+        16-byte records {L / 100, a / 120, b / 120, 0}."""
+        out = DeviceCloud(ctx=self.ctx)
+        rc = _l.lib().rsreg_cloud_lab(self.ctx.h, self.h, out.h)
+        if rc:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out
+
+    def lab(self):
+        """(n, 3) float32: L', a', b' of every record."""
+        out = self.lab_cloud()
+        n, stride = out.info()[:2]
+        if n and stride != 16:
+            raise ValueError("the device cloud does not hold 16-byte colour records")
+        rec = np.zeros((n, 4), np.float32)
+        _l.check(_l.lib().rsreg_cloud_download(out.h, rec.ctypes.data, n), self.ctx.h)
+        out.close()
+        return rec[:, :3].copy()
+
     def _normals_on_device(self, normals):
         """(a DeviceCloud of this context that holds the normals, whether it was made here): a DeviceCloud as it is, a NormalCloud,
         a structured array that starts with normal_x, normal_y, normal_z, or an (n, >= 3) float32 array uploaded."""
@@ -1485,6 +1506,108 @@ class GeneralizedIterativeClosestPoint(IterativeClosestPoint):
         _l.check(_l.lib().rsreg_gicp_end(self.ctx.h, C.byref(res), out.ctypes.data if want_aligned else None, 16), self.ctx.h)
         self.result = res
         return (res, out) if want_aligned else res
+
+
+def lab_tables():
+    """(S (256,), F (4000,)) float32: the sRGB -> linear and CIE f() tables the library converts colours with (rsreg_lab_tables)."""
+    S, F = np.zeros(256, np.float32), np.zeros(4000, np.float32)
+    _l.check(_l.lib().rsreg_lab_tables(S.ctypes.data, F.ctypes.data))
+    return S, F
+
+
+def rgb_to_lab(rgba):
+    """(n, 3) float32 L', a', b' of n packed rgb words (rsreg_rgb_to_lab, host only)."""
+    w = np.ascontiguousarray(rgba, np.uint32).reshape(-1)
+    out = np.zeros((len(w), 3), np.float32)
+    _l.check(_l.lib().rsreg_rgb_to_lab(w.ctypes.data, len(w), out.ctypes.data))
+    return out
+
+
+class GeneralizedIterativeClosestPoint6D(GeneralizedIterativeClosestPoint):
+    """pcl::GeneralizedIterativeClosestPoint6D on the MI355X: GICP whose correspondences are nearest neighbours in
+    (x, y, z, w L', w a', w b') (include/rsreg.h: the GICP6D section).  The colours come from the clouds themselves
+    (rsreg_cloud_lab) unless setSourceLab / setTargetLab hand them in: an (n, >= 3) float32 array or a DeviceCloud of such records."""
+
+    def __init__(self, ctx=None, lab_weight=0.032):
+        super().__init__(ctx)
+        self.lab_weight = float(lab_weight)
+        self._lab = {"source": None, "target": None}
+        self._lab_dirty = {"source": True, "target": True}
+
+    def setInputSource(self, cloud):
+        super().setInputSource(cloud)
+        self._lab["source"], self._lab_dirty["source"] = None, True
+
+    def setInputTarget(self, cloud):
+        super().setInputTarget(cloud)
+        self._lab["target"], self._lab_dirty["target"] = None, True
+
+    def setSourceLab(self, lab):
+        self._lab["source"], self._lab_dirty["source"] = lab, True
+
+    def setTargetLab(self, lab):
+        self._lab["target"], self._lab_dirty["target"] = lab, True
+
+    def _set_lab(self, which, cloud):
+        L, h = _l.lib(), self.ctx.h
+        lab = self._lab[which]
+        set_host = getattr(L, "rsreg_gicp_set_%s_lab" % which)
+        set_cloud = getattr(L, "rsreg_gicp_set_%s_lab_cloud" % which)
+        if lab is None:   # the colours of the cloud itself
+            if isinstance(cloud, tuple):
+                raise ValueError("a cloud given by its device pointer needs setSourceLab / setTargetLab")
+            dev, made = (cloud, False) if isinstance(cloud, DeviceCloud) else (DeviceCloud(cloud, ctx=self.ctx), True)
+            out = dev.lab_cloud()
+            rc = set_cloud(h, out.h)
+            out.close()
+            if made:
+                dev.close()
+            _l.check(rc, h)
+        elif isinstance(lab, DeviceCloud):
+            _l.check(set_cloud(h, lab.h), h)
+        else:
+            a = np.ascontiguousarray(lab, np.float32)
+            if a.ndim != 2 or a.shape[1] < 3:
+                raise ValueError("colours must be a DeviceCloud or an (n, >= 3) float32 array")
+            _l.check(set_host(h, a.ctypes.data, a.shape[0], a.shape[1] * 4), h)
+        self._lab_dirty[which] = False
+
+    def _sync_inputs(self):
+        src_new = self._src_dirty or self.ctx.icp_source_owner is not self
+        tgt_new = self._tgt_dirty or self.ctx.icp_target_owner is not self or getattr(self, "_tgt_gate", None) != self.gparams.max_correspondence_distance
+        if isinstance(self._src, DeviceCloud) and getattr(self, "_src_stamp", None) != self._src.stamp:
+            src_new = True
+        if isinstance(self._tgt, DeviceCloud) and getattr(self, "_tgt_stamp", None) != self._tgt.stamp:
+            tgt_new = True
+        super()._sync_inputs()
+        # (a new source or target drops the colours of the one before)
+        if src_new or self._lab_dirty["source"]:
+            self._set_lab("source", self._src)
+        if tgt_new or self._lab_dirty["target"]:
+            self._set_lab("target", self._tgt)
+
+    def align(self, guess=None):
+        """gicp6d.align(out[, guess]): the aligned cloud, as IterativeClosestPoint.align returns it."""
+        self._sync_inputs()
+        g = _colmajor(guess)
+        gp = g.ctypes.data if g is not None else None
+        res = _l.GicpResult()
+        if isinstance(self._src, DeviceCloud):
+            out = DeviceCloud(ctx=self.ctx)
+            _l.check(_l.lib().rsreg_gicp6d_align_cloud(self.ctx.h, gp, C.byref(self.gparams), self.lab_weight, C.byref(res), out.h), self.ctx.h)
+            self.result = res
+            return out
+        out = self._src.points.copy() if isinstance(self._src, PointCloud) else np.zeros(self._n_src, POINT_DTYPE)
+        _l.check(_l.lib().rsreg_gicp6d_align(self.ctx.h, gp, C.byref(self.gparams), self.lab_weight, C.byref(res), out.ctypes.data if len(out) else None,
+                                             out.dtype.itemsize), self.ctx.h)
+        self.result = res
+        src = self._src if isinstance(self._src, PointCloud) else None
+        return PointCloud(out, width=src.width if src else len(out), height=src.height if src else 1, is_dense=src.is_dense if src else False)
+
+    def begin(self, guess=None):
+        self._sync_inputs()
+        g = _colmajor(guess)
+        _l.check(_l.lib().rsreg_gicp6d_begin(self.ctx.h, g.ctypes.data if g is not None else None, C.byref(self.gparams), self.lab_weight), self.ctx.h)
 
 
 class NormalDistributionsTransform:

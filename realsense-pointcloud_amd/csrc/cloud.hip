@@ -14,6 +14,7 @@
 
 #include "records.hpp"
 #include "cloud_ops.hpp"
+#include "lab_kernels.hpp"
 
 using namespace rsreg;
 
@@ -161,6 +162,8 @@ void cloud_drop(rsreg_ctx *ctx, DevBuf &b)
         ctx->scan_raw = nullptr;
         if (ctx->grid.dense == 2) ctx->have_target = false;
     }
+    // (the same for the records rsreg_gicp_set_target_lab* would read once more)
+    if (ctx->tgt_rec && ctx->tgt_rec >= static_cast<const char *>(b.ptr) && ctx->tgt_rec < static_cast<const char *>(b.ptr) + b.cap) ctx->tgt_rec = nullptr;
     CloudPool &pool = ctx->cloud_pool;
     if (b.cap <= pool.limit && pool.held + b.cap <= pool.limit) {
         if (ctx->src_pending) { (void)ctx->source_enqueued(); (void)hipStreamWaitEvent(ctx->stream, ctx->src.ev_done, 0); }
@@ -994,6 +997,76 @@ int rsreg_gicp_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_
     if (!ctx || !params || !result) return RSREG_ERR_INVALID_ARG;
     if (int rcb = aligned_cloud_begin(ctx, aligned_out)) return rcb;
     int rc = rsreg_gicp_align(ctx, guess, params, result, nullptr, 0);
+    if (!rc) harvest_source_box(ctx);
+    if (rc || !aligned_out) return rc;
+    return aligned_cloud_end(ctx, result->transform, aligned_out);
+}
+
+// ---- GICP6D: RGB -> normalised CIE L*a*b* (lab_kernels.hpp; include/rsreg.h holds the formula), the colours of the ICP source and
+// target from device clouds, and the aligned cloud in HBM
+int rsreg_lab_tables(float srgb_out[256], float f_out[4000])
+{
+    if (!srgb_out || !f_out) return RSREG_ERR_INVALID_ARG;
+    const rsreg::LabTables &t = rsreg::lab_tables();
+    std::memcpy(srgb_out, t.srgb, sizeof(t.srgb));
+    std::memcpy(f_out, t.f, sizeof(t.f));
+    return RSREG_OK;
+}
+
+int rsreg_rgb_to_lab(const uint32_t *rgba, size_t n, float *lab_out)
+{
+    if (n && (!rgba || !lab_out)) return RSREG_ERR_INVALID_ARG;
+    const rsreg::LabTables &t = rsreg::lab_tables();
+    host_parallel_for(n, [=, &t](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) rsreg::lab_from_rgb(t.srgb, t.f, rgba[i], lab_out[3 * i], lab_out[3 * i + 1], lab_out[3 * i + 2]);
+    });
+    return RSREG_OK;
+}
+
+int rsreg_cloud_lab(rsreg_ctx *ctx, const rsreg_cloud *in, rsreg_cloud *out)
+{
+    static constexpr CloudRule kRgbRule{20, true, "records need a packed rgb word at byte 16 and a stride that is a multiple of 4", 0x7ffffff0ull, "cloud too large"};
+    CloudView v;
+    if (!out || out == in) return RSREG_ERR_INVALID_ARG;
+    int rc = cloud_view(ctx, in, out, kRgbRule, v);
+    if (rc) return rc;
+    constexpr size_t kTableBytes = sizeof(rsreg::LabTables);
+    if (!ctx->d_lab_tables.ptr) {
+        RSREG_HIP(ctx, ctx->d_lab_tables.reserve(kTableBytes));
+        RSREG_HIP(ctx, hipMemcpyAsync(ctx->d_lab_tables.ptr, &rsreg::lab_tables(), kTableBytes, hipMemcpyHostToDevice, ctx->stream));
+        RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    void *d_out = nullptr;
+    rc = rsreg_cloud_begin_write_(out, v.n, sizeof(float4), &d_out);
+    if (rc) return rc;
+    if (v.n) {
+        rsreg::k_cloud_lab<<<div_up((uint32_t)v.n, kBlock), kBlock, 0, ctx->stream>>>(v.rec, v.stride, (uint32_t)v.n, ctx->d_lab_tables.as<float>(),
+                                                                                        static_cast<float4 *>(d_out));
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    return rsreg_cloud_end_write_(out, v.n, sizeof(float4), v.width, v.height, v.is_dense);
+}
+
+int rsreg_gicp_set_source_lab_cloud(rsreg_ctx *ctx, const rsreg_cloud *c)
+{
+    if (!ctx || !c || c->ctx != ctx) return RSREG_ERR_INVALID_ARG;
+    RSREG_HIP(ctx, settle(c));
+    return rsreg_gicp_set_lab_device_(ctx, 1, c->n ? c->buf.ptr : nullptr, c->n, c->stride);
+}
+
+int rsreg_gicp_set_target_lab_cloud(rsreg_ctx *ctx, const rsreg_cloud *c)
+{
+    if (!ctx || !c || c->ctx != ctx) return RSREG_ERR_INVALID_ARG;
+    RSREG_HIP(ctx, settle(c));
+    return rsreg_gicp_set_lab_device_(ctx, 0, c->n ? c->buf.ptr : nullptr, c->n, c->stride);
+}
+
+int rsreg_gicp6d_align_cloud(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, double lab_weight, rsreg_gicp_result *result,
+                             rsreg_cloud *aligned_out)
+{
+    if (!ctx || !params || !result) return RSREG_ERR_INVALID_ARG;
+    if (int rcb = aligned_cloud_begin(ctx, aligned_out)) return rcb;
+    int rc = rsreg_gicp6d_align(ctx, guess, params, lab_weight, result, nullptr, 0);
     if (!rc) harvest_source_box(ctx);
     if (rc || !aligned_out) return rc;
     return aligned_cloud_end(ctx, result->transform, aligned_out);

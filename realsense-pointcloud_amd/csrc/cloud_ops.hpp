@@ -31,6 +31,9 @@ int rsreg_icp_set_source_normals_device_(rsreg_ctx *ctx, const void *d_normals, 
 // icp.hip: the GICP covariances of the ICP source (source != 0) or target from records in HBM whose first 48 bytes are six doubles
 // (stride: a multiple of 8), one per record of that cloud, copied on the context's stream
 int rsreg_gicp_set_covariances_device_(rsreg_ctx *ctx, int source, const void *d_cov, size_t n, size_t stride);
+// icp.hip: the GICP6D colours of the ICP source (source != 0) or target from records in HBM whose first 12 bytes are L', a', b'
+// (stride: a multiple of 4), one per record of that cloud, copied on the context's stream
+int rsreg_gicp_set_lab_device_(rsreg_ctx *ctx, int source, const void *d_lab, size_t n, size_t stride);
 // comm.cpp: the in-place sum over all ranks of `count` doubles in HBM, on the context's stream, not waited for; RSREG_ERR_STATE
 // without a communicator
 int rsreg_comm_allreduce_device_(rsreg_ctx *ctx, double *d_buf, int count);

@@ -21,6 +21,7 @@
 #include "cellsort.hpp"
 #include "oscan.hpp"
 #include "fitness_kernels.hpp"
+#include "nn6_kernels.hpp"
 #include "plane_kernels.hpp"
 #include "rejector_kernels.hpp"
 #include "gicp_kernels.hpp"
@@ -437,6 +438,8 @@ int build_grid(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doubl
     std::memset(&ctx->grid_info, 0, sizeof(ctx->grid_info));
     std::memset(&ctx->grid, 0, sizeof(ctx->grid));
     ctx->gate_built_for = max_dist;
+    ctx->tgt_rec = d_pts;   // (rsreg_gicp_set_target_lab* reads the records once more)
+    ctx->tgt_rec_stride = stride;
     if (n > 0xfffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "target too large");
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -614,6 +617,8 @@ int scan_target(rsreg_ctx *ctx, const char *d_pts, size_t n, size_t stride, doub
     std::memset(&ctx->grid_info, 0, sizeof(ctx->grid_info));
     std::memset(&ctx->grid, 0, sizeof(ctx->grid));
     ctx->gate_built_for = max_dist;
+    ctx->tgt_rec = d_pts;
+    ctx->tgt_rec_stride = stride;
     if (n > 0x7ffffff0ull) return fail(ctx, RSREG_ERR_INVALID_ARG, "target too large");
     RSREG_HIP(ctx, ctx->d_tgt_sorted.reserve((n + 8) * sizeof(float4)));
     RSREG_HIP(ctx, ctx->d_scan_keys.reserve(kScanMaxSource * 8));
@@ -871,6 +876,8 @@ int load_source(rsreg_ctx *ctx, const char *d_raw, size_t n, size_t stride)
     RSREG_HIP(ctx, ctx->h_smisc.reserve(kHsWords * sizeof(uint32_t)));
     ctx->icp_fit_ok = false;   // (a new source: no fitness score until it is aligned)
     ctx->have_gicp_cs = false;   // (the covariances of the source before this one)
+    ctx->have_lab_s = false;     // (and its colours)
+    ctx->src_unmerged = false;
     ctx->src_nrm.have = false;   // (and its normals)
     ctx->gicp.active = 0;
     ctx->n_source = n;
@@ -1186,6 +1193,12 @@ int apply_chain(rsreg_ctx *ctx)
     return RSREG_OK;
 }
 
+// the 6-D search of GICP6D is on (rsreg_gicp6d_begin): the pairs' positions then point into its own index's point array
+bool six_on(const rsreg_ctx *ctx) { return ctx->gicp.active && ctx->gicp.six; }
+
+// the (x, y, record, z) array corr_pos points into: the sorted target of the alignment's index, or the 6-D index's points
+const float4 *pair_targets(const rsreg_ctx *ctx) { return six_on(ctx) ? ctx->g6.d_pts.as<float4>() : ctx->d_tgt_sorted.as<float4>(); }
+
 int launch_search(rsreg_ctx *ctx)
 {
     if (int rcu = refuse_unserved(ctx, ctx)) return rcu;
@@ -1200,7 +1213,11 @@ int launch_search(rsreg_ctx *ctx)
     if (n) {
         ScopedEvents ev(ctx, &ctx->ev_nn);
         const GridDev g = grid_dev(ctx, s.prm.max_correspondence_distance);
-        if (ctx->grid.dense == 2) {
+        if (six_on(ctx)) {
+            k_nn_search6<<<div_up(n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_src6_col.as<float4>(), n, grid_dev(ctx->g6),
+                                                                        ctx->d_g6_col.as<float4>(), g.prune2, gate2, ctx->d_corr_pos.as<int>(),
+                                                                        ctx->d_corr_d2.as<float>());
+        } else if (ctx->grid.dense == 2) {
             // the largest float that passes PCL's `if (distance > max_dist_sqr) continue` (compared in double)
             float gate_f = gate2 >= (double)FLT_MAX ? FLT_MAX : (float)gate2;
             if ((double)gate_f > gate2) gate_f = std::nextafterf(gate_f, 0.0f);
@@ -2018,6 +2035,102 @@ int gicp_set_covariances(rsreg_ctx *ctx, bool source, const void *host, const vo
     return RSREG_OK;
 }
 
+// GICP6D: one colour per record of the source (the target), three floats L', a', b' at the head of a record: from the host (waited
+// for: the buffer has been read) or from HBM.  The source: a load that merged exact copies is taken apart again (k_source_unmerge).
+// The target: the x, y, z of its records are taken over beside the colours -- the 6-D index is built from them (gicp6d_prepare).
+int gicp_set_lab(rsreg_ctx *ctx, bool source, const void *host, const void *dev, size_t n, size_t stride)
+{
+    if (!ctx || (n && !host && !dev) || stride < 12 || (dev && (stride & 3))) return RSREG_ERR_INVALID_ARG;
+    if (source) {
+        if (!ctx->have_source) return fail(ctx, RSREG_ERR_NO_SOURCE, "rsreg_icp_set_source not called");
+        if (n != ctx->n_source) return fail(ctx, RSREG_ERR_INVALID_ARG, "one colour per source record: the counts differ");
+    } else {
+        if (!ctx->have_target) return fail(ctx, RSREG_ERR_NO_TARGET, "rsreg_icp_set_target not called");
+        if (n != ctx->n_target_raw) return fail(ctx, RSREG_ERR_INVALID_ARG, "one colour per target record: the counts differ");
+        if (n && !ctx->tgt_rec) return fail(ctx, RSREG_ERR_STATE, "the target cloud's records have changed hands since rsreg_icp_set_target_cloud");
+    }
+    RSREG_HIP(ctx, hipSetDevice(ctx->device));
+    if (source) {
+        int rcj = join_source(ctx);
+        if (rcj) return rcj;
+    }
+    DevBuf &d = source ? ctx->d_lab_s : ctx->d_lab_t;
+    RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (an alignment before this one may still read the buffer)
+    RSREG_HIP(ctx, d.reserve((n + 1) * sizeof(float4)));
+    const uint32_t nb = div_up((uint32_t)n, kBlock);
+    if (n && host) {
+        RSREG_HIP(ctx, hipMemsetAsync(d.ptr, 0, n * sizeof(float4), ctx->stream));
+        RSREG_HIP(ctx, hipMemcpy2DAsync(d.ptr, sizeof(float4), host, stride, 12, n, hipMemcpyHostToDevice, ctx->stream));
+        RSREG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    } else if (n) {
+        k_nn6_pack3<<<nb, kBlock, 0, ctx->stream>>>(static_cast<const char *>(dev), stride, (uint32_t)n, d.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    if (source) {
+        if (n && !ctx->src_plain && !ctx->src_unmerged) {
+            k_source_unmerge<<<nb, kBlock, 0, ctx->stream>>>(ctx->d_src_all.as<float4>(), (uint32_t)n, ctx->d_src.as<float4>(), ctx->d_uniq_of.as<uint32_t>(),
+                                                             ctx->d_first.as<uint32_t>());
+            RSREG_HIP(ctx, hipGetLastError());
+            ctx->n_work = n;
+            ctx->src_unmerged = true;
+        }
+        ctx->have_lab_s = true;
+    } else {
+        RSREG_HIP(ctx, ctx->d_t6_xyz.reserve((n + 1) * sizeof(float4)));
+        if (n) {
+            k_nn6_pack3<<<nb, kBlock, 0, ctx->stream>>>(ctx->tgt_rec, ctx->tgt_rec_stride, (uint32_t)n, ctx->d_t6_xyz.as<float4>());
+            RSREG_HIP(ctx, hipGetLastError());
+            // exact 6-D copies of a record of lower index stay out of the index (nn6_kernels.hpp): a hash set at most half full
+            uint32_t slots = 1024;
+            while (slots < 2 * n && slots < 0x80000000u) slots <<= 1;
+            if (slots < 2 * n) return fail(ctx, RSREG_ERR_INVALID_ARG, "GICP6D: target too large");
+            RSREG_HIP(ctx, ctx->d_tmp.reserve((size_t)slots * 4));
+            uint32_t *table = ctx->d_tmp.as<uint32_t>();
+            RSREG_HIP(ctx, hipMemsetAsync(table, 0xff, (size_t)slots * 4, ctx->stream));
+            k_nn6_copies_insert<<<nb, kBlock, 0, ctx->stream>>>(ctx->d_t6_xyz.as<float4>(), d.as<float4>(), (uint32_t)n, table, slots - 1u);
+            RSREG_HIP(ctx, hipGetLastError());
+            k_nn6_copies_drop<<<nb, kBlock, 0, ctx->stream>>>(ctx->d_t6_xyz.as<float4>(), d.as<float4>(), (uint32_t)n, table, slots - 1u);
+            RSREG_HIP(ctx, hipGetLastError());
+        }
+        ctx->g6_built = false;
+        ctx->have_lab_t = true;
+    }
+    return RSREG_OK;
+}
+
+// what rsreg_gicp6d_begin adds to rsreg_gicp_begin: the 6-D index over every finite target record (once per target and colours) and
+// the two sides' colours times w (every begin: w is the call's)
+int gicp6d_prepare(rsreg_ctx *ctx, float w)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t nt = (uint32_t)ctx->n_target_raw, n = (uint32_t)ctx->n_work;
+    if (!ctx->g6_built) {
+        RSREG_HIP(ctx, ctx->h_g6.reserve(64));
+        const Xyz4Records rd{ctx->d_t6_xyz.as<float4>()};
+        PointGrid &gx = ctx->g6;
+        int rc = grid_build_placed<FitGridPolicy>(ctx, gx, rd, nt, 1, ctx->h_g6.as<uint32_t>(), 0.0, [&](const PointGridDev &g, uint32_t *start, uint32_t *count, size_t) {
+            k_nn6_scatter<<<div_up(nt, kBlock), kBlock, 0, st>>>(rd, nt, g, start, count, gx.d_pts.as<float4>());
+            RSREG_HIP(ctx, hipGetLastError());
+            return (int)RSREG_OK;
+        });
+        if (rc) return rc;
+        ctx->g6_built = true;
+    }
+    const uint32_t np = ctx->g6.dims[0] ? ctx->g6.n_points : 0u;
+    RSREG_HIP(ctx, ctx->d_g6_col.reserve(((size_t)np + 1) * sizeof(float4)));
+    RSREG_HIP(ctx, ctx->d_src6_col.reserve(((size_t)n + 1) * sizeof(float4)));
+    if (np) {
+        k_nn6_target_colours<<<div_up(np, kBlock), kBlock, 0, st>>>(ctx->g6.d_pts.as<float4>(), np, ctx->d_lab_t.as<float4>(), w, ctx->d_g6_col.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    if (n) {
+        k_nn6_source_colours<<<div_up(n, kBlock), kBlock, 0, st>>>(ctx->d_perm.as<uint32_t>(), ctx->d_first.as<uint32_t>(), n, ctx->d_lab_s.as<float4>(), w,
+                                                                  ctx->d_src6_col.as<float4>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    return RSREG_OK;
+}
+
 // the 32 sums at X (column-major double 4 x 4) over the pairs of the last search: launch_plane_sums with k_gicp_reduce
 int gicp_launch_sums(rsreg_ctx *ctx, const double *X, double *sums)
 {
@@ -2033,7 +2146,7 @@ int gicp_launch_sums(rsreg_ctx *ctx, const double *X, double *sums)
     }
     {
         ScopedEvents ev(ctx, &ctx->ev_reduce);
-        k_gicp_reduce<<<nb, kTile, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), ctx->d_tgt_sorted.as<float4>(),
+        k_gicp_reduce<<<nb, kTile, 0, ctx->stream>>>(ctx->d_cur.as<float4>(), ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), pair_targets(ctx),
                                                      ctx->d_gicp_m.as<double>(), Xr, n, ctx->d_plane_partials.as<double>());
         RSREG_HIP(ctx, hipGetLastError());
         int rc = queue_final_reduce(ctx, ctx->d_plane_partials.as<double>(), nb, RSREG_NUM_GICP_SUMS);
@@ -2276,6 +2389,7 @@ int rsreg_icp_set_target_device(rsreg_ctx *ctx, const void *d_points, size_t n, 
     if (!ctx || (n && !d_points) || stride < 12 || (stride & 3)) return RSREG_ERR_INVALID_ARG;
     ctx->tgt_nrm.have = false;   // (of the target before this one)
     ctx->have_gicp_ct = false;
+    ctx->have_lab_t = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     return build_grid(ctx, static_cast<const char *>(d_points), n, stride, max_correspondence_distance);
 }
@@ -2285,6 +2399,7 @@ int rsreg_icp_set_target_scan_(rsreg_ctx *ctx, const void *d_points, size_t n, s
 {
     ctx->tgt_nrm.have = false;
     ctx->have_gicp_ct = false;
+    ctx->have_lab_t = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     return scan_target(ctx, static_cast<const char *>(d_points), n, stride, max_correspondence_distance);
 }
@@ -2296,6 +2411,7 @@ int rsreg_icp_set_target(rsreg_ctx *ctx, const void *points, size_t n, size_t st
     if (!ctx || (n && !points) || stride < 12) return RSREG_ERR_INVALID_ARG;
     ctx->tgt_nrm.have = false;   // (of the target before this one)
     ctx->have_gicp_ct = false;
+    ctx->have_lab_t = false;
     RSREG_HIP(ctx, hipSetDevice(ctx->device));
     rsreg_host_timing &ht = ctx->host_timing;
     // a counting build that was queued and not waited for (build_dense) still reads d_tgt_raw on the main stream, and the
@@ -2357,7 +2473,7 @@ int rsreg_icp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out)
         const bool by_flags = ctx->icp.chain.n > 0, by_copies = !by_flags && filters_on(ctx->icp.prm);
         auto kern = by_flags ? k_export_corr<CorrKeep::flags> : by_copies ? k_export_corr<CorrKeep::copies> : k_export_corr<CorrKeep::matched>;
         const uint32_t *keep = by_flags ? ctx->d_rej_flags.as<uint32_t>() : by_copies ? ctx->d_corr_w.as<uint32_t>() : nullptr;
-        kern<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), keep, ctx->d_tgt_sorted.as<float4>(),
+        kern<<<div_up((uint32_t)n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_corr_pos.as<int>(), ctx->d_corr_d2.as<float>(), keep, pair_targets(ctx),
                                                                       ctx->d_perm.as<uint32_t>(), ctx->d_uniq_of.as<uint32_t>(), ctx->d_first.as<uint32_t>(), (uint32_t)n,
                                                                       d_idx, d_d2);
         RSREG_HIP(ctx, hipGetLastError());
@@ -2574,6 +2690,7 @@ int rsreg_gicp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out)
     if (!ctx) return RSREG_ERR_INVALID_ARG;
     if (!ctx->gicp.active || !ctx->icp.active) return fail(ctx, RSREG_ERR_STATE, "rsreg_gicp_begin not called");
     if (!ctx->have_gicp_cs || !ctx->have_gicp_ct || !ctx->have_target) return fail(ctx, RSREG_ERR_STATE, "a cloud was set after rsreg_gicp_begin: its covariances are gone");
+    if (ctx->gicp.six && !(ctx->have_lab_s && ctx->have_lab_t)) return fail(ctx, RSREG_ERR_STATE, "a cloud was set after rsreg_gicp6d_begin: its colours are gone");
     IcpState &s = ctx->icp;
     s.restart_pending = true;   // the source under the whole current transform, from the records
     s.pending_transform = false;
@@ -2589,7 +2706,7 @@ int rsreg_gicp_search(rsreg_ctx *ctx, int32_t *index_out, float *sqr_dist_out)
             R.r2[c] = (double)s.final_t(2, c);
         }
         ScopedEvents ev(ctx, &ctx->ev_reduce);
-        k_gicp_mahalanobis<<<div_up(n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_corr_pos.as<int>(), ctx->d_tgt_sorted.as<float4>(), ctx->d_perm.as<uint32_t>(),
+        k_gicp_mahalanobis<<<div_up(n, kBlock), kBlock, 0, ctx->stream>>>(ctx->d_corr_pos.as<int>(), pair_targets(ctx), ctx->d_perm.as<uint32_t>(),
                                                                          ctx->d_first.as<uint32_t>(), ctx->d_gicp_cs.as<double>(), ctx->d_gicp_ct.as<double>(), R, n,
                                                                          ctx->d_gicp_m.as<double>());
         RSREG_HIP(ctx, hipGetLastError());
@@ -2695,11 +2812,10 @@ int rsreg_gicp_end(rsreg_ctx *ctx, rsreg_gicp_result *result, void *aligned_out,
     return RSREG_OK;
 }
 
-int rsreg_gicp_align(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, rsreg_gicp_result *result, void *aligned_out, size_t out_stride)
+// the outer iterations of a GICP alignment that has begun (in three or in six dimensions), and its end
+static int gicp_run(rsreg_ctx *ctx, const rsreg_gicp_params &prm, rsreg_gicp_result *result, void *aligned_out, size_t out_stride)
 {
-    int rc = rsreg_gicp_begin(ctx, guess, params);
-    if (rc) return rc;
-    const rsreg_gicp_params prm = *params;
+    int rc = RSREG_OK;
     int done = 0;
     while (!done) {
         rc = rsreg_gicp_search(ctx, nullptr, nullptr);
@@ -2737,6 +2853,47 @@ int rsreg_gicp_align(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params
         if (rc) return rc;
     }
     return rsreg_gicp_end(ctx, result, aligned_out, out_stride);
+}
+
+int rsreg_gicp_align(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, rsreg_gicp_result *result, void *aligned_out, size_t out_stride)
+{
+    int rc = rsreg_gicp_begin(ctx, guess, params);
+    if (rc) return rc;
+    return gicp_run(ctx, *params, result, aligned_out, out_stride);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------- GICP6D
+// pcl::GeneralizedIterativeClosestPoint6D: GICP whose correspondences are nearest neighbours in (x, y, z, w L', w a', w b')
+// (include/rsreg.h holds the contract; nn6_kernels.hpp the search).  Everything behind the search is GICP's.
+int rsreg_gicp_set_source_lab(rsreg_ctx *ctx, const void *lab, size_t n, size_t stride) { return gicp_set_lab(ctx, true, lab, nullptr, n, stride); }
+int rsreg_gicp_set_target_lab(rsreg_ctx *ctx, const void *lab, size_t n, size_t stride) { return gicp_set_lab(ctx, false, lab, nullptr, n, stride); }
+int rsreg_gicp_set_lab_device_(rsreg_ctx *ctx, int source, const void *d_lab, size_t n, size_t stride) { return gicp_set_lab(ctx, source != 0, nullptr, d_lab, n, stride); }
+
+int rsreg_gicp6d_begin(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, double lab_weight)
+{
+    if (!ctx || !params) return RSREG_ERR_INVALID_ARG;
+    if (!(lab_weight >= 0) || !std::isfinite(lab_weight)) return fail(ctx, RSREG_ERR_INVALID_ARG, "GICP6D: the colour weight must be finite and not negative");
+    if (ctx->have_target && ctx->have_source && !(ctx->have_lab_s && ctx->have_lab_t))
+        return fail(ctx, RSREG_ERR_STATE, "GICP6D needs rsreg_gicp_set_source_lab and rsreg_gicp_set_target_lab after the clouds are set");
+    int rc = rsreg_gicp_begin(ctx, guess, params);
+    if (rc) return rc;
+    rc = gicp6d_prepare(ctx, (float)lab_weight);
+    if (rc) {
+        ctx->gicp.active = 0;
+        ctx->icp.active = 0;
+        return rc;
+    }
+    ctx->gicp.six = 1;
+    ctx->gicp.lab_weight = (float)lab_weight;
+    return RSREG_OK;
+}
+
+int rsreg_gicp6d_align(rsreg_ctx *ctx, const float *guess, const rsreg_gicp_params *params, double lab_weight, rsreg_gicp_result *result, void *aligned_out,
+                       size_t out_stride)
+{
+    int rc = rsreg_gicp6d_begin(ctx, guess, params, lab_weight);
+    if (rc) return rc;
+    return gicp_run(ctx, *params, result, aligned_out, out_stride);
 }
 
 int rsreg_icp_grid_info(rsreg_ctx *ctx, rsreg_grid_info *info)

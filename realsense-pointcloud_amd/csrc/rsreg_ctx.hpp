@@ -335,6 +335,8 @@ struct GicpState {
     bool have_search = false;      // d_gicp_m holds the Mahalanobis matrices of the current search
     int inner_evaluations = 0, rank_last = 0;
     double sums_last[RSREG_NUM_GICP_SUMS] = {0};
+    int six = 0;                   // rsreg_gicp6d_begin: the search runs in (x, y, z, w L', w a', w b') over ctx->g6
+    float lab_weight = 0;          // w
 };
 
 }  // namespace rsreg
@@ -391,6 +393,19 @@ struct rsreg_ctx {
     bool have_gicp_cs = false, have_gicp_ct = false;
     rsreg::DevBuf d_gicp_cs, d_gicp_ct, d_gicp_m;
     rsreg::GicpState gicp;
+    // GICP6D (rsreg_gicp6d_*, nn6_kernels.hpp): one colour per source / target RECORD in the caller's order, float4 {L', a', b', 0},
+    // dropped by the next rsreg_icp_set_source* / rsreg_icp_set_target*; the target's x, y, z per record as they were when its
+    // colours were set (float4 {x, y, z, 0}; x = NaN for an exact 6-D copy of a record of lower index); the 6-D search's own index over them, built by the first rsreg_gicp6d_begin that
+    // follows, with the indexed points' colours times w beside it; the working points' colours times w
+    bool have_lab_s = false, have_lab_t = false, g6_built = false;
+    rsreg::DevBuf d_lab_s, d_lab_t, d_t6_xyz, d_g6_col, d_src6_col;
+    rsreg::PointGrid g6;
+    rsreg::PinnedBuf h_g6;
+    // the records the target's index was built from: the context's own copy of a host cloud (d_tgt_raw), else the caller's device
+    // buffer -- read once more by rsreg_gicp_set_target_lab*, never after (nullptr: a cloud handle's buffer has changed hands since)
+    const char *tgt_rec = nullptr;
+    size_t tgt_rec_stride = 0;
+    rsreg::DevBuf d_lab_tables;   // cloud.hip: the 256 + 4000 floats of the RGB -> L*a*b* tables (lab_kernels.hpp), uploaded at first use
 
     // ---- ICP source
     bool have_source = false;
@@ -409,6 +424,7 @@ struct rsreg_ctx {
     rsreg::DevBuf d_plain_ticket; // k_source_plain's ticket word (zero between launches)
     uint32_t plain_box_seq = 0, plain_box_counter = 0;   // the stamp the pending plain load leaves behind its box in h_smisc[48 .. 55] (0: none)
     bool src_plain = false;       // the pending load is k_source_plain on the MAIN stream (every record a query of its own): nothing to wait for at the join
+    bool src_unmerged = false;    // a merged load taken apart again (rsreg_gicp_set_source_lab*): every record a working point of its own
     bool src_on_worker = false;   // ... and its launches are being queued by the context's worker thread right now
     std::unique_ptr<rsreg::SourceWorker> src_worker;   // (created with the first source load; RSREG_NO_WORKER=1: never, the load runs on the caller's thread)
     // everything of a pending source load has been queued on src.stream (so that src.ev_done is the event of THIS load)

@@ -65,6 +65,8 @@ EXPORTS = [
     "rsreg_gicp_params_default", "rsreg_cloud_gicp_covariances", "rsreg_gicp_set_source_covariances", "rsreg_gicp_set_target_covariances",
     "rsreg_gicp_set_source_covariances_cloud", "rsreg_gicp_set_target_covariances_cloud", "rsreg_gicp_begin", "rsreg_gicp_search",
     "rsreg_gicp_sums", "rsreg_gicp_step_from_sums", "rsreg_gicp_update", "rsreg_gicp_end", "rsreg_gicp_align", "rsreg_gicp_align_cloud",
+    "rsreg_lab_tables", "rsreg_rgb_to_lab", "rsreg_cloud_lab", "rsreg_gicp_set_source_lab", "rsreg_gicp_set_target_lab",
+    "rsreg_gicp_set_source_lab_cloud", "rsreg_gicp_set_target_lab_cloud", "rsreg_gicp6d_begin", "rsreg_gicp6d_align", "rsreg_gicp6d_align_cloud",
     "rsreg_iin_params_default", "rsreg_cloud_integral_normals",
     "rsreg_voxel_grid_params_default", "rsreg_voxel_grid", "rsreg_voxel_grid_gpu", "rsreg_cloud_voxel_grid",
     "rsreg_depth_params_default", "rsreg_depth_params_reference", "rsreg_depth_to_cloud", "rsreg_cloud_from_depth", "rsreg_cloud_from_depth_device",
@@ -361,6 +363,15 @@ def lib():
     L.rsreg_gicp_end.argtypes = [vp, C.POINTER(GicpResult), vp, sz]
     L.rsreg_gicp_align.argtypes = [vp, vp, C.POINTER(GicpParams), C.POINTER(GicpResult), vp, sz]
     L.rsreg_gicp_align_cloud.argtypes = [vp, vp, C.POINTER(GicpParams), C.POINTER(GicpResult), vp]
+    L.rsreg_lab_tables.argtypes = [vp, vp]
+    L.rsreg_rgb_to_lab.argtypes = [vp, sz, vp]
+    L.rsreg_cloud_lab.argtypes = [vp, vp, vp]
+    for f in ("rsreg_gicp_set_source_lab", "rsreg_gicp_set_target_lab"):
+        getattr(L, f).argtypes = [vp, vp, sz, sz]
+        getattr(L, f + "_cloud").argtypes = [vp, vp]
+    L.rsreg_gicp6d_begin.argtypes = [vp, vp, C.POINTER(GicpParams), dbl]
+    L.rsreg_gicp6d_align.argtypes = [vp, vp, C.POINTER(GicpParams), dbl, C.POINTER(GicpResult), vp, sz]
+    L.rsreg_gicp6d_align_cloud.argtypes = [vp, vp, C.POINTER(GicpParams), dbl, C.POINTER(GicpResult), vp]
     L.rsreg_transform_cloud.argtypes = [vp, vp, vp, sz, sz, i32, vp]
     L.rsreg_approx_voxel_grid.argtypes = [vp, sz, sz, vp, vp, C.POINTER(sz)]
     L.rsreg_approx_voxel_grid_gpu.argtypes = [vp, vp, sz, sz, vp, vp, C.POINTER(sz)]
