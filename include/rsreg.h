@@ -1324,6 +1324,49 @@ int rsreg_cloud_iss_non_max(rsreg_ctx *ctx, const rsreg_cloud *in, const double 
                             int min_neighbors, uint8_t *is_keypoint_out /* n */);
 int rsreg_cloud_iss_keypoints(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_iss_params *params, rsreg_cloud *out /* may be NULL */,
                               int32_t *index_out /* capacity entries, may be NULL */, size_t capacity, uint64_t *n_keypoints /* may be NULL */);
+/* ---- pcl::EuclideanClusterExtraction over the radius search above: a cloud split into its connected pieces.  PCL 1.9.1
+ * segmentation/impl/extract_clusters.hpp (extractEuclideanClusters), recalled; PCL is not available to check against, so what
+ * follows IS the contract.
+ * Graph: the nodes are the finite records of the cloud.  Records i != j are joined when float32 d2(i, j) < r2, strictly, with
+ *   r2 = (float)((double)tolerance * (double)tolerance): the neighbourhood of rsreg_cloud_radius_count, unchanged, and symmetric
+ *   because L2_Simple is.  Exact copies are joined like any other pair; a record AT the tolerance is not joined.
+ * Cluster: a connected component of this graph whose number of records m satisfies min_cluster_size <= m <= max_cluster_size.  A
+ *   component outside the bounds is dropped whole, never split (PCL compares the finished seed queue with both bounds).
+ * Order: the clusters are ranked by size descending (PCL's std::sort(clusters.rbegin(), clusters.rend(), comparePointClusters));
+ *   inside a cluster the record indices ascend (PCL's std::sort on r.indices).
+ *   DEVIATIONS FROM PCL 1.9.1, stated: PCL's unstable sort leaves the order of equal sizes open -- here a tie goes to the cluster
+ *   whose smallest record index is lower.  A non-finite record belongs to no cluster -- PCL's seed loop would make it a singleton
+ *   when min_cluster_size <= 1.
+ * rsreg_cloud_euclidean_clusters, every output in host memory and nullable:
+ *   labels_out[i] (n): the rank of record i's cluster, 0 the largest; -1 for a non-finite record and for one of a dropped component.
+ *   indices_out (n): the record indices of cluster 0 ascending, then those of cluster 1, ...; entries beyond the last reported
+ *     cluster are not written.
+ *   offsets_out (min(n_clusters, capacity) + 1): offsets_out[c] .. offsets_out[c + 1] is cluster c's slice of indices_out.  Only the
+ *     first `capacity` clusters are reported.
+ *   *n_clusters_out: always the full number of clusters, which may exceed capacity.
+ *   An empty cloud, or one without a finite record: 0 clusters, offsets_out[0] = 0, every label -1, no kernel of the clustering runs.
+ * rsreg_cloud_cluster_filter, the consumer that stays on the device: keeps the records whose cluster rank lies in
+ *   [rank_lo, rank_hi) (negative: the others; a record with label -1 is outside every range).  (0, 1): the largest cluster only;
+ *   (0, UINT32_MAX) with a min_cluster_size: every blob below that size dropped.  out, in == out, keep_organized, is_dense, the
+ *   versioning and *n_kept are those of rsreg_cloud_radius_outlier_removal, through the same flag / scan / gather kernels.
+ * The result is a function of the cloud and the parameters alone: a component's representative is its smallest record index
+ *   whatever order the device linked the edges in, and the ranks are a total order.  The same bytes from any context.
+ * Refused with RSREG_ERR_INVALID_ARG, nothing written and `out` unchanged: a tolerance that is not finite or <= 0,
+ *   min_cluster_size > max_cluster_size, rank_lo > rank_hi, a NULL p, in or out, a cloud of another context, 2^30 records or more.
+ * Both calls build the index (a round trip to the host for the box) and wait for the stream.
+ * Not built: setIndices and setSearchMethod, LabeledEuclideanClusterExtraction, ConditionalEuclideanClustering, RegionGrowing,
+ *   clustering across ranks (every rank clusters the cloud it holds). */
+typedef struct rsreg_cluster_params {
+    double tolerance;            /* setClusterTolerance; must be finite and > 0 */
+    uint32_t min_cluster_size;   /* setMinClusterSize, PCL default 1 */
+    uint32_t max_cluster_size;   /* setMaxClusterSize, PCL default INT_MAX */
+} rsreg_cluster_params;
+void rsreg_cluster_params_default(rsreg_cluster_params *p);   /* tolerance 0: the caller must set it */
+int rsreg_cloud_euclidean_clusters(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cluster_params *p, int32_t *labels_out /* n, may be NULL */,
+                                   uint32_t *indices_out /* n, may be NULL */, uint32_t *offsets_out /* min(n_clusters, capacity) + 1, may be NULL */,
+                                   uint32_t capacity, uint32_t *n_clusters_out /* may be NULL */);
+int rsreg_cloud_cluster_filter(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cluster_params *p, uint32_t rank_lo, uint32_t rank_hi, int negative,
+                               int keep_organized, rsreg_cloud *out, uint64_t *n_kept /* may be NULL */);
 /* ---- pcl::FPFHEstimationOMP with setRadiusSearch(radius): SPFH and FPFH over the radius search above -- a support of fixed
  * metric size, any number of neighbours.  PCL 1.9.1 features/impl/fpfh.hpp (computePointSPFHSignature, weightPointSPFHSignature)
  * and pfh_tools.cpp (computePairFeatures), recalled; PCL is not available to check against, so what follows IS the contract.

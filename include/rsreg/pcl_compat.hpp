@@ -1186,6 +1186,51 @@ template <typename PointT> class RadiusOutlierRemoval {
     std::shared_ptr<Context> ctx_;
 };
 
+// ---- pcl::EuclideanClusterExtraction<PointT> over the exact radius search on the GPU (csrc/cluster_kernels.hpp,
+// rsreg_cloud_euclidean_clusters; include/rsreg.h holds the contract and the stated deviations: ties between equal sizes go to the
+// cluster with the lower smallest record, a non-finite record belongs to no cluster).  extract(): the clusters by size descending,
+// the record indices of each ascending.  PCL's defaults: tolerance 0 (extract() refuses it), sizes 1 .. INT_MAX.  No setIndices,
+// no setSearchMethod.
+struct PointIndices {
+    std::vector<int> indices;
+};
+
+template <typename PointT> class EuclideanClusterExtraction {
+  public:
+    EuclideanClusterExtraction() { rsreg_cluster_params_default(&params_); }
+    explicit EuclideanClusterExtraction(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) { rsreg_cluster_params_default(&params_); }
+    void setInputCloud(const typename PointCloud<PointT>::Ptr &cloud) { input_ = cloud, dinput_ = nullptr; }
+    void setInputCloud(const DeviceCloud<PointT> &cloud) { dinput_ = &cloud, input_.reset(); }   // (must outlive extract())
+    void setClusterTolerance(double tolerance) { params_.tolerance = tolerance; }
+    double getClusterTolerance() const { return params_.tolerance; }
+    void setMinClusterSize(int m) { params_.min_cluster_size = (uint32_t)m; }
+    int getMinClusterSize() const { return (int)params_.min_cluster_size; }
+    void setMaxClusterSize(int m) { params_.max_cluster_size = (uint32_t)m; }
+    int getMaxClusterSize() const { return (int)params_.max_cluster_size; }
+    void extract(std::vector<PointIndices> &clusters)
+    {
+        if (dinput_) return extract(*dinput_, clusters);
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        DeviceCloud<PointT> tmp(*input_, ctx_ ? ctx_ : Context::Default());
+        extract(tmp, clusters);
+    }
+    void extract(const DeviceCloud<PointT> &input, std::vector<PointIndices> &clusters)
+    {
+        rsreg_ctx *c = input.context()->get();
+        const size_t n = input.size();
+        std::vector<uint32_t> indices(n), offsets(n + 1);
+        uint32_t found = 0;
+        check(rsreg_cloud_euclidean_clusters(c, input.handle(), &params_, nullptr, indices.data(), offsets.data(), (uint32_t)n, &found), c);
+        clusters.assign(found, PointIndices{});
+        for (uint32_t k = 0; k < found; ++k) clusters[k].indices.assign(indices.begin() + offsets[k], indices.begin() + offsets[k + 1]);
+    }
+  private:
+    rsreg_cluster_params params_;
+    typename PointCloud<PointT>::Ptr input_;
+    const DeviceCloud<PointT> *dinput_ = nullptr;
+    std::shared_ptr<Context> ctx_;
+};
+
 // ---- pcl::ISSKeypoint3D<PointInT, PointOutT> over the exact radius search on the GPU (csrc/iss_kernels.hpp,
 // rsreg_cloud_iss_keypoints; include/rsreg.h holds the contract and the one stated deviation, the eigen-solve): the records whose
 // scatter over the salient radius has eigenvalue ratios below the two thresholds and whose smallest eigenvalue no neighbour within

@@ -4,4 +4,4 @@ with ``importlib.import_module("realsense-pointcloud_amd")`` or through the ``rs
 alias module at the repo root."""
 from . import cloud, synth  # noqa: F401
 from .cloud import POINT_DTYPE, PointCloud, load_pcd, save_pcd  # noqa: F401
-from .api import CorrespondenceEstimation, CorrespondenceRejector, CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne, CorrespondenceRejectorSampleConsensus, CorrespondenceRejectorSurfaceNormal, CorrespondenceRejectorTrimmed, TransformationEstimationSVD, DepthToCloud, FPFHEstimation, FPFHEstimationOMP, IntegralImageNormalEstimation, ISSKeypoint3D, NormalEstimation, PassThrough, RadiusOutlierRemoval, StatisticalOutlierRemoval, VoxelGrid  # noqa: F401,E402
+from .api import CorrespondenceEstimation, CorrespondenceRejector, CorrespondenceRejectorMedianDistance, CorrespondenceRejectorOneToOne, CorrespondenceRejectorSampleConsensus, CorrespondenceRejectorSurfaceNormal, CorrespondenceRejectorTrimmed, TransformationEstimationSVD, DepthToCloud, EuclideanClusterExtraction, FPFHEstimation, FPFHEstimationOMP, IntegralImageNormalEstimation, ISSKeypoint3D, NormalEstimation, PassThrough, RadiusOutlierRemoval, StatisticalOutlierRemoval, VoxelGrid  # noqa: F401,E402

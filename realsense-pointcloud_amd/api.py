@@ -616,6 +616,36 @@ class DeviceCloud:
         _l.check(rc, self.ctx.h)
         return out, int(kept.value)
 
+    def euclidean_clusters(self, tolerance, min_size=1, max_size=2**31 - 1):
+        """pcl::EuclideanClusterExtraction (rsreg_cloud_euclidean_clusters): the connected components of "float32 d2 < (float)(tolerance
+        * tolerance)" with min_size <= records <= max_size, ranked by size descending (ties: the smallest record index first).
+        Returns (labels, indices, offsets): labels (n,) int32, every record's rank or -1; indices (uint32) the records cluster by
+        cluster, ascending inside one; offsets (n_clusters + 1,) uint32, cluster c is indices[offsets[c]:offsets[c + 1]]."""
+        n = self.info()[0]
+        p = cluster_params(tolerance, min_size, max_size)
+        labels, indices, offsets = np.empty(n, np.int32), np.empty(n, np.uint32), np.empty(n + 1, np.uint32)
+        count = C.c_uint32(0)
+        _l.check(_l.lib().rsreg_cloud_euclidean_clusters(self.ctx.h, self.h, C.byref(p), labels.ctypes.data, indices.ctypes.data, offsets.ctypes.data,
+                                                         n, C.byref(count)), self.ctx.h)
+        offsets = offsets[:count.value + 1].copy()
+        return labels, indices[:int(offsets[-1])].copy(), offsets
+
+    def cluster_filter(self, tolerance, rank_lo=0, rank_hi=1, min_size=1, max_size=2**31 - 1, negative=False, keep_organized=False, out=None):
+        """rsreg_cloud_cluster_filter: keeps the records whose cluster (euclidean_clusters) has a rank in [rank_lo, rank_hi) -- the
+        default: the largest cluster only; negative: the other records.  out: None = a new DeviceCloud, or a DeviceCloud of this
+        context (this one is allowed).  Returns (out, the number of kept records)."""
+        made = out is None
+        if made:
+            out = DeviceCloud(ctx=self.ctx)
+        p = cluster_params(tolerance, min_size, max_size)
+        kept = C.c_uint64(0)
+        rc = _l.lib().rsreg_cloud_cluster_filter(self.ctx.h, self.h, C.byref(p), int(rank_lo), int(rank_hi), int(bool(negative)),
+                                                 int(bool(keep_organized)), out.h, C.byref(kept))
+        if rc and made:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out, int(kept.value)
+
     def normals_radius_cloud(self, radius, viewpoint=None):
         """pcl::NormalEstimation with setRadiusSearch(radius) (rsreg_cloud_normals_radius): a DeviceCloud of 32-byte pcl::Normal
         records; fewer than three neighbours within the radius: NaNs."""
@@ -787,6 +817,16 @@ def iin_params(**kw):
         if k == "viewpoint":
             v = (C.c_float * 3)(*[float(x) for x in v])
         setattr(p, k, v)
+    return p
+
+
+def cluster_params(tolerance, min_size=1, max_size=2**31 - 1):
+    """rsreg_cluster_params: PCL's defaults for the sizes (1, INT_MAX); the tolerance has none."""
+    if not (0 <= int(min_size) < 2**32 and 0 <= int(max_size) < 2**32):
+        raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "cluster sizes are counted in 32 bits")
+    p = _l.ClusterParams()
+    _l.lib().rsreg_cluster_params_default(C.byref(p))
+    p.tolerance, p.min_cluster_size, p.max_cluster_size = float(tolerance), int(min_size), int(max_size)
     return p
 
 
@@ -1989,6 +2029,53 @@ class RadiusOutlierRemoval:
         def run(cin, cout):
             _, self.n_kept = cin.radius_outlier_removal(self.radius, self.min_neighbors, self.negative, self.keep_organized, out=cout)
         return _filter_io(self._in, self.ctx, run)
+
+
+class EuclideanClusterExtraction:
+    """pcl::EuclideanClusterExtraction<PointXYZRGB> on the GPU over the exact radius search (csrc/cluster_kernels.hpp,
+    rsreg_cloud_euclidean_clusters; include/rsreg.h holds the contract).  PCL's defaults: tolerance 0 (extract() refuses it),
+    sizes 1 .. INT_MAX.  extract() gives a list of int32 arrays, a cluster's record indices each, ascending, the largest cluster
+    first.  No setIndices, no setSearchMethod."""
+
+    def __init__(self, ctx=None):
+        self.tolerance = 0.0
+        self.min_cluster_size = 1
+        self.max_cluster_size = 2**31 - 1
+        self._in = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setClusterTolerance(self, tolerance):
+        self.tolerance = float(tolerance)
+
+    def getClusterTolerance(self):
+        return self.tolerance
+
+    def setMinClusterSize(self, m):
+        self.min_cluster_size = int(m)
+
+    def getMinClusterSize(self):
+        return self.min_cluster_size
+
+    def setMaxClusterSize(self, m):
+        self.max_cluster_size = int(m)
+
+    def getMaxClusterSize(self):
+        return self.max_cluster_size
+
+    def extract(self):
+        if self._in is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCloud not called")
+        on_device = isinstance(self._in, DeviceCloud)
+        dev = self._in if on_device else DeviceCloud(self._in, ctx=self.ctx or default_context())
+        try:
+            _, indices, offsets = dev.euclidean_clusters(self.tolerance, self.min_cluster_size, self.max_cluster_size)
+        finally:
+            if not on_device:
+                dev.close()
+        return [indices[offsets[c]:offsets[c + 1]].astype(np.int32) for c in range(len(offsets) - 1)]
 
 
 class ISSKeypoint3D:

@@ -10,6 +10,8 @@
 // (setRadiusSearch): fpfh_radius_kernels.hpp's two walks of the radius index, no neighbour list between them.  setSearchSurface
 // (the *_surface calls): the same radius index over the surface, searched from the records of another cloud (surface_kernels.hpp).
 // pcl::ISSKeypoint3D: iss_kernels.hpp's two walks over ONE radius index (the salient radius'), then the flag / scan / gather.
+// pcl::EuclideanClusterExtraction: cluster_kernels.hpp's union-find inside the walk of the radius index, two sorts for the ranking,
+// then (rsreg_cloud_cluster_filter) the same flag / scan / gather.
 // Everything runs on the context's stream with the index rsreg_ctx::knn and the scratch rsreg_ctx::filt (the radius search:
 // rsreg_ctx::rad too): nothing here reads or writes a buffer of the alignment's index or of the fitness indices.
 #include <cmath>
@@ -23,6 +25,7 @@
 #include "fpfh_radius_kernels.hpp"
 #include "surface_kernels.hpp"
 #include "iss_kernels.hpp"
+#include "cluster_kernels.hpp"
 #include "cloud_ops.hpp"
 
 using namespace rsreg;
@@ -445,6 +448,55 @@ int iss_non_max_device(rsreg_ctx *ctx, const CloudView &v, double non_max_radius
     k_iss_non_max<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, ctx->stream>>>(grid_dev(ctx->knn), radius_query(non_max_radius, ctx->knn),
                                                                                    ctx->rad.d_iss_sal.as<double>(), (uint32_t)min_neighbors, fs.d_flags.as<uint32_t>());
     RSREG_HIP(ctx, hipGetLastError());
+    return RSREG_OK;
+}
+
+
+int cluster_check(rsreg_ctx *ctx, const rsreg_cluster_params &p)
+{
+    if (!(p.tolerance > 0.0) || !std::isfinite(p.tolerance)) return fail(ctx, RSREG_ERR_INVALID_ARG, "the cluster tolerance must be finite and above 0");
+    if (p.min_cluster_size > p.max_cluster_size) return fail(ctx, RSREG_ERR_INVALID_ARG, "min_cluster_size must not exceed max_cluster_size");
+    return RSREG_OK;
+}
+
+// EuclideanClusterExtraction on the device, not waited for (v.n above 0): the index at the tolerance, the hooks, the roots and sizes,
+// the ranking.  Leaves every record's label (cs.d_label), the number of clusters (cs.d_n) and, with `lists`, the clusters' offsets
+// (cs.d_offsets, n + 1 words) and their records cluster by cluster (*d_indices: n words, the records without a cluster at the end).
+// No finite record (*nfin_out = 0): nothing but the index's box has run and nothing is left.
+int cluster_labels_device(rsreg_ctx *ctx, const CloudView &v, const rsreg_cluster_params &p, bool lists, const uint32_t **d_indices, uint32_t *nfin_out)
+{
+    ClusterScratch &cs = ctx->clus;
+    RadiusScratch &rs = ctx->rad;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)v.n, nb = div_up(n, kBlock);
+    RadiusQuery rq;
+    int rc = radius_index_device(ctx, v, p.tolerance, nullptr, &rq, nfin_out);
+    if (rc || !*nfin_out) return rc;
+    for (DevBuf *b : {&cs.d_parent, &cs.d_root, &cs.d_size, &cs.d_rank, &cs.d_label}) RSREG_HIP(ctx, b->reserve(v.n * 4 + 16));
+    RSREG_HIP(ctx, cs.d_offsets.reserve(v.n * 4 + 20));
+    RSREG_HIP(ctx, cs.d_scan.reserve(oscan_scratch_bytes<uint32_t>(v.n + 1)));
+    RSREG_HIP(ctx, cs.d_n.reserve(16));
+    unsigned bits = 1;
+    while (((size_t)n >> bits) != 0) ++bits;   // the keys of both sorts: a rank or n - size below n, and n itself
+    RSREG_HIP(ctx, rs.d_sort.reserve((size_t)osort_plan<uint32_t>(v.n, 0, bits).words * 4));
+    uint32_t *keys[2] = {rs.d_keys[0].as<uint32_t>(), rs.d_keys[1].as<uint32_t>()}, *vals[2] = {rs.d_vals[0].as<uint32_t>(), rs.d_vals[1].as<uint32_t>()};
+    uint32_t *parent = cs.d_parent.as<uint32_t>(), *root = cs.d_root.as<uint32_t>(), *size = cs.d_size.as<uint32_t>(), *rank = cs.d_rank.as<uint32_t>();
+
+    k_cluster_init<<<nb, kBlock, 0, st>>>(n, parent, size);
+    k_cluster_hook<<<std::min<uint32_t>(*nfin_out, 1u << 16), kKnnWave, 0, st>>>(grid_dev(ctx->knn), rq, parent);
+    k_cluster_flatten<<<nb, kBlock, 0, st>>>(v.rec, v.stride, n, parent, root, size);
+    k_cluster_keys<<<nb, kBlock, 0, st>>>(n, root, size, p.min_cluster_size, p.max_cluster_size, keys[0], vals[0]);
+    RSREG_HIP(ctx, hipGetLastError());
+    bool in_first = true;
+    RSREG_HIP(ctx, osort_pairs_cleared<uint32_t>(rs.d_sort.as<uint32_t>(), keys[0], keys[1], vals[0], vals[1], v.n, 0, bits, st, &in_first));
+    int at = in_first ? 0 : 1;
+    k_cluster_rank<<<div_up(n + 1, kBlock), kBlock, 0, st>>>(n, keys[at], vals[at], rank, cs.d_offsets.as<uint32_t>(), cs.d_n.as<uint32_t>());
+    k_cluster_labels<<<nb, kBlock, 0, st>>>(n, root, rank, cs.d_label.as<int32_t>(), lists ? keys[0] : nullptr, lists ? vals[0] : nullptr);
+    RSREG_HIP(ctx, hipGetLastError());
+    if (!lists) return RSREG_OK;
+    RSREG_HIP(ctx, oscan<uint32_t>(cs.d_offsets.as<uint32_t>(), cs.d_offsets.as<uint32_t>(), v.n + 1, 0u, cs.d_scan.ptr, st));
+    RSREG_HIP(ctx, osort_pairs_cleared<uint32_t>(rs.d_sort.as<uint32_t>(), keys[0], keys[1], vals[0], vals[1], v.n, 0, bits, st, &in_first));
+    *d_indices = vals[in_first ? 0 : 1];
     return RSREG_OK;
 }
 
@@ -942,6 +994,91 @@ int rsreg_cloud_normals_radius(rsreg_ctx *ctx, const rsreg_cloud *in, double rad
             k_normals_radius<<<std::min<uint32_t>(nfin, 1u << 16), kKnnWave, 0, ctx->stream>>>(grid_dev(ctx->knn), rq, vp[0], vp[1], vp[2], d_normals, d_any);
         }, any_nan);
     });
+}
+
+void rsreg_cluster_params_default(rsreg_cluster_params *p)
+{
+    if (!p) return;
+    p->tolerance = 0.0;
+    p->min_cluster_size = 1u;
+    p->max_cluster_size = 0x7fffffffu;
+}
+
+int rsreg_cloud_euclidean_clusters(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cluster_params *p, int32_t *labels_out, uint32_t *indices_out,
+                                   uint32_t *offsets_out, uint32_t capacity, uint32_t *n_clusters_out)
+{
+    CloudView v;
+    if (!p) return RSREG_ERR_INVALID_ARG;
+    int rc = cloud_view(ctx, in, nullptr, kXyzRule, v);
+    if (rc) return rc;
+    rc = cluster_check(ctx, *p);
+    if (rc) return rc;
+    ClusterScratch &cs = ctx->clus;
+    hipStream_t st = ctx->stream;
+    uint32_t nfin = 0, count = 0;
+    // at home (pinned): the count | n + 1 offsets | n indices -- what the caller gets of the last two depends on the count
+    const uint32_t *h_offsets = nullptr, *h_indices = nullptr, *d_indices = nullptr;
+    const bool lists = indices_out || offsets_out;
+    if (v.n) {
+        rc = cluster_labels_device(ctx, v, *p, lists, &d_indices, &nfin);
+        if (rc) return rc;
+    }
+    if (nfin) {
+        RSREG_HIP(ctx, cs.host.reserve((2 * v.n + 2) * 4));
+        uint32_t *h = cs.host.as<uint32_t>();
+        h_offsets = h + 1;
+        h_indices = h + 2 + v.n;
+        RSREG_HIP(ctx, hipMemcpyAsync(h, cs.d_n.ptr, 4, hipMemcpyDeviceToHost, st));
+        if (lists) RSREG_HIP(ctx, hipMemcpyAsync(h + 1, cs.d_offsets.ptr, (v.n + 1) * 4, hipMemcpyDeviceToHost, st));
+        if (indices_out) RSREG_HIP(ctx, hipMemcpyAsync(h + 2 + v.n, d_indices, v.n * 4, hipMemcpyDeviceToHost, st));
+        if (labels_out) RSREG_HIP(ctx, hipMemcpyAsync(labels_out, cs.d_label.ptr, v.n * 4, hipMemcpyDeviceToHost, st));
+        RSREG_HIP(ctx, hipStreamSynchronize(st));
+        count = h[0];
+    } else if (labels_out) {
+        std::fill(labels_out, labels_out + v.n, -1);
+    }
+    const uint32_t reported = std::min(count, capacity);
+    if (offsets_out) {
+        if (nfin) std::memcpy(offsets_out, h_offsets, ((size_t)reported + 1) * 4);
+        else offsets_out[0] = 0u;
+    }
+    if (indices_out && reported) std::memcpy(indices_out, h_indices, (size_t)h_offsets[reported] * 4);
+    if (n_clusters_out) *n_clusters_out = count;
+    return RSREG_OK;
+}
+
+int rsreg_cloud_cluster_filter(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cluster_params *p, uint32_t rank_lo, uint32_t rank_hi, int negative,
+                               int keep_organized, rsreg_cloud *out, uint64_t *n_kept)
+{
+    CloudView v;
+    if (!p || !out) return RSREG_ERR_INVALID_ARG;
+    int rc = cloud_view(ctx, in, out, kXyzRule, v);
+    if (rc) return rc;
+    rc = cluster_check(ctx, *p);
+    if (rc) return rc;
+    if (rank_lo > rank_hi) return fail(ctx, RSREG_ERR_INVALID_ARG, "rank_lo must not exceed rank_hi");
+    FilterScratch &fs = ctx->filt;
+    ClusterScratch &cs = ctx->clus;
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)v.n;
+    if (n) {
+        uint32_t nfin = 0;
+        const uint32_t *d_indices = nullptr;
+        rc = cluster_labels_device(ctx, v, *p, false, &d_indices, &nfin);
+        if (rc) return rc;
+        if (!nfin) {   // (the build stopped at the box: no record has a cluster)
+            RSREG_HIP(ctx, cs.d_label.reserve(v.n * 4 + 16));
+            RSREG_HIP(ctx, hipMemsetAsync(cs.d_label.ptr, 0xff, v.n * 4, st));
+        }
+        RSREG_HIP(ctx, fs.d_flags.reserve(v.n * 4 + 16));
+        k_cluster_filter_flags<<<div_up(n, kBlock), kBlock, 0, st>>>(cs.d_label.as<int32_t>(), n, rank_lo, rank_hi, negative ? 1 : 0, fs.d_flags.as<uint32_t>());
+        RSREG_HIP(ctx, hipGetLastError());
+    }
+    uint32_t kept = 0;
+    rc = keep_organized ? organized_into(ctx, v, out, &kept) : compact_into(ctx, v, out, v.is_dense, &kept);
+    if (rc) return rc;
+    if (n_kept) *n_kept = kept;
+    return RSREG_OK;
 }
 
 }  // extern "C"

@@ -222,6 +222,19 @@ struct RadiusScratch {
     DevBuf d_iss_index;            // int32 per record: the keypoints' record indices, ascending
 };
 
+// Scratch of EuclideanClusterExtraction (filters.hip, cluster_kernels.hpp), per record of the cloud being clustered; the two sorts of the
+// ranking go through RadiusScratch's pairs and sort block, free again once the index is placed
+struct ClusterScratch {
+    DevBuf d_parent;               // uint32 per record: the union-find's forest while the hooks run
+    DevBuf d_root, d_size;         // uint32 per record: the smallest record of its component (kClusterNone: non-finite); at a root, the component's records
+    DevBuf d_rank;                 // uint32 per record: at the root of a cluster, its rank; kClusterNone elsewhere
+    DevBuf d_label;                // int32 per record: the rank of its cluster, -1 without one
+    DevBuf d_offsets;              // uint32 per record + 1: the clusters' sizes by rank, then their exclusive prefix sum
+    DevBuf d_scan;                 // the prefix sum's scratch
+    DevBuf d_n;                    // one word: the number of clusters
+    PinnedBuf host;                // where the count, the offsets and the indices land before the caller's share is copied out
+};
+
 // Scratch of feature matching (features.hip, feature_kernels.hpp), per row of the two descriptor clouds of a call; not part of an index
 struct FeatureScratch {
     DevBuf d_valid[2];             // uint32 per row: all 33 floats finite; [0] the source's rows, [1] the target's (source == target: [1] alone)
@@ -573,6 +586,7 @@ struct rsreg_ctx {
     rsreg::PointGrid knn;            // rebuilt by every k-NN call from the cloud it is given
     rsreg::FilterScratch filt;
     rsreg::RadiusScratch rad;        // radius search: it indexes in `knn` too, with a placement of its own
+    rsreg::ClusterScratch clus;      // EuclideanClusterExtraction: over the radius index
 
     // ---- feature matching (features.hip): scratch of its own
     rsreg::FeatureScratch feat;

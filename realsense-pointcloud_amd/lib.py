@@ -58,6 +58,7 @@ EXPORTS = [
     "rsreg_cloud_radius_count", "rsreg_cloud_radius_outlier_removal", "rsreg_cloud_normals_radius",
     "rsreg_cloud_fpfh_radius", "rsreg_cloud_spfh_radius",
     "rsreg_iss_params_default", "rsreg_cloud_iss_saliency", "rsreg_cloud_iss_non_max", "rsreg_cloud_iss_keypoints",
+    "rsreg_cluster_params_default", "rsreg_cloud_euclidean_clusters", "rsreg_cloud_cluster_filter",
     "rsreg_cloud_radius_count_surface", "rsreg_cloud_normals_radius_surface", "rsreg_cloud_fpfh_radius_surface", "rsreg_cloud_spfh_radius_surface",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
@@ -169,6 +170,10 @@ class SciaResult(C.Structure):   # rsreg_scia_result
 class IssParams(C.Structure):   # rsreg_iss_params
     _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double),
                 ("min_neighbors", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ClusterParams(C.Structure):   # rsreg_cluster_params
+    _fields_ = [("tolerance", C.c_double), ("min_cluster_size", C.c_uint32), ("max_cluster_size", C.c_uint32)]
 
 
 class IinParams(C.Structure):   # rsreg_iin_params
@@ -438,6 +443,10 @@ def lib():
     L.rsreg_cloud_iss_saliency.argtypes = [vp, vp, C.POINTER(IssParams), vp, vp, vp]
     L.rsreg_cloud_iss_non_max.argtypes = [vp, vp, vp, dbl, i32, vp]
     L.rsreg_cloud_iss_keypoints.argtypes = [vp, vp, C.POINTER(IssParams), vp, vp, sz, C.POINTER(C.c_uint64)]
+    L.rsreg_cluster_params_default.argtypes = [C.POINTER(ClusterParams)]
+    L.rsreg_cluster_params_default.restype = None
+    L.rsreg_cloud_euclidean_clusters.argtypes = [vp, vp, C.POINTER(ClusterParams), vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.rsreg_cloud_cluster_filter.argtypes = [vp, vp, C.POINTER(ClusterParams), C.c_uint32, C.c_uint32, i32, i32, vp, C.POINTER(C.c_uint64)]
     L.rsreg_cloud_fpfh_radius.argtypes = [vp, vp, vp, dbl, vp]
     L.rsreg_cloud_spfh_radius.argtypes = [vp, vp, vp, dbl, vp, vp]
     L.rsreg_cloud_radius_count_surface.argtypes = [vp, vp, vp, dbl, vp]
