@@ -1367,6 +1367,116 @@ int rsreg_cloud_euclidean_clusters(rsreg_ctx *ctx, const rsreg_cloud *in, const 
                                    uint32_t capacity, uint32_t *n_clusters_out /* may be NULL */);
 int rsreg_cloud_cluster_filter(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cluster_params *p, uint32_t rank_lo, uint32_t rank_hi, int negative,
                                int keep_organized, rsreg_cloud *out, uint64_t *n_kept /* may be NULL */);
+/* ---- plane segmentation: pcl::SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE and SAC_RANSAC -- the dominant
+ * plane of a cloud (floor, table, wall) -- and pcl::ExtractIndices to consume its result: the step in front of
+ * EuclideanClusterExtraction.  PCL 1.9.1 sample_consensus/impl/sac_model_plane.hpp, sac_model_perpendicular_plane.hpp, ransac.hpp and
+ * segmentation/impl/sac_segmentation.hpp, recalled; PCL is not available to check against, so what follows IS the contract, and
+ * where it leaves PCL it says DEVIATION.
+ * Inputs of every entry point: one device cloud of the context whose records start with x, y, z floats (stride >= 12 and a multiple
+ * of 4).  A NULL cloud, a cloud of another context or such a stride: RSREG_ERR_INVALID_ARG, nothing written (the refusals of the
+ * other cloud operations).  A record is FINITE when its three coordinates are.  n = the records of the cloud.  All calls wait for
+ * the stream.
+ * The distance of a record p to a model (a, b, c, d), float32, every operation rounded once, no contraction:
+ *   dist = ((a * p.x + b * p.y) + c * p.z) + d.
+ * p is an INLIER iff it is finite and (double)fabsf(dist) < threshold: strictly.  NaN compares false.  (Implemented as
+ * fabsf(dist) < thr_up with thr_up the least float >= threshold, which is the same predicate.)  threshold negative or NaN:
+ * RSREG_ERR_INVALID_ARG; 0 is allowed and admits nothing.  Every float32 operation is IEEE: denormals are kept, an overflow is
+ * +-inf and inf - inf is NaN.  Any four floats are allowed as a model in rsreg_cloud_plane_count and rsreg_cloud_plane_filter -- a
+ * zero normal, NaN and inf included; a record whose dist is NaN or +-inf is not an inlier.
+ *
+ * HYPOTHESIS h (h = 0, 1, ...) draws record indices with the generator of rsreg_cloud_sac_correspondences, unchanged: index(h, draw)
+ *   as written there, with n the number of records.  Try t = 0 .. 15 takes the records i0, i1, i2 = index(h, 3 t), index(h, 3 t + 1),
+ *   index(h, 3 t + 2), with points p0, p1, p2.  The try is GOOD when the three indices differ, the three records are finite, and with
+ *   (float32; each product rounded, then the subtraction)
+ *     u = p1 - p0; v = p2 - p0; nx = u.y * v.z - u.z * v.y; ny = u.z * v.x - u.x * v.z; nz = u.x * v.y - u.y * v.x;
+ *     n2 = (nx * nx + ny * ny) + nz * nz
+ *   n2 is finite and > 0.  The first good try gives the model: l = sqrtf(n2); a = nx / l; b = ny / l; c = nz / l (sqrt and divide
+ *   correctly rounded); d = -((a * p0.x + b * p0.y) + c * p0.z).  Fewer than three records: no try is good.
+ *   DEVIATION: PCL's rand()-driven sampler and its ratio test for collinear samples are not reproduced.
+ *   THE AXIS CONSTRAINT (SACMODEL_PERPENDICULAR_PLANE) applies when eps_angle > 0 and the axis is not zero.  In double, each written
+ *   operation rounded once, a, b, c the floats above and (ax, ay, az) the axis:
+ *     cs = |(a * ax + b * ay) + c * az| / (sqrt((a * a + b * b) + c * c) * sqrt((ax * ax + ay * ay) + az * az)).
+ *   The model passes iff cs >= cos_eps, with cos_eps = std::cos(eps_angle) computed once on the host and returned in the result.
+ *   DEVIATION: PCL compares acos angles.
+ *   A hypothesis is VALID when it has a good try and, where the constraint applies, its model passes it; otherwise it is INVALID and
+ *   its count is 0.  count[h] = the inliers of model(h) at distance_threshold.
+ * THE STOPPING RULE is PCL's (ransac.hpp), this time with its skip counter (the axis constraint makes invalid hypotheses the common
+ *   case, and a rule that spent an iteration on each would stop after hypothesis 0), replayed sequentially in double over h = 0, 1, ..:
+ *     it = 0; skipped = 0; k = 1; best = -1; while it < k and it < max_iterations and skipped < 10 * max_iterations:
+ *       h invalid: ++skipped, nothing else.
+ *       h valid: if count[h] > best: best = count[h]; winner = h; w = (double)best / (double)n; q = 1 - w * w * w;
+ *         q = min(max(q, DBL_EPSILON), 1 - DBL_EPSILON); k = log(1 - probability) / log(q).  Then ++it.
+ *   DEVIATION: PCL's iterations_ > max_iterations_ off-by-one is not kept (as in rsreg_cloud_sac_correspondences).
+ *   The device scores the hypotheses in batches (at most 11 * max_iterations in all) and may score more than the replay consumes;
+ *   the result does not depend on the batches.  The winner is the FIRST h that reached the final best.
+ *   NO MODEL when n < 3 or best < 3: found = 0, the coefficients are zeros, best_hypothesis and sample are -1, there are no inliers.
+ *   Refused with RSREG_ERR_INVALID_ARG: probability outside (0, 1), max_iterations negative, eps_angle negative or NaN, an axis that
+ *   is not finite, distance_threshold negative or NaN.
+ * REFINEMENT (optimize_coefficients, on by default as in PCL) runs over the winner's inliers.  Ten double sums are taken of
+ *   e = (double)p - (double)p0, p0 the winner's first sample record (RSREG_NUM_PLANE_SEG_SUMS): [0] the number of inliers m,
+ *   [1..3] sum e, [4..9] sum of e.x e.x, e.x e.y, e.x e.z, e.y e.y, e.y e.z, e.z e.z (each product a double product, rounded once).
+ *   They are added in the tree written out for rsreg_cloud_estimate_rigid_svd: term i is record i, and a record that is not an
+ *   inlier is a term of +0.  rsreg_plane_from_sums (host only, no ctx) turns them into a model:
+ *     mean = sum e / m; C = sum e e^T / m - mean mean^T; the normal is the unit eigenvector of C's smallest eigenvalue (cyclic Jacobi
+ *     in double); its sign is chosen so that its dot product with the prior model's (a, b, c) is >= 0; a, b, c are its components
+ *     rounded to float; d = (float)(-normal . (p0 + mean)), in double.
+ *   It returns RSREG_ERR_INVALID_ARG and writes nothing when m < 3 or C is not finite.  The inliers are then selected again under the
+ *   refined model (PCL does the same).  With fewer than 3 inliers, or when rsreg_plane_from_sums refuses, the unrefined model is
+ *   kept; `refined` says which model the result holds.
+ *   DEVIATION: PCL accumulates the covariance in float about the centroid; here double sums relative to p0.
+ * rsreg_cloud_plane_count: the scoring stage alone.  counts_out[h] = the inliers of coeffs[4 h .. 4 h + 3] (host), h < H.  H == 0:
+ *   nothing is written.  n == 0: zeros.
+ * rsreg_cloud_plane_hypotheses: the sampler and the fit alone, for the hypotheses h_first .. h_first + H - 1 (every output host memory
+ *   and nullable).  coeffs_out[4 j ..]: the model, quiet NaN x 4 for an invalid hypothesis; samples_out[4 j ..]: i0, i1, i2 and the
+ *   good try (-1 x 4 after sixteen bad tries; a hypothesis that fails the axis test alone keeps its sample); valid_out[j]: 1 or 0.
+ * rsreg_cloud_plane_segment: SACSegmentation::segment.  params NULL: rsreg_plane_params_default.  coeff_out[4]: the model (refined
+ *   if `refined`).  indices_out: the inliers' record indices, ascending; *n_inliers_out their number -- when it exceeds `capacity`
+ *   the first `capacity` are written and the call still returns RSREG_OK.  coeff_out, indices_out (with capacity 0), n_inliers_out
+ *   and result may be NULL.
+ * rsreg_cloud_plane_filter: keeps the inliers of one model -- negative: every other record, the ones that are not finite included.
+ *   out, in == out, keep_organized, is_dense, the versioning and *n_kept are those of rsreg_cloud_radius_outlier_removal, through
+ *   the same flag / scan / gather kernels.
+ * rsreg_cloud_extract_indices: pcl::ExtractIndices over a HOST list of n_indices int32.  Positive: out record j = in record
+ *   indices[j], order and repeats as given (width = n_indices, height 1).  Negative: the records not named, in input order.  An
+ *   index outside the cloud: RSREG_ERR_INVALID_ARG, checked on the host before anything is launched.  in == out is allowed.
+ * Every output is a function of the cloud and the parameters alone, the same bytes from any context: the counts are integers, the
+ *   generator is a function of (seed, h, draw), every float sum has its order written above.
+ * Not built: the other models (line, sphere, cylinder, normal plane), SAC_LMEDS / MSAC and kin, setSamplesMaxDist, setIndices on the
+ *   segmentation, PCL's refineModel, segmentation across ranks (every rank segments the cloud it holds). */
+#define RSREG_NUM_PLANE_SEG_SUMS 10
+typedef struct rsreg_plane_params {
+    double distance_threshold;     /* setDistanceThreshold; 0: the caller sets it */
+    double probability;            /* 0.99 */
+    double axis[3];                /* setAxis; {0, 0, 0}: no constraint */
+    double eps_angle;              /* setEpsAngle, radians; 0: no constraint */
+    int32_t max_iterations;        /* 50 (SACSegmentation's default) */
+    int32_t optimize_coefficients; /* 1 */
+    uint64_t seed;                 /* 0 */
+} rsreg_plane_params;
+typedef struct rsreg_plane_result {
+    int32_t found;
+    int32_t best_hypothesis;
+    int32_t sample[3];             /* the winner's three records */
+    int32_t iterations;            /* valid hypotheses the replay consumed */
+    int32_t skipped;               /* invalid hypotheses the replay consumed */
+    int32_t refined;               /* 1: coeff_out is the refined model; 0: the winner's own */
+    uint64_t n_inliers;
+    double cos_eps;                /* std::cos(eps_angle) as used; 0 when the constraint does not apply */
+    float unrefined[4];            /* the winner's own model */
+    double sums[RSREG_NUM_PLANE_SEG_SUMS];   /* the refinement's sums; zeros when there was none */
+} rsreg_plane_result;
+void rsreg_plane_params_default(rsreg_plane_params *p);
+int rsreg_plane_from_sums(const double sums[RSREG_NUM_PLANE_SEG_SUMS], const float p0[3], const float prior[4], float coeff_out[4]);
+int rsreg_cloud_plane_count(rsreg_ctx *ctx, const rsreg_cloud *in, const float *coeffs /* H*4 */, size_t H, double threshold,
+                            uint32_t *counts_out /* H */);
+int rsreg_cloud_plane_hypotheses(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_plane_params *params, uint64_t h_first, size_t H,
+                                 float *coeffs_out /* H*4 */, int32_t *samples_out /* H*4 */, int32_t *valid_out /* H */);
+int rsreg_cloud_plane_segment(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_plane_params *params /* may be NULL */, float coeff_out[4],
+                              int32_t *indices_out, size_t capacity, size_t *n_inliers_out, rsreg_plane_result *result /* may be NULL */);
+int rsreg_cloud_plane_filter(rsreg_ctx *ctx, const rsreg_cloud *in, const float coeff[4], double threshold, int negative, int keep_organized,
+                             rsreg_cloud *out, uint64_t *n_kept /* may be NULL */);
+int rsreg_cloud_extract_indices(rsreg_ctx *ctx, const rsreg_cloud *in, const int32_t *indices, size_t n_indices, int negative, rsreg_cloud *out,
+                                uint64_t *n_kept /* may be NULL */);
 /* ---- pcl::FPFHEstimationOMP with setRadiusSearch(radius): SPFH and FPFH over the radius search above -- a support of fixed
  * metric size, any number of neighbours.  PCL 1.9.1 features/impl/fpfh.hpp (computePointSPFHSignature, weightPointSPFHSignature)
  * and pfh_tools.cpp (computePairFeatures), recalled; PCL is not available to check against, so what follows IS the contract.

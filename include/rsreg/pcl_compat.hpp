@@ -1231,6 +1231,114 @@ template <typename PointT> class EuclideanClusterExtraction {
     std::shared_ptr<Context> ctx_;
 };
 
+// ---- pcl::SACSegmentation<PointT> on the GPU for SACMODEL_PLANE and SACMODEL_PERPENDICULAR_PLANE with SAC_RANSAC
+// (csrc/plane_seg_kernels.hpp, rsreg_cloud_plane_segment; include/rsreg.h holds the contract and the stated deviations: the
+// counter-based sampler, the cosine form of the axis test, the double sums of the refinement).  segment(): the inliers' record
+// indices ascending and the four coefficients; both empty when no model was found, as in PCL.  PCL's defaults: max_iterations 50,
+// probability 0.99, optimize_coefficients on, distance_threshold 0.  setSeed is the one addition.  No setIndices, no other model or
+// method: setModelType / setMethodType throw RSREG_ERR_INVALID_ARG for them.
+enum SacModel { SACMODEL_PLANE = 0, SACMODEL_PERPENDICULAR_PLANE = 9 };   // pcl::SacModel's values
+constexpr int SAC_RANSAC = 0;                                             // pcl::SAC_RANSAC
+
+struct ModelCoefficients {
+    std::vector<float> values;
+};
+
+template <typename PointT> class SACSegmentation {
+  public:
+    SACSegmentation() { rsreg_plane_params_default(&params_); }
+    explicit SACSegmentation(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) { rsreg_plane_params_default(&params_); }
+    void setInputCloud(const typename PointCloud<PointT>::Ptr &cloud) { input_ = cloud, dinput_ = nullptr; }
+    void setInputCloud(const DeviceCloud<PointT> &cloud) { dinput_ = &cloud, input_.reset(); }   // (must outlive segment())
+    void setModelType(int model)
+    {
+        if (model != SACMODEL_PLANE && model != SACMODEL_PERPENDICULAR_PLANE)
+            throw Error(RSREG_ERR_INVALID_ARG, "rsreg: SACSegmentation fits SACMODEL_PLANE and SACMODEL_PERPENDICULAR_PLANE only");
+        model_ = model;
+    }
+    int getModelType() const { return model_; }
+    void setMethodType(int method)
+    {
+        if (method != SAC_RANSAC) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: SACSegmentation runs SAC_RANSAC only");
+    }
+    int getMethodType() const { return SAC_RANSAC; }
+    void setDistanceThreshold(double threshold) { params_.distance_threshold = threshold; }
+    double getDistanceThreshold() const { return params_.distance_threshold; }
+    void setMaxIterations(int n) { params_.max_iterations = n; }
+    int getMaxIterations() const { return params_.max_iterations; }
+    void setProbability(double p) { params_.probability = p; }
+    double getProbability() const { return params_.probability; }
+    void setOptimizeCoefficients(bool on) { params_.optimize_coefficients = on ? 1 : 0; }
+    bool getOptimizeCoefficients() const { return params_.optimize_coefficients != 0; }
+    template <typename Vector3> void setAxis(const Vector3 &axis) { for (int k = 0; k < 3; ++k) params_.axis[k] = (double)axis[k]; }   // (Eigen::Vector3f, float[3], ..)
+    void setAxis(double x, double y, double z) { params_.axis[0] = x, params_.axis[1] = y, params_.axis[2] = z; }
+    const double *getAxis() const { return params_.axis; }
+    void setEpsAngle(double eps) { params_.eps_angle = eps; }
+    double getEpsAngle() const { return params_.eps_angle; }
+    void setSeed(uint64_t seed) { params_.seed = seed; }
+    void segment(PointIndices &inliers, ModelCoefficients &coefficients)
+    {
+        if (dinput_) return segment(*dinput_, inliers, coefficients);
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        DeviceCloud<PointT> tmp(*input_, ctx_ ? ctx_ : Context::Default());
+        segment(tmp, inliers, coefficients);
+    }
+    void segment(const DeviceCloud<PointT> &input, PointIndices &inliers, ModelCoefficients &coefficients)
+    {
+        rsreg_ctx *c = input.context()->get();
+        rsreg_plane_params p = params_;
+        if (model_ == SACMODEL_PLANE) p.axis[0] = p.axis[1] = p.axis[2] = p.eps_angle = 0.0;   // (PCL's plain plane model ignores the axis)
+        const size_t n = input.size();
+        std::vector<int32_t> idx(n);
+        float coeff[4];
+        size_t found = 0;
+        check(rsreg_cloud_plane_segment(c, input.handle(), &p, coeff, n ? idx.data() : nullptr, n, &found, &result_), c);
+        inliers.indices.assign(idx.begin(), idx.begin() + (found < n ? found : n));
+        if (result_.found) coefficients.values.assign(coeff, coeff + 4);
+        else coefficients.values.clear();
+    }
+    const rsreg_plane_result &result() const { return result_; }   // engine extra: the last segment()'s iterations, sample and sums
+  private:
+    rsreg_plane_params params_;
+    rsreg_plane_result result_{};
+    int model_ = SACMODEL_PLANE;
+    typename PointCloud<PointT>::Ptr input_;
+    const DeviceCloud<PointT> *dinput_ = nullptr;
+    std::shared_ptr<Context> ctx_;
+};
+
+// ---- pcl::ExtractIndices<PointT> on the GPU (rsreg_cloud_extract_indices): the records an index list names, in its order and with
+// its repeats; setNegative(true): the records it does not name, in input order.  No setKeepOrganized, no setUserFilterValue.
+template <typename PointT> class ExtractIndices {
+  public:
+    ExtractIndices() = default;
+    explicit ExtractIndices(std::shared_ptr<Context> ctx) : ctx_(std::move(ctx)) {}
+    void setInputCloud(const typename PointCloud<PointT>::Ptr &cloud) { input_ = cloud; }
+    void setIndices(const std::shared_ptr<const PointIndices> &indices) { indices_.assign(indices->indices.begin(), indices->indices.end()); }
+    void setIndices(const PointIndices &indices) { indices_.assign(indices.indices.begin(), indices.indices.end()); }
+    void setNegative(bool negative) { negative_ = negative; }
+    bool getNegative() const { return negative_; }
+    void filter(PointCloud<PointT> &output)  // output may be *input
+    {
+        if (!input_) throw Error(RSREG_ERR_INVALID_ARG, "rsreg: setInputCloud not called");
+        DeviceCloud<PointT> tmp(*input_, ctx_ ? ctx_ : Context::Default());
+        filter(tmp, tmp);
+        tmp.download(output);
+    }
+    void filter(const DeviceCloud<PointT> &input, DeviceCloud<PointT> &output)  // output may be the input
+    {
+        check(rsreg_cloud_extract_indices(input.context()->get(), input.handle(), indices_.data(), indices_.size(), negative_, output.handle(), &n_kept_),
+              input.context()->get());
+    }
+    uint64_t kept() const { return n_kept_; }   // engine extra: the last filter()'s number of kept records
+  private:
+    std::vector<int32_t> indices_;
+    bool negative_ = false;
+    uint64_t n_kept_ = 0;
+    typename PointCloud<PointT>::Ptr input_;
+    std::shared_ptr<Context> ctx_;
+};
+
 // ---- pcl::ISSKeypoint3D<PointInT, PointOutT> over the exact radius search on the GPU (csrc/iss_kernels.hpp,
 // rsreg_cloud_iss_keypoints; include/rsreg.h holds the contract and the one stated deviation, the eigen-solve): the records whose
 // scatter over the salient radius has eigenvalue ratios below the two thresholds and whose smallest eigenvalue no neighbour within

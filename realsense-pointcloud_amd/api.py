@@ -646,6 +646,69 @@ class DeviceCloud:
         _l.check(rc, self.ctx.h)
         return out, int(kept.value)
 
+    def plane_count(self, coeffs, threshold):
+        """uint32 per model: the finite records with float32 |((a x + b y) + c z) + d| < threshold, strictly (rsreg_cloud_plane_count;
+        include/rsreg.h holds the arithmetic).  coeffs: (H, 4) float32, or one model."""
+        m = np.ascontiguousarray(np.asarray(coeffs, np.float32).reshape(-1, 4))
+        out = np.zeros(len(m), np.uint32)
+        _l.check(_l.lib().rsreg_cloud_plane_count(self.ctx.h, self.h, m.ctypes.data, len(m), float(threshold), out.ctypes.data), self.ctx.h)
+        return out
+
+    def plane_hypotheses(self, first=0, count=1, **params):
+        """(coeffs (count, 4) float32, samples (count, 4) int32, valid (count,) bool) of the plane hypotheses first .. first + count - 1:
+        the sampler and the fit alone (rsreg_cloud_plane_hypotheses).  An invalid hypothesis's model is NaN; samples: the three
+        records and the try that gave them, -1 after sixteen bad tries.  params: plane_params()."""
+        p = plane_params(**params)
+        coeffs, samples, valid = np.zeros((count, 4), np.float32), np.zeros((count, 4), np.int32), np.zeros(count, np.int32)
+        _l.check(_l.lib().rsreg_cloud_plane_hypotheses(self.ctx.h, self.h, C.byref(p), int(first), count, coeffs.ctypes.data, samples.ctypes.data,
+                                                       valid.ctypes.data), self.ctx.h)
+        return coeffs, samples, valid != 0
+
+    def segment_plane(self, capacity=None, **params):
+        """pcl::SACSegmentation with a plane model and RANSAC (rsreg_cloud_plane_segment): (coefficients (4,) float32, the inliers'
+        record indices int32 ascending, PlaneResult).  params: distance_threshold, max_iterations, probability,
+        optimize_coefficients, axis, eps_angle, seed (plane_params()).  capacity: room for so many indices (None: all); the
+        result's n_inliers is their number, however many were written."""
+        p = plane_params(**params)
+        room = self.info()[0] if capacity is None else int(capacity)
+        coeff, idx = np.zeros(4, np.float32), np.zeros(room, np.int32)
+        found, res = C.c_size_t(0), _l.PlaneResult()
+        _l.check(_l.lib().rsreg_cloud_plane_segment(self.ctx.h, self.h, C.byref(p), coeff.ctypes.data, idx.ctypes.data if room else None, room,
+                                                    C.byref(found), C.byref(res)), self.ctx.h)
+        return coeff, idx[:min(found.value, room)], PlaneResult(res)
+
+    def plane_filter(self, coeff, threshold, negative=False, keep_organized=False, out=None):
+        """rsreg_cloud_plane_filter: keeps the inliers of the model `coeff` (a, b, c, d) at `threshold` -- negative: every other
+        record.  out: None = a new DeviceCloud, or a DeviceCloud of this context (this one is allowed).  Returns (out, the number
+        of kept records)."""
+        made = out is None
+        if made:
+            out = DeviceCloud(ctx=self.ctx)
+        m = np.ascontiguousarray(np.asarray(coeff, np.float32).reshape(4))
+        kept = C.c_uint64(0)
+        rc = _l.lib().rsreg_cloud_plane_filter(self.ctx.h, self.h, m.ctypes.data, float(threshold), int(bool(negative)), int(bool(keep_organized)),
+                                               out.h, C.byref(kept))
+        if rc and made:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out, int(kept.value)
+
+    def extract_indices(self, indices, negative=False, out=None):
+        """pcl::ExtractIndices (rsreg_cloud_extract_indices): the records `indices` names, in that order and with its repeats --
+        negative: the records it does not name, in input order.  out: None = a new DeviceCloud, or a DeviceCloud of this context
+        (this one is allowed).  Returns (out, the number of kept records)."""
+        made = out is None
+        if made:
+            out = DeviceCloud(ctx=self.ctx)
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        kept = C.c_uint64(0)
+        rc = _l.lib().rsreg_cloud_extract_indices(self.ctx.h, self.h, idx.ctypes.data if len(idx) else None, len(idx), int(bool(negative)), out.h,
+                                                  C.byref(kept))
+        if rc and made:
+            out.close()
+        _l.check(rc, self.ctx.h)
+        return out, int(kept.value)
+
     def normals_radius_cloud(self, radius, viewpoint=None):
         """pcl::NormalEstimation with setRadiusSearch(radius) (rsreg_cloud_normals_radius): a DeviceCloud of 32-byte pcl::Normal
         records; fewer than three neighbours within the radius: NaNs."""
@@ -2076,6 +2139,157 @@ class EuclideanClusterExtraction:
             if not on_device:
                 dev.close()
         return [indices[offsets[c]:offsets[c + 1]].astype(np.int32) for c in range(len(offsets) - 1)]
+
+
+SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE = 0, 9    # pcl::SacModel
+SAC_RANSAC = 0                                         # pcl::SAC_RANSAC
+
+
+def plane_params(**kw):
+    """rsreg_plane_params: the defaults (rsreg_plane_params_default) with the given fields replaced; axis: three numbers."""
+    p = _l.PlaneParams()
+    _l.lib().rsreg_plane_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(p._fields_):
+            raise TypeError("rsreg_plane_params has no field %r" % k)
+        if k == "axis":
+            v = (C.c_double * 3)(*[float(a) for a in v])
+        setattr(p, k, v)
+    return p
+
+
+class PlaneResult:
+    """rsreg_plane_result: found, best_hypothesis, sample, iterations, skipped, refined, n_inliers, cos_eps, unrefined (4,), sums (10,)"""
+
+    def __init__(self, r):
+        self.found, self.best_hypothesis, self.sample = bool(r.found), int(r.best_hypothesis), tuple(r.sample)
+        self.iterations, self.skipped, self.refined, self.n_inliers = int(r.iterations), int(r.skipped), bool(r.refined), int(r.n_inliers)
+        self.cos_eps = float(r.cos_eps)
+        self.unrefined = np.array(list(r.unrefined), np.float32)
+        self.sums = np.array(list(r.sums), np.float64)
+
+
+def plane_from_sums(sums, p0, prior):
+    """rsreg_plane_from_sums (host only): the refined model (4,) float32 from the ten sums relative to p0, its normal on the side
+    of `prior`'s; None when there are fewer than three inliers or the covariance is not finite."""
+    s = np.ascontiguousarray(sums, np.float64).reshape(_l.NUM_PLANE_SEG_SUMS)
+    q, m = np.ascontiguousarray(p0, np.float32).reshape(3), np.ascontiguousarray(prior, np.float32).reshape(4)
+    out = np.zeros(4, np.float32)
+    rc = _l.lib().rsreg_plane_from_sums(s.ctypes.data, q.ctypes.data, m.ctypes.data, out.ctypes.data)
+    return None if rc else out
+
+
+class SACSegmentation:
+    """pcl::SACSegmentation<PointXYZRGB> on the GPU for SACMODEL_PLANE and SACMODEL_PERPENDICULAR_PLANE with SAC_RANSAC: batches of
+    plane hypotheses, each scored against every record (csrc/plane_seg_kernels.hpp, rsreg_cloud_plane_segment; include/rsreg.h holds
+    the contract and the stated deviations from PCL).  PCL's defaults: max_iterations 50, probability 0.99, optimize_coefficients
+    on, distance_threshold 0.  segment() gives (the inliers' record indices int32 ascending, the coefficients (4,) float32) -- an
+    empty list and zeros when no model was found; `result` holds the last call's PlaneResult.  setSeed is the one addition."""
+
+    def __init__(self, ctx=None):
+        self.params = plane_params()
+        self.model_type = SACMODEL_PLANE
+        self.method_type = SAC_RANSAC
+        self.result = None
+        self._in = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setModelType(self, model):
+        if model not in (SACMODEL_PLANE, SACMODEL_PERPENDICULAR_PLANE):
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "SACSegmentation fits SACMODEL_PLANE and SACMODEL_PERPENDICULAR_PLANE only")
+        self.model_type = model
+
+    def setMethodType(self, method):
+        if method != SAC_RANSAC:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "SACSegmentation runs SAC_RANSAC only")
+        self.method_type = method
+
+    def setDistanceThreshold(self, threshold):
+        self.params.distance_threshold = float(threshold)
+
+    def getDistanceThreshold(self):
+        return self.params.distance_threshold
+
+    def setMaxIterations(self, n):
+        self.params.max_iterations = int(n)
+
+    def getMaxIterations(self):
+        return self.params.max_iterations
+
+    def setProbability(self, p):
+        self.params.probability = float(p)
+
+    def getProbability(self):
+        return self.params.probability
+
+    def setOptimizeCoefficients(self, on):
+        self.params.optimize_coefficients = int(bool(on))
+
+    def getOptimizeCoefficients(self):
+        return bool(self.params.optimize_coefficients)
+
+    def setAxis(self, axis):
+        self.params.axis = (C.c_double * 3)(*[float(a) for a in axis])
+
+    def getAxis(self):
+        return tuple(self.params.axis)
+
+    def setEpsAngle(self, eps):
+        self.params.eps_angle = float(eps)
+
+    def getEpsAngle(self):
+        return self.params.eps_angle
+
+    def setSeed(self, seed):
+        self.params.seed = int(seed)
+
+    def segment(self):
+        if self._in is None:
+            raise _l.RsregError(_l.RSREG_ERR_INVALID_ARG, "setInputCloud not called")
+        prm = {k: getattr(self.params, k) for k, _ in self.params._fields_}
+        if self.model_type == SACMODEL_PLANE:   # (PCL's plain plane model ignores the axis)
+            prm["axis"], prm["eps_angle"] = (0.0, 0.0, 0.0), 0.0
+        on_device = isinstance(self._in, DeviceCloud)
+        dev = self._in if on_device else DeviceCloud(self._in, ctx=self.ctx or default_context())
+        try:
+            coeff, inliers, self.result = dev.segment_plane(**prm)
+        finally:
+            if not on_device:
+                dev.close()
+        return inliers, coeff
+
+
+class ExtractIndices:
+    """pcl::ExtractIndices<PointXYZRGB> on the GPU (rsreg_cloud_extract_indices): the records an index list names, in its order and
+    with its repeats; setNegative(True): the records it does not name, in input order.  `n_kept` holds the last call's number of
+    kept records."""
+
+    def __init__(self, ctx=None):
+        self.indices = np.zeros(0, np.int32)
+        self.negative = False
+        self.n_kept = None
+        self._in = None
+        self.ctx = ctx
+
+    def setInputCloud(self, cloud):
+        self._in = cloud
+
+    def setIndices(self, indices):
+        self.indices = np.ascontiguousarray(indices, np.int32).reshape(-1)
+
+    def setNegative(self, negative):
+        self.negative = bool(negative)
+
+    def getNegative(self):
+        return self.negative
+
+    def filter(self):
+        def run(cin, cout):
+            _, self.n_kept = cin.extract_indices(self.indices, self.negative, out=cout)
+        return _filter_io(self._in, self.ctx, run)
 
 
 class ISSKeypoint3D:

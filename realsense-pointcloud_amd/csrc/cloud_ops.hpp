@@ -82,6 +82,13 @@ constexpr CloudRule kXyzRule{12, true, "records need x, y, z floats and a stride
 // when the cloud holds records that cannot be reached (their upload failed).
 int cloud_view(rsreg_ctx *ctx, const rsreg_cloud *in, const rsreg_cloud *out_or_null, const CloudRule &rule, CloudView &view);
 
+// ---- filters.hip, for segment.hip: the tail every cloud filter ends in.  ctx->filt.d_flags holds a keep flag (uint32, 0 or 1) per
+// record of `v`, written on the context's stream.
+// flags -> positions -> the kept records, handed to `out` (waits for their number); in == out is allowed
+int compact_into(rsreg_ctx *ctx, const CloudView &v, rsreg_cloud *out, int is_dense, uint32_t *n_kept_out);
+// keep_organized: every record, a removed one with x = y = z = quiet NaN, handed to `out` with the input's width and height
+int organized_into(rsreg_ctx *ctx, const CloudView &v, rsreg_cloud *out, uint32_t *n_kept_out);
+
 // ---- prerej.hip, for scia.hip: the two estimators that score poses against a whole target cloud share the context's PrerejScratch,
 // the target's index and the kernel that adds a launch's partial sums
 struct PrejClouds {

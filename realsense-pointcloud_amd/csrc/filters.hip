@@ -78,6 +78,11 @@ int knn_mean_distance_device(rsreg_ctx *ctx, const CloudView &v, int mean_k, uin
     return RSREG_OK;
 }
 
+}  // namespace
+
+// (declared in cloud_ops.hpp: segment.hip ends its filters in these two as well)
+namespace rsreg {
+
 // flags -> positions -> the kept records in ctx->filt.d_out (waits for their number), handed to `out`
 int compact_into(rsreg_ctx *ctx, const CloudView &v, rsreg_cloud *out, int is_dense, uint32_t *n_kept_out)
 {
@@ -128,6 +133,10 @@ int organized_into(rsreg_ctx *ctx, const CloudView &v, rsreg_cloud *out, uint32_
     *n_kept_out = n - removed;
     return rsreg_cloud_adopt_(out, &fs.d_out, v.n, v.stride, v.width, v.height, removed ? 0 : v.is_dense);
 }
+
+}  // namespace rsreg
+
+namespace {
 
 // The index of the cloud for a radius search and what a walk needs beside it (radius_kernels.hpp), on ctx->stream: pointgrid.hpp's
 // build (one round trip to the host for the box) with the radius as the smallest cell and the ordered placement -- a stable sort of

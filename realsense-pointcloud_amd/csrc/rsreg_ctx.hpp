@@ -263,6 +263,29 @@ struct SacScratch {
     PinnedBuf host;                // counts, samples, rows, sums and words on their way home; a caller's transforms on their way out
 };
 
+// Scratch of the RANSAC plane segmentation and of ExtractIndices (segment.hip, plane_seg_kernels.hpp), per record of the cloud and per
+// hypothesis of a launch; not part of an index.  rsreg_cloud_plane_filter and rsreg_cloud_extract_indices leave their keep flags in
+// FilterScratch, where the filters' scan and gather read them.
+struct PlaneSegScratch {
+    DevBuf d_table;                // 4 floats per hypothesis of a launch: a, b, c, d (NaN: an invalid hypothesis)
+    DevBuf d_sample;               // 4 int32 per hypothesis of a launch: its three records and the try that gave them
+    DevBuf d_valid;                // uint32 per hypothesis of a launch: a good try that passed the axis test
+    DevBuf d_counts;               // uint32 per hypothesis of a launch: its inliers
+    DevBuf d_flags;                // uint32 per record: inlier under the current model
+    DevBuf d_pos, d_scan;          // the inliers' positions, the prefix sum's scratch
+    DevBuf d_out;                  // the inliers' record indices (int32), before they go home
+    DevBuf d_partials, d_sums;     // the ten sums: a slab per workgroup; kPlaneSumsBytes: the totals, then p0's three floats
+    DevBuf d_word;                 // the indices k_plane_emit found (uint64)
+    DevBuf d_index;                // ExtractIndices: the caller's int32 indices in HBM
+    PinnedBuf host;                // counts, samples, validity, rows, sums and words on their way home; a caller's models or indices on their way out
+};
+// d_sums of PlaneSegScratch: RSREG_NUM_PLANE_SEG_SUMS doubles, then (at byte kPlaneSumsP0At) the three floats of p0
+constexpr size_t kPlaneSumsP0At = 10 * sizeof(double);
+constexpr size_t kPlaneSumsBytes = kPlaneSumsP0At + 16;
+// host of PlaneSegScratch while a batch comes home: counts at word 0, validity at word kPlaneMaxBatch (sac_plan.hpp's kSacMaxBatch),
+// samples at word 2 * kPlaneMaxBatch (four a hypothesis), rows at word 6 * kPlaneMaxBatch (four a hypothesis)
+constexpr uint32_t kPlaneHostValidAt = 1, kPlaneHostSampleAt = 2, kPlaneHostTableAt = 6, kPlaneHostBatchWords = 10;   // (in units of the largest batch)
+
 // Index and scratch of SampleConsensusPrerejective (prerej.hip, prerej_kernels.hpp) and, a call at a time, of
 // SampleConsensusInitialAlignment (scia.hip: 16 sample words a hypothesis, errors in d_sums): the target's point grid, rebuilt by every call,
 // and what a round of hypotheses leaves; shares no buffer with another index or with the correspondence rejector
@@ -593,6 +616,9 @@ struct rsreg_ctx {
 
     // ---- pose from correspondences (sac.hip): scratch of its own
     rsreg::SacScratch sac;
+
+    // ---- RANSAC plane segmentation and ExtractIndices (segment.hip): scratch of its own
+    rsreg::PlaneSegScratch pseg;
 
     // ---- pose from descriptor neighbours, scored against the whole target (prerej.hip): index and scratch of its own
     rsreg::PrerejScratch prerej;

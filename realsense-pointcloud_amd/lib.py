@@ -16,11 +16,12 @@ ROOT = os.path.dirname(_HERE)
 DIAG = os.environ.get("RSREG_DIAG", "") == "1"
 SO_PATH = (os.environ.get("RSREG_SO") if DIAG else None) or os.path.join(_HERE, "librsreg_diag.so" if DIAG else "librsreg.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip", "depthcloud.hip", "depth_host.cpp", "features.hip", "sac.hip", "prerej.hip", "scia.hip"]
+SOURCES = ["icp.hip", "ndt.hip", "voxel.hip", "comm.cpp", "voxel_host.cpp", "pcd_host.cpp", "cloud.hip", "edges.hip", "filters.hip", "iinormals.hip", "depthcloud.hip", "depth_host.cpp", "features.hip", "sac.hip", "prerej.hip", "scia.hip", "segment.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) if os.path.isdir(CSRC) else []
 NUM_SUMS = 17
 NUM_PLANE_SUMS = 32                                      # include/rsreg.h: RSREG_NUM_PLANE_SUMS
 NUM_GICP_SUMS = 32                                       # include/rsreg.h: RSREG_NUM_GICP_SUMS
+NUM_PLANE_SEG_SUMS = 10                                  # include/rsreg.h: RSREG_NUM_PLANE_SEG_SUMS
 ESTIMATION_SVD, ESTIMATION_POINT_TO_PLANE_LLS = 0, 1     # include/rsreg.h: rsreg_estimation
 IIN_COVARIANCE_MATRIX, IIN_AVERAGE_3D_GRADIENT, IIN_AVERAGE_DEPTH_CHANGE, IIN_SIMPLE_3D_GRADIENT = 0, 1, 2, 3   # rsreg_iin_method
 IIN_BORDER_IGNORE, IIN_BORDER_MIRROR = 0, 1              # rsreg_iin_border_policy
@@ -59,6 +60,8 @@ EXPORTS = [
     "rsreg_cloud_fpfh_radius", "rsreg_cloud_spfh_radius",
     "rsreg_iss_params_default", "rsreg_cloud_iss_saliency", "rsreg_cloud_iss_non_max", "rsreg_cloud_iss_keypoints",
     "rsreg_cluster_params_default", "rsreg_cloud_euclidean_clusters", "rsreg_cloud_cluster_filter",
+    "rsreg_plane_params_default", "rsreg_plane_from_sums", "rsreg_cloud_plane_count", "rsreg_cloud_plane_hypotheses", "rsreg_cloud_plane_segment",
+    "rsreg_cloud_plane_filter", "rsreg_cloud_extract_indices",
     "rsreg_cloud_radius_count_surface", "rsreg_cloud_normals_radius_surface", "rsreg_cloud_fpfh_radius_surface", "rsreg_cloud_spfh_radius_surface",
     "rsreg_icp_set_target_normals", "rsreg_icp_set_target_normals_cloud", "rsreg_icp_plane_sums", "rsreg_icp_update_plane",
     "rsreg_icp_plane_sums_last", "rsreg_plane_solve_from_sums",
@@ -174,6 +177,17 @@ class IssParams(C.Structure):   # rsreg_iss_params
 
 class ClusterParams(C.Structure):   # rsreg_cluster_params
     _fields_ = [("tolerance", C.c_double), ("min_cluster_size", C.c_uint32), ("max_cluster_size", C.c_uint32)]
+
+
+class PlaneParams(C.Structure):   # rsreg_plane_params
+    _fields_ = [("distance_threshold", C.c_double), ("probability", C.c_double), ("axis", C.c_double * 3), ("eps_angle", C.c_double),
+                ("max_iterations", C.c_int32), ("optimize_coefficients", C.c_int32), ("seed", C.c_uint64)]
+
+
+class PlaneResult(C.Structure):   # rsreg_plane_result
+    _fields_ = [("found", C.c_int32), ("best_hypothesis", C.c_int32), ("sample", C.c_int32 * 3), ("iterations", C.c_int32), ("skipped", C.c_int32),
+                ("refined", C.c_int32), ("n_inliers", C.c_uint64), ("cos_eps", C.c_double), ("unrefined", C.c_float * 4),
+                ("sums", C.c_double * NUM_PLANE_SEG_SUMS)]
 
 
 class IinParams(C.Structure):   # rsreg_iin_params
@@ -447,6 +461,14 @@ def lib():
     L.rsreg_cluster_params_default.restype = None
     L.rsreg_cloud_euclidean_clusters.argtypes = [vp, vp, C.POINTER(ClusterParams), vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     L.rsreg_cloud_cluster_filter.argtypes = [vp, vp, C.POINTER(ClusterParams), C.c_uint32, C.c_uint32, i32, i32, vp, C.POINTER(C.c_uint64)]
+    L.rsreg_plane_params_default.argtypes = [C.POINTER(PlaneParams)]
+    L.rsreg_plane_params_default.restype = None
+    L.rsreg_plane_from_sums.argtypes = [vp, vp, vp, vp]
+    L.rsreg_cloud_plane_count.argtypes = [vp, vp, vp, sz, dbl, vp]
+    L.rsreg_cloud_plane_hypotheses.argtypes = [vp, vp, C.POINTER(PlaneParams), C.c_uint64, sz, vp, vp, vp]
+    L.rsreg_cloud_plane_segment.argtypes = [vp, vp, C.POINTER(PlaneParams), vp, vp, sz, C.POINTER(sz), C.POINTER(PlaneResult)]
+    L.rsreg_cloud_plane_filter.argtypes = [vp, vp, vp, dbl, i32, i32, vp, C.POINTER(C.c_uint64)]
+    L.rsreg_cloud_extract_indices.argtypes = [vp, vp, vp, sz, i32, vp, C.POINTER(C.c_uint64)]
     L.rsreg_cloud_fpfh_radius.argtypes = [vp, vp, vp, dbl, vp]
     L.rsreg_cloud_spfh_radius.argtypes = [vp, vp, vp, dbl, vp, vp]
     L.rsreg_cloud_radius_count_surface.argtypes = [vp, vp, vp, dbl, vp]
